@@ -6,7 +6,10 @@ Workload (BASELINE.json configs[2], the configuration the metric is quoted on; i
   crown_radius=5, pixel size 0.5 m, all-ones mask, compactness=10)  +  zonal mean/var/min/max on all 8 bands.
 One "step" = that whole pipeline once, input already resident in HBM.  value = H*W / step time (Mpixel/s).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--size S] [--no-cpu] [--no-side]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--size S] [--dump-outputs DIR] [--full [--no-cpu] [--no-side]]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its own: the per-stage
+breakdown step, `cpu_baseline` and the side legs below (--no-cpu / --no-side leave those out again).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (fixed, seeded samples; see dump_outputs).
 For N > 1 the driver launches one rank per GPU with torch.distributed.run (RCCL); --gpus must equal WORLD_SIZE.
   --config c3 (default): every rank owns one 16384-row slab (the N = 1 workload) of a (N*16384) x 16384 x 8 raster, and the
       slabs are segmented as ONE raster: halo rows and seam label rows travel by send/recv between neighbouring ranks
@@ -16,13 +19,13 @@ For N > 1 the driver launches one rank per GPU with torch.distributed.run (RCCL)
   --config c4: BASELINE configs[3], the raster is ALWAYS 32768 x 32768 x 8 (tile 2048, overlap 64): N = 1 segments it whole
       (34 GB of raster on one 288-GB GPU), N ranks take 32768/N rows each (8 GPUs: slabs of 4096 rows = 2 tile rows)
       => "scaling": "strong"; this is the case north_star's ">= 6x at 8 GPUs" speaks of.
-Side legs at N = 1 (never `value`; --no-side skips them): the same workload at compactness 0.25 (the author's regime,
+Side legs at N = 1 (never `value`; --full only, --no-side skips them): the same workload at compactness 0.25 (the author's regime,
 notebooks/deepfor.ipynb:402 -- at compactness 10 on [0,1] features the result is nearly a grid), and BASELINE configs[4]
 (8192 x 8192 x 3 quickshift, kernel_size 5, max_dist 10).
 
 The JSON line carries `roofline` (dominant kernel = the SLIC colour sweep slic_assign_kernel<8,true,false,false,false,8>:
 algorithmic bytes (4*C + 4 = 36 B/pixel) x pixels per launch / launch time from HIP events on
-the library's stream) and `cpu_baseline` (the C oracle -- a port, 1 thread -- on one 2048^2 tile of the same
+the library's stream) and, with --full, `cpu_baseline` (the C oracle -- a port, 1 thread -- on one 2048^2 tile of the same
 workload).
 """
 import argparse
@@ -183,6 +186,40 @@ def library_baseline(C, tile, n, compactness):
         return {"error": str(e)[:200]}
 
 
+DUMP_PIXELS = 1 << 21          # label samples per dump (float64: 16 MB)
+DUMP_STAT_VALUES = 1 << 19     # statistics entries (segments x bands) per array (float64: 4 MB)
+
+
+def dump_outputs(out_dir, lab, n, st, rank=0, world=1):
+    """What one step hands its caller -- the label raster, the segment count and the zonal statistics -- as float64 / float32 .npy
+    files under out_dir, 64 MB at most in all: every row and column sum of the labels, the labels of a fixed, seeded sample of pixels
+    and the statistics of a fixed, seeded sample of segments (all of them when they fit).  N > 1: every rank writes its own
+    slab's files (suffix _rank<r>) with 1/N of the samples."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    H, W = lab.shape
+    rs = np.random.RandomState(20240601 + rank)
+
+    def pick(total, k):
+        return np.arange(total) if total <= k else np.sort(rs.randint(0, total, k))
+
+    arrays = {"n_segments": np.array([n], np.float64),
+              "labels_row_sum": lab.sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64),
+              "labels_col_sum": lab.sum(dim=0, dtype=torch.int64).cpu().numpy().astype(np.float64)}
+    px = torch.from_numpy(pick(H * W, DUMP_PIXELS // world)).to(lab.device)
+    arrays["labels_sample_index"] = px.cpu().numpy().astype(np.float64)
+    arrays["labels_sample"] = lab.reshape(-1)[px].cpu().numpy().astype(np.float64)
+    B = len(st["bands"])
+    seg = torch.from_numpy(pick(int(st["count"].shape[0]), DUMP_STAT_VALUES // (B * world))).to(st["count"].device)
+    arrays["stats_sample_index"] = seg.cpu().numpy().astype(np.float64)
+    arrays["stats_count"] = st["count"][seg].cpu().numpy().astype(np.float64)
+    for k in ("mean", "variance", "min", "max"):
+        arrays["stats_" + k] = st[k][seg].cpu().numpy()      # mean / variance float64, min / max float32
+    assert sum(a.nbytes for a in arrays.values()) <= (64 << 20) // world
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,12 +230,17 @@ def main():
     ap.add_argument("--buffer", type=int, default=64)
     ap.add_argument("--bands", type=int, default=8)
     ap.add_argument("--compactness", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-side", action="store_true", help="skip the side legs (exit_on_fixed_point, compactness 0.25, quickshift, configs[3] whole)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-stage breakdown step, the cpu_baseline leg and the side legs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side legs (exit_on_fixed_point, compactness 0.25, quickshift, configs[3] whole)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--host-rng", action="store_true", help="draw the raster's noise with NumPy RandomState on the host (SURVEY 8d's wording; ~1 min)")
     ap.add_argument("--config", choices=("c3", "c4"), default="c3",
                     help="c3: BASELINE configs[2] per GPU (weak scaling); c4: BASELINE configs[3], 32768^2 x 8 split over the ranks (strong)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_side = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -329,8 +371,8 @@ def main():
 
     # An event pair costs ~2.5 us of stream time; with every kernel class bracketed a step records ~420 pairs = 1.1 ms (2 %).
     # The timed steps therefore bracket only the launches of the dominant kernel, the colour sweep -- what the roofline needs,
-    # measured over the whole timed region; the per-stage breakdown comes from one more step AFTER the timed region (all
-    # classes on, like the side legs: never part of `value`).
+    # measured over the whole timed region; with --full the per-stage breakdown comes from one more step AFTER the timed region
+    # (all classes on, like the side legs: never part of `value`).
     parts = {"features_ms": 0.0, "prepass_ms": 0.0, "assign_ms": 0.0, "connectivity_ms": 0.0, "zonal_ms": 0.0}
     parts_steps = 0
     for _ in range(args.warmup):
@@ -351,19 +393,22 @@ def main():
         sweeps += t_seg["sweeps"]
     barrier()
     dt = time.time() - t0
-    ctx.set_profiling(1)
-    _, _, _, t_seg, t_z = step(profile=True)   # the breakdown step (untimed)
-    for k in ("features_ms", "prepass_ms", "assign_ms", "connectivity_ms"):
-        parts[k] += t_seg[k]
-    parts["zonal_ms"] += t_z["zonal_ms"]
-    parts_steps += 1
-    barrier()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lab, n_seg, st, rank, world)
+    if args.full:
+        ctx.set_profiling(1)
+        _, _, _, t_seg, t_z = step(profile=True)   # the breakdown step (untimed)
+        for k in ("features_ms", "prepass_ms", "assign_ms", "connectivity_ms"):
+            parts[k] += t_seg[k]
+        parts["zonal_ms"] += t_z["zonal_ms"]
+        parts_steps += 1
+        barrier()
     if dist is not None:
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     phases_all = None
-    if dist is not None:
+    if dist is not None and args.full:
         # every rank's phase times of the breakdown step (a device synchronisation at every phase boundary: they add up to the call,
         # which is therefore a little slower than a timed step): the line of the first real multi-GPU run has to explain itself
         keys = ["halo_ms", "black_ms", "import_ms", "class0_ms", "class1_ms", "export_ms", "relabel_ms", "owned_labels_ms", "zonal_ms"]
@@ -560,7 +605,7 @@ def main():
                          "pixels_per_launch_avg": round(assign_px / max(1.0, sweeps), 1),
                          "sweep_sum_ms_per_step": round(assign_ms / args.steps, 3), "sweep_busy_ms_per_step": round(assign_busy_ms / args.steps, 3)},
             "stage_ms_per_step": dict({k: round(v / max(1, parts_steps), 3) for k, v in parts.items()},
-                                      source="one step after the timed region, every kernel class bracketed by events"),
+                                      source="one step after the timed region, every kernel class bracketed by events") if args.full else None,
         }
         if not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(C, args.tile, args.buffer, 5, 0.5, args.compactness)

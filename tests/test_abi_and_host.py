@@ -90,10 +90,10 @@ def test_objects_table_columns_follow_reference_order():
 
 def test_objects_table_schema_equals_the_reference_source():
     """create_objects' positional order, defaults and default column list against the reference's own source text
-    (obia/segmentation/segment_statistics.py:392-398 and :66-108), parsed with ast when /root/reference is present (it is
-    not on the GPU box; the expected values are also written out below)."""
-    import ast
+    (obia/segmentation/segment_statistics.py:392-398 and :66-108): its signature, as parsed with ast, is stored in
+    tests/golden/create_objects_signature.json (the expected values are also written out below)."""
     import inspect
+    import json
     from obia_amd.statistics import create_objects, stats_columns
     sig = inspect.signature(create_objects)
     pos = [p.name for p in sig.parameters.values() if p.kind == p.POSITIONAL_OR_KEYWORD]
@@ -105,14 +105,10 @@ def test_objects_table_schema_equals_the_reference_source():
     assert pos == expected
     defaults = {p.name: p.default for p in sig.parameters.values() if p.kind == p.POSITIONAL_OR_KEYWORD and p.default is not p.empty}
     assert defaults["calculate_textural"] is True and defaults["calculate_structural"] is False and defaults["calc_pai"] is True
-    ref = "/root/reference/obia/segmentation/segment_statistics.py"
-    import os
-    if os.path.exists(ref):
-        fn = [n for n in ast.parse(open(ref).read()).body if isinstance(n, ast.FunctionDef) and n.name == "create_objects"][0]
-        names = [a.arg for a in fn.args.args]
-        dflt = [ast.literal_eval(d) for d in fn.args.defaults]
-        assert names == expected
-        assert dict(zip(names[len(names) - len(dflt):], dflt)) == defaults
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "create_objects_signature.json")) as fh:
+        ref = json.load(fh)
+    assert ref["positional"] == expected
+    assert ref["defaults"] == defaults
     # default columns for a 2-band raster: what segment() yields in the reference (segment.py:87-91 passes no textural flag)
     cols = stats_columns([0, 1], [0, 1], calc_pai=True, calc_fhd=True, calc_ch=True, calc_mean_intensity=True,
                          calc_variance_intensity=True, geometry=True)

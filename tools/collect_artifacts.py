@@ -1,9 +1,9 @@
-"""After `gpurun -- 'bash tools/final_artifacts.sh'`: profiles/<round>_traffic.json from the newest counter files, the bench lines and
+"""After `bash tools/final_artifacts.sh` (output folder: ARTIFACTS_DIR, default artifacts/): profiles/<round>_traffic.json from the newest counter files, the bench lines and
 the kernel statistics copied under profiles/.   python tools/collect_artifacts.py <commit> [round prefix, default r04]"""
 import csv, glob, json, os, shutil, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = sys.argv[2] if len(sys.argv) > 2 else "r04"
-go = os.path.join(root, "gpurun_out")
+go = os.path.join(root, os.environ.get("ARTIFACTS_DIR", "artifacts"))
 newest = lambda pat: sorted(glob.glob(os.path.join(go, pat)), key=os.path.getmtime)[-1]   # noqa: E731
 tf, tw = tempfile.mkdtemp(), tempfile.mkdtemp()
 shutil.copy(newest("fa_fetch/*/*_counter_collection.csv"), tf)

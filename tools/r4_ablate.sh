@@ -10,7 +10,7 @@ for comp in 10 0.25; do
   for v in "" _noload _v1 _noacc; do
     lib=obia_amd/csrc/libobia_hip$v.so
     echo "== compactness $comp lib ${v:-HEAD}" >> $out
-    OBIA_HIP_LIB=$lib timeout -k 10 200 python bench.py --no-cpu --no-side --steps 6 --compactness $comp 2>gpurun_out/r4_abl_err.txt | python -c "$pick" >> $out 2>&1
+    OBIA_HIP_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu --no-side --steps 6 --compactness $comp 2>"${out%.txt}_err.txt" | python -c "$pick" >> $out 2>&1
   done
 done
 for comp in 10 0.25; do
