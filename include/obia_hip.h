@@ -218,6 +218,20 @@ int obia_quickshift_f32_dev(obia_ctx *ctx, const float *img_hwc, int H, int W, i
                             double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
                             int32_t *labels_out, int *n_labels_out);
 
+/* Stage-level entry point (device pointers), used by the parity tests to compare each stage of quickshift with the
+ * oracle (obia_oracle_quickshift_stages).  Arguments and results of obia_quickshift_f32_dev, plus these outputs, each
+ * nullable, each one device-to-device copy at the point named (the production entries launch exactly what they did):
+ *   staged_out      [C][H][W] float64: the image after Lab, smoothing and `* ratio` (what the window kernels read)
+ *   noise_out       [H][W] float64: the noise added to the densities (zeros when tie_noise_hw is NULL)
+ *   dens_out        [H][W] float64: densities after P1, noise included
+ *   parent_out      [H][W] int32: nearest pixel of higher density after P2, BEFORE the max_dist cut (itself if none)
+ *   dist_parent_out [H][W] float64: the distance to it after P2 (+inf if none)
+ *   roots_out       [H][W] int32: the root of every pixel after the cut and pointer jumping                          */
+int obia_quickshift_stages_f32_dev(obia_ctx *ctx, const float *img_hwc, int H, int W, int C, double ratio, double kernel_size,
+                                   double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
+                                   int32_t *labels_out, int *n_labels_out, double *staged_out, double *noise_out, double *dens_out,
+                                   int32_t *parent_out, double *dist_parent_out, int32_t *roots_out);
+
 /* ---- B3: tiled driver ------------------------------------------------------------------------------
  * Replaces the tile loops of create_tiled_segments (tiling.py:103-291) on label rasters: pass 1
  * "black" checkerboard tiles on exact windows, pass 2 "white" tiles on windows grown by `buffer`,

@@ -279,8 +279,19 @@ __global__ void qs_labels_kernel(const int *__restrict__ parent, const int *__re
         labels[i] = rank[parent[i]];
 }
 
+// Stage outputs of obia_quickshift_stages_f32_dev (each nullable): one device-to-device copy at the point named, nothing else.
+struct QsStages {
+    double *img;           // [C][H][W] after Lab, smoothing and `* ratio`: what the window kernels read
+    double *noise;         // [H][W] the noise added to the densities (zeros when none)
+    double *dens;          // [H][W] after P1, noise included
+    int32_t *parent;       // [H][W] after P2, before the max_dist cut
+    double *dist_parent;   // [H][W] after P2
+    int32_t *roots;        // [H][W] after pointer jumping
+};
+
 static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, double ratio, double kernel_size, double max_dist,
-                          double sigma, int convert2lab, const double *noise, int normalize_bands, int32_t *labels_out, int *n_labels_out) {
+                          double sigma, int convert2lab, const double *noise, int normalize_bands, int32_t *labels_out, int *n_labels_out,
+                          const QsStages *st = nullptr) {
     if (!img || !labels_out || H <= 0 || W <= 0 || C <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if ((long long)H * W > 0x7fffffffLL) { set_error("raster above 2^31 pixels"); return OBIA_E_INVALID; }
     if (!(kernel_size >= 1.0)) { set_error("`kernel_size` should be >= 1."); return OBIA_E_INVALID; }
@@ -326,6 +337,14 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
         hipLaunchKernelGGL(qs_gauss_axis_kernel, dim3(gg), dim3(256), 0, ctx->stream, d_img, d_tmp, H, W, n * C, 1, d_w, r, 1.0);
         hipLaunchKernelGGL(qs_gauss_axis_kernel, dim3(gg), dim3(256), 0, ctx->stream, d_tmp, d_img, H, W, n * C, 0, d_w, r, ratio);
     }
+    auto d2d = [&](void *dst, const void *src, size_t bytes) {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    };
+    if (st && st->img) OBIA_HIP_TRY(d2d(st->img, d_img, sizeof(double) * (size_t)n * C));
+    if (st && st->noise) {
+        if (noise) OBIA_HIP_TRY(d2d(st->noise, noise, sizeof(double) * (size_t)n));
+        else OBIA_HIP_TRY(hipMemsetAsync(st->noise, 0, sizeof(double) * (size_t)n, ctx->stream));
+    }
     // 2. density, 3. parent
     const double inv = -0.5 / (kernel_size * kernel_size);
     const int side = QT + 2 * kw;
@@ -347,6 +366,10 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
     }
 #undef QS_LAUNCH
     OBIA_HIP_TRY(hipGetLastError());
+    // qs_cut_kernel rewrites the parent array in place: the uncut parents are taken before it
+    if (st && st->dens) OBIA_HIP_TRY(d2d(st->dens, d_dens, sizeof(double) * (size_t)n));
+    if (st && st->parent) OBIA_HIP_TRY(d2d(st->parent, d_par, sizeof(int) * (size_t)n));
+    if (st && st->dist_parent) OBIA_HIP_TRY(d2d(st->dist_parent, d_dp, sizeof(double) * (size_t)n));
     // 4. cut, flatten
     hipLaunchKernelGGL(qs_cut_kernel, dim3(gs), dim3(256), 0, ctx->stream, d_par, d_dp, n, max_dist);
     int *pa = d_par, *pb = d_par2;
@@ -358,6 +381,7 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
         OBIA_TRY(read_back(ctx, &changed, d_flags, sizeof(int)));
         if (!changed) break;
     }
+    if (st && st->roots) OBIA_HIP_TRY(d2d(st->roots, pa, sizeof(int) * (size_t)n));
     // 5. consecutive labels by ascending root index
     hipLaunchKernelGGL(qs_rootcount_kernel, dim3(nb), dim3(256), 0, ctx->stream, pa, n, d_bs);
     hipLaunchKernelGGL(qs_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_bs, nb, d_flags + 1);
@@ -392,6 +416,21 @@ int obia_quickshift_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C
     if (rc != OBIA_OK) return rc;
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     resolve_timing(ctx);
+    return OBIA_OK;
+}
+
+int obia_quickshift_stages_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, double ratio, double kernel_size,
+                                   double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
+                                   int32_t *labels_out, int *n_labels_out, double *staged_out, double *noise_out, double *dens_out,
+                                   int32_t *parent_out, double *dist_parent_out, int32_t *roots_out) {
+    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
+    ctx->arena.reset();
+    const QsStages st{staged_out, noise_out, dens_out, parent_out, dist_parent_out, roots_out};
+    const int rc = quickshift_dev(ctx, img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, tie_noise_hw, normalize_bands,
+                                  labels_out, n_labels_out, &st);
+    if (rc != OBIA_OK) return rc;
+    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return OBIA_OK;
 }
 

@@ -221,27 +221,16 @@ def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, 
     if convert2lab and C != 3:
         raise ValueError("Only RGB images can be converted to Lab space.")
     device_noise = isinstance(rng, str) and rng == "device"
-    if device_noise:
-        if not is_t:
-            raise ValueError('rng="device" needs a CUDA tensor input')
-        noise = None
-    elif random_seed is not None:
-        noise = np.random.RandomState(random_seed).normal(scale=0.00001, size=(H, W))
-    else:
-        noise = (rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)).normal(scale=0.00001, size=(H, W))
-    if noise is not None:
-        noise = np.ascontiguousarray(noise, np.float64)
+    if device_noise and not is_t:
+        raise ValueError('rng="device" needs a CUDA tensor input')
+    noise = None if device_noise else _quickshift_host_noise(H, W, rng, random_seed)
     if is_t:
         if not image.is_cuda:
             raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
         img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
         dev = img.device.index or 0
         c = ctx or _lib.default_context(dev)
-        if device_noise:
-            g = torch.Generator(device=img.device).manual_seed(42)
-            nz = torch.randn((H, W), dtype=torch.float64, device=img.device, generator=g) * 0.00001
-        else:
-            nz = torch.as_tensor(noise, device=img.device)
+        nz = _quickshift_device_noise(H, W, img.device) if device_noise else torch.as_tensor(noise, device=img.device)
         out = torch.empty((H, W), dtype=torch.int32, device=img.device)
         torch.cuda.current_stream(dev).synchronize()
         _lib.check(lib.obia_quickshift_f32_dev(c.handle, img.data_ptr(), H, W, C, float(ratio), float(kernel_size),
@@ -258,6 +247,62 @@ def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, 
                                        float(sigma), int(bool(convert2lab)), _lib.np_ptr(noise), int(bool(_normalize_bands)),
                                        _lib.np_ptr(out), ctypes.byref(n_out)))
     return out.astype(np.int64)
+
+
+def _quickshift_host_noise(H, W, rng, random_seed):
+    if random_seed is not None:
+        noise = np.random.RandomState(random_seed).normal(scale=0.00001, size=(H, W))
+    else:
+        noise = (rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)).normal(scale=0.00001, size=(H, W))
+    return np.ascontiguousarray(noise, np.float64)
+
+
+def _quickshift_device_noise(H, W, device):
+    g = torch.Generator(device=device).manual_seed(42)
+    return torch.randn((H, W), dtype=torch.float64, device=device, generator=g) * 0.00001
+
+
+def _quickshift_stages(image, ratio=1.0, kernel_size=5, max_dist=10, sigma=0, convert2lab=True, rng=42, *, random_seed=None,
+                       ctx=None, _normalize_bands=False):
+    """Test and diagnostic entry (obia_quickshift_stages_f32_dev): one quickshift call that also returns what each stage
+    produced, for comparison with the oracle (oracle.quickshift_stages).  Same arguments and noise as ``quickshift``; a NumPy
+    input is copied to cuda:0.  Returns a dict of CUDA tensors: ``image`` (C, H, W) float64 as the window kernels read it,
+    ``noise`` (H, W) float64, ``dens`` (H, W) float64, ``parent`` (H, W) int32 before the max_dist cut (itself where no
+    neighbour has a higher density), ``dist_parent`` (H, W) float64 (+inf there), ``roots`` (H, W) int32, ``labels``
+    (H, W) int32, and ``n_labels``, an int."""
+    if not np.isscalar(sigma) or not (float(sigma) >= 0.0):
+        raise ValueError("sigma: a number >= 0 (the width of the Gaussian pre-smoothing on both raster axes)")
+    if kernel_size < 1:
+        raise ValueError("`kernel_size` should be >= 1.")
+    lib = _lib.load()
+    if not _is_torch(image):
+        image = torch.as_tensor(np.ascontiguousarray(image, np.float32), device="cuda")
+    if not image.is_cuda:
+        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
+    img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
+    H, W, C = img.shape
+    if convert2lab and C != 3:
+        raise ValueError("Only RGB images can be converted to Lab space.")
+    dev = img.device
+    if isinstance(rng, str) and rng == "device":
+        nz = _quickshift_device_noise(H, W, dev)
+    else:
+        nz = torch.as_tensor(_quickshift_host_noise(H, W, rng, random_seed), device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = {"image": torch.empty((C, H, W), **f64), "noise": torch.empty((H, W), **f64), "dens": torch.empty((H, W), **f64),
+           "parent": torch.empty((H, W), **i32), "dist_parent": torch.empty((H, W), **f64), "roots": torch.empty((H, W), **i32),
+           "labels": torch.empty((H, W), **i32)}
+    c = ctx or _lib.default_context(dev.index or 0)
+    n_out = ctypes.c_int(0)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_quickshift_stages_f32_dev(c.handle, img.data_ptr(), H, W, C, float(ratio), float(kernel_size), float(max_dist),
+                                                  float(sigma), int(bool(convert2lab)), nz.data_ptr(), int(bool(_normalize_bands)),
+                                                  out["labels"].data_ptr(), ctypes.byref(n_out), out["image"].data_ptr(),
+                                                  out["noise"].data_ptr(), out["dens"].data_ptr(), out["parent"].data_ptr(),
+                                                  out["dist_parent"].data_ptr(), out["roots"].data_ptr()))
+    out["n_labels"] = n_out.value
+    return out
 
 
 def enforce_connectivity(labels, min_size, max_size, start_label=1, ctx=None):

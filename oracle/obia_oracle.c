@@ -664,3 +664,87 @@ int obia_oracle_quickshift_core(const double *image, const double *noise, int64_
     free(rank); free(dens); free(parent); free(dist_parent);
     return OBIA_OK;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * The stages of obia_oracle_quickshift_core, for the stage-level GPU tests (obia_quickshift_stages_f32_dev).
+ * The same arithmetic in the same order as the core (which stays as it is, pinned on the goldens); in addition it
+ * returns the densities (noise included), the parents BEFORE the max_dist cut (itself where no neighbour has a higher
+ * density), dist_parent (+inf there), the roots, and per pixel a bit mask of the near-ties at which a last-bit
+ * difference in the arithmetic (device exp vs glibc, pow/cbrt of the Lab conversion) could change the result:
+ *   bit 0  density tie:  some window neighbour q has |dens[q] - dens[p]| <= tau * dens[p]
+ *   bit 1  distance tie: among the higher-density neighbours the two smallest squared distances differ by <= tau * best
+ *   bit 2  cut tie:      |dist_parent - max_dist| <= tau * max_dist
+ * labels_out as the core's.  Arrays are caller-allocated, H*W each.
+ * ------------------------------------------------------------------------------------------ */
+int obia_oracle_quickshift_stages(const double *image, const double *noise, int64_t H, int64_t W, int C,
+                                  double kernel_size, double max_dist, double tau, double *dens, int64_t *parent,
+                                  double *dist_parent, int64_t *roots, int64_t *labels_out, uint8_t *flags)
+{
+    const double inv_ks2 = -0.5 / (kernel_size * kernel_size);
+    const int64_t kw = (int64_t)ceil(3.0 * kernel_size);
+    const int64_t npix = H * W;
+    for (int64_t r = 0; r < H; ++r)
+        for (int64_t c = 0; c < W; ++c) {
+            int64_t r0 = r - kw > 0 ? r - kw : 0, r1 = r + kw + 1 < H ? r + kw + 1 : H;
+            int64_t c0 = c - kw > 0 ? c - kw : 0, c1 = c + kw + 1 < W ? c + kw + 1 : W;
+            const double *cur = image + (r * W + c) * C;
+            double acc = 0.0;
+            for (int64_t r_ = r0; r_ < r1; ++r_)
+                for (int64_t c_ = c0; c_ < c1; ++c_) {
+                    double dist = 0.0;
+                    const double *o = image + (r_ * W + c_) * C;
+                    for (int ch = 0; ch < C; ++ch) { double t = cur[ch] - o[ch]; dist += t * t; }
+                    double tr = (double)(r - r_), tc = (double)(c - c_);
+                    dist += tr * tr;
+                    dist += tc * tc;
+                    acc += exp(dist * inv_ks2);
+                }
+            dens[r * W + c] = acc;
+        }
+    for (int64_t i = 0; i < npix; ++i) { dens[i] += noise[i]; parent[i] = i; flags[i] = 0; }
+    for (int64_t r = 0; r < H; ++r)
+        for (int64_t c = 0; c < W; ++c) {
+            int64_t r0 = r - kw > 0 ? r - kw : 0, r1 = r + kw + 1 < H ? r + kw + 1 : H;
+            int64_t c0 = c - kw > 0 ? c - kw : 0, c1 = c + kw + 1 < W ? c + kw + 1 : W;
+            const int64_t p = r * W + c;
+            const double *cur = image + p * C;
+            const double cd = dens[p];
+            double closest = INFINITY, second = INFINITY;
+            for (int64_t r_ = r0; r_ < r1; ++r_)
+                for (int64_t c_ = c0; c_ < c1; ++c_) {
+                    const int64_t q = r_ * W + c_;
+                    if (q != p && fabs(dens[q] - cd) <= tau * fabs(cd)) flags[p] |= 1;
+                    if (dens[q] > cd) {
+                        double dist = 0.0;
+                        const double *o = image + q * C;
+                        for (int ch = 0; ch < C; ++ch) { double t = cur[ch] - o[ch]; dist += t * t; }
+                        double tr = (double)(r - r_), tc = (double)(c - c_);
+                        dist += tr * tr;
+                        dist += tc * tc;
+                        if (dist < closest) { second = closest; closest = dist; parent[p] = q; }
+                        else if (dist < second) second = dist;
+                    }
+                }
+            if (second - closest <= tau * closest) flags[p] |= 2;   /* false when fewer than two candidates (inf - x, inf - inf) */
+            dist_parent[p] = sqrt(closest);
+            if (fabs(dist_parent[p] - max_dist) <= tau * max_dist) flags[p] |= 4;
+        }
+    for (int64_t i = 0; i < npix; ++i) roots[i] = dist_parent[i] > max_dist ? i : parent[i];
+    for (;;) {
+        int changed = 0;
+        for (int64_t i = 0; i < npix; ++i) {
+            int64_t p = roots[roots[i]];
+            if (p != roots[i]) { roots[i] = p; changed = 1; }
+        }
+        if (!changed) break;
+    }
+    int64_t *rank = (int64_t *)malloc(sizeof(int64_t) * (size_t)npix);
+    if (!rank) return OBIA_ENOMEM;
+    int64_t n = 0;
+    for (int64_t i = 0; i < npix; ++i) rank[i] = -1;
+    for (int64_t i = 0; i < npix; ++i) rank[roots[i]] = 0;
+    for (int64_t i = 0; i < npix; ++i) if (rank[i] == 0) rank[i] = n++;
+    for (int64_t i = 0; i < npix; ++i) labels_out[i] = rank[roots[i]];
+    free(rank);
+    return OBIA_OK;
+}

@@ -359,3 +359,41 @@ def quickshift_core(image_f64, noise, kernel_size, max_dist):
     if rc:
         raise RuntimeError(f"oracle quickshift rc={rc}")
     return out
+
+
+def quickshift_stages(image_f64, noise, kernel_size, max_dist, tau=1e-12):
+    """obia_oracle_quickshift_stages: the core's arithmetic, returning every stage and the per-pixel near-tie flags (bit 0 density,
+    bit 1 distance, bit 2 cut at max_dist; see obia_oracle.c).  ``parent`` is taken before the max_dist cut."""
+    image_f64 = np.ascontiguousarray(image_f64, np.float64)
+    noise = np.ascontiguousarray(noise, np.float64)
+    H, W, C = image_f64.shape
+    out = {"dens": np.empty((H, W), np.float64), "parent": np.empty((H, W), np.int64),
+           "dist_parent": np.empty((H, W), np.float64), "roots": np.empty((H, W), np.int64),
+           "labels": np.empty((H, W), np.int64), "flags": np.empty((H, W), np.uint8)}
+    rc = lib().obia_oracle_quickshift_stages(_ptr(image_f64), _ptr(noise), _i64(H), _i64(W), ctypes.c_int(C),
+                                             ctypes.c_double(kernel_size), ctypes.c_double(max_dist), ctypes.c_double(tau),
+                                             _ptr(out["dens"]), _ptr(out["parent"]), _ptr(out["dist_parent"]), _ptr(out["roots"]),
+                                             _ptr(out["labels"]), _ptr(out["flags"]))
+    if rc:
+        raise RuntimeError(f"oracle quickshift stages rc={rc}")
+    return out
+
+
+def rgb2lab_f64(rgb):
+    """scikit-image 0.18.3 rgb2lab on a float64 (H, W, 3) image (D65, 2 degrees): rgb2xyz then xyz2lab (color/colorconv.py),
+    every step in float64.  The 3 x 3 product is written out (x = r*m0 + g*m1 + b*m2, left to right, no FMA) as the library's
+    kernel does; NumPy's matmul may sum in another order, which the fixtures allow (see tests/test_oracle_quickshift_stages.py)."""
+    arr = np.array(rgb, dtype=np.float64, copy=True)
+    mask = arr > 0.04045
+    arr[mask] = np.power((arr[mask] + 0.055) / 1.055, 2.4)
+    arr[~mask] /= 12.92
+    m = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
+    white = np.array([0.95047, 1.0, 1.08883])
+    xyz = np.empty_like(arr)
+    for i in range(3):
+        xyz[..., i] = (arr[..., 0] * m[i, 0] + arr[..., 1] * m[i, 1] + arr[..., 2] * m[i, 2]) / white[i]
+    mask = xyz > 0.008856
+    xyz[mask] = np.cbrt(xyz[mask])
+    xyz[~mask] = 7.787 * xyz[~mask] + 16.0 / 116.0
+    x, y, z = xyz[..., 0], xyz[..., 1], xyz[..., 2]
+    return np.stack([116.0 * y - 16.0, 500.0 * (x - y), 200.0 * (y - z)], -1)

@@ -1,11 +1,13 @@
 """GPU parity of quickshift (BASELINE config 5) against the scikit-image 0.18.3 golden vectors and
 the oracle.  float64 on both sides; the only difference is exp/pow/cbrt (device libm vs glibc), which can flip a
-parent only on near-ties: stated tolerance ARI >= 0.99, label count within 2 %."""
+parent only on near-ties: labels IDENTICAL to the goldens (the stage hook and the oracle's near-tie flags say why wherever
+they would not be, tests/qs_stages.py); the earlier bar (ARI >= 0.99, label count within 2 %) is kept beside it."""
 import os
 
 import numpy as np
 import pytest
 
+from tests import qs_stages as qs
 from tests.metrics import adjusted_rand_index
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ torch = pytest.importorskip("torch")
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def test_quickshift_vs_skimage_goldens():
+def test_quickshift_vs_skimage_goldens(oracle):
     from obia_amd.segmentation import quickshift
     z = np.load(os.path.join(GOLD, "quickshift_small.npz"))
     for i in range(3):
@@ -28,6 +30,12 @@ def test_quickshift_vs_skimage_goldens():
         assert ari >= 0.99, f"case {i}: ARI {ari} ({(lab != gold).mean():.3%} px differ)"
         assert abs(n_l - n_g) <= max(1, 0.02 * n_g)
         assert lab.min() == 0 and lab.max() == n_l - 1          # consecutive ids by root order
+        # stage by stage: the staged image is scikit-image's float64 Lab image (x ratio 1), the labels the golden's exactly
+        g = qs.run_gpu(raw, ratio=1.0, kernel_size=float(ks), max_dist=float(md), convert2lab=True, random_seed=42, _normalize_bands=True)
+        o = oracle.quickshift_stages(z[f"lab{i}"] * 1.0, g["noise"], float(ks), float(md), tau=qs.TAU)
+        assert np.array_equal(o["labels"], gold)
+        qs.check(g, o, float(md), "B", staged_ref=z[f"lab{i}"] * 1.0, name=f"quickshift_small {i}")
+        assert np.array_equal(g["labels"], gold) and np.array_equal(lab, gold), f"case {i}: {(lab != gold).sum()} px differ"
 
 
 def test_quickshift_with_sigma_vs_skimage_goldens(oracle):
@@ -45,6 +53,14 @@ def test_quickshift_with_sigma_vs_skimage_goldens(oracle):
         n_l, n_g = len(np.unique(lab)), len(np.unique(gold))
         assert ari >= 0.99, f"case {i}: ARI {ari} ({(lab != gold).mean():.3%} px differ)"
         assert abs(n_l - n_g) <= max(1, 0.02 * n_g)
+        # stage by stage: the staged image is SciPy's smoothed float64 image x ratio, the labels the golden's exactly
+        g = qs.run_gpu(raw, ratio=float(ratio), kernel_size=float(ks), max_dist=float(md), sigma=float(sg), convert2lab=bool(lab_flag),
+                       random_seed=42, _normalize_bands=True)
+        ref_img = z[f"smoothed{i}"] * float(ratio)
+        o = oracle.quickshift_stages(ref_img, g["noise"], float(ks), float(md), tau=qs.TAU)
+        assert np.array_equal(o["labels"], gold)
+        qs.check(g, o, float(md), "B", staged_ref=ref_img, name=f"quickshift_sigma {i}")
+        assert np.array_equal(g["labels"], gold) and np.array_equal(lab, gold), f"case {i}: {(lab != gold).sum()} px differ"
     rs = np.random.RandomState(11)
     H, W, C = 75, 93, 4
     yy, xx = np.mgrid[0:H, 0:W]
@@ -53,6 +69,7 @@ def test_quickshift_with_sigma_vs_skimage_goldens(oracle):
     ref = oracle.quickshift_core(oracle.quickshift_smooth(img.astype(np.float64), 1.3) * 0.5, noise, 3.0, 8.0)
     out = quickshift(img, ratio=0.5, kernel_size=3.0, max_dist=8.0, sigma=1.3, convert2lab=False, random_seed=5)
     assert adjusted_rand_index(out, ref) >= 0.99 and abs(len(np.unique(out)) - len(np.unique(ref))) <= max(1, 0.02 * len(np.unique(ref)))
+    assert np.array_equal(out, ref), f"{(out != ref).sum()} px differ"
     with pytest.raises(ValueError):
         quickshift(img, sigma=-1.0, convert2lab=False)
 
@@ -96,12 +113,15 @@ def test_quickshift_any_band_count_and_kernel_size(oracle, C, ks, md):
     assert abs(len(np.unique(lab)) - len(np.unique(ref))) <= max(1, 0.02 * len(np.unique(ref)))
 
 
-def test_config5_full_size_quickshift_properties():
-    """BASELINE configs[4] at full size: 8192 x 8192 x 3, quickshift(kernel_size=5, max_dist=10).  No oracle finishes this;
+def test_config5_full_size_quickshift_properties(oracle):
+    """BASELINE configs[4] at full size: 8192 x 8192 x 3, quickshift(kernel_size=5, max_dist=10).  No oracle finishes this whole;
+    the stage hook pins the forest exactly (roots are fixed points, every root is its own cut parent, every pixel shares its cut
+    parent's root, every link climbs to a strictly higher density, labels are the rank of the root among the roots -- the scan runs
+    16 chunks per thread here), and the oracle checks three crops of the hook's staged image and noise.  Earlier
     properties: consecutive ids 0..N-1 in ascending order of each segment's root pixel (np.unique(..., return_inverse)),
     every link of the forest is shorter than max_dist in the 5-D feature space so no segment reaches farther than its
     pixel count allows, a second run is bit-identical, and the count sits in the range the 512-pixel goldens predict."""
-    from obia_amd.segmentation import quickshift
+    from obia_amd.segmentation import quickshift, _quickshift_stages
     S = 8192
     g = torch.Generator(device="cuda").manual_seed(5)
     yy = torch.arange(S, device="cuda", dtype=torch.float32)[:, None]
@@ -109,7 +129,8 @@ def test_config5_full_size_quickshift_properties():
     img = torch.stack([0.5 + 0.4 * torch.sin(xx / (11 + 3 * c)) * torch.cos(yy / (13 + 2 * c))
                        + 0.02 * torch.randn((S, S), device="cuda", generator=g) for c in range(3)], -1).clamp_(0, 1).contiguous()
     lab = quickshift(img, kernel_size=5, max_dist=10, ratio=1.0, rng="device")
-    lab2 = quickshift(img, kernel_size=5, max_dist=10, ratio=1.0, rng="device")
+    st = _quickshift_stages(img, kernel_size=5, max_dist=10, ratio=1.0, rng="device")
+    lab2 = st["labels"]
     assert torch.equal(lab, lab2)
     n = int(lab.max().item()) + 1
     assert int(lab.min().item()) == 0
@@ -121,6 +142,43 @@ def test_config5_full_size_quickshift_properties():
     # any forest: first pixels are distinct and every id has one
     assert int(torch.unique(first).numel()) == n
     assert 1e4 <= n <= 2e6
+    # the forest, exactly
+    idx = torch.arange(S * S, device="cuda", dtype=torch.int64)
+    roots = st["roots"].reshape(-1).to(torch.int64)
+    dens = st["dens"].reshape(-1)
+    cutp = torch.where(st["dist_parent"].reshape(-1) > 10.0, idx, st["parent"].reshape(-1).to(torch.int64))
+    assert torch.equal(roots[roots], roots)
+    is_root = roots == idx
+    assert torch.equal(cutp[is_root], idx[is_root])
+    assert torch.equal(roots[cutp], roots)
+    link = cutp != idx
+    assert bool((dens[cutp[link]] > dens[link]).all())
+    rank = torch.cumsum(is_root.to(torch.int64), 0) - 1
+    assert torch.equal(rank[roots], flat) and st["n_labels"] == n == int(is_root.sum().item())
+    # three crops against the oracle, on the hook's staged image and noise: densities >= kw from a cut edge, parents >= 2 kw
+    kw = 15
+    for name, (y0, x0) in {"top-left": (0, 0), "bottom-right": (S - 150, S - 150), "centre": (S // 2 - 75, S // 2 - 75)}.items():
+        ys, xs = slice(y0, y0 + 150), slice(x0, x0 + 150)
+        crop = st["image"][:, ys, xs].permute(1, 2, 0).contiguous().cpu().numpy()
+        o = oracle.quickshift_stages(crop, st["noise"][ys, xs].contiguous().cpu().numpy(), 5.0, 10.0, tau=qs.TAU)
+
+        def inner(m):   # rows / columns at least m from every crop edge that is not an image edge
+            r = np.arange(150)
+            ok_y = ((r >= m) | (y0 == 0)) & ((r < 150 - m) | (y0 + 150 == S))
+            ok_x = ((r >= m) | (x0 == 0)) & ((r < 150 - m) | (x0 + 150 == S))
+            return ok_y[:, None] & ok_x[None, :]
+        d1, d2 = inner(kw), inner(2 * kw)
+        gd = st["dens"][ys, xs].cpu().numpy()
+        np.testing.assert_allclose(gd[d1], o["dens"][d1], rtol=qs.DENS_RTOL, atol=0, err_msg=name)
+        gp = st["parent"][ys, xs].cpu().numpy().astype(np.int64)
+        op = o["parent"]
+        op_global = (op // 150 + y0) * S + (op % 150 + x0)
+        untied = d2 & ((o["flags"] & 1) == 0)
+        assert np.array_equal(gp[untied], op_global[untied]), f"{name}: {(gp[untied] != op_global[untied]).sum()} parents differ"
+        same = d2 & (gp == op_global)
+        gdp = st["dist_parent"][ys, xs].cpu().numpy()
+        assert np.array_equal(gdp[same], o["dist_parent"][same]), name
+        assert untied.sum() >= 0.9 * d2.sum()
 
 
 def test_quickshift_device_noise_matches_the_goldens_away_from_ties():
