@@ -192,6 +192,35 @@ int obia_label_edges_u8_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, int 
 int obia_sample_labels_i32_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, int W, const double *inverse_affine6,
                                const double *points_xy, int64_t n_points, int outside_value, int32_t *labels_out);
 
+/* ---- cost surface (obia/utils/cost.py: make_cost_surface and its layers) ------------------------------------------
+ * All pointers are DEVICE pointers unless marked HOST; every call is asynchronous on the context's stream except the
+ * two that return a count (select, edge count), which read it back.  Exactness contract: DESIGN.md "Cost surface".
+ * obia_cost_bands_f32_dev    : (H, W, 8) float32 WorldView-3 raster (C B G Y R RE N1 N2, 16-byte aligned) -> the C band
+ *                              and 1 - ndvi(R, N1), float32, in one pass.
+ * obia_cost_ndvi_f32_dev     : clip((nir - red) / (nir + red + 1e-9), -1, 1), float32.
+ * obia_cost_sobel_f32_dev    : hypot(sobel(chm, axis=1), sobel(chm, axis=0)), mode "nearest", float32.
+ * obia_cost_select_dev       : exact order statistics of the non-NaN values of a float32 (is_f64 = 0) or float64 plane:
+ *                              n_valid_out and bits4_out (HOST) = the float's bits of the values of rank floor(v), floor(v)+1
+ *                              at v = (n_valid - 1) * q_lo, then at q_hi (both neighbours are the last value when v >= n_valid
+ *                              - 1); np.nanpercentile's interpolation is left to the caller.  1 <= n < 2^32.
+ * obia_cost_entropy_f32_dev  : u8 = (normalise(pan) * 255) with the given (lo, hi), then skimage's rank entropy over disk(3),
+ *                              float64; table_30x32 (DEVICE) [pop][count] = (c/pop) * log(c/pop) / ln 2, column 0 = 0.
+ * obia_cost_normalise_dev    : nan_to_num((clip(x, lo, hi) - lo) / (hi - lo)) of a float32 / float64 plane, float64 out.
+ * obia_cost_edge_count_dev   : number of pixels whose label differs from the pixel below or to the right.
+ * obia_cost_combine_dev      : clip(((w0 g + w1 p) + w2 t) + w3 e, 0, 1) -> float32 (NaN -> -9999), each layer stretched
+ *                              by its (lo4[k], hi4[k]) (HOST arrays, as w4); labels may be NULL (edge term 0.0).       */
+int obia_cost_bands_f32_dev(obia_ctx *ctx, const float *hwc8, int64_t n_pixels, float *pan_out, float *gap_out);
+int obia_cost_ndvi_f32_dev(obia_ctx *ctx, const float *red, const float *nir, int64_t n, float *out);
+int obia_cost_sobel_f32_dev(obia_ctx *ctx, const float *chm, int H, int W, float *grad_out);
+int obia_cost_select_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n, double q_lo, double q_hi, int64_t *n_valid_out,
+                         uint64_t *bits4_out);
+int obia_cost_entropy_f32_dev(obia_ctx *ctx, const float *pan, int H, int W, double lo, double hi, const double *table_30x32,
+                              double *out);
+int obia_cost_normalise_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n, double lo, double hi, double *out);
+int obia_cost_edge_count_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, int W, int64_t *n_edge_out);
+int obia_cost_combine_dev(obia_ctx *ctx, const float *grad, const float *gap, const double *tex, const int32_t *labels_hw, int H,
+                          int W, const double *lo4, const double *hi4, const double *w4, float *out);
+
 /* ---- next row f3: GLCM texture statistics per (label, band) ------------------------------------------------------
  * Restates calculate_textural_stats (segment_statistics.py:179-298) on the masked bounding-box crop of every segment,
  * for the band PLANE the code evidently means (the reference indexes a column, :214; see oracle/glcm.py): crop of the

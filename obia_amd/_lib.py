@@ -64,6 +64,14 @@ _SIGNATURES = {
     "obia_texture_stats_f32_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P]),
     "obia_label_edges_u8_dev": (_I, [_P, _P, _I, _I, _P, _P]),
     "obia_sample_labels_i32_dev": (_I, [_P, _P, _I, _I, _P, _P, ctypes.c_int64, _I, _P]),
+    "obia_cost_bands_f32_dev": (_I, [_P, _P, ctypes.c_int64, _P, _P]),
+    "obia_cost_ndvi_f32_dev": (_I, [_P, _P, _P, ctypes.c_int64, _P]),
+    "obia_cost_sobel_f32_dev": (_I, [_P, _P, _I, _I, _P]),
+    "obia_cost_select_dev": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "obia_cost_entropy_f32_dev": (_I, [_P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "obia_cost_normalise_dev": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
+    "obia_cost_edge_count_dev": (_I, [_P, _P, _I, _I, _P]),
+    "obia_cost_combine_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "obia_polygon_count_i32_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_polygon_rings_i32_dev": (_I, [_P, _P, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
     "obia_quickshift_f32": (_I, [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P, ctypes.POINTER(_I)]),
