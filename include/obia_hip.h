@@ -152,14 +152,16 @@ int obia_zonal_stats_f32_dev(obia_ctx *ctx, const float *raw_hwc, const int32_t 
  * Completes calculate_spectral_stats (segment_statistics.py:173-175: scipy.stats.skew / kurtosis with their defaults,
  * bias=True, fisher=True; NaN for nearly constant data as scipy >= 1.9 does, with float32 eps).  Second pass over
  * (labels, raw) with the per-label means as pivots (central power sums in float64).
+ *   var_out (may be NULL): receives the central m2 of this pass -- the variance about the first pass's mean, which
+ *   replaces the first pass's variance (same value within float64 rounding, no shift conversions)
  *   _dev : mean_dev = the mean table of obia_zonal_stats_f32_dev [n_labels*n_bands]; outputs on the device
  *   host : runs both passes itself; outputs [n_labels*n_bands] float64 on the host                              */
 int obia_zonal_moments_f32_dev(obia_ctx *ctx, const float *raw_hwc, const int32_t *labels_hw, int H, int W, int C,
                                const int32_t *bands, int n_bands, int n_labels, int start_label,
-                               const double *mean_dev, double *skew_out, double *kurt_out);
+                               const double *mean_dev, double *skew_out, double *kurt_out, double *var_out);
 int obia_zonal_moments_f32(obia_ctx *ctx, const float *raw_hwc, const int32_t *labels_hw, int H, int W, int C,
                            const int32_t *bands, int n_bands, int n_labels, int start_label,
-                           double *skew_out, double *kurt_out);
+                           double *skew_out, double *kurt_out, double *var_out);
 
 /* ---- next row f1: label raster -> polygon rings ------------------------------------------------------------------
  * Replaces the vectorisation loop of create_segments (segment_boundaries.py:59-77: per segment id a full-raster

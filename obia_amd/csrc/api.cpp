@@ -274,12 +274,12 @@ int obia_zonal_stats_f32(obia_ctx *ctx, const float *raw, const int32_t *labels,
 
 int obia_zonal_moments_f32_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                                const int32_t *bands, int n_bands, int n_labels, int start_label, const double *mean_dev,
-                               double *skew_out, double *kurt_out) {
+                               double *skew_out, double *kurt_out, double *var_out) {
     OBIA_TRY(check_ctx(ctx));
     if (!raw || !labels || !mean_dev || !skew_out || !kurt_out) { set_error("null pointer argument"); return OBIA_E_INVALID; }
     ctx->arena.reset();
     begin_timing(ctx);
-    OBIA_TRY(zonal_moments_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, mean_dev, skew_out, kurt_out));
+    OBIA_TRY(zonal_moments_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, mean_dev, skew_out, kurt_out, var_out));
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     resolve_timing(ctx);
     return OBIA_OK;
@@ -287,7 +287,7 @@ int obia_zonal_moments_f32_dev(obia_ctx *ctx, const float *raw, const int32_t *l
 
 int obia_zonal_moments_f32(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                            const int32_t *bands, int n_bands, int n_labels, int start_label, double *skew_out,
-                           double *kurt_out) {
+                           double *kurt_out, double *var_out) {
     OBIA_TRY(check_ctx(ctx));
     if (!raw || !labels || !skew_out || !kurt_out || H <= 0 || W <= 0 || C <= 0 || n_labels < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     const size_t npix = (size_t)H * W;
@@ -309,10 +309,11 @@ int obia_zonal_moments_f32(obia_ctx *ctx, const float *raw, const int32_t *label
     if (rc == OBIA_OK && hipMemcpyAsync(d_raw, raw, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
     if (rc == OBIA_OK && hipMemcpyAsync(d_lab, labels, npix * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
     if (rc == OBIA_OK) rc = obia_zonal_stats_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_cnt, d_mean, d_var, d_mn, d_mx);
-    if (rc == OBIA_OK) rc = obia_zonal_moments_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_mean, d_skew, d_kurt);
+    if (rc == OBIA_OK) rc = obia_zonal_moments_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_mean, d_skew, d_kurt, d_var);
     if (rc == OBIA_OK && n_labels > 0) {
         bool ok = hipMemcpyAsync(skew_out, d_skew, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(kurt_out, d_kurt, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+                  hipMemcpyAsync(kurt_out, d_kurt, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                  (!var_out || hipMemcpyAsync(var_out, d_var, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         if (!ok) rc = OBIA_E_HIP;
     }
     (void)hipStreamSynchronize(ctx->stream);

@@ -211,6 +211,6 @@ int zonal_stats_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int 
                     int64_t *count, double *mean, double *var, float *mn, float *mx);
 int zonal_moments_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                       const int32_t *bands_host, int n_bands, int n_labels, int start_label, const double *mean,
-                      double *skew, double *kurt);
+                      double *skew, double *kurt, double *var /* nullable: m2 written here */);
 
 }  // namespace obia

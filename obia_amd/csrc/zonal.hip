@@ -3,8 +3,9 @@
 // Replaces the per-segment loop of obia create_objects (segment_statistics.py:475-491):
 //   crop_image_to_bbox + mask_image_with_polygon (utils/utils.py:37-67)  -> "pixels of label p"
 //   calculate_spectral_stats (segment_statistics.py:143-172)            -> np.mean / np.var / np.min / np.max
-// One pass over (labels, raw raster); kernel shape described at zonal_kernel.  Sums are float64 (sum, sum of
-// squares); variance = E[x^2] - E[x]^2 in float64 meets the 1e-5 relative tolerance for uint16-range rasters.
+// One pass over (labels, raw raster); kernel shape described at zonal_kernel.  Sums are float64 and SHIFTED: every
+// (label, band) sums x - P and (x - P)^2 about a pivot P that is one of its own pixel values, so the variance
+// S2/n - (S1/n)^2 does not cancel on bright, nearly flat segments (E[x^2] - E[x]^2 lost up to all digits there: 4e6 +- 1).
 #include "slic.hpp"
 
 namespace obia {
@@ -25,6 +26,22 @@ namespace obia {
 #define ZSLOTS 64
 #endif
 constexpr int Z_MAXB = 16, Z_ROWS = ZR;
+constexpr unsigned Z_NOPIV = 0x7fc00001u;   // "no pivot yet" (a NaN pattern: a pivot is never NaN)
+
+// Pivots.  A run of one label down a lane's column sums about its OWN pivot (its first non-NaN value per band); when the
+// run closes, its sums move to the pivot of the tile's slot, at flush the slot's sums move to the global pivot of
+// (label, band).  Slot and global pivots are claimed by the first writer (compare-and-swap from Z_NOPIV), so every
+// pivot is a pixel value of the segment and each move is  S1' = S1 + n d,  S2' = S2 + d (2 S1 + n d),  d = P_old - P_new,
+// with |d| <= max - min of the segment: no term is larger than the segment's spread.
+__device__ __forceinline__ float claim_pivot(unsigned *piv, float cand) {
+    const unsigned old = atomicCAS(piv, Z_NOPIV, __float_as_uint(cand));
+    return old == Z_NOPIV ? cand : __uint_as_float(old);
+}
+__device__ __forceinline__ void move_pivot(double &s1, double &s2, double n, float from, float to) {
+    const double d = (double)from - (double)to;
+    s2 = fma(d, fma(n, d, 2.0 * s1), s2);
+    s1 = fma(n, d, s1);
+}
 
 struct BandList { int n; int identity; int b[Z_MAXB]; };   // identity: b[i] == i for every i < n
 // (the bands of a lane: 16 or 12 bytes at a 4-byte aligned address -- gfx950 loads a dwordx4 / dwordx3 from any dword address, the
@@ -77,19 +94,21 @@ __global__ __launch_bounds__(ZTW * LPP) __attribute__((amdgpu_waves_per_eu(ZW, Z
                                                          int H, int W, int C, BandList bl, int n_labels, int start_label,
                                                          unsigned *__restrict__ g_cnt, unsigned *__restrict__ g_nan,
                                                          double *__restrict__ g_sum, double *__restrict__ g_sq,
-                                                         unsigned *__restrict__ g_mn, unsigned *__restrict__ g_mx) {
+                                                         unsigned *__restrict__ g_mn, unsigned *__restrict__ g_mx,
+                                                         unsigned *__restrict__ g_piv) {
     constexpr int NBP = LPP * BPL, NT = ZTW * LPP;   // band slots of a pixel, lanes of the workgroup
     __shared__ int s_key[ZSLOTS];
     __shared__ unsigned s_cnt[ZSLOTS];
     __shared__ unsigned s_nan[ZSLOTS][NBP];
     __shared__ double s_sum[ZSLOTS][NBP], s_sq[ZSLOTS][NBP];
     __shared__ float s_mn[ZSLOTS][NBP], s_mx[ZSLOTS][NBP];   // (+inf, -inf) = nothing but NaNs so far
+    __shared__ unsigned s_piv[ZSLOTS][NBP];                  // pivot of the slot's sums (float bits), Z_NOPIV = none yet
     const int tid = threadIdx.x;
     const int nb = bl.n;
     for (int i = tid; i < ZSLOTS; i += NT) { s_key[i] = -1; s_cnt[i] = 0; }
     for (int i = tid; i < ZSLOTS * NBP; i += NT) {
         (&s_sum[0][0])[i] = 0.0; (&s_sq[0][0])[i] = 0.0; (&s_nan[0][0])[i] = 0u;
-        (&s_mn[0][0])[i] = INFINITY; (&s_mx[0][0])[i] = -INFINITY;
+        (&s_mn[0][0])[i] = INFINITY; (&s_mx[0][0])[i] = -INFINITY; (&s_piv[0][0])[i] = Z_NOPIV;
     }
     __syncthreads();
     const int tiles_x = (W + ZTW - 1) / ZTW;
@@ -125,21 +144,28 @@ __global__ __launch_bounds__(ZTW * LPP) __attribute__((amdgpu_waves_per_eu(ZW, Z
 
     int rl = -1;
     unsigned rn = 0;
-    double rs[BPL], rq[BPL];
-    float rmn[BPL], rmx[BPL];
+    bool rpiv = true;                                   // every band of the run has its pivot (a first non-NaN value)
+    double rs[BPL], rq[BPL];                            // sum (x - rp), sum (x - rp)^2 over the run's non-NaN values
+    float rmn[BPL], rmx[BPL], rp[BPL];                  // rp: the run's pivot, NaN until the band has a value
+    unsigned rnan = 0;                                  // NaN values of the run, 8 bits per band (a run is at most ZTH rows)
+    static_assert(ZTH < 256, "NaN counts of a run are packed in bytes");
 #pragma unroll
-    for (int b = 0; b < BPL; ++b) { rs[b] = 0.0; rq[b] = 0.0; rmn[b] = INFINITY; rmx[b] = -INFINITY; }
+    for (int b = 0; b < BPL; ++b) { rs[b] = 0.0; rq[b] = 0.0; rmn[b] = INFINITY; rmx[b] = -INFINITY; rp[b] = 0.0f; }
     auto close_run = [&]() {
         if (rl < 0) return;
         const int slot = find_slot(rl);
         if (slot >= 0) {
-            // no conditions on this path (it is executed by the whole wave whenever ONE lane closes a run): a run of NaNs only
-            // adds 0 and folds (+inf, -inf), a band slot past the last band collects zeros nobody reads
+            // a run of NaNs only folds (+inf, -inf); a band slot past the last band collects zeros nobody reads
             if (q == 0) atomicAdd(&s_cnt[slot], rn);
 #pragma unroll
             for (int b = 0; b < BPL; ++b) {
-                atomicAdd(&s_sum[slot][BPL * q + b], rs[b]);
-                atomicAdd(&s_sq[slot][BPL * q + b], rq[b]);
+                const unsigned nv = rn - ((rnan >> (8 * b)) & 0xffu);
+                if (nv) {
+                    double s1 = rs[b], s2 = rq[b];
+                    move_pivot(s1, s2, (double)nv, rp[b], claim_pivot(&s_piv[slot][BPL * q + b], rp[b]));
+                    atomicAdd(&s_sum[slot][BPL * q + b], s1);
+                    atomicAdd(&s_sq[slot][BPL * q + b], s2);
+                }
                 __hip_atomic_fetch_min(&s_mn[slot][BPL * q + b], rmn[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_min_f32
                 __hip_atomic_fetch_max(&s_mx[slot][BPL * q + b], rmx[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -149,8 +175,10 @@ __global__ __launch_bounds__(ZTW * LPP) __attribute__((amdgpu_waves_per_eu(ZW, Z
             for (int b = 0; b < BPL; ++b) {
                 if (b >= nbq || !(rmn[b] <= rmx[b])) continue;   // band absent, or only NaNs in this run
                 const size_t o = (size_t)rl * nb + BPL * q + b;
-                unsafeAtomicAdd(&g_sum[o], rs[b]);
-                unsafeAtomicAdd(&g_sq[o], rq[b]);
+                double s1 = rs[b], s2 = rq[b];
+                move_pivot(s1, s2, (double)(rn - ((rnan >> (8 * b)) & 0xffu)), rp[b], claim_pivot(&g_piv[o], rp[b]));
+                unsafeAtomicAdd(&g_sum[o], s1);
+                unsafeAtomicAdd(&g_sq[o], s2);
                 atomicMin(&g_mn[o], zkey(rmn[b]));
                 atomicMax(&g_mx[o], zkey(rmx[b]));
             }
@@ -198,39 +226,46 @@ __global__ __launch_bounds__(ZTW * LPP) __attribute__((amdgpu_waves_per_eu(ZW, Z
 #pragma unroll
             for (int j = 0; j < Z_ROWS; ++j) {
                 const int l = lab[half][j];
+                const float *v = val[half][j];
                 if (l != rl) {
                     close_run();
-                    rl = l; rn = 0;
+                    rl = l; rn = 0; rpiv = true; rnan = 0;
 #pragma unroll
-                    for (int b = 0; b < BPL; ++b) { rs[b] = 0.0; rq[b] = 0.0; rmn[b] = INFINITY; rmx[b] = -INFINITY; }
+                    for (int b = 0; b < BPL; ++b) {
+                        rs[b] = 0.0; rq[b] = 0.0; rmn[b] = INFINITY; rmx[b] = -INFINITY;
+                        rp[b] = v[b]; rpiv &= (v[b] == v[b]);   // the run's first values are its pivots
+                    }
                 }
                 if (l < 0) continue;
                 rn += 1;
-                const float *v = val[half][j];
-                bool clean = true;
+                bool clean = rpiv;
 #pragma unroll
                 for (int b = 0; b < BPL; ++b) clean &= (v[b] == v[b]);
                 if (clean) {   // (a band slot past the last band holds 0)
 #pragma unroll
                     for (int b = 0; b < BPL; ++b) {
-                        const double dv = (double)v[b];
+                        const double dv = (double)v[b] - (double)rp[b];
                         rs[b] += dv; rq[b] = fma(dv, dv, rq[b]);
                         rmn[b] = zmin(rmn[b], v[b]); rmx[b] = zmax(rmx[b], v[b]);
                     }
                 } else {
+                    rpiv = true;
 #pragma unroll
                     for (int b = 0; b < BPL; ++b) {
                         if (v[b] == v[b]) {
-                            const double dv = (double)v[b];
+                            if (!(rp[b] == rp[b])) rp[b] = v[b];   // the band's first value in this run
+                            const double dv = (double)v[b] - (double)rp[b];
                             rs[b] += dv; rq[b] = fma(dv, dv, rq[b]);
                             rmn[b] = zmin(rmn[b], v[b]); rmx[b] = zmax(rmx[b], v[b]);
                         } else {
+                            rnan += 1u << (8 * b);
                             // NaN pixels are dropped per band (`band[~isnan]`, segment_statistics.py:145-147): remember how
                             // many, the per-band count is (label count - NaN count).  Rare: direct atomics.
                             const int slot = find_slot(l);
                             if (slot >= 0) atomicAdd(&s_nan[slot][BPL * q + b], 1u);
                             else if (b < nbq) atomicAdd(&g_nan[(size_t)l * nb + BPL * q + b], 1u);
                         }
+                        rpiv &= (rp[b] == rp[b]);
                     }
                 }
             }
@@ -245,27 +280,32 @@ __global__ __launch_bounds__(ZTW * LPP) __attribute__((amdgpu_waves_per_eu(ZW, Z
         if (b == 0 && s_cnt[slot]) atomicAdd(&g_cnt[l], s_cnt[slot]);
         if (s_nan[slot][b]) atomicAdd(&g_nan[(size_t)l * nb + b], s_nan[slot][b]);
         if (!(s_mn[slot][b] <= s_mx[slot][b])) continue;   // only NaNs (or nothing) for this band
-        unsafeAtomicAdd(&g_sum[(size_t)l * nb + b], s_sum[slot][b]);
-        unsafeAtomicAdd(&g_sq[(size_t)l * nb + b], s_sq[slot][b]);
+        double s1 = s_sum[slot][b], s2 = s_sq[slot][b];
+        const float ps = __uint_as_float(s_piv[slot][b]);
+        move_pivot(s1, s2, (double)(s_cnt[slot] - s_nan[slot][b]), ps, claim_pivot(&g_piv[(size_t)l * nb + b], ps));
+        unsafeAtomicAdd(&g_sum[(size_t)l * nb + b], s1);
+        unsafeAtomicAdd(&g_sq[(size_t)l * nb + b], s2);
         atomicMin(&g_mn[(size_t)l * nb + b], zkey(s_mn[slot][b]));
         atomicMax(&g_mx[(size_t)l * nb + b], zkey(s_mx[slot][b]));
     }
 }
 
 __global__ void zonal_init_kernel(unsigned *g_cnt, unsigned *g_bcnt, double *g_sum, double *g_sq, unsigned *g_mn, unsigned *g_mx,
-                                  long long n_labels, int nb) {
+                                  unsigned *g_piv, long long n_labels, int nb) {
     const long long n = n_labels * nb;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         g_sum[i] = 0.0; g_sq[i] = 0.0; g_bcnt[i] = 0u; g_mn[i] = 0xffffffffu; g_mx[i] = 0u;   // g_bcnt holds NaN counts
+        g_piv[i] = Z_NOPIV;
         if (i < n_labels) g_cnt[i] = 0;
     }
 }
 
-// mean / variance divide by the number of non-NaN pixels of the band, as `band[~isnan]` does.
+// mean / variance divide by the number of non-NaN pixels of the band, as `band[~isnan]` does; the sums are about the pivot P:
+// mean = P + S1/n, variance = S2/n - (S1/n)^2.
 __global__ void zonal_finalize_kernel(const unsigned *__restrict__ g_cnt, const unsigned *__restrict__ g_bcnt,
                                       const double *__restrict__ g_sum,
                                       const double *__restrict__ g_sq, const unsigned *__restrict__ g_mn,
-                                      const unsigned *__restrict__ g_mx, long long n_labels, int nb,
+                                      const unsigned *__restrict__ g_mx, const unsigned *__restrict__ g_piv, long long n_labels, int nb,
                                       int64_t *__restrict__ count, double *__restrict__ mean, double *__restrict__ var,
                                       float *__restrict__ mn, float *__restrict__ mx) {
     const long long n = n_labels * nb;
@@ -278,7 +318,7 @@ __global__ void zonal_finalize_kernel(const unsigned *__restrict__ g_cnt, const 
         } else {
             const double m = g_sum[i] / (double)c;
             double v = g_sq[i] / (double)c - m * m;
-            mean[i] = m;
+            mean[i] = (double)__uint_as_float(g_piv[i]) + m;
             var[i] = v < 0.0 ? 0.0 : v;
             mn[i] = zunkey(g_mn[i]);
             mx[i] = zunkey(g_mx[i]);
@@ -436,12 +476,13 @@ __global__ __launch_bounds__(ZTW / 4 * NBP) __attribute__((amdgpu_waves_per_eu(Z
 __global__ void zonal_moments_finalize_kernel(const unsigned *__restrict__ g_n, const double *__restrict__ g_s2,
                                               const double *__restrict__ g_s3, const double *__restrict__ g_s4,
                                               const double *__restrict__ mean, long long n, double *__restrict__ skew,
-                                              double *__restrict__ kurt) {
+                                              double *__restrict__ kurt, double *__restrict__ var) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const unsigned c = g_n[i];
         double sk = NAN, ku = NAN;
         if (c > 0) {
             const double m2 = g_s2[i] / (double)c, m3 = g_s3[i] / (double)c, m4 = g_s4[i] / (double)c;
+            if (var) var[i] = m2;                                      // the central m2: the variance with no cancellation
             const double t = 1.1920928955078125e-07 * mean[i];      // float32 eps * mean
             if (!(m2 <= t * t)) {
                 sk = m3 / (m2 * sqrt(m2));
@@ -454,7 +495,7 @@ __global__ void zonal_moments_finalize_kernel(const unsigned *__restrict__ g_n, 
 
 int zonal_moments_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                       const int32_t *bands_host, int n_bands, int n_labels, int start_label, const double *mean,
-                      double *skew, double *kurt) {
+                      double *skew, double *kurt, double *var) {
     ScopedSpan span(ctx, T_ZONAL);
     if (H <= 0 || W <= 0 || C <= 0 || n_labels < 0) { set_error("bad zonal_moments shape"); return OBIA_E_INVALID; }
     BandList bl;
@@ -504,7 +545,7 @@ int zonal_moments_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, in
     int ib = cdiv((long long)nlb, 256);
     if (ib > 4096) ib = 4096;
     hipLaunchKernelGGL(zonal_moments_finalize_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_n, g_s2, g_s3, g_s4, mean,
-                       (long long)nlb, skew, kurt);
+                       (long long)nlb, skew, kurt, var);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
@@ -536,16 +577,16 @@ int zonal_stats_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int 
     const size_t nl = (size_t)n_labels, nlb = nl * bl.n;
     unsigned *g_cnt = A.get<unsigned>(nl), *g_bcnt = A.get<unsigned>(nlb);
     double *g_sum = A.get<double>(nlb), *g_sq = A.get<double>(nlb);
-    unsigned *g_mn = A.get<unsigned>(nlb), *g_mx = A.get<unsigned>(nlb);
-    if (!g_cnt || !g_bcnt || !g_sum || !g_sq || !g_mn || !g_mx) return OBIA_E_NOMEM;
+    unsigned *g_mn = A.get<unsigned>(nlb), *g_mx = A.get<unsigned>(nlb), *g_piv = A.get<unsigned>(nlb);
+    if (!g_cnt || !g_bcnt || !g_sum || !g_sq || !g_mn || !g_mx || !g_piv) return OBIA_E_NOMEM;
     int ib = cdiv((long long)nlb, 256);
     if (ib > 4096) ib = 4096;
-    hipLaunchKernelGGL(zonal_init_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx, (long long)n_labels, bl.n);
+    hipLaunchKernelGGL(zonal_init_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx, g_piv, (long long)n_labels, bl.n);
     const int tiles = cdiv(W, ZTW) * cdiv(H, ZTH);
     const bool ident = bl.identity && bl.n == C;
 #define LAUNCH_ZONAL_MODE(LPPV, BPLV, MODEV)                                                                        \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(zonal_kernel<LPPV, BPLV, MODEV>), dim3(tiles), dim3(ZTW * LPPV), 0, ctx->stream, raw, labels, H, W, C, \
-                       bl, n_labels, start_label, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx)
+                       bl, n_labels, start_label, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx, g_piv)
 #define LAUNCH_ZONAL(LPPV)                                                                                          \
     do {                                                                                                            \
         if (ident && bl.n == 4 * LPPV) LAUNCH_ZONAL_MODE(LPPV, 4, 0);                                               \
@@ -563,7 +604,7 @@ int zonal_stats_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int 
     else LAUNCH_ZONAL(4);
 #undef LAUNCH_ZONAL
 #undef LAUNCH_ZONAL_MODE
-    hipLaunchKernelGGL(zonal_finalize_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx,
+    hipLaunchKernelGGL(zonal_finalize_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx, g_piv,
                        (long long)n_labels, bl.n, count, mean, var, mn, mx);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;

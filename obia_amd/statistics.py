@@ -33,7 +33,8 @@ def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None,
 
     ``moments=True`` adds ``skewness`` and ``kurtosis`` (N,B) float64: scipy.stats.skew / kurtosis with their defaults
     (segment_statistics.py:173-175), computed by a second pass with the per-label means as pivots
-    (obia_zonal_moments_f32_dev).
+    (obia_zonal_moments_f32_dev); ``variance`` is then that pass's central m2.  The first pass alone sums about a pivot
+    pixel of each segment (zonal.hip), so both stay accurate on bright, nearly flat segments.
     """
     lib = _lib.load()
     if _is_torch(raw):
@@ -71,7 +72,7 @@ def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None,
             kurt = torch.full_like(mean, float("nan"))
             _lib.check(lib.obia_zonal_moments_f32_dev(c.handle, r.data_ptr(), lab.data_ptr(), H, W, C, _lib.np_ptr(barr), B,
                                                       n_labels, int(start_label), mean.data_ptr(), skew.data_ptr(),
-                                                      kurt.data_ptr()))
+                                                      kurt.data_ptr(), var.data_ptr()))
             out["skewness"], out["kurtosis"] = skew, kurt
         return out
     r = np.ascontiguousarray(raw, dtype=np.float32)
@@ -104,7 +105,8 @@ def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None,
         skew = np.full((n_labels, B), np.nan, np.float64)
         kurt = np.full((n_labels, B), np.nan, np.float64)
         _lib.check(lib.obia_zonal_moments_f32(c.handle, _lib.np_ptr(r), _lib.np_ptr(lab), H, W, C, _lib.np_ptr(barr), B,
-                                              n_labels, int(start_label), _lib.np_ptr(skew), _lib.np_ptr(kurt)))
+                                              n_labels, int(start_label), _lib.np_ptr(skew), _lib.np_ptr(kurt),
+                                              _lib.np_ptr(var)))
         out["skewness"], out["kurtosis"] = skew, kurt
     return out
 
