@@ -339,8 +339,8 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
  * 6 = maskSLIC spatial-only pre-pass sweeps (ms), 7 = pixels actually processed by the launches of 0
  * (sum; tiles skipped by exit_on_fixed_point are not counted), 8 = the same for the pre-pass launches,
  * 9 = pixels of the launches of 0 that also stored their labels (only the last sweep of a batch does),
- * 10 / 11 = time during which at least one colour / pre-pass sweep was running (equals 0 / 6 unless the batch's problems run
- * as groups on side streams, OBIA_SWEEP_GROUPS).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0 and
+ * 10 / 11 = time during which at least one colour / pre-pass sweep was running (equals 0 / 6: the sweeps run one after the
+ * other).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0 and
  * 6 are sums of the kernels' own start-to-end times, as a rocprofv3 kernel trace reports them.
  * 12 = batches of the call whose sweeps ran a second time with every sweep storing its labels (a valid pixel that no window
  * reached keeps the label of the sweep before: DESIGN.md 3.2 item 5) -- counted whether profiling is on or not.

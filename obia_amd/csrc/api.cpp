@@ -73,7 +73,16 @@ int slic_single(obia_ctx *ctx, const float *img, int H, int W, int C, const uint
         set_error("mask is empty: nothing to segment");
         return OBIA_E_EMPTY;
     }
+    const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
     OBIA_TRY(slic_run_sweeps(ctx, b));
+    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    bool repeat = false;
+    OBIA_TRY(slic_sweeps_settle(ctx, &repeat));
+    if (repeat) {
+        A.rewind(sweeps_mk);
+        b.d_mask4 = nullptr;   // (the sweeps packed it above the mark)
+        OBIA_TRY(slic_rerun_storing(ctx, b));
+    }
     return OBIA_OK;
 }
 

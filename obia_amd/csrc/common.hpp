@@ -58,8 +58,8 @@ struct Timing {
     double assign_store_px = 0;             // ... of the colour sweeps that also stored their labels (the last sweep of a batch)
     int sweeps = 0;
     int batch_repeats = 0;                  // batches whose sweeps ran again with every sweep storing its labels (a valid pixel no window reached)
-    // time during which at least one colour (pre-pass) sweep was running: equals assign_ms (prepass_ms) when the sweeps run one
-    // after the other, less when groups of problems run side by side (slic_run_sweeps)
+    // time during which at least one colour (pre-pass) sweep was running: the sweeps run one after the other, so this equals
+    // assign_ms (prepass_ms)
     double assign_busy_ms = 0, prepass_busy_ms = 0;
 };
 
@@ -73,7 +73,7 @@ struct obia_ctx {
     void *pinned = nullptr;          // small pinned host staging buffer for scalar read-backs
     size_t pinned_bytes = 0;
     unsigned long long *defer_buf = nullptr;   // pinned landing area of a read-back that is looked at after a LATER synchronisation
-    bool defer_pending = false;                // (slic_run_sweeps with defer: the orphan flag and pixel counters of the sweeps)
+    bool defer_pending = false;                // (slic_run_sweeps: the orphan flag and pixel counters of the sweeps)
     // visited map of the connectivity stage's component walks (cc.hip): every walk clears its own marks, so the map is all zero
     // between calls and is cleared as a whole only when it grows or after a call that did not complete (cc_visited_dirty)
     int32_t *cc_visited = nullptr;
@@ -88,12 +88,10 @@ struct obia_ctx {
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;
     size_t events_used = 0;
-    // side streams of the sweep loop (slic_run_sweeps: groups of problems run their prep / sweep chains side by side, so
-    // that one group's sweep fills the ramp, the tail and the launch gaps of the others'); created on first use
-    static constexpr int MAX_SIDE = 3;
-    hipStream_t side[MAX_SIDE] = {nullptr, nullptr, nullptr};
-    hipEvent_t fork_ev = nullptr, join_ev[MAX_SIDE] = {nullptr, nullptr, nullptr};
-    hipEvent_t aux_fork = nullptr, aux_join = nullptr;   // the tiler's white feature pass beside the black sweeps (tiling.hip)
+    // side stream of the tiler's white feature pass beside the black sweeps (tiling.hip) and its fork / join events; created on
+    // first use
+    hipStream_t side = nullptr;
+    hipEvent_t aux_fork = nullptr, aux_join = nullptr;
 };
 
 namespace obia {
@@ -122,7 +120,7 @@ int read_back(obia_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
 // (pageable, short-lived) buffer is free at once; the ring is recycled at the next read_back (everything queued before it
 // has then executed).
 int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
-int side_streams(obia_ctx *ctx, int n);   // makes sure side[0..n) and their events exist
+int side_stream(obia_ctx *ctx);   // makes sure `side` and its events exist
 // Developer aid (OBIA_DEBUG_SYNC=1): synchronise the stream and report the stage on stderr, so that an asynchronous GPU fault
 // is pinned on the stage that caused it.  A no-op otherwise.
 void debug_sync(obia_ctx *ctx, const char *stage);

@@ -117,15 +117,10 @@ ScopedSpan::~ScopedSpan() {
     if (on) (void)hipEventRecord(ctx->spans[idx].b, ctx->stream);
 }
 
-int side_streams(obia_ctx *ctx, int n) {
-    if (n > obia_ctx::MAX_SIDE) n = obia_ctx::MAX_SIDE;
-    if (!ctx->fork_ev) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
+int side_stream(obia_ctx *ctx) {
     if (!ctx->aux_fork) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->aux_fork, hipEventDisableTiming));
     if (!ctx->aux_join) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->aux_join, hipEventDisableTiming));
-    for (int i = 0; i < n; ++i) {
-        if (!ctx->side[i]) OBIA_HIP_TRY(hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking));
-        if (!ctx->join_ev[i]) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->join_ev[i], hipEventDisableTiming));
-    }
+    if (!ctx->side) OBIA_HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     return OBIA_OK;
 }
 
@@ -283,11 +278,7 @@ void obia_destroy(obia_ctx *ctx) {
     if (ctx->defer_buf) (void)hipHostFree(ctx->defer_buf);
     if (ctx->cc_visited) (void)hipFree(ctx->cc_visited);
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-    for (int i = 0; i < obia_ctx::MAX_SIDE; ++i) {
-        if (ctx->side[i]) (void)hipStreamDestroy(ctx->side[i]);
-        if (ctx->join_ev[i]) (void)hipEventDestroy(ctx->join_ev[i]);
-    }
-    if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
+    if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
     if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);

@@ -357,8 +357,6 @@ __global__ __launch_bounds__(256) void features_planes_kernel(const float *__res
 // 5.1 -> 4.8 at 1, none at 10).  Lab features span ~100 units where normalised bands span 1: a three-band raster at compactness
 // 10 is as colour-dominated as eight bands at 0.1 (`bench.py --bands 3`: 462 us per sweep launch without the bound).
 bool slic_use_colour_bound(float ratio, bool to_lab) {
-    static const char *env = std::getenv("OBIA_COLOUR_BOUND");   // developer switch (A/B timing)
-    if (env) return env[0] == '1';
     return ratio * (to_lab ? 100.0f : 1.0f) >= 2.0f;
 }
 
@@ -579,7 +577,6 @@ int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *non
 
 float slic_prescale(float ratio, int normalize, int to_lab, bool slic_zero) {
     if (!normalize || to_lab || slic_zero || !(ratio > 0.0f) || !(ratio < 3.0e38f)) return 1.0f;
-    if (const char *e = std::getenv("OBIA_NO_PRESCALE"); e && atoi(e) != 0) return 1.0f;   // developer switch (A/B timing; the labels are the same either way)
     int e = 0;
     (void)std::frexp((double)ratio, &e);   // the largest normalised feature is 1 * ratio: the rule of slic_features_finish
     int s = 29 - e;

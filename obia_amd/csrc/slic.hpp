@@ -149,7 +149,7 @@ int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Hs,
 // every tie the same, and the sweeps convert a feature to fixed point by truncation alone (SlicBatch::fscale, taken from the largest
 // |feature| as before, comes out as 1).  1 when the range is not known beforehand (no normalisation, Lab) or SLIC-zero is on.
 float slic_prescale(float ratio, int normalize, int to_lab, bool slic_zero);
-// Does a batch with this image ratio (1 / compactness; to_lab: the features are Lab, ~100 units wide) use the colour-box bound?  (OBIA_COLOUR_BOUND=0/1 overrides.)
+// Does a batch with this image ratio (1 / compactness; to_lab: the features are Lab, ~100 units wide) use the colour-box bound?
 bool slic_use_colour_bound(float ratio, bool to_lab = false);
 
 // Seeds (grid or masked grid), fills K / steps / bins in b.probs, uploads descriptors.
@@ -163,15 +163,16 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
 // valid (unmasked) pixels per problem: mask.sum() (tiling.py:133, slic_superpixels.py:322)
 int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid);
 
-// Runs the sweeps; labels (pre-connectivity) land in b.d_labels.
-// mode 0: complete when it returns (one read-back: the orphan flag -- a valid pixel no window reached makes the batch run again with
-//         every sweep storing its labels -- and the profiling counters).
-// mode 1: the read-back is only QUEUED (round 4: one host round trip less per batch).  The caller synchronises the stream for its own
-//         reasons afterwards (the connectivity stage reads its counters back) and then calls slic_sweeps_settle(); when that reports
-//         `repeat`, the labels are not final: the caller runs mode 2 and whatever it had computed from the labels again.
-// mode 2: the repeat itself (every sweep stores its labels), complete when it returns.
-int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode = 0);
-int slic_sweeps_settle(obia_ctx *ctx, SlicBatch &b, bool *repeat);
+// Runs the sweeps; labels (pre-connectivity) land in b.d_labels.  Three steps, the same for every caller:
+// slic_run_sweeps queues the sweeps and the read-back of their orphan flag (a valid pixel no window reached) and pixel counters, and
+// returns without a host synchronisation.  Once the caller has synchronised the stream for its own reasons (the tiler: the
+// connectivity stage reads its counters back), slic_sweeps_settle looks at the flag.  When it reports `repeat`, the labels are not
+// final: the caller rewinds the arena to a mark taken before slic_run_sweeps (b.d_mask4 as it was then: the sweeps pack the mask
+// above the mark when it was null), calls slic_rerun_storing -- every sweep stores its labels; complete when it returns -- and
+// computes again whatever it had computed from the labels.
+int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b);
+int slic_sweeps_settle(obia_ctx *ctx, bool *repeat);
+int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b);
 
 // Connectivity enforcement on a batch of dense label maps laid out back to back (pix_off); labels come
 // out consecutive over the whole batch, in problem order then raster order of each component's first pixel.

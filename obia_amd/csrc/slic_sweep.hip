@@ -74,9 +74,6 @@ constexpr int PPT = 4;          // pixels per lane (vertical strip)
 #ifndef LEAN_WAVES
 #define LEAN_WAVES 8
 #endif
-#ifndef OBIA_SWEEP_GROUPS_DEFAULT
-#define OBIA_SWEEP_GROUPS_DEFAULT 1
-#endif
 #ifndef ASSIGN_WAVES
 #define ASSIGN_WAVES 6
 #endif
@@ -510,7 +507,7 @@ __device__ __forceinline__ void slic_assign_body(
 #define OBIA_XCD_GROUP 2
 #endif
     constexpr int XG = OBIA_XCD_GROUP;   // consecutive tiles that share an XCD
-    // (a launch covers the tiles [tile_base, total_tiles_all) of the batch: one group of problems, see slic_run_sweeps)
+    // (a launch covers the tiles [tile_base, total_tiles_all) of the batch; slic_run_sweeps launches them all: tile_base = 0)
     const int gtile = tile_base + (((int)(blockIdx.x >> 3) / XG) * 8 + (int)(blockIdx.x & 7)) * XG + (int)(blockIdx.x >> 3) % XG;
     if (gtile >= total_tiles_all) return;
     // the tile's list state (scalar loads that depend on the block index alone: in flight beside the problem descriptor)
@@ -1342,10 +1339,6 @@ __global__ __launch_bounds__(256) void slic_maxdist_kernel(const SlicProblem *__
         }
 }
 
-// A group of consecutive problems of the batch whose prep / sweep chain runs on its own stream (slic_run_sweeps): the
-// centroids [k0, k1), bins [cell0, cell1) and tiles [tile0, tile1) of the batch's tables.
-struct SweepGroup { int k0, k1, cell0, cell1, tile0, tile1; long long pix0, pix1; hipStream_t stream; int p0, p1, kmax; };   // [p0, p1): the group's problems, kmax: their largest K
-
 struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; null when the option is off)
     int *bin_stamp = nullptr, *tile_lp = nullptr, *cache_k = nullptr;
     unsigned long long *cache_q = nullptr;
@@ -1354,18 +1347,18 @@ struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; 
 template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
-                          const KernelSpan &span, const SweepGroup &sg, const int *head_cur) {
+                          const KernelSpan &span, const int *head_cur) {
     constexpr int XGH = OBIA_XCD_GROUP;
-    if (sg.tile1 <= sg.tile0) return;
-    dim3 grid(8 * XGH * (unsigned)((sg.tile1 - sg.tile0 + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
+    const int ntiles = (int)b.total_tiles_all;
+    dim3 grid(8 * XGH * (unsigned)((ntiles + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
     const int RQ = acc_record_qwords(CP);
     int tpp = b.probs.empty() ? 0 : b.probs[0].tiles_x * b.probs[0].tiles_y;   // tiles per problem if all problems agree, else 0
     for (auto &P : b.probs) if (P.tiles_x * P.tiles_y != tpp) tpp = 0;
 #define LAUNCH_K_(...)                                                                                               \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, sg.stream, span.a, span.b, 0, b.d_probs, b.d_feat,   \
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, b.d_probs, b.d_feat,   \
                           b.d_mask, b.d_mask4, b.d_cent, head_cur, b.d_labels, b.d_acc, RQ, accumulate, store_labels, b.start_label,      \
                           (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
-                          b.d_tile_prob, sg.tile1, orphan_flag, tpp, b.d_fbox, sg.tile0, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req)
+                          b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, 0, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req)
     // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
     // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
     const int pad = CP - b.C;
@@ -1457,15 +1450,26 @@ __global__ void fill_i32_kernel(int32_t *p, long long n, int32_t v) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = v;
 }
 
-int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode) {
-    auto fill_labels = [&]() {   // nearest[:] = start_label - 1, once (before the loop of _slic_cython)
-        long long n = b.total_pix;
-        int blocks = cdiv(n, 256 * 8);
-        if (blocks > 65535) blocks = 65535;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, n, b.start_label - 1);
-    };
-    // (nearest[:] = start_label - 1 is written further down, and only when some pixel can keep that value)
+// nearest[:] = start_label - 1 (before the loop of _slic_cython)
+static void fill_labels(obia_ctx *ctx, SlicBatch &b) {
+    const long long n = b.total_pix;
+    int blocks = cdiv(n, 256 * 8);
+    if (blocks > 65535) blocks = 65535;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, n, b.start_label - 1);
+}
+
+// h: the 513 slots of the sweeps' pixel counters (slic_run_sweeps); the profiling totals of the batch
+static void fold_counters(obia_ctx *ctx, const unsigned long long *h) {
+    if (ctx->profiling)
+        for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
+}
+
+// Queues every sweep of the batch on the context's stream.  repeat: the batch runs again from the seeds with every sweep storing
+// its labels (slic_rerun_storing).  *d_px_out: the pixel counters of the sweeps, 256 slots each for the colour and the pre-pass
+// sweeps, and in slot 512 the orphan flag of the sweeps that do not store their labels; null when the batch has no sweep.
+static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long long **d_px_out) {
+    *d_px_out = nullptr;
     if (std::getenv("OBIA_DEBUG_SYNC"))
         for (size_t p = 0; p < b.probs.size(); ++p) {
             const SlicProblem &P = b.probs[p];
@@ -1473,15 +1477,13 @@ int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode) {
                     p, P.H, P.W, P.K, P.sy, P.sx, P.ncy, P.ncx, P.cell_off, P.cent_off, P.tiles_y, P.tiles_x, P.tile_off, P.n_valid,
                     b.total_cent, b.total_cells, b.total_tiles_all);
         }
-    if (b.total_tiles <= 0 || b.max_iter <= 0) { fill_labels(); return OBIA_OK; }   // no sweep: every pixel keeps the fill value
+    if (b.total_tiles <= 0 || b.max_iter <= 0) { fill_labels(ctx, b); return OBIA_OK; }   // no sweep: every pixel keeps the fill value
     // the sweep addresses a footprint's pixels as a 64-bit wave-uniform base plus a 32-bit lane offset (16 rows x W x 64 B)
     for (auto &P : b.probs)
         if (P.W >= (1 << 22)) { set_error("rasters / tile windows wider than 4194303 pixels are not supported (got %d)", P.W); return OBIA_E_UNSUPPORTED; }
     const int passes = b.masked ? 2 : 1;   // maskSLIC: spatial-only pre-pass first (slic_superpixels.py:310-314)
     const int RQ = acc_record_qwords(b.CP);
     Arena &A = ctx->arena;
-    // pixel counters (profiling): 256 slots each for the colour sweeps and the pre-pass sweeps, summed on the host;
-    // slot 512: the orphan flag of the sweeps that do not store their labels
     unsigned long long *d_px = A.get<unsigned long long>(513);
     if (!d_px) return OBIA_E_NOMEM;
     int *d_orphan = reinterpret_cast<int *>(d_px + 512);
@@ -1505,8 +1507,8 @@ int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode) {
         b.d_ref = A.get<float>((size_t)b.total_cent * 2);
         if (!b.d_tl_k || !b.d_tl_fp || !b.d_tl_meta || !b.d_tl_req || !b.d_ref) return OBIA_E_NOMEM;
     }
-    int maxh_z = 1;
-    for (auto &P : b.probs) if (P.H > maxh_z) maxh_z = P.H;
+    int maxh_z = 1, kmax = 1;
+    for (auto &P : b.probs) { if (P.H > maxh_z) maxh_z = P.H; if (P.K > kmax) kmax = P.K; }
     if (b.masked && b.d_mask && !b.d_mask4) {   // the packed mask of the sweeps (problems whose mask hides nothing never read it); the
                                                 // tiler's mask kernel writes it on the way (tiling.hip: tile_mask_kernel<true>)
         b.d_mask4 = A.get<unsigned>((size_t)b.total_m4);
@@ -1517,118 +1519,71 @@ int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode) {
     }
     if (maxh_z > 4096) maxh_z = 4096;
 
-    // Groups of problems.  The sweeps of ONE launch end with a tail (the last workgroups run on a half-empty chip), the next
-    // launch starts with a ramp (every workgroup stages its candidates before anyone computes), and between them sit two launch
-    // gaps and the small prep kernel: ~25 us per iteration that a white tile row (4 tiles, 130-us sweeps) cannot hide.  The
-    // problems of a batch never exchange anything during the sweeps, so consecutive problems are dealt into groups whose
-    // prep -> sweep chains CAN run on streams of their own (OBIA_SWEEP_GROUPS=2..4): one group's sweep fills the bubbles of the
-    // others'.  Same kernels, same arithmetic, same integer accumulators per problem: the labels do not depend on the grouping
-    // (tests/test_gpu_sweep_groups.py).  Measured on the headline workload: 2 groups +2 % (5715-5724 -> 5824-5858 Mpixel/s), 4
-    // groups -5 %: kernels that share the chip slow each other down by most of what the hidden bubbles gain (the union of the
-    // colour sweeps' run time grows from 19.3 to 20.5 ms per step), and the per-launch durations no longer mean anything -- so
-    // the default is ONE group, the option stays for batches of many small problems.
-    // Always one group when a step of the loop touches the whole batch (SLIC-zero's max-distance pass) or in the debug mode.
-    std::vector<SweepGroup> groups;
-    {
-        const char *env_groups = std::getenv("OBIA_SWEEP_GROUPS");   // (read per batch: the tests switch it inside one process)
-        int ng = (env_groups && atoi(env_groups) > 0) ? atoi(env_groups) : OBIA_SWEEP_GROUPS_DEFAULT;
-        if (ng > 1 + obia_ctx::MAX_SIDE) ng = 1 + obia_ctx::MAX_SIDE;
-        if (ng > b.nprob) ng = b.nprob;
-        if (b.slic_zero || std::getenv("OBIA_DEBUG_SYNC")) ng = 1;
-        if (ng < 1) ng = 1;
-        if (ng > 1) OBIA_TRY(side_streams(ctx, ng - 1));
-        // consecutive problems, balanced by tiles (the sweep's unit of work): group g starts at the first problem whose first tile
-        // lies at or beyond g / ng of the batch's tiles
-        std::vector<int> cut(1, 0);
-        for (int g = 1; g < ng; ++g) {
-            const long long want = b.total_tiles_all * (long long)g / ng;
-            int p = cut.back();
-            while (p < b.nprob && b.probs[p].tile_off < want) ++p;
-            if (p > cut.back() && p < b.nprob) cut.push_back(p);
-        }
-        cut.push_back(b.nprob);
-        for (size_t g = 0; g + 1 < cut.size(); ++g) {
-            const SlicProblem &P0 = b.probs[cut[g]];
-            const bool last = cut[g + 1] >= b.nprob;
-            SweepGroup sg;
-            sg.k0 = P0.cent_off;   sg.k1 = last ? b.total_cent : b.probs[cut[g + 1]].cent_off;
-            sg.cell0 = P0.cell_off; sg.cell1 = last ? b.total_cells : b.probs[cut[g + 1]].cell_off;
-            sg.tile0 = P0.tile_off; sg.tile1 = last ? (int)b.total_tiles_all : b.probs[cut[g + 1]].tile_off;
-            sg.pix0 = P0.pix_off;   sg.pix1 = last ? b.total_pix : b.probs[cut[g + 1]].pix_off;
-            sg.stream = g == 0 ? ctx->stream : ctx->side[g - 1];
-            sg.p0 = cut[g]; sg.p1 = cut[g + 1]; sg.kmax = 1;
-            for (int p = sg.p0; p < sg.p1; ++p) if (b.probs[p].K > sg.kmax) sg.kmax = b.probs[p].K;
-            groups.push_back(sg);
-        }
+    // store_all = false: only the very last sweep stores its labels (the others' labels are dead stores unless a valid pixel is
+    // reached by no window -- see the label stage of the sweep); true: every sweep stores, the reference's literal behaviour,
+    // needed by the fixed-point replay (labels "already in place"), by SLIC-zero (its max-colour-distance pass reads the last
+    // assignment) and by the repeat.
+    const bool store_all = repeat || b.exit_on_fixed_point || b.slic_zero;
+    // The fill value survives in exactly one kind of pixel: a valid one that no window reached ("orphan").  When only the last sweep
+    // stores, such a pixel raises the flag and the caller repeats the batch (slic_sweeps_settle) -- unless the batch has ONE sweep in
+    // all, where the fill value is what the reference keeps.  Every other pixel is written by the last sweep (masked ones included):
+    // the 1.2 GB fill of a bench batch is skipped on the common path.
+    if (store_all || passes * b.max_iter <= 1) {
+        fill_labels(ctx, b);
+        debug_sync(ctx, "sweeps: label fill");
     }
-
-    // All sweeps of the batch.  store_all = false: only the very last sweep stores its labels (the others' labels are dead
-    // stores unless a valid pixel is reached by no window -- see the label stage of the sweep); true: every sweep stores, the
-    // reference's literal behaviour, needed by the fixed-point replay (labels "already in place") and by SLIC-zero (its
-    // max-colour-distance pass reads the last assignment).
-    auto run_all = [&](bool store_all) -> int {
-        OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
-        OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
-        // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
-        OBIA_HIP_TRY(hipMemsetAsync(b.d_tl_meta, 0xff, sizeof(int) * 3 * (size_t)b.total_tiles_all, ctx->stream));
-        debug_sync(ctx, "sweeps: memsets");
-        if (groups.size() > 1) {   // fork: the side streams start after everything queued on the context's stream so far
-            OBIA_HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
-            for (size_t g = 1; g < groups.size(); ++g) OBIA_HIP_TRY(hipStreamWaitEvent(groups[g].stream, ctx->fork_ev, 0));
+    if (repeat) OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
+    const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
+    OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
+    OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
+    // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
+    OBIA_HIP_TRY(hipMemsetAsync(b.d_tl_meta, 0xff, sizeof(int) * 3 * (size_t)b.total_tiles_all, ctx->stream));
+    debug_sync(ctx, "sweeps: memsets");
+    bool first = true;
+    int sweep_no = 0;
+    for (int pass = 0; pass < passes; ++pass) {
+        const int ignore_color = (b.masked && pass == 0) ? 1 : 0;
+        const bool last_pass = (pass == passes - 1);
+        if (pass > 0 && store_all) {
+            // the main pass is a second call of _slic_cython (slic_superpixels.py:310-318): `nearest` starts from the fill
+            // value again, a pixel no window reaches in its first sweep does not inherit a pre-pass label.  (Only when the
+            // pre-pass stored labels at all: otherwise the fill of the batch's start is still in place.)
+            fill_labels(ctx, b);
+            // (exit_on_fixed_point: no tile may replay "labels already in place" across the refill -- every tile is evaluated
+            // by the first sweep of the main pass)
+            if (fp.tile_lp) OBIA_HIP_TRY(hipMemsetAsync(fp.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all, ctx->stream));
         }
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const SweepGroup &sg = groups[gi];
-        bool first = true;
-        int sweep_no = 0;
-        for (int pass = 0; pass < passes; ++pass) {
-            const int ignore_color = (b.masked && pass == 0) ? 1 : 0;
-            const bool last_pass = (pass == passes - 1);
-            if (pass > 0 && store_all && sg.pix1 > sg.pix0) {
-                // the main pass is a second call of _slic_cython (slic_superpixels.py:310-318): `nearest` starts from the fill
-                // value again, a pixel no window reaches in its first sweep does not inherit a pre-pass label.  (Only when the
-                // pre-pass stored labels at all: otherwise the fill of the batch's start is still in place.)
-                const long long n = sg.pix1 - sg.pix0;
-                int blocks = cdiv(n, 256 * 8);
-                if (blocks > 65535) blocks = 65535;
-                hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, sg.stream, b.d_labels + sg.pix0, n, b.start_label - 1);
-                // (exit_on_fixed_point: no tile may replay "labels already in place" across the refill -- every tile of the group
-                // is evaluated by the first sweep of the main pass)
-                if (fp.tile_lp && sg.tile1 > sg.tile0)
-                    OBIA_HIP_TRY(hipMemsetAsync(fp.tile_lp + sg.tile0, 0, sizeof(int) * (size_t)(sg.tile1 - sg.tile0), sg.stream));
-            }
-            for (int it = 0; it < b.max_iter; ++it) {
-                int *head_cur = b.d_head + (size_t)(sweep_no & 1) * b.total_cells;
-                int *head_nxt = b.d_head + (size_t)((sweep_no + 1) & 1) * b.total_cells;
-                ++sweep_no;   // sweep ids start at 1
-                // SLIC-zero: the per-cluster colour scale restarts at 1 with the colour pass and is carried afterwards
-                const int zmode = (b.slic_zero && !ignore_color) ? (it == 0 ? 2 : 1) : 0;
-                const long long nk = sg.k1 > sg.k0 ? sg.k1 - sg.k0 : 1;   // (at least one block: it also resets the group's bins)
-                const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
+        for (int it = 0; it < b.max_iter; ++it) {
+            int *head_cur = b.d_head + (size_t)(sweep_no & 1) * b.total_cells;
+            int *head_nxt = b.d_head + (size_t)((sweep_no + 1) & 1) * b.total_cells;
+            ++sweep_no;   // sweep ids start at 1
+            // SLIC-zero: the per-cluster colour scale restarts at 1 with the colour pass and is carried afterwards
+            const int zmode = (b.slic_zero && !ignore_color) ? (it == 0 ? 2 : 1) : 0;
 #define LAUNCH_PREP_LANE(CPV)                                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), dim3(cdiv(sg.kmax, 64), sg.p1 > sg.p0 ? sg.p1 - sg.p0 : 1), dim3(64), 0, \
-                       sg.stream, b.d_probs, sg.p1 > sg.p0 ? sg.p0 : 0, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent,  \
-                       head_cur, head_nxt, sg.cell1, fp.bin_stamp, sweep_no, sg.cell0, b.d_ref, b.d_tl_req)
-                if (!prep_grouped) {
-                    switch (b.CP) {
-                        case 4: LAUNCH_PREP_LANE(4); break;
-                        case 8: LAUNCH_PREP_LANE(8); break;
-                        case 12: LAUNCH_PREP_LANE(12); break;
-                        default: LAUNCH_PREP_LANE(16); break;
-                    }
-                } else if (RQ == 16)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<16>), dim3(cdiv(nk * 16, 256)), dim3(256), 0,
-                                       sg.stream, b.d_probs, b.d_cent_prob, sg.k1, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
-                                       1.0 / b.fscale, b.d_cent, head_cur, head_nxt, sg.cell1, fp.bin_stamp, sweep_no, sg.k0, sg.cell0, b.d_ref, b.d_tl_req);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<32>), dim3(cdiv(nk * 32, 256)), dim3(256), 0,
-                                       sg.stream, b.d_probs, b.d_cent_prob, sg.k1, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
-                                       1.0 / b.fscale, b.d_cent, head_cur, head_nxt, sg.cell1, fp.bin_stamp, sweep_no, sg.k0, sg.cell0, b.d_ref, b.d_tl_req);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), dim3(cdiv(kmax, 64), b.nprob), dim3(64), 0, ctx->stream, \
+                       b.d_probs, 0, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
+                       b.total_cells, fp.bin_stamp, sweep_no, 0, b.d_ref, b.d_tl_req)
+            if (!prep_grouped) {
+                switch (b.CP) {
+                    case 4: LAUNCH_PREP_LANE(4); break;
+                    case 8: LAUNCH_PREP_LANE(8); break;
+                    case 12: LAUNCH_PREP_LANE(12); break;
+                    default: LAUNCH_PREP_LANE(16); break;
+                }
+            } else if (RQ == 16)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<16>), dim3(cdiv(b.total_cent * 16LL, 256)), dim3(256), 0,
+                                   ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
+                                   1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<32>), dim3(cdiv(b.total_cent * 32LL, 256)), dim3(256), 0,
+                                   ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
+                                   1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
 #undef LAUNCH_PREP_LANE
-                b.d_head_cur = head_cur;
-                debug_sync(ctx, "sweeps: prep");
-                first = false;
-                if (zmode == 1) {   // the centroids just moved: raise max_dist_color from the assignment of the last sweep
-                    dim3 zg(maxh_z, b.nprob);
+            b.d_head_cur = head_cur;
+            debug_sync(ctx, "sweeps: prep");
+            first = false;
+            if (zmode == 1) {   // the centroids just moved: raise max_dist_color from the assignment of the last sweep
+                dim3 zg(maxh_z, b.nprob);
 #define LAUNCH_MAXDIST(CPV)                                                                                           \
     do {                                                                                                              \
         if (b.masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_maxdist_kernel<CPV, true>), zg, dim3(256), 0, ctx->stream, b.d_probs, \
@@ -1636,99 +1591,75 @@ int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b, int mode) {
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_maxdist_kernel<CPV, false>), zg, dim3(256), 0, ctx->stream, b.d_probs, \
                                 b.d_feat, b.d_mask, b.d_labels, b.d_cent, b.start_label, b.C);                     \
     } while (0)
-                    switch (b.CP) {
-                        case 4: LAUNCH_MAXDIST(4); break;
-                        case 8: LAUNCH_MAXDIST(8); break;
-                        case 12: LAUNCH_MAXDIST(12); break;
-                        default: LAUNCH_MAXDIST(16); break;
-                    }
+                switch (b.CP) {
+                    case 4: LAUNCH_MAXDIST(4); break;
+                    case 8: LAUNCH_MAXDIST(8); break;
+                    case 12: LAUNCH_MAXDIST(12); break;
+                    default: LAUNCH_MAXDIST(16); break;
+                }
 #undef LAUNCH_MAXDIST
-                }
-                // the update after the very last sweep is never read: skip its accumulation
-                const bool very_last = last_pass && it == b.max_iter - 1;
-                const int accumulate = very_last ? 0 : 1;
-                const int accum_color = (!ignore_color || it == b.max_iter - 1) ? 1 : 0;
-                const int store_labels = store_all ? 2 : (very_last ? 1 : 0);   // (see orphan_needs_repeat)
-                // the last pre-pass sweep is the only one of its pass that folds colours (they seed the main pass): the
-                // caches written by the earlier pre-pass sweeps hold no colour sums, so it evaluates every tile
-                const int use_cache = (ignore_color && it == b.max_iter - 1) ? 0 : 1;
-                if (sg.tile1 > sg.tile0) {   // (an empty group launches nothing: no span either -- its pooled events would keep an older recording)
-                    KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
-                    unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
-                    if (gi == 0 && ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
-                    switch (b.CP) {
-                        case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, sg, head_cur); break;
-#ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
-                        case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, sg, head_cur); break;
-                        case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, sg, head_cur); break;
-                        case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, sg, head_cur); break;
-#endif
-                        default: set_error("bad CP"); return OBIA_E_INVALID;
-                    }
-                }
-                debug_sync(ctx, ignore_color ? "sweeps: pre-pass sweep" : "sweeps: colour sweep");
             }
+            // the update after the very last sweep is never read: skip its accumulation
+            const bool very_last = last_pass && it == b.max_iter - 1;
+            const int accumulate = very_last ? 0 : 1;
+            const int accum_color = (!ignore_color || it == b.max_iter - 1) ? 1 : 0;
+            const int store_labels = store_all ? 2 : (very_last ? 1 : 0);   // (see orphan_needs_repeat)
+            // the last pre-pass sweep is the only one of its pass that folds colours (they seed the main pass): the
+            // caches written by the earlier pre-pass sweeps hold no colour sums, so it evaluates every tile
+            const int use_cache = (ignore_color && it == b.max_iter - 1) ? 0 : 1;
+            {
+                KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
+                unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
+                if (ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
+                switch (b.CP) {
+                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+#ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
+                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+#endif
+                    default: set_error("bad CP"); return OBIA_E_INVALID;
+                }
+            }
+            debug_sync(ctx, ignore_color ? "sweeps: pre-pass sweep" : "sweeps: colour sweep");
         }
-        }
-        for (size_t g = 1; g < groups.size(); ++g) {   // join: whatever follows on the context's stream sees every group's labels
-            OBIA_HIP_TRY(hipEventRecord(ctx->join_ev[g - 1], groups[g].stream));
-            OBIA_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->join_ev[g - 1], 0));
-        }
-        OBIA_HIP_TRY(hipGetLastError());
-        return OBIA_OK;
-    };
-    static const bool env_store_all = std::getenv("OBIA_STORE_ALL_LABELS") != nullptr;   // developer switch (A/B timing)
-    const bool store_all = b.exit_on_fixed_point || b.slic_zero || env_store_all;
-    // The fill value survives in exactly one kind of pixel: a valid one that no window reached ("orphan").  When only the last sweep
-    // stores, such a pixel raises the flag and the batch is repeated below (with the fill) -- unless the batch has ONE sweep in all,
-    // where the fill value is what the reference keeps.  Every other pixel is written by the last sweep (masked ones included): the
-    // 1.2 GB fill of a bench batch is skipped on the common path.
-    if (store_all || passes * b.max_iter <= 1) {
-        fill_labels();
-        debug_sync(ctx, "sweeps: label fill");
     }
-    unsigned long long h[513];
-    if (mode == 2) {   // the repeat of a batch whose deferred flag said "orphan": every sweep stores its labels
-        ctx->timing.batch_repeats += 1;
-        fill_labels();
-        OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
-        OBIA_TRY(run_all(true));
-        OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
-        if (ctx->profiling)
-            for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
-        return OBIA_OK;
-    }
-    OBIA_TRY(run_all(store_all));
-    if (mode == 1 && !store_all) {   // the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle
-        if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(h), hipHostMallocDefault));
-        OBIA_HIP_TRY(hipMemcpyAsync(ctx->defer_buf, d_px, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        ctx->defer_pending = true;
-        return OBIA_OK;
-    }
-    OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
-    if (!store_all && (h[512] & 0xffffffffull) != 0ull) {
-        // a pixel needed the label of an earlier sweep: repeat the batch from the seeds with every sweep storing its labels
-        ctx->timing.batch_repeats += 1;
-        fill_labels();
-        OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
-        OBIA_TRY(run_all(true));
-        OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
-    }
-    if (ctx->profiling)
-        for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
+    OBIA_HIP_TRY(hipGetLastError());
+    *d_px_out = d_px;
     return OBIA_OK;
 }
 
-// (see slic.hpp) the stream has been synchronised since slic_run_sweeps(..., 1) returned
-int slic_sweeps_settle(obia_ctx *ctx, SlicBatch &b, bool *repeat) {
-    (void)b;
+int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b) {
+    ctx->defer_pending = false;   // (also when this call fails: a settle after it finds nothing to look at)
+    unsigned long long *d_px = nullptr;
+    OBIA_TRY(queue_sweeps(ctx, b, false, &d_px));
+    if (!d_px) return OBIA_OK;
+    // the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle
+    if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(unsigned long long) * 513, hipHostMallocDefault));
+    OBIA_HIP_TRY(hipMemcpyAsync(ctx->defer_buf, d_px, sizeof(unsigned long long) * 513, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->defer_pending = true;
+    return OBIA_OK;
+}
+
+// (see slic.hpp) the stream has been synchronised since slic_run_sweeps returned
+int slic_sweeps_settle(obia_ctx *ctx, bool *repeat) {
     *repeat = false;
     if (!ctx->defer_pending) return OBIA_OK;
     ctx->defer_pending = false;
     const unsigned long long *h = ctx->defer_buf;
     if ((h[512] & 0xffffffffull) != 0ull) { *repeat = true; return OBIA_OK; }   // (the repeat counts its own pixels)
-    if (ctx->profiling)
-        for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
+    fold_counters(ctx, h);
+    return OBIA_OK;
+}
+
+int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b) {
+    ctx->timing.batch_repeats += 1;
+    unsigned long long *d_px = nullptr;
+    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px));
+    if (!d_px) return OBIA_OK;
+    unsigned long long h[513];
+    OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
+    fold_counters(ctx, h);
     return OBIA_OK;
 }
 

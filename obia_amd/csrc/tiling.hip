@@ -353,11 +353,7 @@ struct TileState {
 // The feature pass of the white tiles (bound by HBM, few vector instructions) runs on a side stream beside the black batch's
 // sweeps, whose first nine launches -- the spatial pre-pass -- are bound by vector issue and move no data: 46.62 / 46.48 ->
 // 46.10 / 46.00 ms per step (two pairs on one box; the pre-pass gives back 0.4 ms of the 2.7 ms hidden).  Round 2 had measured the
-// same idea as a loss on the round-1 kernels.  OBIA_WHITE_FEATURES_BESIDE=0 puts the pass back in line (A/B, debugging).
-static bool white_features_beside() {
-    const char *e = std::getenv("OBIA_WHITE_FEATURES_BESIDE");
-    return e ? atoi(e) != 0 : true;
-}
+// same idea as a loss on the round-1 kernels.
 
 static int grid_rows(const std::vector<TileWin> &wins) {   // row-walking kernels: one block per row (capped)
     int g = 1;
@@ -433,8 +429,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         }
     }
     b.d_labels = A.get<int32_t>((size_t)off);
-    int32_t *d_final = A.get<int32_t>((size_t)off);
-    if (!d_wins || !b.d_windows || !b.d_mask || !b.d_feat || !b.d_labels || !d_final) return OBIA_E_NOMEM;
+    if (!d_wins || !b.d_windows || !b.d_mask || !b.d_feat || !b.d_labels) return OBIA_E_NOMEM;
     OBIA_TRY(upload_async(ctx, d_wins, wins.data(), sizeof(TileWin) * np));   // (pinned ring: no stream sync per small table)
     OBIA_TRY(upload_async(ctx, b.d_windows, b.windows.data(), sizeof(SrcWindow) * np));
     int *d_tile_any = A.get<int>(np);
@@ -485,8 +480,10 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     }
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid));
     debug_sync(ctx, "tiler: plan_and_seed");
-    if (!white && S.pf.d_feat && !S.pf.launched && white_features_beside()) OBIA_TRY(prefetch_white_launch(ctx, S, true));
-    OBIA_TRY(slic_run_sweeps(ctx, b, 1));   // (the orphan flag is looked at after the connectivity stage's own synchronisation)
+    if (!white && S.pf.d_feat && !S.pf.launched) OBIA_TRY(prefetch_white_launch(ctx, S, true));
+    const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
+    unsigned *const mask4 = b.d_mask4;        // (null: the sweeps pack the mask above the mark)
+    OBIA_TRY(slic_run_sweeps(ctx, b));   // (the orphan flag is looked at after the connectivity stage's own synchronisation)
     debug_sync(ctx, "tiler: sweeps");
     int n_new = 0;
     CcResolve resolve{};
@@ -499,12 +496,14 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
             const int mx = mxd >= 2147483647.0 ? 2147483647 : (int)mxd;
             cps[p] = CcProblem{P.H, P.W, P.pix_off, (int)(S.sp.min_size_factor * segment_size), mx > 0 ? mx : 1};
         }
-        OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, d_final, &n_new, &resolve));
+        OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve));
         bool repeat = false;
-        OBIA_TRY(slic_sweeps_settle(ctx, b, &repeat));
+        OBIA_TRY(slic_sweeps_settle(ctx, &repeat));
         if (repeat) {   // rare: a valid pixel no window reached kept a label that was not stored -- sweeps with stored labels, stage again
-            OBIA_TRY(slic_run_sweeps(ctx, b, 2));
-            OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, d_final, &n_new, &resolve));
+            A.rewind(sweeps_mk);
+            b.d_mask4 = mask4;
+            OBIA_TRY(slic_rerun_storing(ctx, b));
+            OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve));
         }
         debug_sync(ctx, "tiler: connectivity");
     } else {
@@ -746,8 +745,8 @@ static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside) {
     if (beside) {
         // `beside`: on a side stream, forked here and joined in prefetch_white_fetch -- the caller queues the black batch's
         // spatial pre-pass next, a kernel that is bound by vector issue and moves no data, beside this pass, which is bound by HBM
-        OBIA_TRY(side_streams(ctx, obia_ctx::MAX_SIDE));
-        hipStream_t side = ctx->side[obia_ctx::MAX_SIDE - 1];
+        OBIA_TRY(side_stream(ctx));
+        hipStream_t side = ctx->side;
         OBIA_HIP_TRY(hipEventRecord(ctx->aux_fork, ctx->stream));
         OBIA_HIP_TRY(hipStreamWaitEvent(side, ctx->aux_fork, 0));
         OBIA_TRY(slic_features_launch(side, S.C, CP, (int)NP, pf.d_windows, pf.maxh, S.img, S.W, 1, to_lab,
@@ -869,8 +868,7 @@ struct obia_tiler {
 // between returned while that pass could still read the caller's raster and write arena memory the next call hands out again).
 static int fail_quiesced(obia_ctx *ctx, int rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < obia_ctx::MAX_SIDE; ++i)
-        if (ctx->side[i]) (void)hipStreamSynchronize(ctx->side[i]);
+    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
     return rc;
 }
 

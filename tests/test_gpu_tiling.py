@@ -158,7 +158,7 @@ def test_tiler_with_a_corner_length_that_is_not_a_whole_number_of_pixels(oracle,
 
 def test_tiler_batch_with_orphan_pixels_equals_the_oracle(oracle):
     """A valid pixel that no window reaches keeps the label of the sweep before, which the tiler's sweeps do not store: the batch's
-    orphan flag -- read after the connectivity stage since round 4 (slic_run_sweeps mode 1, slic_sweeps_settle) -- makes the batch
+    orphan flag -- read after the connectivity stage since round 4 (slic_sweeps_settle) -- makes the batch
     run again with every sweep storing, and the connectivity stage with it.  Islands of a few valid pixels far from every seed
     (farther than two grid steps) produce such pixels in black and in white tiles."""
     from obia_amd.tiling import create_tiled_segments
@@ -180,3 +180,45 @@ def test_tiler_batch_with_orphan_pixels_equals_the_oracle(oracle):
     assert ctx.timing()["batch_repeats"] >= 1, "the case is meant to take the repeat path"
     assert n == n_ref and np.array_equal(lab, ref)
     assert (lab[~mask] == 0).all()
+
+
+def test_tiler_large_batches_with_orphan_pixels_equal_the_oracle(oracle):
+    """The orphan construction above on 512-pixel tiles: blocks that get the seeds in tile columns 0 and 2, islands of a few valid
+    pixels in columns 1 and 3, so that the black batch (four tiles) and the white batches hold islands.  The repeat rewinds the
+    arena to the mark before the first sweeps and runs them again with several problems in flight."""
+    from obia_amd import _lib
+    from obia_amd.tiling import create_tiled_segments
+    from oracle import tiler
+    rs = np.random.RandomState(13)
+    H, W = 1024, 2048
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    img = np.stack([350 * np.sin(xx / (9 + 3 * c)) * np.cos(yy / (12 + 2 * c)) + 900 + 60 * c + rs.normal(0, 22, (H, W)) for c in range(4)], -1).astype(np.float32)
+    mask = np.zeros((H, W), bool)
+    mask[:, 0:160] = True                     # blocks that get the seeds, farther than the buffer from the island columns' windows
+    mask[:, 1088:1248] = True
+    mask[10:H:128, 700:702] = True            # islands, two and three pixels wide
+    mask[70:H:128, 1700:1703] = True
+    kw = dict(tile_size=512, buffer=32, crown_radius=6.0, pixel_size=(1.0, 1.0), compactness=10.0)
+    ctx = _lib.Context(0)
+    ref, n_ref = tiler.create_tiled_segments(img, mask, **kw)
+    lab, n = create_tiled_segments(torch.as_tensor(img).cuda(), input_mask=mask, ctx=ctx, **kw)
+    lab = lab.cpu().numpy()
+    assert ctx.timing()["batch_repeats"] >= 1, "the case is meant to take the repeat path"
+    assert n == n_ref and np.array_equal(lab, ref)
+    assert (lab[~mask] == 0).all()
+
+
+def test_sweep_timing_sum_and_union():
+    """obia_last_timing classes 0 / 10: the colour sweeps' durations (events bound to the dispatches) add up to the time during
+    which one of them runs: the sweeps run one after the other."""
+    from obia_amd import _lib
+    from obia_amd.tiling import create_tiled_segments
+    rs = np.random.RandomState(5)
+    img = torch.as_tensor(rs.rand(1024, 1280, 8).astype(np.float32)).cuda()
+    ctx = _lib.Context(0)
+    ctx.set_profiling(2)
+    kw = dict(tile_size=256, buffer=32, crown_radius=4, pixel_size=(0.5, 0.5), compactness=10.0, ctx=ctx)
+    create_tiled_segments(img, **kw)
+    t1 = ctx.timing()
+    assert t1["sweeps"] > 0 and t1["assign_ms"] > 0
+    assert abs(t1["assign_busy_ms"] - t1["assign_ms"]) <= 0.01 * t1["assign_ms"] + 0.005
