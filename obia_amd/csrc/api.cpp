@@ -35,38 +35,20 @@ int check_slic_args(const float *img, int H, int W, int C, const obia_slic_param
 int slic_single(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                 const obia_slic_params *p, SlicBatch &b, const ExternalSeeds *ext = nullptr) {
     Arena &A = ctx->arena;
-    b.nprob = 1;
-    b.C = C;
-    b.CP = (C + 3) & ~3;
-    b.masked = mask != nullptr;
-    b.start_label = p->start_label;
-    b.max_iter = p->max_num_iter;
-    b.exit_on_fixed_point = p->exit_on_fixed_point != 0;
-    b.slic_zero = p->slic_zero != 0;
-    for (int i = 0; i < 3; ++i) { b.sigma[i] = p->sigma_zyx[i]; b.spacing[i] = p->spacing_zyx[i]; }
-    const bool direct = (float)b.spacing[1] != 1.0f || (float)b.spacing[2] != 1.0f;   // anisotropic spacing: the direct sweep path (slic_sweep.hip)
-    if (direct) b.exit_on_fixed_point = false;
-    b.total_pix = (long long)H * W;
-    SlicProblem P{};
-    P.H = H; P.W = W; P.pix_off = 0; P.feat_off = 0; P.XB = feat_xb(W); P.fb_off = 0;
-    b.probs.assign(1, P);
+    slic_batch_settings(b, *p, C, p->normalize_bands, mask != nullptr);
     b.windows.assign(1, SrcWindow{0, 0, H, W, 0, 0, 0});
+    OBIA_TRY(slic_batch_layout(b));
     b.d_windows = A.get<SrcWindow>(1);
-    b.total_feat_f4 = feat_block_f4(H, W, b.CP);
     b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
     b.d_labels = A.get<int32_t>((size_t)b.total_pix);
     if (!b.d_windows || !b.d_feat || !b.d_labels) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemcpyAsync(b.d_windows, b.windows.data(), sizeof(SrcWindow), hipMemcpyHostToDevice, ctx->stream));
     b.d_mask = const_cast<uint8_t *>(mask);
-    const int to_lab = (C == 3 && p->convert2lab != 0) ? 1 : 0;
-    const float ratio = (float)(1.0 / p->compactness);   // `image * ratio`: float32 array times Python float
-    b.col_lb = slic_use_colour_bound(ratio, to_lab != 0) && !b.slic_zero && !b.exit_on_fixed_point && !direct;
     if (b.col_lb) {
-        b.d_fbox = A.get<float>((size_t)feat_boxes(H, W) * 2 * b.CP);
+        b.d_fbox = A.get<float>((size_t)b.total_boxes * 2 * b.CP);
         if (!b.d_fbox) return OBIA_E_NOMEM;
     }
-    b.prescale = slic_prescale(ratio, p->normalize_bands, to_lab, b.slic_zero);
-    OBIA_TRY(slic_prepare_features(ctx, b, img, H, W, p->normalize_bands, to_lab, ratio * b.prescale));
+    OBIA_TRY(slic_prepare_features(ctx, b, img, W));
     std::vector<int> nseg(1, p->n_segments);
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, nullptr, ext));
     if (b.probs[0].K <= 0) {
@@ -148,11 +130,7 @@ static int slic_full_impl(obia_ctx *ctx, const float *img, int H, int W, int C, 
         rc = slic_single(ctx, img, H, W, C, mask, params, b, ext);
         if (rc == OBIA_OK) {
             if (params->enforce_connectivity) {
-                // segment_size = mask.sum() / n_centroids  |  prod(shape) / n_centroids  (slic_superpixels.py:321-326)
-                const double segment_size = (double)b.probs[0].n_valid / (double)b.probs[0].K;
-                const int min_size = (int)(params->min_size_factor * segment_size);
-                const double mxd = params->max_size_factor * segment_size;
-                const int max_size = mxd >= 2147483647.0 ? 2147483647 : (mxd < 1.0 ? 1 : (int)mxd);
+                const auto [min_size, max_size] = slic_cc_sizes(params->min_size_factor, params->max_size_factor, b.probs[0].n_valid, b.probs[0].K);
                 rc = enforce_connectivity_dev(ctx, b.d_labels, H, W, min_size, max_size, params->start_label, labels_out, &n_labels);
             } else {
                 hipError_t e = hipMemcpyAsync(labels_out, b.d_labels, sizeof(int32_t) * (size_t)H * W, hipMemcpyDeviceToDevice, ctx->stream);

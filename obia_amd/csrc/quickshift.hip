@@ -307,11 +307,10 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
     const long long n = (long long)H * W;
     // 1. obia's per-band normalisation (float32, segment_boundaries.py:32-33) through the SLIC feature kernels
     SlicBatch b;
-    b.nprob = 1; b.C = C; b.CP = (C + 3) & ~3; b.total_pix = n;
-    SlicProblem P{}; P.H = H; P.W = W;
-    b.probs.assign(1, P);
+    b.C = C; b.CP = (C + 3) & ~3; b.normalize = normalize_bands;
     b.feat_planes = false;   // pixel-major features: qs_prepare_kernel reads them per pixel
     b.windows.assign(1, SrcWindow{0, 0, H, W, 0, 0, 0});
+    OBIA_TRY(slic_batch_layout(b));
     b.d_windows = A.get<SrcWindow>(1);
     b.d_feat = A.get<float>((size_t)n * b.CP);
     double *d_img = A.get<double>((size_t)n * C);
@@ -321,7 +320,7 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
     int *d_bs = A.get<int>(nb), *d_flags = A.get<int>(4);
     if (!b.d_windows || !b.d_feat || !d_img || !d_dens || !d_dp || !d_par || !d_par2 || !d_rank || !d_bs || !d_flags) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemcpyAsync(b.d_windows, b.windows.data(), sizeof(SrcWindow), hipMemcpyHostToDevice, ctx->stream));
-    OBIA_TRY(slic_prepare_features(ctx, b, img, H, W, normalize_bands, 0, 1.0f));
+    OBIA_TRY(slic_prepare_features(ctx, b, img, W));
     int gs = cdiv(n, 256 * 4);
     if (gs > 65535) gs = 65535;
     const bool smoothing = sigma > 1e-15;

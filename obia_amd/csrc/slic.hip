@@ -433,13 +433,12 @@ int gaussian_weights_host(double sigma, bool sigma_is_f32, std::vector<double> &
 }
 
 // scratch arrays and the three weight tables
-int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, long long maxpix, int CP, int np) {
+int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, int CP, int np) {
     if (!sm.on()) return OBIA_OK;
     Arena &A = ctx->arena;
     sm.tmp_a = A.get<float>((size_t)total_pix * CP);
     sm.tmp_b = A.get<float>((size_t)total_pix * CP);
     sm.d_scratch = A.get<unsigned>((size_t)np);
-    sm.maxpix = maxpix;
     if (!sm.tmp_a || !sm.tmp_b || !sm.d_scratch) return OBIA_E_NOMEM;
     for (int ax = 0; ax < 3; ++ax) {
         if (!(sm.sigma[ax] > 1e-15)) continue;
@@ -456,9 +455,12 @@ int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, long long
 
 // Launch half of the feature pass on `stream`: min / max of every band of every window, then the features.
 // d_keys layout for np windows: keys[np][C][2] (min, max as ordered uints) | nonfinite[np] | max|feature| bits [np].
-int slic_features_launch(hipStream_t stream, int C, int CP, int np, const SrcWindow *d_windows, int maxh, const float *src, int Ws,
-                         int normalize, int to_lab, float ratio, float *d_feat, unsigned *d_keys, bool planes, float *d_fbox,
-                         const SmoothSpec *smooth) {
+int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth) {
+    const int C = b.C, CP = b.CP, np = b.nprob, maxh = b.maxh, normalize = b.normalize, to_lab = b.to_lab;
+    const SrcWindow *d_windows = b.d_windows;
+    const float ratio = b.feat_ratio;
+    float *d_feat = b.d_feat, *d_fbox = b.col_lb ? b.d_fbox : nullptr;
+    const bool planes = b.feat_planes;
     if (C < 1 || C > 16) { set_error("band count %d not supported (1..16)", C); return OBIA_E_UNSUPPORTED; }
     const size_t nkeys = (size_t)np * C * 2, ntot = nkeys + 2 * (size_t)np;
     unsigned *d_nonfinite = d_keys + nkeys, *d_maxabs = d_nonfinite + np;
@@ -497,7 +499,7 @@ int slic_features_launch(hipStream_t stream, int C, int CP, int np, const SrcWin
         }
 #undef LAUNCH_UNSCALED
         float *cur = smooth->tmp_a, *oth = smooth->tmp_b;
-        long long nb = (smooth->maxpix * CP + 255) / 256;
+        long long nb = (b.maxpix * CP + 255) / 256;
         dim3 gg((unsigned)(nb < 65535 ? (nb < 1 ? 1 : nb) : 65535), np);
         for (int ax = 0; ax < 3; ++ax) {
             if (!(smooth->sigma[ax] > 1e-15)) continue;
@@ -531,12 +533,11 @@ int slic_features_launch(hipStream_t stream, int C, int CP, int np, const SrcWin
 
 // Host half: constant / non-finite bands (-> skip flags or an error) and the fixed-point scale of the batch.  `keys`,
 // `nonfinite`, `maxabs` point at the read-back entries of the batch's FIRST window (np consecutive windows).
-int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *nonfinite, const unsigned *maxabs_bits, int normalize,
-                         std::vector<int> *skip) {
+int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *nonfinite, const unsigned *maxabs_bits, std::vector<int> *skip) {
     const int C = b.C, np = b.nprob;
     auto k2f = [](unsigned k) { unsigned bb = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &bb, 4); return f; };
     if (skip) skip->assign(np, 0);
-    if (normalize) {
+    if (b.normalize) {
         for (int p = 0; p < np; ++p) {
             bool bad = nonfinite[p] != 0;
             int cb = -1;
@@ -584,26 +585,64 @@ float slic_prescale(float ratio, int normalize, int to_lab, bool slic_zero) {
     return (float)std::ldexp(1.0, s);
 }
 
-int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Hs, int Ws, int normalize,
-                          int to_lab, float ratio, std::vector<int> *skip) {
-    (void)Hs;
+void slic_batch_settings(SlicBatch &b, const obia_slic_params &p, int C, int normalize_bands, bool masked) {
+    b.C = C;
+    b.CP = (C + 3) & ~3;
+    b.masked = masked;
+    b.start_label = p.start_label;
+    b.max_iter = p.max_num_iter;
+    b.slic_zero = p.slic_zero != 0;
+    for (int i = 0; i < 3; ++i) { b.sigma[i] = p.sigma_zyx[i]; b.spacing[i] = p.spacing_zyx[i]; }
+    b.direct = (float)b.spacing[1] != 1.0f || (float)b.spacing[2] != 1.0f;   // anisotropic spacing: the direct sweep path (slic_sweep.hip)
+    b.exit_on_fixed_point = p.exit_on_fixed_point != 0 && !b.direct;
+    b.normalize = normalize_bands;
+    b.to_lab = (C == 3 && p.convert2lab != 0) ? 1 : 0;
+    const float ratio = (float)(1.0 / p.compactness);   // `image * ratio`: float32 array times Python float
+    b.col_lb = slic_use_colour_bound(ratio, b.to_lab != 0) && !b.slic_zero && !b.exit_on_fixed_point && !b.direct;
+    b.prescale = slic_prescale(ratio, normalize_bands, b.to_lab, b.slic_zero);
+    b.feat_ratio = ratio * b.prescale;
+}
+
+int slic_batch_layout(SlicBatch &b) {
+    b.nprob = (int)b.windows.size();
+    b.probs.assign(b.windows.size(), SlicProblem{});
+    long long off = 0, foff = 0, boff = 0, m4 = 0;
+    for (int p = 0; p < b.nprob; ++p) {
+        SrcWindow &w = b.windows[p];
+        SlicProblem &P = b.probs[p];
+        P.H = w.h; P.W = w.w; P.XB = feat_xb(w.w);
+        P.pix_off = w.pix_off = off;
+        P.feat_off = w.feat_off = foff;
+        P.fb_off = w.fb_off = boff;
+        P.m4_off = (int)m4;
+        const long long n = (long long)w.h * w.w;
+        if (n > b.maxpix) b.maxpix = n;
+        if (w.h > b.maxh) b.maxh = w.h;
+        off += n;
+        foff += feat_block_f4(w.h, w.w, b.CP);
+        boff += feat_boxes(w.h, w.w);
+        m4 += (long long)((w.h + 3) / 4) * w.w;
+    }
+    if (off > 0x7fffffffLL || m4 > 0x7fffffffLL) { set_error("batch of %lld pixels too large", off); return OBIA_E_INVALID; }
+    b.total_pix = off; b.total_feat_f4 = foff; b.total_boxes = boff;
+    b.total_m4 = m4 > 0 ? m4 : 1;
+    return OBIA_OK;
+}
+
+int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Ws, std::vector<int> *skip) {
     ScopedSpan span(ctx, T_FEAT);
-    const int C = b.C, np = b.nprob;
-    const size_t nkeys = (size_t)np * C * 2, ntot = nkeys + 2 * (size_t)np;
+    const int np = b.nprob;
+    const size_t nkeys = (size_t)np * b.C * 2, ntot = nkeys + 2 * (size_t)np;
     unsigned *d_keys = ctx->arena.get<unsigned>(ntot);
     if (!d_keys) return OBIA_E_NOMEM;
-    int maxh = 1;
-    long long maxpix = 1;
-    for (auto &w : b.windows) { if (w.h > maxh) maxh = w.h; if ((long long)w.h * w.w > maxpix) maxpix = (long long)w.h * w.w; }
     SmoothSpec sm;
     for (int i = 0; i < 3; ++i) sm.sigma[i] = b.sigma[i];
-    OBIA_TRY(smooth_prepare(ctx, sm, b.total_pix, maxpix, b.CP, np));
-    OBIA_TRY(slic_features_launch(ctx->stream, C, b.CP, np, b.d_windows, maxh, src, Ws, normalize, to_lab, ratio, b.d_feat, d_keys,
-                                  b.feat_planes, (b.col_lb && b.feat_planes) ? b.d_fbox : nullptr, &sm));
+    OBIA_TRY(smooth_prepare(ctx, sm, b.total_pix, b.CP, np));
+    OBIA_TRY(slic_features_launch(ctx->stream, b, src, Ws, d_keys, &sm));
     // one read-back: min/max keys (constant-band check), non-finite flags, max|feature| per window
     std::vector<unsigned> host(ntot);
     OBIA_TRY(read_back(ctx, host.data(), d_keys, ntot * sizeof(unsigned)));
-    return slic_features_finish(b, host.data(), host.data() + nkeys, host.data() + nkeys + np, normalize, skip);
+    return slic_features_finish(b, host.data(), host.data() + nkeys, host.data() + nkeys + np, skip);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -757,9 +796,7 @@ int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid) {
         int *d_cnt = A.get<int>(np);
         if (!d_cnt) return OBIA_E_NOMEM;
         OBIA_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int) * np, ctx->stream));
-        long long maxpix = 1;
-        for (auto &P : b.probs) { long long n = (long long)P.H * P.W; if (n > maxpix) maxpix = n; }
-        int blocks = cdiv(maxpix, 256 * 16 * 32);
+        int blocks = cdiv(b.maxpix, 256 * 16 * 32);
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(count_valid_kernel, dim3(blocks, np), dim3(256), 0, ctx->stream, b.d_probs, b.d_mask, d_cnt);
         OBIA_TRY(read_back(ctx, nvalid.data(), d_cnt, sizeof(int) * np));
@@ -774,7 +811,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     const int np = b.nprob;
     if (ext && (np != 1 || ext->n < 1 || !ext->yx)) { set_error("external seeds need one raster and at least one seed"); return OBIA_E_INVALID; }
     Arena &A = ctx->arena;
-    // problems carry H, W, pix_off already (set by the caller); upload a first version for the
+    // problems carry H, W and their offsets already (slic_batch_layout); upload a first version for the
     // counting / seeding kernels
     if (!b.d_probs) b.d_probs = A.get<SlicProblem>(np);
     if (!b.d_probs) return OBIA_E_NOMEM;
@@ -855,7 +892,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     }
     // window steps, bins, tiles
     int cell_off = 0, tile_max = 0;
-    long long tiles_all = 0, m4_total = 0;
+    long long tiles_all = 0;
     for (int p = 0; p < np; ++p) {
         SlicProblem &P = b.probs[p];
         P.K = K[p];
@@ -868,9 +905,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
         const float stepf = (float)stepmax[p];
         P.spatial_w = (float)(1.0 / ((double)stepf * (double)stepf)) * (b.prescale * b.prescale);   // (a power of two: exact)
         P.sp_y = (float)b.spacing[1]; P.sp_x = (float)b.spacing[2];   // np.ascontiguousarray(spacing, dtype=image dtype)
-        P.direct = (P.sp_y != 1.0f || P.sp_x != 1.0f) ? 1 : 0;
-        P.m4_off = (int)m4_total;
-        m4_total += (long long)((P.H + 3) / 4) * P.W;
+        P.direct = b.direct ? 1 : 0;
         P.cell_off = cell_off;
         long long nc = (long long)P.ncy * P.ncx;
         if (cell_off + nc > 0x7fff0000LL) { set_error("too many bins in one batch"); return OBIA_E_INVALID; }
@@ -893,8 +928,6 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     }
     b.total_cells = cell_off > 0 ? cell_off : 1;
     b.total_tiles = tile_max;
-    if (m4_total > 0x7fffffffLL) { set_error("mask of the batch too large"); return OBIA_E_INVALID; }
-    b.total_m4 = m4_total > 0 ? m4_total : 1;
     OBIA_TRY(upload_async(ctx, b.d_probs, b.probs.data(), sizeof(SlicProblem) * np));
     const int RS = CENT_REC + b.CP;
     b.d_cent = A.get<float>((size_t)b.total_cent * RS);

@@ -75,7 +75,13 @@ struct SlicBatch {
     bool masked = false;
     int start_label = 1;
     int max_iter = 10;
-    long long total_pix = 0;
+    // settings: filled by slic_batch_settings from the caller's parameters, the same for every batch of one call
+    bool direct = false;               // anisotropic `spacing`: every tile takes the direct sweep path (SlicProblem::direct)
+    int normalize = 0, to_lab = 0;     // feature pass: per-band normalisation of each window, Lab conversion
+    float feat_ratio = 1.0f;           // what the feature pass multiplies by: float(1 / compactness) * prescale
+    // layout: filled by slic_batch_layout from `windows`
+    long long total_pix = 0, total_boxes = 0, maxpix = 1;   // total_boxes: records of d_fbox; maxpix: pixels of the largest window
+    int maxh = 1;                      // rows of the tallest window
     int total_cent = 0, total_cells = 0, total_tiles = 0;   // total_tiles: largest tile count of one problem (grid.x)
     long long total_tiles_all = 0;                          // sum over problems (per-tile state of exit_on_fixed_point)
     std::vector<SlicProblem> probs;    // host copy
@@ -129,21 +135,16 @@ struct SmoothSpec {
     double *d_w[3] = {nullptr, nullptr, nullptr};   // [radius + 1]: centre first
     int radius[3] = {0, 0, 0};
     unsigned *d_scratch = nullptr;                  // [np] (max |feature| of the unscaled pass: not used)
-    long long maxpix = 0;                           // pixels of the largest window
     bool on() const { return sigma[0] > 1e-15 || sigma[1] > 1e-15 || sigma[2] > 1e-15; }
 };
-int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, long long maxpix, int CP, int np);
+int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, int CP, int np);
 int gaussian_weights_host(double sigma, bool sigma_is_f32, std::vector<double> &w);   // returns the radius; w[0] = centre weight
-int slic_features_launch(hipStream_t stream, int C, int CP, int np, const SrcWindow *d_windows, int maxh, const float *src, int Ws,
-                         int normalize, int to_lab, float ratio, float *d_feat, unsigned *d_keys, bool planes = true,
-                         float *d_fbox = nullptr,    // d_fbox (plane layout only): the footprints' colour boxes from the same pass
-                         const SmoothSpec *smooth = nullptr);
-int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *nonfinite, const unsigned *maxabs_bits, int normalize,
-                         std::vector<int> *skip);
-int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Hs, int Ws,
-                          int normalize, int to_lab, float ratio, std::vector<int> *skip = nullptr);
+// (b.d_fbox, plane layout only: the footprints' colour boxes come out of the same pass)
+int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth = nullptr);
+int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *nonfinite, const unsigned *maxabs_bits, std::vector<int> *skip);
+int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Ws, std::vector<int> *skip = nullptr);
 // The part of the fixed-point scale of the colour sums that is known BEFORE the features are computed -- normalised bands times
-// `ratio` reach exactly `ratio` -- as a power of two.  The caller multiplies it into the ratio it hands to the feature pass (exact: the
+// `ratio` reach exactly `ratio` -- as a power of two.  slic_batch_settings multiplies it into the ratio of the feature pass (exact: the
 // planes hold the reference's features times 2^s) and stores it in SlicBatch::prescale; slic_plan_and_seed scales the spatial weight
 // by its square, the centroid colours follow from the sums: every distance is the reference's times 2^(2s), every comparison and
 // every tie the same, and the sweeps convert a feature to fixed point by truncation alone (SlicBatch::fscale, taken from the largest
@@ -151,6 +152,19 @@ int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Hs,
 float slic_prescale(float ratio, int normalize, int to_lab, bool slic_zero);
 // Does a batch with this image ratio (1 / compactness; to_lab: the features are Lab, ~100 units wide) use the colour-box bound?
 bool slic_use_colour_bound(float ratio, bool to_lab = false);
+// The two halves of a batch's description, each derived in one place.  Settings: everything that follows from the caller's
+// parameters (spacing other than (1, 1) turns exit_on_fixed_point and the colour bound off: the direct sweep path has neither).
+// Layout: the caller puts (y0, x0, h, w) of every window into b.windows; the offsets of the windows in the dense per-pixel arrays,
+// the feature planes, the colour boxes and the packed mask, b.probs (H, W and the same offsets), nprob and the totals follow.
+void slic_batch_settings(SlicBatch &b, const obia_slic_params &p, int C, int normalize_bands, bool masked);
+int slic_batch_layout(SlicBatch &b);
+// The component sizes connectivity merges below / cuts at: segment_size = mask.sum() / n_centroids  |  prod(shape) / n_centroids
+// (slic_superpixels.py:321-326; 1 for a problem without centroids), max_size clamped to [1, INT_MAX].
+inline std::pair<int, int> slic_cc_sizes(double min_size_factor, double max_size_factor, int n_valid, int K) {
+    const double segment_size = K > 0 ? (double)n_valid / (double)K : 1.0;
+    const double mxd = max_size_factor * segment_size;
+    return {(int)(min_size_factor * segment_size), mxd >= 2147483647.0 ? 2147483647 : (mxd >= 1.0 ? (int)mxd : 1)};
+}
 
 // Seeds (grid or masked grid), fills K / steps / bins in b.probs, uploads descriptors.
 // n_segments[p] = requested segments of problem p.

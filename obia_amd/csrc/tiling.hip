@@ -35,7 +35,7 @@ namespace obia {
 //           it is neither `within` nor `overlaps` (not selected)                                             tiling.py:205-210
 //   cl*_any pixels that meet the square's interior at all: a segment with such a pixel is not `within`       tiling.py:220-231
 // (equal when a is a whole number -- even buffer, pixel size 1 or 0.5 -- which is every case rounds 1-3 tested)
-struct TileWin { int y0, x0, h, w; long long pix_off; int cly, clx; int cly_in, clx_in, cly_any, clx_any; int m4_off; };   // m4_off: SlicProblem::m4_off
+struct TileWin { int y0, x0, h, w; long long pix_off; int cly, clx; int cly_in, clx_in, cly_any, clx_any; int m4_off; };   // pix_off, m4_off: copied from SlicProblem
 
 // wave-aggregated histogram add: lanes of a wave that hold the same key add once
 __device__ __forceinline__ void wave_hist_add(unsigned *hist, int key, bool active) {
@@ -332,18 +332,14 @@ struct TileState {
     int clx, cly, clx_in, cly_in, clx_any, cly_any;   // corner squares in pixels (see TileWin)
     obia_tiling_params tp;
     obia_slic_params sp;
+    SlicBatch settings;    // slic_batch_settings of (sp, C): every batch of the tiler, and the white prefetch, starts as a copy
     // features of ALL white tiles, prepared in one batch (they depend on the raster only): windows in processing order,
     // one dense buffer, keys read back once before the white pass
     struct PreFeat {
         bool ready = false;
-        std::vector<TileWin> wins;
-        std::vector<SrcWindow> windows;
+        SlicBatch b;                     // windows, layout and feature buffers of the whole set (b.d_feat null: no prefetch)
         std::vector<unsigned> host;      // keys | nonfinite | max|feature| of all windows
-        float *d_feat = nullptr;
-        float *d_fbox = nullptr;         // footprint colour boxes of the same windows (low compactness only)
-        SrcWindow *d_windows = nullptr;
         unsigned *d_keys = nullptr;
-        int maxh = 1;
         bool launched = false;
         bool on_side = false;            // the pass was queued on a side stream (beside the black sweeps): join before it is read
         size_t cursor = 0;               // next window to be consumed by a white batch
@@ -369,66 +365,34 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     if (np == 0) return OBIA_OK;
     Arena &A = ctx->arena;
     const Arena::Mark mk = A.mark();
-    SlicBatch b;
-    b.nprob = np;
-    b.C = S.C;
-    b.CP = (S.C + 3) & ~3;
-    b.masked = true;       // the tiler always hands a mask to slic (tiling.py:137-143): maskSLIC structure
-    b.start_label = 1;
-    b.max_iter = S.sp.max_num_iter;
-    b.exit_on_fixed_point = S.sp.exit_on_fixed_point != 0;
-    b.slic_zero = S.sp.slic_zero != 0;
-    b.prescale = slic_prescale((float)(1.0 / S.sp.compactness), 1, (S.C == 3 && S.sp.convert2lab != 0) ? 1 : 0, b.slic_zero);   // (the prefetched planes carry the same factor)
-    for (int i = 0; i < 3; ++i) { b.sigma[i] = S.sp.sigma_zyx[i]; b.spacing[i] = S.sp.spacing_zyx[i]; }
-    const bool direct = (float)b.spacing[1] != 1.0f || (float)b.spacing[2] != 1.0f;   // anisotropic spacing: the direct sweep path
-    if (direct) b.exit_on_fixed_point = false;
-    long long off = 0, foff = 0, boff = 0, maxpix = 1, m4 = 0;
-    b.probs.resize(np);
-    b.windows.resize(np);
-    for (int p = 0; p < np; ++p) {
-        wins[p].pix_off = off;
-        wins[p].m4_off = (int)m4;                      // the rule of slic_plan_and_seed (same order of problems): SlicProblem::m4_off
-        m4 += (long long)((wins[p].h + 3) / 4) * wins[p].w;
-        SlicProblem P{};
-        P.H = wins[p].h; P.W = wins[p].w; P.pix_off = off; P.feat_off = foff; P.XB = feat_xb(wins[p].w); P.fb_off = boff;
-        b.probs[p] = P;
-        b.windows[p] = SrcWindow{wins[p].y0, wins[p].x0, wins[p].h, wins[p].w, off, foff, boff};
-        const long long n = (long long)wins[p].h * wins[p].w;
-        if (n > maxpix) maxpix = n;
-        off += n;
-        foff += feat_block_f4(wins[p].h, wins[p].w, b.CP);
-        boff += feat_boxes(wins[p].h, wins[p].w);
-    }
-    b.total_feat_f4 = foff;
-    b.col_lb = slic_use_colour_bound((float)(1.0 / S.sp.compactness), S.C == 3 && S.sp.convert2lab != 0) && !b.slic_zero && !b.exit_on_fixed_point && !direct;
-    if (off > 0x7fffffffLL) { set_error("tile batch of %lld pixels too large", off); return OBIA_E_INVALID; }
-    b.total_pix = off;
+    SlicBatch b = S.settings;
+    for (auto &t : wins) b.windows.push_back(SrcWindow{t.y0, t.x0, t.h, t.w, 0, 0, 0});
+    OBIA_TRY(slic_batch_layout(b));
+    for (int p = 0; p < np; ++p) { wins[p].pix_off = b.probs[p].pix_off; wins[p].m4_off = b.probs[p].m4_off; }
     TileWin *d_wins = A.get<TileWin>(np);
     b.d_windows = A.get<SrcWindow>(np);
-    b.d_mask = A.get<uint8_t>((size_t)off);
-    if (m4 > 0x7fffffffLL) { set_error("tile batch of %lld pixels too large", off); return OBIA_E_INVALID; }
-    unsigned *d_mask4 = A.get<unsigned>((size_t)(m4 > 0 ? m4 : 1));   // the packed mask of the sweeps, written by tile_mask_kernel<true>
+    b.d_mask = A.get<uint8_t>((size_t)b.total_pix);
+    unsigned *d_mask4 = A.get<unsigned>((size_t)b.total_m4);   // the packed mask of the sweeps, written by tile_mask_kernel<true>
     if (!d_mask4) return OBIA_E_NOMEM;
     const bool pre = white && S.pf.ready;
     if (pre) {
         // this batch is the next np windows of the prefetched set (same order, same sizes: checked)
-        if (S.pf.cursor + np > S.pf.wins.size()) { set_error("white batch beyond the prefetched windows"); return OBIA_E_INVALID; }
-        for (int p = 0; p < np; ++p) {
-            const TileWin &a = S.pf.wins[S.pf.cursor + p];
-            if (a.y0 != wins[p].y0 || a.x0 != wins[p].x0 || a.h != wins[p].h || a.w != wins[p].w) { set_error("white batch does not match the prefetched windows"); return OBIA_E_INVALID; }
-        }
-        // (the prefetched planes of these windows lie back to back in the same order: the batch's feat_off values, which
-        // start at 0, are offsets from the first window's block)
-        b.d_feat = S.pf.d_feat + 4 * (size_t)S.pf.windows[S.pf.cursor].feat_off;
-        if (b.col_lb) b.d_fbox = S.pf.d_fbox + (size_t)S.pf.windows[S.pf.cursor].fb_off * 2 * b.CP;
+        const SlicBatch &pb = S.pf.b;
+        if (S.pf.cursor + np > pb.windows.size()) { set_error("white batch beyond the prefetched windows"); return OBIA_E_INVALID; }
+        const SrcWindow *a = &pb.windows[S.pf.cursor];
+        for (int p = 0; p < np; ++p)
+            if (a[p].y0 != wins[p].y0 || a[p].x0 != wins[p].x0 || a[p].h != wins[p].h || a[p].w != wins[p].w) { set_error("white batch does not match the prefetched windows"); return OBIA_E_INVALID; }
+        // (the batch's feat_off / fb_off values start at 0: offsets from the first window's block in the prefetched set)
+        b.d_feat = pb.d_feat + 4 * (size_t)a[0].feat_off;
+        if (b.col_lb) b.d_fbox = pb.d_fbox + (size_t)a[0].fb_off * 2 * b.CP;
     } else {
-        b.d_feat = A.get<float>(4 * (size_t)foff);
+        b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
         if (b.col_lb) {
-            b.d_fbox = A.get<float>((size_t)boff * 2 * b.CP);
+            b.d_fbox = A.get<float>((size_t)b.total_boxes * 2 * b.CP);
             if (!b.d_fbox) return OBIA_E_NOMEM;
         }
     }
-    b.d_labels = A.get<int32_t>((size_t)off);
+    b.d_labels = A.get<int32_t>((size_t)b.total_pix);
     if (!d_wins || !b.d_windows || !b.d_mask || !b.d_feat || !b.d_labels) return OBIA_E_NOMEM;
     OBIA_TRY(upload_async(ctx, d_wins, wins.data(), sizeof(TileWin) * np));   // (pinned ring: no stream sync per small table)
     OBIA_TRY(upload_async(ctx, b.d_windows, b.windows.data(), sizeof(SrcWindow) * np));
@@ -454,14 +418,13 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     }
     // per-tile normalisation of every band (create_segments normalises the tile it is given, :32-33)
     std::vector<int> skip;
-    const int to_lab = (S.C == 3 && S.sp.convert2lab != 0) ? 1 : 0;
     if (pre) {
-        const size_t NP = S.pf.wins.size(), nkeys = NP * (size_t)S.C * 2;
+        const size_t NP = S.pf.b.windows.size(), nkeys = NP * (size_t)S.C * 2;
         const unsigned *h = S.pf.host.data();
-        OBIA_TRY(slic_features_finish(b, h + S.pf.cursor * (size_t)S.C * 2, h + nkeys + S.pf.cursor, h + nkeys + NP + S.pf.cursor, 1, &skip));
+        OBIA_TRY(slic_features_finish(b, h + S.pf.cursor * (size_t)S.C * 2, h + nkeys + S.pf.cursor, h + nkeys + NP + S.pf.cursor, &skip));
         S.pf.cursor += np;
     } else {
-        OBIA_TRY(slic_prepare_features(ctx, b, S.img, S.H, S.W, 1, to_lab, (float)(1.0 / S.sp.compactness) * b.prescale, &skip));
+        OBIA_TRY(slic_prepare_features(ctx, b, S.img, S.W, &skip));
     }
     std::vector<int> nvalid;
     debug_sync(ctx, "tiler: mask + features");
@@ -480,7 +443,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     }
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid));
     debug_sync(ctx, "tiler: plan_and_seed");
-    if (!white && S.pf.d_feat && !S.pf.launched) OBIA_TRY(prefetch_white_launch(ctx, S, true));
+    if (!white && S.pf.b.d_feat && !S.pf.launched) OBIA_TRY(prefetch_white_launch(ctx, S, true));
     const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
     unsigned *const mask4 = b.d_mask4;        // (null: the sweeps pack the mask above the mark)
     OBIA_TRY(slic_run_sweeps(ctx, b));   // (the orphan flag is looked at after the connectivity stage's own synchronisation)
@@ -491,10 +454,8 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         std::vector<CcProblem> cps(np);
         for (int p = 0; p < np; ++p) {
             const SlicProblem &P = b.probs[p];
-            const double segment_size = P.K > 0 ? (double)P.n_valid / (double)P.K : 1.0;
-            const double mxd = S.sp.max_size_factor * segment_size;
-            const int mx = mxd >= 2147483647.0 ? 2147483647 : (int)mxd;
-            cps[p] = CcProblem{P.H, P.W, P.pix_off, (int)(S.sp.min_size_factor * segment_size), mx > 0 ? mx : 1};
+            const auto [min_size, max_size] = slic_cc_sizes(S.sp.min_size_factor, S.sp.max_size_factor, P.n_valid, P.K);
+            cps[p] = CcProblem{P.H, P.W, P.pix_off, min_size, max_size};
         }
         OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve));
         bool repeat = false;
@@ -643,6 +604,8 @@ static int tiler_init(obia_ctx *ctx, TileState &S, const float *img, const uint8
     if (cap > 0x7ffffff0LL) { set_error("too many segments for int32 ids"); return OBIA_E_INVALID; }
     S.H = H; S.W = W; S.C = C; S.Hg = Hg; S.row0 = row0; S.img = img; S.inmask = mask; S.G = labels; S.tp = *tp; S.sp = *sp;
     S.id_cap = (int)cap; S.next_id = 1;
+    slic_batch_settings(S.settings, *sp, C, 1, true);   // the tiler always hands a mask to slic (tiling.py:137-143): maskSLIC structure
+    S.settings.start_label = 1;                         // (labels local to a tile; the raster's ids are the tiler's own)
     S.seg_size = A.get<unsigned>((size_t)cap);
     S.inside = A.get<unsigned>((size_t)cap);
     S.alive = A.get<uint8_t>((size_t)cap);
@@ -695,53 +658,42 @@ static int prefetch_white_plan(obia_ctx *ctx, TileState &S, int white_order) {
     TileState::PreFeat &pf = S.pf;
     pf = TileState::PreFeat();
     if (S.sp.sigma_zyx[0] > 0.0 || S.sp.sigma_zyx[1] > 0.0 || S.sp.sigma_zyx[2] > 0.0) return OBIA_OK;   // Gaussian pre-smoothing: per-batch features (slic_prepare_features holds the smoothing passes)
+    SlicBatch b = S.settings;
     for (int cls = 0; cls < (white_order == 1 ? 2 : 1); ++cls)
         for (int tj = 0; tj < nty; ++tj) {
             if (white_order == 1 && (tj & 1) != cls) continue;
             for (int ti = 0; ti < ntx; ++ti) {
                 if ((ti + tj) % 2 == 0) continue;
                 const TileWin t = white_window(S, tj, ti);
-                if (t.h > 0 && t.w > 0) pf.wins.push_back(t);
+                if (t.h <= 0 || t.w <= 0) continue;
+                if (t.y0 < 0 || t.y0 + t.h > S.H) return OBIA_OK;   // the batches report the halo error
+                b.windows.push_back(SrcWindow{t.y0, t.x0, t.h, t.w, 0, 0, 0});
             }
         }
-    const size_t NP = pf.wins.size();
+    const size_t NP = b.windows.size();
     if (NP == 0) return OBIA_OK;
-    long long off = 0, foff = 0, boff = 0;
-    const int CP = (S.C + 3) & ~3;
-    pf.windows.resize(NP);
-    for (size_t p = 0; p < NP; ++p) {
-        const TileWin &t = pf.wins[p];
-        if (t.y0 < 0 || t.y0 + t.h > S.H) { pf = TileState::PreFeat(); return OBIA_OK; }   // the batches report the halo error
-        pf.windows[p] = SrcWindow{t.y0, t.x0, t.h, t.w, off, foff, boff};
-        off += (long long)t.h * t.w;
-        foff += feat_block_f4(t.h, t.w, CP);
-        boff += feat_boxes(t.h, t.w);
-        if (t.h > pf.maxh) pf.maxh = t.h;
-    }
-    if ((double)foff * 16.0 > 32.0 * 1024 * 1024 * 1024) { pf = TileState::PreFeat(); return OBIA_OK; }   // too big to hold: per-batch features
+    // too big to hold: per-batch features
+    if (slic_batch_layout(b) != OBIA_OK || (double)b.total_feat_f4 * 16.0 > 32.0 * 1024 * 1024 * 1024) return OBIA_OK;
     Arena &A = ctx->arena;
     const size_t ntot = NP * (size_t)S.C * 2 + 2 * NP;
-    pf.d_windows = A.get<SrcWindow>(NP);
+    b.d_windows = A.get<SrcWindow>(NP);
     pf.d_keys = A.get<unsigned>(ntot);
-    pf.d_feat = A.get<float>(4 * (size_t)foff);
-    if (!pf.d_windows || !pf.d_keys || !pf.d_feat) return OBIA_E_NOMEM;
-    if (slic_use_colour_bound((float)(1.0 / S.sp.compactness), S.C == 3 && S.sp.convert2lab != 0) && !S.sp.slic_zero && !S.sp.exit_on_fixed_point &&
-        (float)S.sp.spacing_zyx[1] == 1.0f && (float)S.sp.spacing_zyx[2] == 1.0f) {
-        pf.d_fbox = A.get<float>((size_t)boff * 2 * CP);
-        if (!pf.d_fbox) return OBIA_E_NOMEM;
+    b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
+    if (!b.d_windows || !pf.d_keys || !b.d_feat) return OBIA_E_NOMEM;
+    if (b.col_lb) {
+        b.d_fbox = A.get<float>((size_t)b.total_boxes * 2 * b.CP);
+        if (!b.d_fbox) return OBIA_E_NOMEM;
     }
     pf.host.resize(ntot);
+    pf.b = std::move(b);
     return OBIA_OK;
 }
 
 static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside) {
     TileState::PreFeat &pf = S.pf;
-    if (pf.launched || !pf.d_feat) return OBIA_OK;
+    if (pf.launched || !pf.b.d_feat) return OBIA_OK;
     pf.launched = true;
-    const size_t NP = pf.wins.size();
-    const int CP = (S.C + 3) & ~3;
-    OBIA_TRY(upload_async(ctx, pf.d_windows, pf.windows.data(), sizeof(SrcWindow) * NP));
-    const int to_lab = (S.C == 3 && S.sp.convert2lab != 0) ? 1 : 0;
+    OBIA_TRY(upload_async(ctx, pf.b.d_windows, pf.b.windows.data(), sizeof(SrcWindow) * pf.b.windows.size()));
     if (beside) {
         // `beside`: on a side stream, forked here and joined in prefetch_white_fetch -- the caller queues the black batch's
         // spatial pre-pass next, a kernel that is bound by vector issue and moves no data, beside this pass, which is bound by HBM
@@ -749,20 +701,18 @@ static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside) {
         hipStream_t side = ctx->side;
         OBIA_HIP_TRY(hipEventRecord(ctx->aux_fork, ctx->stream));
         OBIA_HIP_TRY(hipStreamWaitEvent(side, ctx->aux_fork, 0));
-        OBIA_TRY(slic_features_launch(side, S.C, CP, (int)NP, pf.d_windows, pf.maxh, S.img, S.W, 1, to_lab,
-                                      (float)(1.0 / S.sp.compactness) * slic_prescale((float)(1.0 / S.sp.compactness), 1, to_lab, S.sp.slic_zero != 0), pf.d_feat, pf.d_keys, true, pf.d_fbox));
+        OBIA_TRY(slic_features_launch(side, pf.b, S.img, S.W, pf.d_keys));
         OBIA_HIP_TRY(hipEventRecord(ctx->aux_join, side));
         pf.on_side = true;
         return OBIA_OK;
     }
     ScopedSpan span(ctx, T_FEAT);
-    OBIA_TRY(slic_features_launch(ctx->stream, S.C, CP, (int)NP, pf.d_windows, pf.maxh, S.img, S.W, 1, to_lab,
-                                  (float)(1.0 / S.sp.compactness) * slic_prescale((float)(1.0 / S.sp.compactness), 1, to_lab, S.sp.slic_zero != 0), pf.d_feat, pf.d_keys, true, pf.d_fbox));
+    OBIA_TRY(slic_features_launch(ctx->stream, pf.b, S.img, S.W, pf.d_keys));
     return OBIA_OK;
 }
 
 static int prefetch_white_fetch(obia_ctx *ctx, TileState &S) {
-    if (!S.pf.d_feat) return OBIA_OK;
+    if (!S.pf.b.d_feat) return OBIA_OK;
     OBIA_TRY(prefetch_white_launch(ctx, S));
     if (S.pf.on_side) { OBIA_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0)); S.pf.on_side = false; }
     OBIA_TRY(read_back(ctx, S.pf.host.data(), S.pf.d_keys, S.pf.host.size() * sizeof(unsigned)));
