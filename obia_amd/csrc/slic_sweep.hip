@@ -1304,6 +1304,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, 
     slic_assign_body<CP, MASKED, true, FIXPT, false, true, false>(OBIA_ASSIGN_ARGS);
 }
 
+#include "slic_spatial.hip"   // slic_spatial_kernel: the same sweeps decided by runs on pixel rows
+
 #ifdef OBIA_STAMP
 extern "C" void obia_debug_timeline(unsigned long long *out, int nwaves) {   // 24 qwords per wave, waves of tile t at 4t .. 4t+3
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tl), sizeof(unsigned long long) * 24 * (size_t)nwaves);
@@ -1347,7 +1349,7 @@ struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; 
 template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
-                          const KernelSpan &span, const int *head_cur) {
+                          const KernelSpan &span, const int *head_cur, bool prepass_visits) {
     constexpr int XGH = OBIA_XCD_GROUP;
     const int ntiles = (int)b.total_tiles_all;
     dim3 grid(8 * XGH * (unsigned)((ntiles + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
@@ -1380,9 +1382,15 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
         else LAUNCH_K_(slic_assign_collb_kernel<CP, M>);                                                             \
     } while (0)
 #define LAUNCH_LEAN_(M, F) LAUNCH_K_(slic_prepass_kernel<CP, M, F>)
+    // a spatial-only sweep that stores no labels and keeps no fixed-point cache is decided by runs (slic_spatial.hip); the others,
+    // and all of them under the developer switch, by the pixel-by-pixel kernel
 #define LAUNCH_ASSIGN(M, I)                                                                                          \
     do {                                                                                                             \
-        if ((I) && !accum_color) { if (fp.bin_stamp) LAUNCH_LEAN_(M, true); else LAUNCH_LEAN_(M, false); }           \
+        if ((I) && !accum_color) {                                                                                   \
+            if (fp.bin_stamp) LAUNCH_LEAN_(M, true);                                                                 \
+            else if (store_labels || prepass_visits) LAUNCH_LEAN_(M, false);                                         \
+            else LAUNCH_K_(slic_spatial_kernel<CP>);                                                                 \
+        }                                                                                                            \
         else if (b.slic_zero && !(I)) LAUNCH_ASSIGN_(M, false, false, true);                                         \
         else if (fp.bin_stamp) LAUNCH_ASSIGN_(M, I, true, false);                                                    \
         else if (b.col_lb && b.d_fbox && !(I)) LAUNCH_COLLB_(M);                                                     \
@@ -1534,6 +1542,7 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     }
     if (repeat) OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
     const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
+    const bool prepass_visits = std::getenv("OBIA_PREPASS_VISITS") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prepass_runs.py): the spatial pre-pass by pixel visits, not runs
     OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
     OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
     // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
@@ -1612,11 +1621,11 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
                 unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
                 if (ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
                 switch (b.CP) {
-                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
 #ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
-                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
-                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
-                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur); break;
+                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
+                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
+                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
 #endif
                     default: set_error("bad CP"); return OBIA_E_INVALID;
                 }

@@ -9,7 +9,7 @@ src=${SRC:-slic_sweep}
 cd "$(dirname "$0")/../obia_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -std=c++17 -Wall -Wno-unused-result "$@" -c $src.hip -o ${src}_$name.o 2>&1 | grep -E "error" || true
 objs=""
-for o in context api slic slic_sweep cc zonal tiling quickshift polygons consumers texture; do
+for o in context api slic slic_sweep cc zonal tiling quickshift polygons consumers texture cost; do
     if [ "$o" = "$src" ]; then objs="$objs ${src}_$name.o"; else objs="$objs $o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libobia_hip_$name.so $objs
