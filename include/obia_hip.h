@@ -332,6 +332,41 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
                            int32_t *fmap_dev, int fmap_cap, int32_t *code_of_dev, int32_t *ids_out_dev,
                            int *first_new_out, int *n_new_out, int *max_owner_id_out);
 
+/* ---- seeds (obia/utils/seeds.py): CHM / density peaks and the cost-aware merge of seed points ------------------
+ * Peaks of a float32 (H, W) plane: scipy.ndimage.gaussian_filter(plane, sigma) when sigma > 0 (mode "reflect", float32
+ * intermediate), then plane == maximum_filter(plane, size = 2 * min_dist_px + 1) and plane >= threshold.  A NaN never wins
+ * the maximum and a NaN pixel is never a peak.  min_dist_px <= 32.
+ *   smooth_out  [H][W] float32: the smoothed plane (not written, may be NULL, when sigma == 0)
+ *   flags_out   uint8, H * W rounded up to a multiple of 4096 bytes, 16-byte aligned: 1 = peak
+ *   offsets_out int32 [ceil(H * W / 4096) + 1]: peaks before each 4096-pixel chunk; the last entry is the count
+ *   n_peaks_out (host): the count -- the one read-back.
+ * The gather writes the peaks in row-major order (np.where): row, col, smooth[row, col], plane[row, col]; `smooth` is
+ * `plane` itself when sigma == 0.  Outputs hold n_peaks entries.                                                     */
+int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double sigma, int min_dist_px, float threshold,
+                         float *smooth_out, uint8_t *flags_out, int32_t *offsets_out, int64_t *n_peaks_out);
+int obia_seeds_peaks_gather_dev(obia_ctx *ctx, const float *plane, const float *smooth, const uint8_t *flags, const int32_t *offsets,
+                                int H, int W, int64_t n_peaks, int32_t *rows_out, int32_t *cols_out, float *smooth_val_out,
+                                float *raw_val_out);
+/* Pairwise merge of n <= 2^20 seeds at (xs, ys) (float64, device): D(i, j) of _build_distance_matrix (seeds.py:148-163),
+ * float32, evaluated on the fly and never stored.  cost [H][W] float32 (device); inv6 (host) = the inverse geotransform
+ * a, b, c, d, e, f with col = a x + b y + c, row = d x + e y + f; ts_host [samples] = the interior float32 values of
+ * np.linspace(0, 1, samples + 2) as doubles, samples <= 128.
+ * link : cluster_out[i] (int32, device) = the connected component of i in the graph D <= float32(eps), numbered by smallest
+ *        member -- the labels of DBSCAN(eps, min_samples = 1, metric = "precomputed").  nonneg != 0 promises cost >= 0
+ *        everywhere: with weight >= 0 a pair whose float32(xy_dist) > float32(eps) then skips its gathers (same result).
+ * stats: stats4_out (host) = min, lower middle, upper middle, max of the n (n - 1) / 2 values (np.median is the float32 mean of
+ *        the two middle values); all NaN and *n_nan_out > 0 when any D is NaN.
+ * matrix: the full symmetric n x n matrix for n <= 512 (test hook).                                                    */
+int obia_seeds_pair_link_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
+                             const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host, double eps,
+                             int nonneg, int32_t *cluster_out, int *n_clusters_out);
+int obia_seeds_pair_stats_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
+                              const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host,
+                              float *stats4_out, int64_t *n_nan_out);
+int obia_seeds_pair_matrix_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
+                               const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host,
+                               float *matrix_out);
+
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
  * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of

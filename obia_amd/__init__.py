@@ -4,5 +4,6 @@ from .segmentation import slic, quickshift, create_segments, segments_table, seg
 from .statistics import zonal_stats, create_objects, stats_columns  # noqa: F401
 from .polygons import polygonize, PolygonTable  # noqa: F401
 from .geopackage import write_geopackage, read_geopackage  # noqa: F401
+from .seeds import make_chm_seeds, make_density_seeds, make_canonical_seeds  # noqa: F401
 
 __version__ = "0.1.0"

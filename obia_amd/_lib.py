@@ -72,6 +72,12 @@ _SIGNATURES = {
     "obia_cost_normalise_dev": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
     "obia_cost_edge_count_dev": (_I, [_P, _P, _I, _I, _P]),
     "obia_cost_combine_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "obia_seeds_peaks_dev": (_I, [_P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_float, _P, _P, _P, _P]),
+    "obia_seeds_peaks_gather_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, ctypes.c_int64, _P, _P, _P, _P]),
+    "obia_seeds_pair_link_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_double, ctypes.c_double, _I, _P, ctypes.c_double, _I, _P,
+                                      ctypes.POINTER(_I)]),
+    "obia_seeds_pair_stats_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_double, ctypes.c_double, _I, _P, _P, _P]),
+    "obia_seeds_pair_matrix_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_double, ctypes.c_double, _I, _P, _P]),
     "obia_polygon_count_i32_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_polygon_rings_i32_dev": (_I, [_P, _P, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
     "obia_quickshift_f32": (_I, [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P, ctypes.POINTER(_I)]),

@@ -27,7 +27,8 @@ _SRS_ROWS = [
 
 
 def _wkb_envelope(wkb):
-    """(minx, maxx, miny, maxy) of a little-endian WKB Polygon / MultiPolygon (the two types obia_amd.polygons emits)."""
+    """(minx, maxx, miny, maxy) of a little-endian WKB Polygon / MultiPolygon (the two types obia_amd.polygons emits) or
+    Point (obia_amd.seeds)."""
     def poly(off):
         nr, = struct.unpack_from("<I", wkb, off + 5)
         off += 9
@@ -41,6 +42,9 @@ def _wkb_envelope(wkb):
             off += 4 + 16 * n
         return off, lo, hi
     t, = struct.unpack_from("<I", wkb, 1)
+    if t == 1:
+        x, y = struct.unpack_from("<2d", wkb, 5)
+        return x, x, y, y
     if t == 3:
         _, lo, hi = poly(0)
     elif t == 6:
@@ -62,10 +66,10 @@ def gpkg_blob(wkb, srs_id):
 
 
 def write_geopackage(path, wkb_list, columns, table="segments", srs_epsg=None, geometry_type=None, srs_wkt=None):
-    """Write one feature table.  ``wkb_list``: WKB bytes per feature; ``columns``: dict name -> sequence (ints or floats)
-    of the same length.  ``srs_epsg``: EPSG code of the coordinates (None: undefined cartesian, srs_id -1).
+    """Write one feature table.  ``wkb_list``: WKB bytes per feature; ``columns``: dict name -> sequence (ints, floats or
+    strings) of the same length.  ``srs_epsg``: EPSG code of the coordinates (None: undefined cartesian, srs_id -1).
     ``geometry_type``: the name registered in gpkg_geometry_columns; None = "POLYGON" when every blob is a WKB Polygon,
-    "MULTIPOLYGON" when every blob is a MultiPolygon, "GEOMETRY" for a mix (quickshift labels can come out as MultiPolygons:
+    "MULTIPOLYGON" when every blob is a MultiPolygon, "POINT" when every blob is a Point, "GEOMETRY" for a mix (quickshift labels can come out as MultiPolygons:
     strict readers reject a POLYGON table that holds one).  ``srs_wkt``: the WKT definition of a non-4326 EPSG code; without it
     the row says "undefined" and a reader resolves the CRS from organization / organization_coordsys_id (most do)."""
     n = len(wkb_list)
@@ -100,12 +104,12 @@ def write_geopackage(path, wkb_list, columns, table="segments", srs_epsg=None, g
                          None if srs_wkt else "definition not carried by the writer: resolve by organization / organization_coordsys_id"))
         if geometry_type is None:
             kinds = {struct.unpack_from("<I", w, 1)[0] & 0xff for w in wkb_list}
-            geometry_type = "POLYGON" if kinds <= {3} else ("MULTIPOLYGON" if kinds == {6} else "GEOMETRY")
+            geometry_type = "POLYGON" if kinds <= {3} else ("MULTIPOLYGON" if kinds == {6} else "POINT" if kinds == {1} else "GEOMETRY")
         names = list(columns)
         types = {}
         for k in names:
             a = np.asarray(columns[k])
-            types[k] = "INTEGER" if a.dtype.kind in "iub" else "REAL"
+            types[k] = "INTEGER" if a.dtype.kind in "iub" else ("TEXT" if a.dtype.kind in "USO" else "REAL")
         cols_sql = "".join(f', "{k}" {types[k]}' for k in names)
         cur.execute(f'CREATE TABLE "{table}" (fid INTEGER PRIMARY KEY AUTOINCREMENT NOT NULL, geom BLOB{cols_sql})')
         blobs = [gpkg_blob(w, srs_id) for w in wkb_list]
@@ -117,7 +121,10 @@ def write_geopackage(path, wkb_list, columns, table="segments", srs_epsg=None, g
         pycols = []
         for k in names:
             a = np.asarray(columns[k])
-            pycols.append([int(v) for v in a] if types[k] == "INTEGER" else [None if v != v else float(v) for v in a])
+            if types[k] == "TEXT":
+                pycols.append([str(v) for v in a])
+            else:
+                pycols.append([int(v) for v in a] if types[k] == "INTEGER" else [None if v != v else float(v) for v in a])
         q = f'INSERT INTO "{table}" (geom{"".join(", " + chr(34) + k + chr(34) for k in names)}) VALUES ({",".join("?" * (1 + len(names)))})'
         cur.executemany(q, zip(blobs, *pycols))
         cur.execute("INSERT INTO gpkg_contents (table_name, data_type, identifier, min_x, min_y, max_x, max_y, srs_id) VALUES (?,?,?,?,?,?,?,?)",
