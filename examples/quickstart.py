@@ -6,7 +6,7 @@
     create_tiled_segments()  -> the same for a raster that is processed in tiles (obia.utils.tiling, :62-291)
     slic_edge(), label_segments() -> the consumers of the label raster       (utils/cost.py:44-48, utils/utils.py:12-34)
 
-Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv and quickstart_segments.geojson next to itself.
+Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
     python examples/quickstart.py
 """
 import json
@@ -20,6 +20,7 @@ from obia_amd import segment, create_objects                       # noqa: E402
 from obia_amd.tiling import create_tiled_segments                  # noqa: E402
 from obia_amd.consumers import slic_edge, label_segments           # noqa: E402
 from obia_amd.polygons import polygonize                           # noqa: E402
+from obia_amd.cost import rasterise_slic_gpkg                      # noqa: E402
 
 
 class Image:
@@ -53,8 +54,12 @@ def main():
     # 3. the tiled driver (checkerboard tiles with overlap), then texture columns for one band
     mask = np.ones((H, W), np.uint8)
     mask[:40, :60] = 0
-    labels, n = create_tiled_segments(data, input_mask=mask, tile_size=256, buffer=32, crown_radius=5, pixel_size=(0.5, 0.5),
-                                      compactness=0.25)
+    here = os.path.dirname(os.path.abspath(__file__))
+    labels, n = create_tiled_segments(data, output_dir=here, input_mask=mask, tile_size=256, buffer=32, crown_radius=5,
+                                      pixel_size=(0.5, 0.5), affine_transformation=image.affine_transformation, compactness=0.25)
+    # ... which wrote segments.gpkg like the reference; the way back to the label raster (what make_cost_surface(slic=...) takes)
+    profile = {"height": H, "width": W, "transform": (0.5, 0.0, 300000.0, 0.0, -0.5, 2200000.0)}      # rasterio order
+    assert np.array_equal(rasterise_slic_gpkg(os.path.join(here, "segments.gpkg"), profile), labels)
     table = create_objects(labels, image, spectral_bands=[0], textural_bands=[0], calculate_textural=True)
     print(f"create_tiled_segments(): {n} segments; create_objects(): columns {list(table.columns)[:5]} ...")
 

@@ -181,6 +181,26 @@ int obia_polygon_rings_i32_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, i
                                int64_t cap_rings, int64_t cap_vertices, int32_t *ring_label, uint8_t *ring_is_hole,
                                int64_t *ring_offset, int32_t *xy, int64_t *n_rings_out, int64_t *n_vertices_out);
 
+/* ---- row f4, the way back: polygon rings -> label raster -----------------------------------------------------------
+ * Replaces rasterio.features.rasterize(shapes, fill, all_touched=False) of rasterise_slic_gpkg (utils/cost.py:51-86).
+ *   xy_pix       (V, 2) double PIXEL coordinates (x = column axis, y = row axis, (0,0) = top-left corner of the raster)
+ *   ring_offset  (n_rings + 1) int64, starts at 0, never decreases; ring r owns vertices [ring_offset[r], ring_offset[r+1])
+ *                and is closed by an edge from its last vertex to its first (a repeated first vertex adds nothing)
+ *   ring_shape   (n_rings) int32, non-decreasing: the shape every ring belongs to (exterior rings and holes alike)
+ *   shape_value  (n_shapes) int32 burn value of every shape
+ *   out_hw       (H, W) int32 on the device
+ * An edge (x0,y0)->(x1,y1) counts for the pixel centre (xc, yc) = (c + 0.5, r + 0.5) when (y0 <= yc) != (y1 <= yc) and
+ * x0 + (yc - y0) * (x1 - x0) / (y1 - y0) <= xc (doubles, this order, no contraction); a shape covers the pixel iff an odd
+ * number of its edges count; the pixel gets the value of the LAST covering shape in input order, else `fill`.  Rings may
+ * lie outside the raster.  H * W, V, n_rings or n_shapes at or above 2^31: OBIA_E_UNSUPPORTED.
+ * obia_rasterize_info (developer aid): info[0], info[1] = shapes the last call of this process handled one wave each /
+ * sent to the banded large-shape path; info[2], info[3] = the most edges and the longest bounding-box side (pixel
+ * centres) of the one-wave path.                                                                                      */
+int obia_rasterize_polygons_dev(obia_ctx *ctx, const double *xy_pix, const int64_t *ring_offset, int64_t n_rings,
+                                const int32_t *ring_shape, const int32_t *shape_value, int64_t n_shapes,
+                                int H, int W, int32_t fill, int32_t *out_hw);
+int obia_rasterize_info(int64_t info[4]);
+
 /* ---- next row f4: consumers of the label raster -----------------------------------------------------------------
  * obia_label_edges_u8_dev   : `slic_edge` (obia/utils/cost.py:44-48): edge[y][x] = 1 when the label differs from the
  *                             pixel below or from the pixel to the right; n_edge_out = number of edge pixels (the

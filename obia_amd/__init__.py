@@ -2,7 +2,8 @@
 iosefa/obia (segment(method="slic"), create_tiled_segments).  See DESIGN.md / INTEGRATION.md."""
 from .segmentation import slic, quickshift, create_segments, segments_table, segment, Segments, normalize_band  # noqa: F401
 from .statistics import zonal_stats, create_objects, stats_columns  # noqa: F401
-from .polygons import polygonize, PolygonTable  # noqa: F401
+from .polygons import polygonize, rasterize, PolygonTable  # noqa: F401
+from .cost import rasterise_slic_gpkg  # noqa: F401
 from .geopackage import write_geopackage, read_geopackage  # noqa: F401
 from .seeds import make_chm_seeds, make_density_seeds, make_canonical_seeds  # noqa: F401
 

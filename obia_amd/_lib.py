@@ -80,6 +80,8 @@ _SIGNATURES = {
     "obia_seeds_pair_matrix_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_double, ctypes.c_double, _I, _P, _P]),
     "obia_polygon_count_i32_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_polygon_rings_i32_dev": (_I, [_P, _P, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
+    "obia_rasterize_polygons_dev": (_I, [_P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _I, _I, ctypes.c_int32, _P]),
+    "obia_rasterize_info": (_I, [ctypes.POINTER(ctypes.c_int64)]),
     "obia_quickshift_f32": (_I, [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P, ctypes.POINTER(_I)]),
     "obia_quickshift_f32_dev": (_I, [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P, ctypes.POINTER(_I)]),
     "obia_quickshift_stages_f32_dev": (_I, [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P,

@@ -4,8 +4,9 @@ float64, the surface float32).  The layers run in libobia_hip.so (cost.hip); the
 from the order statistics the device selects (np.nanpercentile's linear method, restated operation for operation) and
 builds the entropy term table with libm ``log``.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out.
 
-The label raster stands for ``segments.gpkg`` as in obia_amd.consumers: rasterising polygons is not built, and neither is
-the nodata mask of the reference's masked WorldView-3 read ("Cost surface")."""
+``make_cost_surface`` takes the label raster; ``rasterise_slic_gpkg`` (cost.py:51-86) makes that raster from a stored
+``segments.gpkg`` on the GPU (obia_amd.polygons.rasterize).  The nodata mask of the reference's masked WorldView-3 read is
+not built (DESIGN.md, "Cost surface")."""
 import ctypes
 import math
 import os
@@ -249,6 +250,91 @@ def texture_entropy(pan, ctx=None, _raw=False):
     return _out(out, is_t)
 
 
+# ------------------------------------------------------------------------------------------- segments.gpkg -> label raster
+def _profile_transform(t):
+    """rasterio's ``profile["transform"]`` -- six numbers (a, b, xoff, d, e, yoff) or an object with attributes a..f -- as this
+    package's [a, b, d, e, xoff, yoff]."""
+    if all(hasattr(t, k) for k in "abcdef"):
+        t = (t.a, t.b, t.c, t.d, t.e, t.f)
+    try:
+        a, b, xoff, d, e, yoff = [float(v) for v in t][:6]
+    except Exception:
+        raise ValueError("tgt_profile['transform'] must be six numbers (a, b, xoff, d, e, yoff) or an Affine") from None
+    return [a, b, d, e, xoff, yoff]
+
+
+def _wkb_is_empty(wkb):
+    import struct
+    if wkb is None or len(wkb) < 9:
+        return True
+    kind, n = struct.unpack_from("<II", wkb, 1)
+    if kind == 3:
+        return n == 0 or struct.unpack_from("<I", wkb, 9)[0] == 0
+    return n == 0
+
+
+def rasterise_slic_gpkg(gpkg_path, tgt_profile, ctx=None, as_tensor=False):
+    """Rasterise the polygons of a ``segments.gpkg`` (column ``segment_id``) onto the target grid: obia/utils/cost.py:51-86
+    without geopandas / rasterio -- the file is read with obia_amd.geopackage, the polygons are burned on the GPU
+    (obia_amd.polygons.rasterize: fill 0, pixel centres, later rows over earlier ones).
+
+    ``tgt_profile``: mapping with ``height``, ``width`` and ``transform`` (rasterio order (a, b, xoff, d, e, yoff), or an object
+    with attributes a..f); optional ``bounds`` (west, south, east, north): only shapes whose envelope meets them are burned (a
+    superset of the reference's bbox read -- shapes outside burn nothing); optional ``crs``: must name the layer's EPSG code,
+    reprojection is not built (NotImplementedError).  Rows whose ``segment_id`` ``int()`` cannot convert and empty geometries
+    are skipped.  Returns the (H, W) int32 label raster ``make_cost_surface(slic=...)`` takes (a CUDA tensor with
+    ``as_tensor=True``)."""
+    from .geopackage import read_geopackage, _wkb_envelope
+    from .segmentation import _epsg_of
+    try:
+        H, W = int(tgt_profile["height"]), int(tgt_profile["width"])
+        transform = tgt_profile["transform"]
+    except (KeyError, TypeError):
+        raise ValueError("tgt_profile must be a mapping with height, width and transform") from None
+    if H <= 0 or W <= 0:
+        raise ValueError(f"tgt_profile height and width must be positive, got {H} x {W}")
+    aff = _profile_transform(transform)
+    bounds = tgt_profile.get("bounds")
+    if bounds is not None:
+        try:
+            west, south, east, north = [float(v) for v in bounds]
+        except Exception:
+            raise ValueError("tgt_profile['bounds'] must be (west, south, east, north)") from None
+    wkbs, cols, srs_id = read_geopackage(os.fspath(gpkg_path), table="segments")
+    if "segment_id" not in cols:
+        raise ValueError("the segments table has no 'segment_id' column")
+    rows = list(zip(wkbs, cols["segment_id"]))
+    if bounds is not None:
+        kept = []
+        for w, seg in rows:
+            if _wkb_is_empty(w):
+                continue
+            minx, maxx, miny, maxy = _wkb_envelope(w)
+            if maxx >= west and minx <= east and maxy >= south and miny <= north:
+                kept.append((w, seg))
+        rows = kept
+    if not rows:
+        raise SystemExit("SLIC GPKG has no polygons over this tile.")
+    crs = tgt_profile.get("crs")
+    if crs is not None:
+        want = _epsg_of(getattr(crs, "to_epsg", lambda: crs)())
+        if want is None or want != srs_id:
+            raise NotImplementedError(f"the layer's srs_id is {srs_id} and the target crs is {crs!r}: reprojection is not built")
+    shapes, ids = [], []
+    for w, seg in rows:
+        try:
+            seg_id = int(seg)
+        except Exception:
+            continue
+        if not _wkb_is_empty(w):
+            shapes.append(w)
+            ids.append(seg_id)
+    if not shapes:
+        raise SystemExit("No valid SLIC polygons with 'segment_id' found.")
+    from .polygons import rasterize
+    return rasterize(shapes, (H, W), aff, values=np.asarray(ids, np.int64), fill=0, ctx=ctx, as_tensor=as_tensor)
+
+
 # ------------------------------------------------------------------------------------------------------ the cost surface
 def _read_band(path, idx=1):
     """read_band (cost.py:14-18) through GDAL: band ``idx`` as float32, nodata -> NaN."""
@@ -302,7 +388,8 @@ def make_cost_surface(wv3, chm, out=None, slic=None, weights=(0.5, 0.25, 0.25, 0
     wv3  : (H, W, 8) array or CUDA tensor (C, B, G, Y, R, RE, N1, N2), an object with ``img_data``, or a path (GDAL).
     chm  : (H, W) canopy height model, NaN = nodata; array, tensor or path.
     slic : (H, W) label raster (the rasterised ``segments.gpkg``), a path to one, or None: then the first three weights are
-           renormalised, the edge term is 0 and a warning says so.  A .gpkg path raises NotImplementedError.
+           renormalised, the edge term is 0 and a warning says so.  A .gpkg path raises NotImplementedError: to use a
+           GeoPackage, pass ``slic=rasterise_slic_gpkg(path, profile)``.
     out  : GeoTIFF path (GDAL) or None.  The surface is returned either way (a CUDA tensor when wv3 is one).
     ``_layers``: a dict that receives the (lo, hi) each layer was stretched with (test hook).
     """

@@ -138,7 +138,7 @@ def write_geopackage(path, wkb_list, columns, table="segments", srs_epsg=None, g
 
 def read_geopackage(path, table="segments"):
     """Read a feature table back: (list of WKB bytes, dict column -> list, srs_id).  Checks the container's magic numbers,
-    the metadata rows and every blob's GeoPackageBinary header."""
+    the metadata rows and every blob's GeoPackageBinary header.  A NULL geometry comes back as None."""
     con = sqlite3.connect(path)
     try:
         cur = con.cursor()
@@ -156,6 +156,11 @@ def read_geopackage(path, table="segments"):
     wkbs, cols = [], {c: [] for c in others}
     for r in rows:
         b = r[0]
+        if b is None:
+            wkbs.append(None)
+            for c, v in zip(others, r[1:]):
+                cols[c].append(v)
+            continue
         if b[:2] != b"GP":
             raise ValueError("geometry blob without the GeoPackageBinary magic")
         flags = b[3]

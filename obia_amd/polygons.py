@@ -208,3 +208,159 @@ def _assign_parts(xy_pix, off, ring_label, ring_hole):
 def _shoelace(ring):
     x, y = ring[:, 0], ring[:, 1]
     return 0.5 * float(np.sum(x[:-1] * y[1:] - x[1:] * y[:-1]))
+
+
+# ------------------------------------------------------------------------------------------------- polygons -> label raster
+def to_pixel(xy, affine_transformation=None):
+    """Map coordinates -> pixel coordinates (x = column axis, y = row axis, (0, 0) = top-left corner of the raster) on the
+    host in NumPy float64: ``col = ra*x + rb*y + rc``, ``row = rd*x + re*y + rf`` with the six numbers of
+    :func:`obia_amd.seeds.invert_affine`.  ``None`` means the coordinates are pixel coordinates already.  This is the one
+    place the transform is applied, so the rasteriser and anything that checks it start from the same bits."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    if affine_transformation is None:
+        return xy
+    from .seeds import invert_affine
+    if len(affine_transformation) != 6:
+        raise ValueError("affine_transformation must hold six values [a, b, d, e, xoff, yoff]")
+    ra, rb, rc, rd, re, rf = invert_affine(affine_transformation)
+    x, y = xy[:, 0], xy[:, 1]
+    return np.stack([ra * x + rb * y + rc, rd * x + re * y + rf], axis=1)
+
+
+def _rings_of_wkb(wkbs):
+    """(xy (V, 2) float64, ring_offset, ring_shape) of a sequence of little-endian WKB Polygon / MultiPolygon blobs: one shape
+    per blob, its rings (exterior rings and holes of all parts) in file order."""
+    from .geopackage import wkb_rings
+    chunks, lens, shape = [], [], []
+    for i, w in enumerate(wkbs):
+        if not isinstance(w, (bytes, bytearray, memoryview)):
+            raise ValueError(f"shape {i} is not WKB bytes")
+        w = bytes(w)
+        if len(w) < 9 or w[0] != 1 or struct.unpack_from("<I", w, 1)[0] not in (3, 6):
+            raise ValueError(f"shape {i} is not a little-endian WKB Polygon or MultiPolygon")
+        try:
+            parts = wkb_rings(w)
+        except (struct.error, ValueError) as e:
+            raise ValueError(f"shape {i}: truncated WKB") from e
+        for part in parts:
+            for ring in part:
+                chunks.append(ring)
+                lens.append(len(ring))
+                shape.append(i)
+    xy = np.concatenate(chunks) if chunks else np.zeros((0, 2), np.float64)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return xy, off, np.asarray(shape, np.int32)
+
+
+def _is_tensor(x):
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _host(x):
+    return x.cpu().numpy() if _is_tensor(x) else np.asarray(x)
+
+
+def rasterize(shapes, out_shape, affine_transformation=None, values=None, fill=0, ctx=None, as_tensor=False):
+    """Burn polygons into an (H, W) int32 raster: ``rasterio.features.rasterize(shapes, out_shape, fill=fill,
+    all_touched=False)`` (rasterise_slic_gpkg, obia/utils/cost.py:78-85) on the GPU -- the way back from :func:`polygonize`.
+
+    ``shapes``: a :class:`PolygonTable` (one shape per polygon, in table order), a sequence of little-endian WKB ``Polygon`` /
+    ``MultiPolygon`` bytes (one shape per blob), or the ring arrays themselves as a tuple ``(xy (V, 2), ring_offset (R + 1,),
+    ring_shape (R,))`` of NumPy arrays or CUDA tensors, ``ring_shape`` non-decreasing.  ``values``: the burn value of every shape
+    (int32); default ``table.labels`` for a table and 1..N otherwise.  ``affine_transformation``: [a, b, d, e, xoff, yoff] of
+    the coordinates as elsewhere (inverted and applied on the host in float64, :func:`to_pixel`); None: the coordinates are
+    pixel-corner coordinates.
+
+    The rule: pixel (r, c) has its centre at (c + 0.5, r + 0.5); an edge (x0, y0) -> (x1, y1) of a shape
+    counts when ``(y0 <= yc) != (y1 <= yc)`` and ``x0 + (yc - y0) * (x1 - x0) / (y1 - y0) <= xc``; the shape covers the pixel
+    iff an odd number of its edges count (even-odd over all its rings, the ring roles are not used).  A pixel gets the value of
+    the last shape in input order that covers it, ``fill`` when none does.  Rings may lie partly or wholly outside the raster.
+    Returns an (H, W) int32 NumPy array, or a CUDA tensor with ``as_tensor=True``.  There is no CPU path.
+    """
+    try:
+        H, W = (int(v) for v in out_shape)
+    except Exception:
+        raise ValueError(f"out_shape must be (H, W), got {out_shape!r}") from None
+    if H <= 0 or W <= 0 or tuple(out_shape) != (H, W):
+        raise ValueError(f"out_shape must be two positive integers, got {out_shape!r}")
+    if H * W >= 2 ** 31:
+        raise NotImplementedError(f"rasters of 2^31 pixels or more are not supported (got {H} x {W})")
+    on_device = False
+    if isinstance(shapes, PolygonTable):
+        xy, off, n_shapes = shapes.xy, shapes.ring_offset, len(shapes)
+        rshape = np.searchsorted(shapes.labels, shapes.ring_label).astype(np.int32)
+        default_values = shapes.labels
+    elif isinstance(shapes, tuple) and len(shapes) == 3 and not isinstance(shapes[0], (bytes, bytearray, memoryview)):
+        xy, off, rshape = shapes
+        on_device = any(_is_tensor(t) for t in shapes)
+        if on_device and not all(_is_tensor(t) and t.is_cuda for t in shapes):
+            raise ValueError("ring arrays must be all NumPy arrays or all CUDA tensors")
+        if not on_device:
+            xy, off, rshape = np.asarray(xy), np.asarray(off), np.asarray(rshape)
+        if len(xy.shape) != 2 or xy.shape[1] != 2:
+            raise ValueError(f"xy must be (V, 2), got shape {tuple(xy.shape)}")
+        if len(off.shape) != 1 or len(rshape.shape) != 1 or off.shape[0] != rshape.shape[0] + 1:
+            raise ValueError("ring_offset must hold one more entry than ring_shape")
+        n_shapes = (int(rshape.max()) + 1) if rshape.shape[0] else 0
+        if values is not None:
+            n_shapes = len(values)
+        default_values = None
+    else:
+        if isinstance(shapes, (bytes, bytearray, str)) or not hasattr(shapes, "__len__"):
+            raise ValueError("shapes must be a PolygonTable, a sequence of WKB bytes or (xy, ring_offset, ring_shape)")
+        xy, off, rshape = _rings_of_wkb(shapes)
+        n_shapes = len(shapes)
+        default_values = None
+    if values is None:
+        values = default_values if default_values is not None else np.arange(1, n_shapes + 1)
+    values = _host(values)
+    if values.ndim != 1 or len(values) != n_shapes:
+        raise ValueError(f"values holds {values.size} entries for {n_shapes} shapes")
+    if values.size and (values.dtype.kind not in "iub" or values.min() < -2 ** 31 or values.max() >= 2 ** 31):
+        raise ValueError("values must be integers that fit int32")
+    if not -2 ** 31 <= int(fill) < 2 ** 31:
+        raise ValueError("fill must fit int32")
+    # the ring tables are small: check them on the host whichever side they live on
+    off_h, rshape_h = _host(off).astype(np.int64), _host(rshape).astype(np.int64)
+    if off_h[0] != 0 or off_h[-1] != xy.shape[0] or (np.diff(off_h) < 0).any():
+        raise ValueError("ring_offset must start at 0, never decrease and end at the number of vertices")
+    if rshape_h.size and ((np.diff(rshape_h) < 0).any() or rshape_h[0] < 0 or rshape_h[-1] >= n_shapes):
+        raise ValueError("ring_shape must not decrease and must lie in [0, number of shapes)")
+    if max(xy.shape[0], n_shapes, rshape_h.size) >= 2 ** 31:
+        raise NotImplementedError("2^31 or more vertices, rings or shapes are not supported")
+    if not on_device and not np.isfinite(np.asarray(xy, dtype=np.float64)).all():
+        raise ValueError("vertex coordinates must be finite")
+    if affine_transformation is not None or not on_device:
+        xy = to_pixel(_host(xy), affine_transformation)       # (raises ValueError for a singular or malformed transform)
+
+    if torch is None:
+        raise ImportError("obia_amd.polygons needs torch for device memory")
+    lib = _lib.load()
+    if on_device:
+        dev = shapes[0].device.index or 0
+        c = ctx or _lib.default_context(dev)
+    else:
+        c = ctx or _lib.default_context(0)
+        dev = c.device
+    d = f"cuda:{dev}"
+    xy_d = torch.as_tensor(xy, device=d).to(torch.float64).contiguous()
+    if on_device and not bool(torch.isfinite(xy_d).all()):
+        raise ValueError("vertex coordinates must be finite")
+    off_d = torch.as_tensor(off_h, device=d)
+    rs_d = torch.as_tensor(rshape_h.astype(np.int32), device=d)
+    val_d = torch.as_tensor(np.ascontiguousarray(values, dtype=np.int32), device=d)
+    out = torch.empty((H, W), dtype=torch.int32, device=d)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_rasterize_polygons_dev(c.handle, xy_d.data_ptr() if xy_d.numel() else None, off_d.data_ptr(),
+                                               int(rs_d.numel()), rs_d.data_ptr() if rs_d.numel() else None,
+                                               val_d.data_ptr() if val_d.numel() else None, n_shapes, H, W, int(fill),
+                                               out.data_ptr()))
+    return out if as_tensor else out.cpu().numpy()
+
+
+def rasterize_info():
+    """Developer aid: {"small", "large"} = shapes the last :func:`rasterize` of this process handled one wave each / through the
+    banded large-shape path, and the limits of the one-wave path ("max_edges", "max_side" in pixel centres)."""
+    info = (ctypes.c_int64 * 4)()
+    _lib.check(_lib.load().obia_rasterize_info(info))
+    return {"small": int(info[0]), "large": int(info[1]), "max_edges": int(info[2]), "max_side": int(info[3])}
