@@ -132,6 +132,41 @@ int obia_slic_seeded_f32_dev(obia_ctx *ctx, const float *img_hwc, int H, int W, 
                              const obia_slic_params *params, const obia_slic_seeds *seeds, int stage,
                              int32_t *labels_out, int *n_out);
 
+/* SLIC stage by stage (tests and diagnostics): the call of obia_slic_assign_only_f32_dev -- the same function runs both, so the same
+ * settings, layout, candidate lists, colour bound and repeat on orphans -- that also hands out what the stages produced.  `seeds` is
+ * nullable (the library's seeding rule).  Every pointer of `stages` is a nullable DEVICE buffer; the scalars are written on return.
+ *   features   (H, W, C) float32: the features the sweeps read -- normalise -> Lab -> Gaussian -> * float32(1 / compactness) -- taken
+ *              out of the sweeps' own plane layout and divided by `prescale` (a power of two: exact)
+ *   seeds_yx   (K, 2) float32: the initial centroid positions
+ *   centroids  (K, 2 + C) float32: cy, cx, colours / prescale of the records the LAST sweep assigned from.  With max_num_iter = N these
+ *              are the centroids of sweep N and labels_pre the labels of sweep N; the sums are integers, so a run with another N
+ *              reproduces the earlier sweeps exactly.  Needs max_num_iter >= 1.
+ *   labels_pre (H, W) int32: labels before connectivity
+ *   centroid_capacity  rows that seeds_yx / centroids hold (K above it is OBIA_E_INVALID; H * W always suffices)
+ *   prepass_only  1 with a mask: stop after the spatial-only pre-pass, so that centroids / labels_pre are those of its last sweep
+ *              (sweep max_num_iter, or prepass_iters when that is given) (labels_pre: what that sweep assigns; the full run never stores them).  The centroids the colour pass
+ *              starts from are `centroids` of a full run with max_num_iter = 1.
+ *   prepass_iters  with a mask: sweeps of the spatial pre-pass; 0 = max_num_iter, as every other entry point runs it.  Colour sweeps
+ *              N - 1 and N after the SAME pre-pass come from two runs with this count fixed and max_num_iter = N - 1, N.
+ *   K, step, prescale, fscale  out: centroid count; `step` of _slic_cython; the power of two folded into the planes and the centroid
+ *              colours; the power of two the colour sums are truncated at, in units of the handed-out features: a pixel adds
+ *              (int)(feature * fscale) to its centroid's 64-bit sum -- the largest power of two with max|feature| * fscale < 2^29.  */
+typedef struct obia_slic_stages {
+    float *features;
+    float *seeds_yx;
+    float *centroids;
+    int32_t *labels_pre;
+    int32_t centroid_capacity;
+    int32_t prepass_only;
+    int32_t prepass_iters;
+    int32_t K;
+    double step;
+    double prescale;
+    double fscale;
+} obia_slic_stages;
+int obia_slic_stages_f32_dev(obia_ctx *ctx, const float *img_hwc, int H, int W, int C, const uint8_t *mask,
+                             const obia_slic_params *params, const obia_slic_seeds *seeds, obia_slic_stages *stages);
+
 /* ---- B2: zonal-statistics operator ----------------------------------------------------------------
  * Replaces the per-segment loop crop_image_to_bbox -> mask_image_with_polygon ->
  * calculate_spectral_stats (segment_statistics.py:475-491, :143-172; utils/utils.py:37-67), batched

@@ -33,6 +33,14 @@ class SlicSeeds(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class SlicStages(ctypes.Structure):
+    """obia_slic_stages (include/obia_hip.h): stage outputs of obia_slic_stages_f32_dev."""
+    _fields_ = [("features", ctypes.c_void_p), ("seeds_yx", ctypes.c_void_p), ("centroids", ctypes.c_void_p),
+                ("labels_pre", ctypes.c_void_p), ("centroid_capacity", ctypes.c_int32), ("prepass_only", ctypes.c_int32),
+                ("prepass_iters", ctypes.c_int32), ("K", ctypes.c_int32), ("step", ctypes.c_double), ("prescale", ctypes.c_double),
+                ("fscale", ctypes.c_double)]
+
+
 class TilingParams(ctypes.Structure):
     """obia_tiling_params (include/obia_hip.h)."""
     _fields_ = [("crown_radius", ctypes.c_double), ("pixel_width", ctypes.c_double),
@@ -56,6 +64,8 @@ _SIGNATURES = {
     "obia_slic_assign_only_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), _P, ctypes.POINTER(_I)]),
     "obia_slic_seeded_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), ctypes.POINTER(SlicSeeds), _I, _P,
                                       ctypes.POINTER(_I)]),
+    "obia_slic_stages_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), ctypes.POINTER(SlicSeeds),
+                                      ctypes.POINTER(SlicStages)]),
     "obia_enforce_connectivity_i32_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
     "obia_zonal_stats_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "obia_zonal_stats_f32_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),

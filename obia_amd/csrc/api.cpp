@@ -33,9 +33,12 @@ int check_slic_args(const float *img, int H, int W, int C, const obia_slic_param
 
 // Whole-raster SLIC up to the pre-connectivity labels (device pointers).  On return b holds the plan.
 int slic_single(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
-                const obia_slic_params *p, SlicBatch &b, const ExternalSeeds *ext = nullptr) {
+                const obia_slic_params *p, SlicBatch &b, const ExternalSeeds *ext = nullptr, bool prepass_only = false,
+                int prepass_iters = 0) {
     Arena &A = ctx->arena;
     slic_batch_settings(b, *p, C, p->normalize_bands, mask != nullptr);
+    b.prepass_only = prepass_only && b.masked;
+    b.prepass_iter = b.masked ? prepass_iters : 0;
     b.windows.assign(1, SrcWindow{0, 0, H, W, 0, 0, 0});
     OBIA_TRY(slic_batch_layout(b));
     b.d_windows = A.get<SrcWindow>(1);
@@ -90,28 +93,51 @@ static int check_seeds(const obia_slic_seeds *seeds, int H, int W, ExternalSeeds
     return OBIA_OK;
 }
 
-static int slic_assign_only_impl(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
-                                 const obia_slic_params *params, const ExternalSeeds *ext, int32_t *labels_pre_out,
-                                 int *n_centroids_out) {
+// The sweeps of one raster and whatever of their stages the caller asked for: the body of obia_slic_assign_only_f32_dev (labels_pre
+// alone) and of obia_slic_stages_f32_dev.
+static int slic_stages_impl(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
+                            const obia_slic_params *params, const ExternalSeeds *ext, obia_slic_stages *st) {
     OBIA_TRY(check_ctx(ctx));
     OBIA_TRY(check_slic_args(img, H, W, C, params));
-    if (!labels_pre_out) { set_error("null output"); return OBIA_E_INVALID; }
+    if (!st) { set_error("null output"); return OBIA_E_INVALID; }
+    if (st->prepass_iters < 0) { set_error("prepass_iters must be >= 0"); return OBIA_E_INVALID; }
+    if (st->centroids && params->max_num_iter < 1) { set_error("centroids: no sweep ran (max_num_iter = 0)"); return OBIA_E_INVALID; }
     ctx->arena.reset();
     begin_timing(ctx);
     SlicBatch b;
     int rc;
     {
         ScopedSpan total(ctx, T_TOTAL);
-        rc = slic_single(ctx, img, H, W, C, mask, params, b, ext);
-        if (rc == OBIA_OK) {
-            hipError_t e = hipMemcpyAsync(labels_pre_out, b.d_labels, sizeof(int32_t) * (size_t)H * W, hipMemcpyDeviceToDevice, ctx->stream);
+        rc = slic_single(ctx, img, H, W, C, mask, params, b, ext, st->prepass_only != 0, st->prepass_iters);
+        if (rc == OBIA_OK && (st->seeds_yx || st->centroids) && b.probs[0].K > st->centroid_capacity) {
+            set_error("%d centroids, room for %d", b.probs[0].K, st->centroid_capacity);
+            rc = OBIA_E_INVALID;
+        }
+        if (rc == OBIA_OK && st->labels_pre) {
+            hipError_t e = hipMemcpyAsync(st->labels_pre, b.d_labels, sizeof(int32_t) * (size_t)H * W, hipMemcpyDeviceToDevice, ctx->stream);
             if (e != hipSuccess) { set_error("copy failed: %s", hipGetErrorString(e)); rc = OBIA_E_HIP; }
         }
+        if (rc == OBIA_OK && (st->features || st->seeds_yx || st->centroids))
+            rc = slic_stage_outputs(ctx, b, st->features, st->seeds_yx, st->centroids);
     }
     if (rc != OBIA_OK) return rc;
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     resolve_timing(ctx);
-    if (n_centroids_out) *n_centroids_out = b.probs[0].K;
+    st->K = b.probs[0].K;
+    st->step = (double)b.step[0];
+    st->prescale = (double)b.prescale;
+    st->fscale = b.fscale * (double)b.prescale;   // in units of the handed-out features
+    return OBIA_OK;
+}
+
+static int slic_assign_only_impl(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
+                                 const obia_slic_params *params, const ExternalSeeds *ext, int32_t *labels_pre_out,
+                                 int *n_centroids_out) {
+    if (!labels_pre_out) { set_error("null output"); return OBIA_E_INVALID; }
+    obia_slic_stages st{};
+    st.labels_pre = labels_pre_out;
+    OBIA_TRY(slic_stages_impl(ctx, img, H, W, C, mask, params, ext, &st));
+    if (n_centroids_out) *n_centroids_out = st.K;
     return OBIA_OK;
 }
 
@@ -165,6 +191,15 @@ int obia_slic_seeded_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int 
     if (stage == 1) return slic_assign_only_impl(ctx, img, H, W, C, mask, params, &ext, labels_out, n_out);
     if (stage != 0) { set_error("stage must be 0 (full) or 1 (labels before connectivity)"); return OBIA_E_INVALID; }
     return slic_full_impl(ctx, img, H, W, C, mask, params, &ext, labels_out, n_out);
+}
+
+int obia_slic_stages_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
+                             const obia_slic_params *params, const obia_slic_seeds *seeds, obia_slic_stages *stages) {
+    if (!seeds) return slic_stages_impl(ctx, img, H, W, C, mask, params, nullptr, stages);
+    if (H <= 0 || W <= 0) { set_error("bad image shape"); return OBIA_E_INVALID; }
+    ExternalSeeds ext{};
+    OBIA_TRY(check_seeds(seeds, H, W, ext));
+    return slic_stages_impl(ctx, img, H, W, C, mask, params, &ext, stages);
 }
 
 int obia_slic_f32(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,

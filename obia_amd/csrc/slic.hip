@@ -824,6 +824,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     if (ext && nvalid[0] <= 0) { set_error("the mask has no valid pixel"); return OBIA_E_EMPTY; }
     std::vector<SeedGrid> grids(np);
     std::vector<double> stepmax(np);
+    b.step.assign(np, 1.0f);
     int cent_off = 0;
     for (int p = 0; p < np; ++p) {
         SlicProblem &P = b.probs[p];
@@ -903,6 +904,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
         P.ncy = cdiv(P.H, P.sy);
         P.ncx = cdiv(P.W, P.sx);
         const float stepf = (float)stepmax[p];
+        b.step[p] = stepf;
         P.spatial_w = (float)(1.0 / ((double)stepf * (double)stepf)) * (b.prescale * b.prescale);   // (a power of two: exact)
         P.sp_y = (float)b.spacing[1]; P.sp_x = (float)b.spacing[2];   // np.ascontiguousarray(spacing, dtype=image dtype)
         P.direct = b.direct ? 1 : 0;
@@ -936,6 +938,52 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     b.d_acc = A.get<unsigned long long>(acc_q);
     if (!b.d_cent || !b.d_head || !b.d_acc) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * acc_q, ctx->stream));
+    return OBIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// stage outputs (obia_slic_stages_f32_dev)
+// ------------------------------------------------------------------------------------------------
+// quad-row planes -> (H, W, C): the float4 of (quad row y / 4, column x, channel c) sits at
+// feat_off + ((y / 4 * XB + x / 16) * CP + c) * 16 + x % 16 (slic.hpp), its component y % 4 is the pixel's
+__global__ __launch_bounds__(256) void stage_features_kernel(const float *__restrict__ feat, SlicProblem P, int C, int CP, float inv_prescale,
+                                                             float *__restrict__ out) {
+    const long long n = (long long)P.H * P.W * C;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        const long long pix = i / C;
+        const int y = (int)(pix / P.W), x = (int)(pix % P.W);
+        const long long f4 = P.feat_off + (((long long)(y >> 2) * P.XB + (x >> 4)) * CP + c) * 16 + (x & 15);
+        out[i] = feat[4 * f4 + (y & 3)] * inv_prescale;
+    }
+}
+
+// centroid records {cy, cx, window, link, -, colour[CP]} -> rows {cy, cx, colour[C] / prescale}
+__global__ void stage_centroids_kernel(const float *__restrict__ cent, int cent_off, int K, int C, int CP, float inv_prescale,
+                                       float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)K * (2 + C)) return;
+    const int k = (int)(i / (2 + C)), f = (int)(i % (2 + C));
+    const float *rec = cent + (size_t)(cent_off + k) * (CENT_REC + CP);
+    out[i] = f < 2 ? rec[f] : rec[CENT_REC + f - 2] * inv_prescale;
+}
+
+int slic_stage_outputs(obia_ctx *ctx, const SlicBatch &b, float *features, float *seeds_yx, float *centroids) {
+    if (b.nprob != 1 || !b.feat_planes) { set_error("stage outputs: one raster in the plane layout"); return OBIA_E_INVALID; }
+    const SlicProblem &P = b.probs[0];
+    const float inv_prescale = 1.0f / b.prescale;
+    if (features) {
+        const long long n = (long long)P.H * P.W * b.C;
+        long long blocks = (n + 255) / 256;
+        if (blocks > 65535) blocks = 65535;
+        hipLaunchKernelGGL(stage_features_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, b.d_feat, P, b.C, b.CP, inv_prescale, features);
+    }
+    if (seeds_yx && P.K > 0)
+        OBIA_HIP_TRY(hipMemcpyAsync(seeds_yx, b.d_seed + 2 * (size_t)P.cent_off, sizeof(float) * 2 * (size_t)P.K, hipMemcpyDeviceToDevice, ctx->stream));
+    if (centroids && P.K > 0)
+        hipLaunchKernelGGL(stage_centroids_kernel, dim3(cdiv((long long)P.K * (2 + b.C), 256)), dim3(256), 0, ctx->stream, b.d_cent, P.cent_off,
+                           P.K, b.C, b.CP, inv_prescale, centroids);
+    OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
 

@@ -118,6 +118,9 @@ struct SlicBatch {
     float prescale = 1.0f;             // power of two already folded into the feature planes, the spatial weight and the centroid colours (slic_prescale); fscale is what is left
     bool exit_on_fixed_point = false;
     bool slic_zero = false;            // SLIC-zero: colour term scaled by the cluster's largest colour distance so far
+    bool prepass_only = false;         // stage entry only (obia_slic_stages::prepass_only): a masked batch stops after its spatial pre-pass
+    int prepass_iter = 0;              // stage entry only (obia_slic_stages::prepass_iters): sweeps of the pre-pass, 0 = max_iter
+    std::vector<float> step;           // per problem: `step` of _slic_cython, max(steps) of the seeding grid (slic_plan_and_seed)
 };
 
 // Feature preparation for every problem of the batch: per-band min/max of its window, then
@@ -187,6 +190,11 @@ int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid);
 int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b);
 int slic_sweeps_settle(obia_ctx *ctx, bool *repeat);
 int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b);
+
+// What obia_slic_stages_f32_dev hands out of a finished single-raster batch (each pointer nullable, device memory): the features the
+// sweeps read -- de-tiled from the quad-row planes by the layout formula above and divided by b.prescale (a power of two: exact) --
+// as (H, W, C); the seeds (K, 2); the centroid records the last sweep assigned from as (K, 2 + C) rows {cy, cx, colours / prescale}.
+int slic_stage_outputs(obia_ctx *ctx, const SlicBatch &b, float *features, float *seeds_yx, float *centroids);
 
 // Connectivity enforcement on a batch of dense label maps laid out back to back (pix_off); labels come
 // out consecutive over the whole batch, in problem order then raster order of each component's first pixel.

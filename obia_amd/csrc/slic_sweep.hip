@@ -1489,7 +1489,10 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     // the sweep addresses a footprint's pixels as a 64-bit wave-uniform base plus a 32-bit lane offset (16 rows x W x 64 B)
     for (auto &P : b.probs)
         if (P.W >= (1 << 22)) { set_error("rasters / tile windows wider than 4194303 pixels are not supported (got %d)", P.W); return OBIA_E_UNSUPPORTED; }
-    const int passes = b.masked ? 2 : 1;   // maskSLIC: spatial-only pre-pass first (slic_superpixels.py:310-314)
+    const int passes = (b.masked && !b.prepass_only) ? 2 : 1;   // maskSLIC: spatial-only pre-pass first (slic_superpixels.py:310-314)
+    // sweeps of the pre-pass: max_iter like every pass, unless the stage entry asks for another count (obia_slic_stages::prepass_iters)
+    const int pre_iter = (b.masked && b.prepass_iter > 0) ? b.prepass_iter : b.max_iter;
+    const int total_sweeps = b.masked ? pre_iter + (passes - 1) * b.max_iter : b.max_iter;
     const int RQ = acc_record_qwords(b.CP);
     Arena &A = ctx->arena;
     unsigned long long *d_px = A.get<unsigned long long>(513);
@@ -1536,7 +1539,7 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     // stores, such a pixel raises the flag and the caller repeats the batch (slic_sweeps_settle) -- unless the batch has ONE sweep in
     // all, where the fill value is what the reference keeps.  Every other pixel is written by the last sweep (masked ones included):
     // the 1.2 GB fill of a bench batch is skipped on the common path.
-    if (store_all || passes * b.max_iter <= 1) {
+    if (store_all || total_sweeps <= 1) {
         fill_labels(ctx, b);
         debug_sync(ctx, "sweeps: label fill");
     }
@@ -1562,7 +1565,8 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             // by the first sweep of the main pass)
             if (fp.tile_lp) OBIA_HIP_TRY(hipMemsetAsync(fp.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all, ctx->stream));
         }
-        for (int it = 0; it < b.max_iter; ++it) {
+        const int iters = ignore_color ? pre_iter : b.max_iter;
+        for (int it = 0; it < iters; ++it) {
             int *head_cur = b.d_head + (size_t)(sweep_no & 1) * b.total_cells;
             int *head_nxt = b.d_head + (size_t)((sweep_no + 1) & 1) * b.total_cells;
             ++sweep_no;   // sweep ids start at 1
@@ -1609,13 +1613,13 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
 #undef LAUNCH_MAXDIST
             }
             // the update after the very last sweep is never read: skip its accumulation
-            const bool very_last = last_pass && it == b.max_iter - 1;
+            const bool very_last = last_pass && it == iters - 1;
             const int accumulate = very_last ? 0 : 1;
-            const int accum_color = (!ignore_color || it == b.max_iter - 1) ? 1 : 0;
+            const int accum_color = (!ignore_color || it == iters - 1) ? 1 : 0;
             const int store_labels = store_all ? 2 : (very_last ? 1 : 0);   // (see orphan_needs_repeat)
             // the last pre-pass sweep is the only one of its pass that folds colours (they seed the main pass): the
             // caches written by the earlier pre-pass sweeps hold no colour sums, so it evaluates every tile
-            const int use_cache = (ignore_color && it == b.max_iter - 1) ? 0 : 1;
+            const int use_cache = (ignore_color && it == iters - 1) ? 0 : 1;
             {
                 KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
                 unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;

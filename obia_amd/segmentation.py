@@ -189,6 +189,59 @@ def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spac
     return out.astype(np.int64)
 
 
+def _slic_stages(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spacing=None, convert2lab=None,
+                 slic_zero=False, start_label=1, mask=None, *, exit_on_fixed_point=False, ctx=None, seeds=None,
+                 _normalize_bands=False, prepass_only=False, prepass_iters=0):
+    """Test and diagnostic entry (obia_slic_stages_f32_dev): the call of ``slic(..., _stage="pre")`` -- the library runs both through
+    one function -- that also returns what the stages produced.  A NumPy image is copied to cuda:0.  Returns a dict: CUDA tensors
+    ``features`` (H, W, C) float32 as the sweeps read them (divided by ``prescale``), ``seeds_yx`` (K, 2), ``centroids`` (K, 2 + C):
+    cy, cx, colours of the records the LAST sweep assigned from, ``labels_pre`` (H, W) int32; and the numbers ``K``, ``step``,
+    ``prescale``, ``fscale`` (include/obia_hip.h: obia_slic_stages).  ``max_num_iter=N`` gives the centroids and labels of sweep N;
+    with a mask, ``prepass_only=True`` stops after the spatial pre-pass, so that they are those of ITS sweep N, and ``prepass_iters=M`` gives
+    the pre-pass M sweeps whatever ``max_num_iter`` is (0: ``max_num_iter``, as ``slic`` runs it)."""
+    params = make_params(n_segments, compactness, max_num_iter, convert2lab, False, 0.5, 3, slic_zero, start_label, _normalize_bands,
+                         exit_on_fixed_point, sigma, spacing)
+    lib = _lib.load()
+    if not _is_torch(image):
+        image = torch.as_tensor(np.ascontiguousarray(image, np.float32), device="cuda")
+    if not image.is_cuda:
+        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
+    img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
+    H, W, C = img.shape
+    dev = img.device
+    m = None
+    if mask is not None:
+        m = _lib.mask_bytes(torch.as_tensor(np.asarray(mask) != 0 if not _is_torch(mask) else mask, device=dev))
+        if tuple(m.shape) != (H, W):
+            raise ValueError("image and mask should have the same shape.")
+    sd = None
+    cap = H * W
+    if seeds is not None:
+        yx = np.ascontiguousarray(seeds[0], np.float64)
+        st = [float(v) for v in np.ravel(seeds[1])]
+        st = [1.0] + st if len(st) == 2 else st
+        sd = _lib.SlicSeeds()
+        sd.yx, sd.n = yx.ctypes.data, yx.shape[0]
+        sd.steps_zyx[:] = st
+        cap = yx.shape[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"features": torch.empty((H, W, C), **f32), "seeds_yx": torch.empty((cap, 2), **f32),
+           "centroids": torch.empty((cap, 2 + C), **f32), "labels_pre": torch.empty((H, W), dtype=torch.int32, device=dev)}
+    s = _lib.SlicStages()
+    s.features, s.seeds_yx, s.labels_pre = out["features"].data_ptr(), out["seeds_yx"].data_ptr(), out["labels_pre"].data_ptr()
+    s.centroids = out["centroids"].data_ptr() if params.max_num_iter >= 1 else None
+    s.centroid_capacity, s.prepass_only, s.prepass_iters = cap, int(bool(prepass_only)), int(prepass_iters)
+    c = ctx or _lib.default_context(dev.index or 0)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_slic_stages_f32_dev(c.handle, img.data_ptr(), H, W, C, m.data_ptr() if m is not None else None,
+                                            ctypes.byref(params), ctypes.byref(sd) if sd is not None else None, ctypes.byref(s)))
+    out["seeds_yx"], out["centroids"] = out["seeds_yx"][:s.K], out["centroids"][:s.K]
+    if params.max_num_iter < 1:
+        del out["centroids"]
+    out.update(K=int(s.K), step=float(s.step), prescale=float(s.prescale), fscale=float(s.fscale))
+    return out
+
+
 def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, sigma=0, convert2lab=True,
                rng=42, *, random_seed=None, channel_axis=-1, ctx=None, _normalize_bands=False):
     """Drop-in for ``skimage.segmentation.quickshift`` as obia calls it

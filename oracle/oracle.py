@@ -179,18 +179,21 @@ def gaussian_filter_zyx(img_hwc, sigma, spacing=None):
 
 
 def slic_core(image_scaled, segments, step, max_iter=10, mask=None, slic_zero=False,
-              ignore_color=False, start_label=1):
-    """_slic_cython; `segments` (K,2+C) float32 is updated in place. Returns labels (H,W) int64."""
+              ignore_color=False, start_label=1, spacing_yx=None):
+    """_slic_cython; `segments` (K,2+C) float32 is updated in place. Returns labels (H,W) int64.
+    spacing_yx: slic()'s `spacing` of the row and column axes (float32, as the image's dtype), None = (1, 1)."""
     image_scaled = np.ascontiguousarray(image_scaled, np.float32)
     H, W, C = image_scaled.shape
     assert segments.dtype == np.float32 and segments.flags.c_contiguous and segments.shape[1] == 2 + C
     if mask is not None:
         mask = np.ascontiguousarray(mask, np.uint8)
     labels = np.empty((H, W), np.int64)
-    rc = lib().obia_oracle_slic_core(_ptr(image_scaled), _ptr(mask), _ptr(segments), _i64(H), _i64(W),
-                                     ctypes.c_int(C), _i64(segments.shape[0]), ctypes.c_float(step),
-                                     ctypes.c_int(max_iter), ctypes.c_int(bool(slic_zero)),
-                                     ctypes.c_int(bool(ignore_color)), ctypes.c_int(start_label), _ptr(labels))
+    sy, sx = (1.0, 1.0) if spacing_yx is None else (float(np.float32(spacing_yx[0])), float(np.float32(spacing_yx[1])))
+    rc = lib().obia_oracle_slic_core_sp(_ptr(image_scaled), _ptr(mask), _ptr(segments), _i64(H), _i64(W),
+                                        ctypes.c_int(C), _i64(segments.shape[0]), ctypes.c_float(step),
+                                        ctypes.c_int(max_iter), ctypes.c_int(bool(slic_zero)),
+                                        ctypes.c_int(bool(ignore_color)), ctypes.c_int(start_label), _ptr(labels),
+                                        ctypes.c_float(sy), ctypes.c_float(sx))
     if rc:
         raise RuntimeError(f"oracle slic_core rc={rc}")
     return labels

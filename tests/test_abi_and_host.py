@@ -36,6 +36,18 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.load().obia_abi_version() == 2
 
 
+def test_stage_struct_matches_header(lib):
+    """obia_slic_stages: four pointers, four int32, three doubles, in the header's order."""
+    S = lib.SlicStages
+    assert ctypes.sizeof(S) == 72
+    assert [(n, getattr(S, n).offset) for n, _ in S._fields_] == [
+        ("features", 0), ("seeds_yx", 8), ("centroids", 16), ("labels_pre", 24), ("centroid_capacity", 32), ("prepass_only", 36),
+        ("prepass_iters", 40), ("K", 44), ("step", 48), ("prescale", 56), ("fscale", 64)]
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct obia_slic_stages \{(.*?)\} obia_slic_stages;", txt, flags=re.S).group(1)
+    assert re.findall(r"(\w+);", body) == [n for n, _ in S._fields_]
+
+
 def test_param_structs_match_header(lib):
     p = lib.SlicParams()
     lib.load().obia_slic_default_params(ctypes.byref(p))
