@@ -5,6 +5,7 @@
     Segments.polygons()      -> polygons in map coordinates                   (create_segments back half, :59-77)
     create_tiled_segments()  -> the same for a raster that is processed in tiles (obia.utils.tiling, :62-291)
     slic_edge(), label_segments() -> the consumers of the label raster       (utils/cost.py:44-48, utils/utils.py:12-34)
+    classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
     python examples/quickstart.py
@@ -21,6 +22,7 @@ from obia_amd.tiling import create_tiled_segments                  # noqa: E402
 from obia_amd.consumers import slic_edge, label_segments           # noqa: E402
 from obia_amd.polygons import polygonize                           # noqa: E402
 from obia_amd.cost import rasterise_slic_gpkg                      # noqa: E402
+from obia_amd.classify import classify                             # noqa: E402
 
 
 class Image:
@@ -69,6 +71,24 @@ def main():
     labelled, mixed = label_segments(labels, image.affine_transformation, pts, ["canopy", "masked corner"])
     print(f"slic_edge(): {100 * float(edges.mean()):.1f} % edge pixels; label_segments(): {labelled}, mixed {mixed}")
     assert len(polygonize(labels, start_label=1)) == n
+
+    # 5. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
+    try:
+        import sklearn  # noqa: F401
+    except ImportError:
+        print("classify(): skipped, scikit-learn is not installed")
+        return
+    py, px = np.mgrid[5:H:20, 5:W:20]
+    pts = np.stack([300000.0 + 0.5 * (px.ravel() + 0.5), 2200000.0 - 0.5 * (py.ravel() + 0.5)], 1)
+    classes = np.digitize(data[py.ravel(), px.ravel(), 0], [900, 1100]) + 1            # three classes from band 0
+    labelled, _ = label_segments(labels, image.affine_transformation, pts, classes)
+    objects = create_objects(labels, image, calculate_textural=False, geometry=False)
+    training = objects[objects["segment_id"].isin(list(labelled))].copy()
+    training["feature_class"] = [labelled[int(s)] for s in training["segment_id"]]
+    result = classify(objects, training, n_estimators=50, random_state=0)
+    class_raster = result.to_raster(labels)
+    print(f"classify(): {len(training)} training segments, classes {sorted(set(result.classified['predicted_class']))}, "
+          f"mean margin {float(result.classified['prediction_margin'].mean()):.2f}, class raster {class_raster.shape}")
 
 
 if __name__ == "__main__":

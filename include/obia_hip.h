@@ -422,6 +422,45 @@ int obia_seeds_pair_matrix_dev(obia_ctx *ctx, const double *xs, const double *ys
                                const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host,
                                float *matrix_out);
 
+/* ---- classification (obia/classification/classify.py): the prediction half, for the whole segment table at once -----
+ * Training stays scikit-learn on the host; these two calls replace the StandardScaler of classify.py:126-129 and the per-row
+ * loop of :135-158.  All pointers are DEVICE pointers unless marked HOST; both calls synchronise the stream before they return.
+ * obia_table_scale_dev : table (n_rows, n_features) float64, row-major.  mean_out / scale_out [n_features] float64: per column
+ *                        over its non-NaN values, n of them: mean = sum / n; var = (sum (x - mean)^2 - (sum (x - mean))^2 / n) / n
+ *                        (scikit-learn's _incremental_mean_and_var); scale = sqrt(var), or 1 where
+ *                        var <= n eps var + (n mean eps)^2 (StandardScaler's constant-feature rule); an all-NaN column gives NaN
+ *                        for both.  scaled_out (n_rows, n_features) float32 = (float)((x - mean) / scale), in float64 until the
+ *                        cast.  No floating-point atomics: partial sums are added in an order that (n_rows, n_features) fix.
+ * obia_forest_predict_dev : x (n_rows, n_features) float32.  Per tree a walk from its root: v = x[row][feature]; NaN goes left
+ *                        iff missing_go_to_left, anything else goes left iff (double)v <= threshold; a node with left < 0 is a
+ *                        leaf.  proba[row] = (sum over trees 0 .. T-1, in that order, float64, of value[leaf]) / (double)T.
+ *                        acceptable (n_rows, n_classes) uint8, nullable: 1 = the class is a candidate for that row (NULL: all).
+ *                        Outputs, each nullable: proba_out (n_rows, n_classes) float64, never filtered; pred_out [n_rows] int32 =
+ *                        the first maximum of proba over the candidates (-1 when there is none); margin_out [n_rows] float64 =
+ *                        the largest minus the second largest candidate value (0 on a tie at the top).
+ *                        More than 64 classes, 4096 features, 65536 trees or 2^31 - 1 nodes: OBIA_E_UNSUPPORTED.  A node whose
+ *                        feature or children point outside [0, n_features) / its own tree: OBIA_E_INVALID (no walk follows it).
+ * obia_forest: the trees' nodes one after the other.  left / right are indices within the node's OWN tree (scikit-learn's
+ * children_left / children_right); tree t owns nodes [tree_offset[t], tree_offset[t + 1]) (the last one up to n_nodes) and its
+ * root is the first of them.  value (n_nodes, n_classes) float64: what a leaf adds.  missing_go_to_left is nullable (all 0).   */
+typedef struct obia_forest {
+    const double *threshold;
+    const int32_t *feature;
+    const int32_t *left;
+    const int32_t *right;
+    const uint8_t *missing_go_to_left;
+    const int64_t *tree_offset;       /* [n_trees], device */
+    const int64_t *tree_offset_host;  /* the same values, HOST */
+    const double *value;
+    int64_t n_nodes;
+    int32_t n_trees;
+    int32_t n_classes;
+} obia_forest;
+int obia_table_scale_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
+                         float *scaled_out);
+int obia_forest_predict_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest,
+                            const uint8_t *acceptable, double *proba_out, int32_t *pred_out, double *margin_out);
+
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
  * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of

@@ -48,6 +48,13 @@ class TilingParams(ctypes.Structure):
                 ("white_order", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class Forest(ctypes.Structure):
+    """obia_forest (include/obia_hip.h): the flat node arrays of a tree ensemble."""
+    _fields_ = [("threshold", ctypes.c_void_p), ("feature", ctypes.c_void_p), ("left", ctypes.c_void_p), ("right", ctypes.c_void_p),
+                ("missing_go_to_left", ctypes.c_void_p), ("tree_offset", ctypes.c_void_p), ("tree_offset_host", ctypes.c_void_p),
+                ("value", ctypes.c_void_p), ("n_nodes", ctypes.c_int64), ("n_trees", ctypes.c_int32), ("n_classes", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _SIGNATURES = {
@@ -110,6 +117,8 @@ _SIGNATURES = {
     "obia_tiler_finalize": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "obia_tiler_import_seam": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_int)]),
+    "obia_table_scale_dev": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
+    "obia_forest_predict_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Forest), _P, _P, _P, _P]),
     "obia_set_profiling": (_I, [_P, _I]),
     "obia_last_timing": (ctypes.c_double, [_P, _I]),
 }

@@ -1,0 +1,383 @@
+"""Host-side mirror of ``obia.classification.classify`` (classify.py:68-175) with the prediction half on the GPU.
+
+Training stays scikit-learn on the host: it sees a few hundred labelled rows and is the reference's own estimator.  What touches
+the whole segment table runs on the device (libobia_hip.so, csrc/classify.hip):
+
+    standard_scale  ``StandardScaler().fit(x).transform(x)`` of classify.py:126-129 plus the forest's cast to float32
+    forest_predict  the ``segments.iterrows()`` loop of :135-158 -- ``predict_proba`` / ``predict`` row by row, the class filter
+                    and the margin -- as one tree walk per (row, tree) for all rows at once
+
+The arithmetic is scikit-learn's: ``proba`` is bit-identical to ``RandomForestClassifier.predict_proba`` with
+``n_jobs=None``.  There is no CPU path.
+"""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _lib
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+MAX_CLASSES, MAX_FEATURES, MAX_TREES = 64, 4096, 65536
+_FOREST_ARRAYS = ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset", "value")
+_DROPPED = ["feature_class", "geometry", "segment_id"]
+
+
+def _is_torch(x):
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+class Forest:
+    """A fitted tree ensemble as flat arrays: the nodes of all trees one after the other.
+
+    ``threshold`` (n,) float64, ``feature`` (n,) int32, ``left`` / ``right`` (n,) int32 -- indices within the node's own tree, -1 at
+    a leaf, as scikit-learn's ``children_left`` / ``children_right`` -- ``missing_go_to_left`` (n,) uint8, ``tree_offset`` (T,) int64
+    (the first node of every tree, its root), ``value`` (n, K) float64 (what a leaf adds to ``proba`` before the division by T:
+    the tree's own ``predict_proba`` row) and ``classes_`` (K,).
+    """
+
+    def __init__(self, threshold, feature, left, right, missing_go_to_left, tree_offset, value, classes_, n_features=None):
+        self.threshold = np.ascontiguousarray(threshold, np.float64)
+        self.feature = np.ascontiguousarray(feature, np.int32)
+        self.left = np.ascontiguousarray(left, np.int32)
+        self.right = np.ascontiguousarray(right, np.int32)
+        self.missing_go_to_left = np.ascontiguousarray(missing_go_to_left, np.uint8)
+        self.tree_offset = np.ascontiguousarray(tree_offset, np.int64)
+        self.value = np.ascontiguousarray(value, np.float64)
+        self.classes_ = np.asarray(classes_)
+        if self.classes_.dtype == object:
+            raise ValueError("classes_ must be numbers or strings, not Python objects")
+        n = self.threshold.shape[0]
+        if n == 0 or self.tree_offset.ndim != 1 or self.tree_offset.shape[0] == 0:
+            raise ValueError("a forest needs at least one tree with one node")
+        for name in ("feature", "left", "right", "missing_go_to_left"):
+            if getattr(self, name).shape != (n,):
+                raise ValueError(f"{name} must hold one entry per node ({n})")
+        if self.value.ndim != 2 or self.value.shape != (n, len(self.classes_)):
+            raise ValueError("value must be (number of nodes, number of classes)")
+        off = self.tree_offset
+        if off[0] != 0 or (np.diff(off) <= 0).any() or off[-1] >= n:
+            raise ValueError("tree_offset must start at 0, increase and stay below the number of nodes")
+        size = np.diff(np.concatenate([off, [n]]))
+        per_node = np.repeat(size, size)
+        inner = self.left >= 0
+        if ((self.left[inner] >= per_node[inner]).any() or (self.right[inner] < 0).any() or (self.right[inner] >= per_node[inner]).any()
+                or (self.feature[inner] < 0).any()):
+            raise ValueError("a node's children or feature are out of range")
+        self.n_features = int(n_features) if n_features is not None else (int(self.feature[inner].max()) + 1 if inner.any() else 1)
+        if inner.any() and int(self.feature[inner].max()) >= self.n_features:
+            raise ValueError("a node tests a feature beyond n_features")
+        self._dev = {}
+
+    n_nodes = property(lambda self: int(self.threshold.shape[0]))
+    n_trees = property(lambda self: int(self.tree_offset.shape[0]))
+    n_classes = property(lambda self: int(self.value.shape[1]))
+
+    @classmethod
+    def from_sklearn(cls, rf):
+        """Read a fitted ``RandomForestClassifier`` (or any ensemble whose ``estimators_`` are single-output
+        ``DecisionTreeClassifier``\\ s that vote by averaging ``predict_proba``)."""
+        parts = {k: [] for k in _FOREST_ARRAYS}
+        offset = 0
+        for est in rf.estimators_:
+            t = est.tree_
+            if t.value.shape[1] != 1:
+                raise NotImplementedError("multi-output trees are not supported")
+            n = int(t.node_count)
+            v = np.array(t.value[:, 0, :], dtype=np.float64)
+            # what DecisionTreeClassifier.predict_proba returns for a leaf: current versions store class fractions and return
+            # them untouched; older ones store weighted counts and divide by the row sum (0 -> 1)
+            root = float(v[0].sum())
+            if abs(root - float(t.weighted_n_node_samples[0])) < abs(root - 1.0):
+                norm = v.sum(axis=1)
+                norm[norm == 0.0] = 1.0
+                v = v / norm[:, None]
+            parts["threshold"].append(np.asarray(t.threshold, np.float64))
+            parts["feature"].append(np.asarray(t.feature, np.int32))
+            parts["left"].append(np.asarray(t.children_left, np.int32))
+            parts["right"].append(np.asarray(t.children_right, np.int32))
+            mgl = getattr(t, "missing_go_to_left", None)
+            parts["missing_go_to_left"].append(np.zeros(n, np.uint8) if mgl is None else np.asarray(mgl, np.uint8))
+            parts["tree_offset"].append(offset)
+            parts["value"].append(v)
+            offset += n
+        if not parts["value"]:
+            raise ValueError("the ensemble has no trees")
+        cat = {k: np.concatenate(v) for k, v in parts.items() if k != "tree_offset"}
+        return cls(tree_offset=np.asarray(parts["tree_offset"], np.int64), classes_=np.asarray(rf.classes_),
+                   n_features=int(rf.n_features_in_), **cat)
+
+    def save(self, path):
+        """Plain ``.npz`` of the arrays and ``classes_``; nothing pickled."""
+        np.savez(path, classes_=self.classes_, n_features=np.int64(self.n_features), **{k: getattr(self, k) for k in _FOREST_ARRAYS})
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(classes_=z["classes_"], n_features=int(z["n_features"]), **{k: z[k] for k in _FOREST_ARRAYS})
+
+    def _on(self, device):
+        d = self._dev.get(str(device))
+        if d is None:
+            d = self._dev[str(device)] = {k: torch.as_tensor(getattr(self, k), device=device) for k in _FOREST_ARRAYS}
+        return d
+
+
+def standard_scale(table, ctx=None):
+    """``StandardScaler().fit(table).transform(table)`` followed by the forest's cast: returns ``(X32, mean, scale)`` with X32
+    (N, F) float32 and ``mean`` / ``scale`` (F,) float64 (obia_table_scale_dev).  Per column the NaNs are left out of the count,
+    the mean and the two-pass variance; a column scikit-learn treats as constant gets scale 1; an all-NaN column stays NaN.
+    NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    is_t = _is_torch(table)
+    if is_t and not table.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(table.shape)
+    if len(shape) != 2 or shape[1] == 0:
+        raise ValueError("table must be (rows, features)")
+    if shape[0] == 0:
+        raise ValueError("the table has no rows")
+    lib = _lib.load()
+    if is_t:
+        t = table.to(torch.float64).contiguous()
+    else:
+        c0 = ctx or _lib.default_context(0)
+        t = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float64), device=f"cuda:{c0.device}")
+    dev = t.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    N, F = shape
+    mean = torch.empty((F,), dtype=torch.float64, device=t.device)
+    scale = torch.empty_like(mean)
+    out = torch.empty((N, F), dtype=torch.float32, device=t.device)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_table_scale_dev(c.handle, t.data_ptr(), N, F, mean.data_ptr(), scale.data_ptr(), out.data_ptr()))
+    if is_t:
+        return out, mean, scale
+    return out.cpu().numpy(), mean.cpu().numpy(), scale.cpu().numpy()
+
+
+def _check_candidates(acceptable, n_rows, n_classes):
+    """The reference raises where a row has fewer than two candidate classes (``np.partition(..., -2)`` on one value, ``idxmax``
+    on none, classify.py:150-151,157): so does this, before anything is launched."""
+    if acceptable is None:
+        if n_classes < 2:
+            raise ValueError("prediction needs at least two classes (the margin is the difference of the two largest probabilities)")
+        return
+    if tuple(acceptable.shape) != (n_rows, n_classes):
+        raise ValueError(f"acceptable must be (rows, classes) = ({n_rows}, {n_classes}), got {tuple(acceptable.shape)}")
+    few = (acceptable != 0).sum(1) < 2
+    if bool(few.any()):
+        first = int(few.nonzero()[0][0]) if not _is_torch(few) else int(few.nonzero()[0, 0])
+        raise ValueError(f"row {first} has fewer than two acceptable classes among classes_")
+
+
+def forest_predict(forest, X32, acceptable=None, ctx=None):
+    """Prediction of ``forest`` for every row of ``X32`` (N, F) float32: returns ``(pred, margin, proba)``.
+
+    ``proba`` (N, K) float64 is ``RandomForestClassifier.predict_proba`` bit for bit (leaf rows added in float64 in tree order,
+    divided by the number of trees), never filtered.  ``acceptable``: optional (N, K) boolean mask in ``classes_`` order;
+    ``pred`` (N,) int32 is the index into ``classes_`` of the first maximum of ``proba`` over the row's acceptable classes
+    (all classes without a mask), ``margin`` (N,) float64 the largest minus the second largest of those values.  A row with
+    fewer than two candidates raises ValueError.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    if not isinstance(forest, Forest):
+        raise TypeError("forest must be an obia_amd.classify.Forest (Forest.from_sklearn(rf))")
+    is_t = _is_torch(X32)
+    if is_t and not X32.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(X32.shape)
+    if len(shape) != 2:
+        raise ValueError("X32 must be (rows, features)")
+    N, F = shape
+    if N == 0:
+        raise ValueError("the table has no rows")
+    if F < forest.n_features:
+        raise ValueError(f"the forest tests feature {forest.n_features - 1}, the table has {F} columns")
+    K = forest.n_classes
+    if K > MAX_CLASSES or F > MAX_FEATURES or forest.n_trees > MAX_TREES or forest.n_nodes >= 2 ** 31:
+        raise NotImplementedError(f"forest_predict supports at most {MAX_CLASSES} classes, {MAX_FEATURES} features, {MAX_TREES} trees "
+                                  f"and 2^31 - 1 nodes (got {K}, {F}, {forest.n_trees}, {forest.n_nodes})")
+    _check_candidates(acceptable, N, K)
+    lib = _lib.load()
+    if is_t:
+        x = X32.to(torch.float32).contiguous()
+    else:
+        c0 = ctx or _lib.default_context(0)
+        x = torch.as_tensor(np.ascontiguousarray(X32, dtype=np.float32), device=f"cuda:{c0.device}")
+    dev = x.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    mask = None if acceptable is None else _lib.mask_bytes(acceptable, device=x.device)
+    d = forest._on(x.device)
+    fs = _lib.Forest(*(d[k].data_ptr() for k in ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset")),
+                     forest.tree_offset.ctypes.data, d["value"].data_ptr(), forest.n_nodes, forest.n_trees, K)
+    proba = torch.empty((N, K), dtype=torch.float64, device=x.device)
+    pred = torch.empty((N,), dtype=torch.int32, device=x.device)
+    margin = torch.empty((N,), dtype=torch.float64, device=x.device)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_forest_predict_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(fs), None if mask is None else mask.data_ptr(),
+                                           proba.data_ptr(), pred.data_ptr(), margin.data_ptr()))
+    if is_t:
+        return pred, margin, proba
+    return pred.cpu().numpy(), margin.cpu().numpy(), proba.cpu().numpy()
+
+
+class ClassifiedImage:
+    """The reference's result object (classify.py:12-65): ``classified`` (the segment table with ``predicted_class`` and
+    ``prediction_margin``), ``confusion_matrix``, ``report``, ``shap_values``, ``transform``, ``crs``, ``params``."""
+
+    def __init__(self, classified, confusion_matrix, report, shap_values, transform, crs, params):
+        self.classified = classified
+        self.report = report
+        self.confusion_matrix = confusion_matrix
+        self.shap_values = shap_values
+        self.params = params
+        self.transform = transform
+        self.crs = crs
+
+    def to_raster(self, labels, start_label=1, fill=0):
+        """Class per pixel: a gather of ``predicted_class`` through the label raster.  The table's rows are the labels that
+        exist, in ascending order (as create_objects numbers them); pixels below ``start_label`` get ``fill``.  Classes must be
+        integers.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out (int32)."""
+        if torch is None:
+            raise ImportError("obia_amd.classify needs torch for device memory")
+        cls = np.asarray(self.classified["predicted_class"])
+        try:
+            cls_i = cls.astype(np.int64)
+            exact = bool(np.all(cls_i == cls))
+        except (TypeError, ValueError):
+            exact = False
+        if not exact or (cls_i.size and (cls_i.min() < -2 ** 31 or cls_i.max() >= 2 ** 31)):
+            raise ValueError("to_raster needs integer classes that fit int32")
+        is_t = _is_torch(labels)
+        if is_t:
+            lab = labels.to(torch.int64)
+        else:
+            lab = torch.as_tensor(np.ascontiguousarray(labels), device=f"cuda:{_lib.default_context(0).device}").to(torch.int64)
+        valid = lab >= start_label
+        present = torch.unique(lab[valid])
+        if present.numel() != len(cls_i):
+            raise ValueError(f"the label raster holds {present.numel()} segments, the table {len(cls_i)} rows")
+        n = int(present[-1].item()) - start_label + 1 if present.numel() else 0
+        lut = torch.full((n + 1,), int(fill), dtype=torch.int32, device=lab.device)       # (last entry: pixels below start_label)
+        lut[present - start_label] = torch.as_tensor(cls_i, device=lab.device).to(torch.int32)
+        out = lut[torch.where(valid, lab - start_label, torch.full_like(lab, n))]
+        return out if is_t else out.cpu().numpy()
+
+
+def _zone_wkb(geom):
+    """One zone geometry as little-endian WKB: bytes as they are, an object with ``.wkb`` (shapely), or one (V, 2) ring."""
+    if isinstance(geom, (bytes, bytearray, memoryview)):
+        return bytes(geom)
+    if hasattr(geom, "wkb"):
+        return bytes(geom.wkb)
+    ring = np.asarray(geom, dtype="<f8")
+    if ring.ndim != 2 or ring.shape[1] != 2 or ring.shape[0] < 3:
+        raise ValueError("a zone geometry must be WKB bytes or a (V, 2) ring")
+    return struct.pack("<BII", 1, 3, 1) + struct.pack("<I", ring.shape[0]) + ring.tobytes()
+
+
+def acceptable_mask(acceptable_classes_gdf, classes_, labels, affine_transformation=None, start_label=1, ctx=None):
+    """The (segments, classes) boolean mask of ``classify(acceptable_classes_gdf=...)`` on the label raster.
+
+    ``acceptable_classes_gdf``: a table with ``geometry`` (WKB bytes, shapely geometries or (V, 2) rings) and
+    ``acceptable_classes`` (a list of class values per row).  The zones are burnt with :func:`obia_amd.polygons.rasterize` in
+    reverse table order, so the first row wins a pixel; a segment's zone is the lowest row index under its pixel centres (the
+    ``min`` of :func:`obia_amd.statistics.zonal_stats` on that raster) -- the reference's ``intersections.iloc[0]``
+    (classify.py:140-143).  A segment under no zone accepts every class.  One row per existing label, ascending.
+    Deviation: the reference's ``intersects`` also counts a zone that only touches a segment's border or covers
+    none of its pixel centres; the raster rule does not."""
+    from .polygons import rasterize
+    from .statistics import zonal_stats
+    geoms = list(acceptable_classes_gdf["geometry"])
+    wanted = list(acceptable_classes_gdf["acceptable_classes"])
+    nz = len(geoms)
+    if nz >= 2 ** 24:
+        raise NotImplementedError("2^24 or more zones are not supported")
+    lab = labels if _is_torch(labels) else np.asarray(labels)
+    H, W = (int(v) for v in lab.shape)
+    classes_ = np.asarray(classes_)
+    zone_rows = np.stack([np.isin(classes_, np.asarray(list(w))) for w in wanted]) if nz else np.zeros((0, len(classes_)), bool)
+    order = np.arange(nz - 1, -1, -1)
+    zr = rasterize([_zone_wkb(geoms[i]) for i in order], (H, W), affine_transformation=affine_transformation,
+                   values=order.astype(np.int32), fill=-1, ctx=ctx, as_tensor=True)
+    plane = zr.to(torch.float32)
+    plane[zr < 0] = float("nan")                       # zonal_stats drops NaN pixels: no zone here
+    lab_t = lab if _is_torch(lab) else torch.as_tensor(np.ascontiguousarray(lab, dtype=np.int32), device=zr.device)
+    st = zonal_stats(plane[:, :, None].contiguous(), lab_t, start_label=start_label, ctx=ctx)
+    present = (st["count"] > 0).cpu().numpy()
+    zone = st["min"][:, 0].cpu().numpy()[present]
+    mask = np.ones((int(present.sum()), len(classes_)), bool)
+    has = ~np.isnan(zone)
+    mask[has] = zone_rows[zone[has].astype(np.int64)]
+    return mask
+
+
+def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf', test_size=0.2, compute_reports=False,
+             compute_shap=False, sample_shap=False, *, acceptable=None, labels=None, affine_transformation=None, start_label=1,
+             ctx=None, **kwargs):
+    """Mirror of obia ``classify`` (classify.py:68-175): same positional order and defaults.
+
+    On the host, as the reference does it: ``feature_class`` / ``geometry`` / ``segment_id`` are dropped,
+    ``train_test_split(random_state=42)``, a ``StandardScaler`` per split, ``RandomForestClassifier(**kwargs).fit``, the
+    reports when asked.  On the device: :func:`standard_scale` on the segments' feature columns and :func:`forest_predict` for
+    all rows at once instead of one ``predict_proba`` call per row.  ``segments`` gains ``predicted_class`` (the class value)
+    and ``prediction_margin`` and is returned inside a :class:`ClassifiedImage`.
+
+    ``acceptable``: (N, K) boolean mask in ``classes_`` order, or ``acceptable_classes_gdf`` (see :func:`acceptable_mask`; needs
+    ``segments.attrs["labels"]`` or ``labels=``, and ``affine_transformation=`` when the zones are in map coordinates).
+    ``method='mlp'`` and ``compute_shap=True`` are not implemented."""
+    if method == 'mlp':
+        raise NotImplementedError("method='mlp' is not implemented: only the random forest predicts on the GPU")
+    if method != 'rf':
+        raise ValueError('An unsupported classification algorithm was requested')
+    if compute_shap:
+        raise NotImplementedError("compute_shap=True is not implemented")
+    import pandas as pd
+    from sklearn.ensemble import RandomForestClassifier
+    from sklearn.model_selection import train_test_split
+    from sklearn.preprocessing import StandardScaler
+
+    x = training_classes.drop(_DROPPED, axis=1)
+    y = training_classes['feature_class']
+    x_train, x_test, y_train, y_test = train_test_split(x, y, test_size=test_size, random_state=42)
+    x_train = StandardScaler().fit_transform(x_train)
+    classifier = RandomForestClassifier(**kwargs)
+    classifier.fit(x_train, y_train)
+    report = cm = None
+    if compute_reports:
+        from sklearn.metrics import classification_report, confusion_matrix
+        y_pred = classifier.predict(StandardScaler().fit_transform(x_test))
+        cm = confusion_matrix(y_test, y_pred)
+        report = classification_report(y_test, y_pred)
+
+    x_pred = segments.drop(_DROPPED, axis=1, errors='ignore')
+    forest = Forest.from_sklearn(classifier)
+    if acceptable is None and acceptable_classes_gdf is not None:
+        if labels is None:
+            labels = getattr(segments, "attrs", {}).get("labels")
+        if labels is None:
+            raise ValueError("acceptable_classes_gdf needs the label raster: segments.attrs['labels'] or labels=")
+        acceptable = acceptable_mask(acceptable_classes_gdf, forest.classes_, labels, affine_transformation=affine_transformation,
+                                     start_label=start_label, ctx=ctx)
+        if acceptable.shape[0] != len(segments):
+            raise ValueError(f"the label raster holds {acceptable.shape[0]} segments, the table {len(segments)} rows")
+    X32, _, _ = standard_scale(np.ascontiguousarray(x_pred.to_numpy(dtype=np.float64)), ctx=ctx)
+    pred, margin, _ = forest_predict(forest, X32, acceptable=None if acceptable is None else np.asarray(acceptable), ctx=ctx)
+
+    segments['predicted_class'] = forest.classes_[pred]
+    segments['prediction_margin'] = margin
+    for col in segments.columns:                      # classify.py:165-173
+        if col == 'geometry' or not isinstance(segments[col].dtype, np.dtype):
+            continue
+        if np.issubdtype(segments[col].dtype, np.integer):
+            segments[col] = segments[col].astype(pd.Int64Dtype())
+        elif np.issubdtype(segments[col].dtype, np.floating):
+            segments[col] = segments[col].astype(float)
+    return ClassifiedImage(segments, cm, report, None, None, None, classifier.get_params())
