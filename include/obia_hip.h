@@ -113,8 +113,8 @@ int obia_enforce_connectivity_i32_dev(obia_ctx *ctx, const int32_t *labels_in, i
                                       int32_t *labels_out, int *n_labels_out);
 
 /* B1 with caller-supplied initial centroids instead of the library's seeding rule: the output of scikit-image's
- * own `_get_mask_centroids(mask, n_segments)` (slic_superpixels.py:14-68: RandomState / kmeans2 / pdist -- RNG and
- * version dependent, so the library does not restate it) or of `_get_grid_centroids` (:71-104).  Everything after
+ * own `_get_mask_centroids(mask, n_segments)` (slic_superpixels.py:14-68: RandomState / kmeans2 / pdist --
+ * obia_mask_centroids_dev below restates everything after the random picks) or of `_get_grid_centroids` (:71-104).  Everything after
  * the seeding is the reference's: `step = max(steps)` (:288), spatial-only pre-pass when a mask is given (:310-314),
  * main pass, connectivity with segment_size = mask.sum() / n_centroids (:321-326).  This is how the maskSLIC path
  * every tile of create_tiled_segments takes (tiling.py:121-143) is pinned on scikit-image output.
@@ -131,6 +131,28 @@ typedef struct obia_slic_seeds {
 int obia_slic_seeded_f32_dev(obia_ctx *ctx, const float *img_hwc, int H, int W, int C, const uint8_t *mask,
                              const obia_slic_params *params, const obia_slic_seeds *seeds, int stage,
                              int32_t *labels_out, int *n_out);
+
+/* maskSLIC seeds as scikit-image 0.18 computes them (`_get_mask_centroids`, slic_superpixels.py:14-68), bit for bit, from the random
+ * picks on: the picks come from NumPy's `RandomState(123)` and stay the caller's (obia_amd.segmentation.mask_centroids draws them).
+ * "Rank" = position of a valid pixel among the mask's valid pixels in row-major order.
+ *   1. code book = the pixels of rank picks[0..n_picks): the initial centroids; points = the pixels of rank dense_picks[0..n_dense),
+ *      or every valid pixel when dense_picks is null
+ *   2. `iters` iterations (scikit-image: 5) of scipy.cluster.vq.kmeans2: every point joins the FIRST centroid at the least
+ *      ((0 + dz*dz) + dy*dy) + dx*dx (float64, separate multiply and add); a centroid becomes sum / count of its points, one
+ *      division per coordinate; a centroid without points stays where it is
+ *   3. per centroid the FIRST other centroid at the least sqrt(squared distance) (pdist + argmin: roots are compared);
+ *      steps = abs(centroids - centroids[closest]).mean(0), columns summed in row order
+ * The sums are 64-bit integer atomics, so two calls agree bit for bit.  One lane per point (step 2) or centroid (step 3) scans the
+ * code book through LDS, OBIA_MASK_SEEDS_CHUNK centroids at a time: brute force, n_points * n_picks distances per iteration.
+ *   mask                  DEVICE (H, W) uint8, any non-zero byte = valid
+ *   picks, dense_picks    HOST int64, strictly ascending, every value in [0, n_valid)
+ *   centroids_yx_out      HOST (n_picks, 2) float64 (y, x): the layout obia_slic_seeds.yx takes
+ *   steps_zyx_out         HOST 3 float64, depth axis first (0 for the one-plane depth axis): obia_slic_seeds.steps_zyx
+ * OBIA_E_INVALID: a null pointer, n_picks < 1, n_dense < 1 with dense_picks given, iters < 0, an unsorted or out-of-range pick.    */
+#define OBIA_MASK_SEEDS_CHUNK 1024
+int obia_mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int32_t n_picks,
+                            const int64_t *dense_picks, int64_t n_dense, int iters, double *centroids_yx_out,
+                            double *steps_zyx_out);
 
 /* SLIC stage by stage (tests and diagnostics): the call of obia_slic_assign_only_f32_dev -- the same function runs both, so the same
  * settings, layout, candidate lists, colour bound and repeat on orphans -- that also hands out what the stages produced.  `seeds` is

@@ -13,6 +13,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("OBIA_HIP_LIB") or os.path.join(_CSRC, "libobia_hip.so")
 
 OBIA_OK = 0
+MASK_SEEDS_CHUNK = 1024   # OBIA_MASK_SEEDS_CHUNK (include/obia_hip.h): centroids the seeding kernels stage in LDS at a time
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_EMPTY, E_NONFINITE = -1, -2, -3, -4, -5, -6
 
 
@@ -71,6 +72,7 @@ _SIGNATURES = {
     "obia_slic_assign_only_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), _P, ctypes.POINTER(_I)]),
     "obia_slic_seeded_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), ctypes.POINTER(SlicSeeds), _I, _P,
                                       ctypes.POINTER(_I)]),
+    "obia_mask_centroids_dev": (_I, [_P, _P, _I, _I, _P, ctypes.c_int32, _P, ctypes.c_int64, _I, _P, _P]),
     "obia_slic_stages_f32_dev": (_I, [_P, _P, _I, _I, _I, _P, ctypes.POINTER(SlicParams), ctypes.POINTER(SlicSeeds),
                                       ctypes.POINTER(SlicStages)]),
     "obia_enforce_connectivity_i32_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),

@@ -202,6 +202,30 @@ int obia_slic_stages_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int 
     return slic_stages_impl(ctx, img, H, W, C, mask, params, &ext, stages);
 }
 
+static int check_picks(const char *what, const int64_t *v, long long n) {
+    if (v[0] < 0) { set_error("mask centroids: %s %lld is negative", what, (long long)v[0]); return OBIA_E_INVALID; }
+    for (long long i = 1; i < n; ++i)
+        if (v[i] <= v[i - 1]) {
+            set_error("mask centroids: %ss must be strictly ascending (%lld follows %lld at %lld)", what, (long long)v[i], (long long)v[i - 1], i);
+            return OBIA_E_INVALID;
+        }
+    return OBIA_OK;
+}
+
+int obia_mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int32_t n_picks,
+                            const int64_t *dense_picks, int64_t n_dense, int iters, double *centroids_yx_out, double *steps_zyx_out) {
+    OBIA_TRY(check_ctx(ctx));
+    if (!mask || !picks || !centroids_yx_out || !steps_zyx_out) { set_error("mask centroids: null pointer argument"); return OBIA_E_INVALID; }
+    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) { set_error("mask centroids: bad mask shape (%d, %d)", H, W); return OBIA_E_INVALID; }
+    if (n_picks < 1) { set_error("mask centroids: need at least one pick (got %d)", n_picks); return OBIA_E_INVALID; }
+    if (dense_picks && (n_dense < 1 || n_dense > 0x7fffffffLL)) { set_error("mask centroids: bad dense pick count %lld", (long long)n_dense); return OBIA_E_INVALID; }
+    if (iters < 0) { set_error("mask centroids: iters must be >= 0"); return OBIA_E_INVALID; }
+    OBIA_TRY(check_picks("pick", picks, n_picks));
+    if (dense_picks) OBIA_TRY(check_picks("dense pick", dense_picks, n_dense));
+    return mask_centroids_dev(ctx, mask, H, W, picks, n_picks, dense_picks, dense_picks ? (long long)n_dense : 0, iters, centroids_yx_out,
+                              steps_zyx_out);
+}
+
 int obia_slic_f32(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                   const obia_slic_params *params, int32_t *labels_out, int *n_labels_out) {
     OBIA_TRY(check_ctx(ctx));

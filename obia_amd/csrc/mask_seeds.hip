@@ -1,0 +1,253 @@
+// mask_seeds.hip -- maskSLIC seeding as scikit-image 0.18 does it (`_get_mask_centroids`, slic_superpixels.py:14-68), bit for bit:
+// k-means (scipy.cluster.vq.kmeans2, 5 iterations) on a random subset of the valid pixels, started from a sparser random subset,
+// then per centroid the nearest other centroid (pdist + argmin) for `steps`.  The random picks are the caller's (NumPy's frozen
+// legacy generator stays in NumPy); everything from the picks on is here.
+//
+// Why a parallel version can be bit-exact:
+//   * a point's label is a per-point argmin with a fixed tie rule -- ascending centroid index, strict `<` -- and every lane scans the
+//     code book in exactly that order;
+//   * the distance is ((0 + dz*dz) + dy*dy) + dx*dx in float64 with separate multiply and add; dz is exactly 0, so the first two
+//     terms are dy*dy exactly.  The Makefile's -ffp-contract=off keeps multiply and add apart;
+//   * a cluster's sum is a sum of integer pixel coordinates: 64-bit integer atomics, exact and order-free, so two runs agree bit for
+//     bit; the mean is one IEEE division per coordinate;
+//   * pdist compares ROOTS: two different squares can round to one root, and then the lower index wins.  sqrt is monotonic, so a
+//     root needs computing only when the square is below the best square so far -- same index in every case, no K x K roots.
+// No K x K matrix and no (n_valid, 3) coordinate table are stored.
+#include "slic.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace obia {
+namespace {
+
+constexpr int MS_THREADS = 256;
+constexpr int MS_CHUNK = OBIA_MASK_SEEDS_CHUNK;   // centroids staged in LDS at a time: 1024 x (y, x) float64 = 16 KiB
+
+// ---- rank -> coordinate ---------------------------------------------------------------------------------------------------------
+// valid pixels of each mask row
+__global__ __launch_bounds__(MS_THREADS) void ms_row_count_kernel(const uint8_t *__restrict__ mask, int W, int *__restrict__ rowcnt) {
+    __shared__ int part[MS_THREADS / 64];
+    const uint8_t *row = mask + (size_t)blockIdx.x * W;
+    int c = 0;
+    for (int x = threadIdx.x; x < W; x += MS_THREADS) c += row[x] != 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) rowcnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// exclusive prefix over the rows (one workgroup): rowoff[r] = rank of row r's first valid pixel, rowoff[H] = n_valid
+__global__ __launch_bounds__(1024) void ms_row_scan_kernel(const int *__restrict__ rowcnt, int H, long long *__restrict__ rowoff) {
+    __shared__ long long s[1024];
+    __shared__ long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int r0 = 0; r0 < H; r0 += 1024) {
+        const int r = r0 + (int)threadIdx.x;
+        const long long v = r < H ? rowcnt[r] : 0;
+        s[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {
+            const long long t = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0;
+            __syncthreads();
+            s[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (r < H) rowoff[r] = carry + s[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry += s[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rowoff[H] = carry;
+}
+
+// One workgroup per mask row: the rank of every valid pixel (row offset + prefix inside the row); a pixel whose rank is picks[j]
+// writes (y, x) to out[j].  picks == nullptr: every valid pixel, out[rank].  j < n_picks by the search, rank < n_valid = rowoff[H].
+__global__ __launch_bounds__(MS_THREADS) void ms_gather_kernel(const uint8_t *__restrict__ mask, int W, const long long *__restrict__ rowoff,
+                                                               const long long *__restrict__ picks, long long n_picks,
+                                                               int2 *__restrict__ out) {
+    __shared__ int wave_cnt[MS_THREADS / 64];
+    const int y = blockIdx.x;
+    const long long first = rowoff[y];
+    if (rowoff[y + 1] == first) return;   // (uniform over the workgroup) no valid pixel in this row
+    const uint8_t *row = mask + (size_t)y * W;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long base = first;
+    for (int x0 = 0; x0 < W; x0 += MS_THREADS) {
+        const int x = x0 + (int)threadIdx.x;
+        const bool v = x < W && row[x] != 0;
+        const unsigned long long b = __ballot(v);
+        if (lane == 0) wave_cnt[wave] = __popcll(b);
+        __syncthreads();
+        // set bits of the ballot below this lane (mbcnt: no 64-bit shift by a register, tools/check_shift64.py)
+        int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u)), total = 0;
+        for (int w = 0; w < MS_THREADS / 64; ++w) {
+            const int c = wave_cnt[w];
+            if (w < wave) before += c;
+            total += c;
+        }
+        if (v) {
+            const long long rank = base + before;
+            if (!picks) {
+                out[rank] = make_int2(y, x);
+            } else {
+                long long lo = 0, hi = n_picks;
+                while (lo < hi) {
+                    const long long mid = (lo + hi) >> 1;
+                    if (picks[mid] < rank) lo = mid + 1; else hi = mid;
+                }
+                if (lo < n_picks && picks[lo] == rank) out[lo] = make_int2(y, x);
+            }
+        }
+        base += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void ms_init_book_kernel(const int2 *__restrict__ seeds, int K, double2 *__restrict__ book) {
+    const int k = blockIdx.x * MS_THREADS + threadIdx.x;
+    if (k < K) book[k] = make_double2((double)seeds[k].x, (double)seeds[k].y);
+}
+
+// ---- k-means --------------------------------------------------------------------------------------------------------------------
+// One lane per point; the code book passes through LDS in index order, MS_CHUNK centroids at a time (every lane reads the same
+// address: a broadcast).  The label goes straight into the cluster's integer sums: acc[3k] = sum y, [3k + 1] = sum x, [3k + 2] = count.
+__global__ __launch_bounds__(MS_THREADS) void ms_assign_kernel(const int2 *__restrict__ pts, long long n, const double2 *__restrict__ book, int K,
+                                                               unsigned long long *__restrict__ acc) {
+    __shared__ double2 sb[MS_CHUNK];
+    const long long i = (long long)blockIdx.x * MS_THREADS + threadIdx.x;
+    const bool live = i < n;
+    const int2 p = live ? pts[i] : make_int2(0, 0);
+    const double py = (double)p.x, px = (double)p.y;
+    double best = INFINITY;
+    int lab = 0;
+    for (int c0 = 0; c0 < K; c0 += MS_CHUNK) {
+        const int m = min(MS_CHUNK, K - c0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < m; t += MS_THREADS) sb[t] = book[c0 + t];
+        __syncthreads();
+        for (int j = 0; j < m; ++j) {
+            const double2 c = sb[j];
+            const double dy = py - c.x, dx = px - c.y;
+            const double d = dy * dy + dx * dx;   // (0 + 0 * 0) + dy * dy is dy * dy exactly
+            if (d < best) { best = d; lab = c0 + j; }
+        }
+    }
+    if (live) {
+        atomicAdd(&acc[3 * (size_t)lab], (unsigned long long)p.x);
+        atomicAdd(&acc[3 * (size_t)lab + 1], (unsigned long long)p.y);
+        atomicAdd(&acc[3 * (size_t)lab + 2], 1ull);
+    }
+}
+
+// new centroid = sum / count, one division per coordinate (the sums are below 2^53: exact as float64); a cluster without points
+// keeps its centroid.  Clears the sums for the next iteration.
+__global__ __launch_bounds__(MS_THREADS) void ms_finalise_kernel(unsigned long long *__restrict__ acc, int K, double2 *__restrict__ book) {
+    const int k = blockIdx.x * MS_THREADS + threadIdx.x;
+    if (k >= K) return;
+    const unsigned long long sy = acc[3 * (size_t)k], sx = acc[3 * (size_t)k + 1], cnt = acc[3 * (size_t)k + 2];
+    if (cnt) {
+        const double c = (double)cnt;
+        book[k] = make_double2((double)sy / c, (double)sx / c);
+    }
+    acc[3 * (size_t)k] = 0; acc[3 * (size_t)k + 1] = 0; acc[3 * (size_t)k + 2] = 0;
+}
+
+// ---- nearest other centroid -----------------------------------------------------------------------------------------------------
+// One lane per centroid i, the same LDS-chunked ascending scan over j != i.  closest[i] = the first j that minimises
+// sqrt(dy*dy + dx*dx); with K = 1 there is no other centroid and closest[0] = 0 (argmin of an all-infinite row).
+__global__ __launch_bounds__(MS_THREADS) void ms_nearest_kernel(const double2 *__restrict__ book, int K, int *__restrict__ closest) {
+    __shared__ double2 sb[MS_CHUNK];
+    const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+    const bool live = i < K;
+    const double2 ci = live ? book[i] : make_double2(0.0, 0.0);
+    double best_sq = INFINITY, best_rt = INFINITY;
+    int bj = 0;
+    for (int c0 = 0; c0 < K; c0 += MS_CHUNK) {
+        const int m = min(MS_CHUNK, K - c0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < m; t += MS_THREADS) sb[t] = book[c0 + t];
+        __syncthreads();
+        for (int j = 0; j < m; ++j) {
+            const double2 c = sb[j];
+            const double dy = ci.x - c.x, dx = ci.y - c.y;
+            const double s = dy * dy + dx * dx;
+            if (s < best_sq && c0 + j != i) {
+                // a square at or above best_sq has a root at or above best_rt; below it the root may still be EQUAL: roots decide
+                const double r = sqrt(s);
+                if (r < best_rt) { best_rt = r; bj = c0 + j; }
+                best_sq = s;
+            }
+        }
+    }
+    if (live) closest[i] = bj;
+}
+
+}  // namespace
+
+int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int K, const int64_t *dense, long long n_dense,
+                       int iters, double *centroids_yx_out, double *steps_zyx_out) {
+    Arena &A = ctx->arena;
+    A.reset();
+    int *rowcnt = A.get<int>((size_t)H);
+    long long *rowoff = A.get<long long>((size_t)H + 1);
+    if (!rowcnt || !rowoff) return OBIA_E_NOMEM;
+    hipLaunchKernelGGL(ms_row_count_kernel, dim3(H), dim3(MS_THREADS), 0, ctx->stream, mask, W, rowcnt);
+    hipLaunchKernelGGL(ms_row_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, rowcnt, H, rowoff);
+    OBIA_HIP_TRY(hipGetLastError());
+    long long n_valid = 0;
+    OBIA_TRY(read_back(ctx, &n_valid, rowoff + H, sizeof(long long)));
+    // the picks are sorted (checked by the caller): the last one bounds them all
+    if (picks[K - 1] >= n_valid) {
+        set_error("mask centroids: pick %lld out of range, the mask has %lld valid pixels", (long long)picks[K - 1], n_valid);
+        return OBIA_E_INVALID;
+    }
+    if (dense && dense[n_dense - 1] >= n_valid) {
+        set_error("mask centroids: dense pick %lld out of range, the mask has %lld valid pixels", (long long)dense[n_dense - 1], n_valid);
+        return OBIA_E_INVALID;
+    }
+    const long long n_pts = dense ? n_dense : n_valid;
+    if ((double)n_pts * (double)std::max(H, W) >= 9007199254740992.0) {   // coordinate sums must stay exact as float64
+        set_error("mask centroids: %lld points on a (%d, %d) raster overflow the exact sums", n_pts, H, W);
+        return OBIA_E_UNSUPPORTED;
+    }
+    long long *d_picks = A.get<long long>((size_t)K);
+    long long *d_dense = dense ? A.get<long long>((size_t)n_dense) : nullptr;
+    int2 *seeds = A.get<int2>((size_t)K);
+    int2 *pts = A.get<int2>((size_t)n_pts);
+    double2 *book = A.get<double2>((size_t)K);
+    unsigned long long *acc = A.get<unsigned long long>(3 * (size_t)K);
+    int *closest = A.get<int>((size_t)K);
+    if (!d_picks || (dense && !d_dense) || !seeds || !pts || !book || !acc || !closest) return OBIA_E_NOMEM;
+    OBIA_TRY(upload_async(ctx, d_picks, picks, sizeof(long long) * (size_t)K));
+    if (dense) OBIA_TRY(upload_async(ctx, d_dense, dense, sizeof(long long) * (size_t)n_dense));
+    OBIA_HIP_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 3 * (size_t)K, ctx->stream));
+    hipLaunchKernelGGL(ms_gather_kernel, dim3(H), dim3(MS_THREADS), 0, ctx->stream, mask, W, rowoff, d_picks, (long long)K, seeds);
+    hipLaunchKernelGGL(ms_gather_kernel, dim3(H), dim3(MS_THREADS), 0, ctx->stream, mask, W, rowoff, d_dense, n_dense, pts);
+    const dim3 kgrid(cdiv(K, MS_THREADS));
+    hipLaunchKernelGGL(ms_init_book_kernel, kgrid, dim3(MS_THREADS), 0, ctx->stream, seeds, K, book);
+    for (int it = 0; it < iters; ++it) {
+        hipLaunchKernelGGL(ms_assign_kernel, dim3(cdiv(n_pts, MS_THREADS)), dim3(MS_THREADS), 0, ctx->stream, pts, n_pts, book, K, acc);
+        hipLaunchKernelGGL(ms_finalise_kernel, kgrid, dim3(MS_THREADS), 0, ctx->stream, acc, K, book);
+    }
+    hipLaunchKernelGGL(ms_nearest_kernel, kgrid, dim3(MS_THREADS), 0, ctx->stream, book, K, closest);
+    OBIA_HIP_TRY(hipGetLastError());
+    std::vector<int> h_closest((size_t)K);
+    OBIA_HIP_TRY(hipMemcpyAsync(centroids_yx_out, book, sizeof(double2) * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
+    OBIA_TRY(read_back(ctx, h_closest.data(), closest, sizeof(int) * (size_t)K));
+    // steps = abs(centroids - centroids[closest]).mean(0): NumPy reduces axis 0 of the C-ordered (K, 3) array row by row, one running
+    // sum per column, then divides by K.  K values: on the host.  The depth column is all zeros.
+    double sy = 0.0, sx = 0.0;
+    for (int i = 0; i < K; ++i) {
+        const double *a = centroids_yx_out + 2 * (size_t)i, *b = centroids_yx_out + 2 * (size_t)h_closest[(size_t)i];
+        sy += std::fabs(a[0] - b[0]);
+        sx += std::fabs(a[1] - b[1]);
+    }
+    steps_zyx_out[0] = 0.0;
+    steps_zyx_out[1] = sy / (double)K;
+    steps_zyx_out[2] = sx / (double)K;
+    return OBIA_OK;
+}
+
+}  // namespace obia

@@ -196,6 +196,11 @@ int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b);
 // as (H, W, C); the seeds (K, 2); the centroid records the last sweep assigned from as (K, 2 + C) rows {cy, cx, colours / prescale}.
 int slic_stage_outputs(obia_ctx *ctx, const SlicBatch &b, float *features, float *seeds_yx, float *centroids);
 
+// maskSLIC seeds as scikit-image computes them, from the random picks on (mask_seeds.hip; arguments: obia_mask_centroids_dev, which
+// has checked them -- picks sorted and >= 0, K >= 1, n_dense >= 1 when dense is given).  mask: device; everything else: host.
+int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int K, const int64_t *dense, long long n_dense,
+                       int iters, double *centroids_yx_out, double *steps_zyx_out);
+
 // Connectivity enforcement on a batch of dense label maps laid out back to back (pix_off); labels come
 // out consecutive over the whole batch, in problem order then raster order of each component's first pixel.
 struct CcProblem { int H, W; long long pix_off; int min_size; int max_size; };   // component sizes: merge below min, cut at max

@@ -22,6 +22,7 @@ except Exception:  # pragma: no cover
 _SLIC_KWARGS = ("n_segments", "compactness", "max_num_iter", "max_iter", "sigma", "spacing", "convert2lab",
                 "enforce_connectivity", "min_size_factor", "max_size_factor", "slic_zero", "start_label", "mask",
                 "channel_axis", "multichannel", "exit_on_fixed_point")
+_SEEDINGS = ("grid", "skimage")
 
 
 def _is_torch(x):
@@ -97,10 +98,94 @@ def _check_common(sigma, spacing, channel_axis, multichannel, sigma_ok=False):
         raise NotImplementedError("multichannel=False (3-D volumes) is not implemented")
 
 
+def _mask_seed_picks(n_valid, n_segments):
+    """The two random draws of scikit-image's ``_get_mask_centroids`` (slic_superpixels.py:22-50), as sorted int64 ranks among the
+    valid pixels: the initial centroids, and the points k-means runs on (None: every valid pixel, no second draw).  NumPy's legacy
+    ``RandomState`` stream is frozen, so this stays NumPy's."""
+    rnd = np.random.RandomState(123)
+    idx_full = np.arange(n_valid, dtype=int)
+    idx = np.sort(rnd.choice(idx_full, min(n_segments, n_valid), replace=False))
+    n_dense = int(100 * n_segments)     # dense_factor ** 2 spatial axes
+    dense = np.sort(rnd.choice(idx_full, n_dense, replace=False)) if n_valid > n_dense else None
+    return np.ascontiguousarray(idx, np.int64), None if dense is None else np.ascontiguousarray(dense, np.int64)
+
+
+def mask_centroids(mask, n_segments, ctx=None):
+    """scikit-image's ``_get_mask_centroids(mask[np.newaxis], n_segments, True)`` (0.18: slic_superpixels.py:14-68), bit for bit, on the
+    GPU: the seeds maskSLIC starts from.  ``mask``: (H, W) NumPy array or CUDA tensor, non-zero = valid.  Returns
+    ``(centroids (K, 3) float64 as (0, y, x), steps (3,) float64)`` on the host, K = min(n_segments, valid pixels).
+
+    The random picks are drawn here with ``np.random.RandomState(123)``; k-means (5 iterations on up to 100 * n_segments points),
+    the nearest-other-centroid search and ``steps`` run in the library (obia_mask_centroids_dev): brute force,
+    points x centroids float64 distances per iteration.  ValueError with fewer than two valid pixels or ``n_segments < 2`` (the
+    reference ends up with a zero step there and divides by it)."""
+    if torch is None:
+        raise ImportError("mask_centroids needs torch (device plumbing)")
+    n_segments = int(n_segments)
+    if n_segments < 2:
+        raise ValueError("mask_centroids: n_segments must be at least 2")
+    if _is_torch(mask):
+        if not mask.is_cuda:
+            raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
+        m = _lib.mask_bytes(mask)
+    else:
+        m = np.asarray(mask)
+        if m.ndim != 2:
+            raise ValueError("mask must be (H, W)")
+        if np.count_nonzero(m) < 2:      # (before anything touches the device)
+            raise ValueError("mask_centroids: the mask needs at least two valid pixels")
+        dev = ctx.device if ctx is not None else 0
+        m = torch.as_tensor(np.ascontiguousarray(m != 0).view(np.uint8), device=f"cuda:{dev}")
+    if m.dim() != 2:
+        raise ValueError("mask must be (H, W)")
+    H, W = m.shape
+    n_valid = int(torch.count_nonzero(m))
+    if n_valid < 2:
+        raise ValueError("mask_centroids: the mask needs at least two valid pixels")
+    idx, dense = _mask_seed_picks(n_valid, n_segments)
+    yx = np.empty((len(idx), 2), np.float64)
+    steps = np.empty(3, np.float64)
+    dev = m.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(_lib.load().obia_mask_centroids_dev(c.handle, m.data_ptr(), H, W, _lib.np_ptr(idx), len(idx), _lib.np_ptr(dense),
+                                                   0 if dense is None else len(dense), 5, _lib.np_ptr(yx), _lib.np_ptr(steps)))
+    return np.concatenate([np.zeros((len(yx), 1)), yx], 1), steps
+
+
+def _slic_skimage_seeding(image, mask, seeds, n_segments, ctx, kw):
+    """``slic(..., seeding="skimage")``: mask_centroids, then the seeded entry point.  A NumPy image is copied to the GPU."""
+    if mask is None:
+        raise ValueError('seeding="skimage" is the maskSLIC seeding: it needs a mask')
+    if seeds is not None:
+        raise ValueError('seeding="skimage" computes the seeds: do not pass seeds= with it')
+    if int(n_segments) < 2:
+        raise ValueError('seeding="skimage" needs n_segments >= 2')
+    if torch is None:
+        raise ImportError('seeding="skimage" needs torch (device plumbing)')
+    if _is_torch(image) and not image.is_cuda:
+        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
+    img = image if _is_torch(image) else np.asarray(image)
+    if len(img.shape) not in (2, 3):
+        raise ValueError("image must be (H,W) or (H,W,C)")
+    if not _is_torch(mask):
+        mask = np.asarray(mask) != 0
+        if np.count_nonzero(mask) < 2:      # (before anything touches the device)
+            raise ValueError('seeding="skimage" needs at least two valid pixels in the mask')
+    if tuple(mask.shape) != tuple(img.shape[:2]):
+        raise ValueError("image and mask should have the same shape.")
+    dev_img = img if _is_torch(img) else torch.as_tensor(np.ascontiguousarray(img, dtype=np.float32),
+                                                         device=f"cuda:{ctx.device if ctx is not None else 0}")
+    m = _lib.mask_bytes(mask if _is_torch(mask) else np.ascontiguousarray(mask), device=dev_img.device)
+    cent, steps = mask_centroids(m, n_segments, ctx=ctx)
+    out = slic(dev_img, n_segments=n_segments, mask=m, seeds=(cent[:, 1:], steps), ctx=ctx, **kw)
+    return out if _is_torch(image) else out.cpu().numpy().astype(np.int64)
+
+
 def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spacing=None, convert2lab=None,
          enforce_connectivity=True, min_size_factor=0.5, max_size_factor=3, slic_zero=False, start_label=1,
          mask=None, *, channel_axis=-1, max_iter=None, multichannel=None, exit_on_fixed_point=False, ctx=None,
-         seeds=None, _normalize_bands=False, _stage="full"):
+         seeds=None, seeding="grid", _normalize_bands=False, _stage="full"):
     """Drop-in for ``skimage.segmentation.slic`` on 2-D multichannel rasters (the call at
     obia/segmentation/segment_boundaries.py:51), executed on the GPU.
 
@@ -117,6 +202,11 @@ def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spac
     seeds : ``(centroids_yx (K,2), steps)`` -- initial centroids to use instead of the library's seeding rule, e.g.
         the output of scikit-image's own ``_get_mask_centroids`` / ``_get_grid_centroids`` (``steps`` as returned
         there: 3 values, depth axis first, or 2 values (y, x)).  CUDA tensor images only.  Not a scikit-image argument.
+    seeding : ``"grid"`` (default) -- with a mask, the deterministic masked-grid rule of DESIGN.md 5; ``"skimage"`` -- with a mask,
+        scikit-image 0.18's own maskSLIC seeds (:func:`mask_centroids`: RandomState(123) picks, 5 k-means iterations, nearest-centroid
+        steps, bit for bit), after which the call is the seeded one: scikit-image's partition, at the price of a brute-force k-means.
+        NumPy images and CUDA tensors.  ValueError without a mask, together with ``seeds=``, with ``n_segments < 2`` or fewer than two
+        valid pixels.  Not a scikit-image argument.
     exit_on_fixed_point : stop sweeping once a sweep starts from centroids bit-identical to the previous sweep's
         (every later sweep would reproduce the same labels): same result as all ``max_num_iter`` sweeps, less
         work on rasters that converge early (e.g. compactness 10 on [0,1] features).  Not a scikit-image argument.
@@ -127,6 +217,14 @@ def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spac
         max_num_iter = max_iter
     if start_label not in (0, 1):
         raise ValueError("start_label should be 0 or 1.")
+    if seeding not in _SEEDINGS:
+        raise ValueError(f'seeding must be "grid" or "skimage" (got {seeding!r})')
+    if seeding == "skimage":
+        return _slic_skimage_seeding(image, mask, seeds, n_segments, ctx, dict(
+            compactness=compactness, max_num_iter=max_num_iter, sigma=sigma, spacing=spacing, convert2lab=convert2lab,
+            enforce_connectivity=enforce_connectivity, min_size_factor=min_size_factor, max_size_factor=max_size_factor,
+            slic_zero=slic_zero, start_label=start_label, channel_axis=channel_axis, multichannel=multichannel,
+            exit_on_fixed_point=exit_on_fixed_point, _normalize_bands=_normalize_bands, _stage=_stage))
     params = make_params(n_segments, compactness, max_num_iter, convert2lab, enforce_connectivity, min_size_factor,
                          max_size_factor, slic_zero, start_label, _normalize_bands, exit_on_fixed_point, sigma, spacing)
     lib = _lib.load()
@@ -404,7 +502,8 @@ def segments_table(labels, image=None, start_label=0, ctx=None):
     return df
 
 
-def create_segments(image, segmentation_bands=None, method="slic", inplace_normalize=False, as_table=False, ctx=None, **kwargs):
+def create_segments(image, segmentation_bands=None, method="slic", inplace_normalize=False, as_table=False, ctx=None, *,
+                    seeding="grid", **kwargs):
     """Mirror of obia create_segments (segment_boundaries.py:18-78).
 
     ``image``: object with ``img_data`` (H,W,C) float32 (obia ``Image``), or the array itself.
@@ -416,6 +515,8 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
     Every band of the raster is min-max normalised before band selection, as the reference does
     (:32-33) -- on the GPU, on a private copy: the caller's ``img_data`` is NOT mutated unless
     ``inplace_normalize=True`` reproduces that side effect on the host.
+
+    ``seeding``: :func:`slic`'s argument (``"skimage"``: scikit-image's own maskSLIC seeds; slic with a mask only).
     """
     img_data = image.img_data if hasattr(image, "img_data") else image
     num_bands = img_data.shape[2]
@@ -430,7 +531,11 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
         sel = img_data[:, :, list(segmentation_bands)]
     else:
         sel = np.asarray(img_data)[:, :, list(segmentation_bands)]
+    if seeding not in _SEEDINGS:
+        raise ValueError(f'seeding must be "grid" or "skimage" (got {seeding!r})')
     if method == "quickshift":
+        if seeding != "grid":
+            raise ValueError('seeding="skimage" is a slic argument: quickshift has no seeds')
         qs_kw = ("ratio", "kernel_size", "max_dist", "return_tree", "sigma", "convert2lab", "rng", "random_seed", "channel_axis")
         unknown = [k for k in kwargs if k not in qs_kw]
         if unknown:
@@ -445,7 +550,7 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
         raise TypeError(f"slic() got an unexpected keyword argument '{unknown[0]}'")
     kwargs.setdefault("start_label", 1)   # scikit-image >= 0.19 default (pyproject.toml:23 pins >= 0.23.2)
     # normalisation is per band, so selecting first and normalising the selected bands is identical
-    segments = slic(sel, ctx=ctx, _normalize_bands=True, **kwargs)
+    segments = slic(sel, ctx=ctx, seeding=seeding, _normalize_bands=True, **kwargs)
     if inplace_normalize and not _is_torch(img_data):
         for i in range(num_bands):
             img_data[:, :, i] = normalize_band(img_data[:, :, i])
@@ -506,14 +611,15 @@ def _epsg_of(crs):
 
 def segment(image, segmentation_bands=None, statistics_bands=None, method="slic", calc_mean=True, calc_variance=True,
             calc_skewness=True, calc_kurtosis=True, calc_contrast=True, calc_dissimilarity=True, calc_homogeneity=True,
-            calc_ASM=True, calc_energy=True, calc_correlation=True, ctx=None, **kwargs):
+            calc_ASM=True, calc_energy=True, calc_correlation=True, ctx=None, *, seeding="grid", **kwargs):
     """Mirror of obia.segmentation.segment.segment (segment.py:63-93): create_segments then create_objects.
 
     Statistics are taken from the RAW raster values (the reference re-reads them from the file,
     utils/utils.py:47; here ``image.img_data`` is still raw because create_segments does not mutate it).
+    ``seeding``: :func:`slic`'s argument, handed to create_segments.
     """
     from .statistics import create_objects
-    labels = create_segments(image, segmentation_bands=segmentation_bands, method=method, ctx=ctx, **kwargs)
+    labels = create_segments(image, segmentation_bands=segmentation_bands, method=method, ctx=ctx, seeding=seeding, **kwargs)
     # ids of the objects table: every label the segmentation produced.  quickshift numbers from 0; slic from start_label
     # (0 or 1), and with a mask the masked pixels carry -1 (segment_boundaries.py:55-64 skips only that id)
     first = 0 if method == "quickshift" else int(kwargs.get("start_label", 1))
