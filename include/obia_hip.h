@@ -371,6 +371,32 @@ int obia_tiled_slic_f32(obia_ctx *ctx, const float *img_hwc, const uint8_t *mask
                         const obia_tiling_params *tiling, const obia_slic_params *params,
                         int32_t *labels_out, int64_t *n_segments_out);
 
+/* Seeding rule of the tiles.  OBIA_SEEDING_GRID (the default of the calls above and of a new session): the deterministic
+ * masked-grid rule.  OBIA_SEEDING_SKIMAGE: every tile is seeded as scikit-image 0.18 seeds maskSLIC (`_get_mask_centroids`,
+ * slic_superpixels.py:14-68 -- what every tile of the reference goes through, tiling.py:137-143), from the tile's own mask
+ * window: for a white tile the input mask minus kept segments and corner squares.  The random picks stay the caller's (NumPy's
+ * frozen legacy generator): the library asks `picks` for the two sorted rank lists of (n_valid, n_segments) of each tile and
+ * runs the kernels of obia_mask_centroids_dev on the window (5 k-means iterations); K = min(n_segments, n_valid) centroids,
+ * step = max(steps) as it comes out of the seeding -- not divided by `spacing`, like slic(seeding="skimage") of the
+ * single-raster call.  A tile with n_segments < 2 or fewer than two valid pixels is skipped like an empty tile (scikit-image
+ * divides by a zero step there; the reference's tile loop swallows the ValueError, tiling.py:149-150).
+ *   obia_pick_fn: user, the tile's valid-pixel count and n_segments in; *idx / *n_idx = min(n_segments, n_valid) strictly
+ *   ascending ranks among the valid pixels of the tile window in row-major order (the initial centroids), *dense / *n_dense =
+ *   the ranks of the points k-means runs on, *dense = NULL: every valid pixel.  Returns 0, anything else fails the call with
+ *   OBIA_E_INVALID.  The pointers stay valid until the next call of the function; it is called on the host thread of the
+ *   library call, once per tile that is segmented.
+ * Selecting OBIA_SEEDING_SKIMAGE without a function is OBIA_E_INVALID.                                                       */
+#define OBIA_SEEDING_GRID 0
+#define OBIA_SEEDING_SKIMAGE 1
+typedef int (*obia_pick_fn)(void *user, int64_t n_valid, int32_t n_segments, const int64_t **idx, int32_t *n_idx,
+                            const int64_t **dense, int64_t *n_dense);
+int obia_tiled_slic_seeded_f32_dev(obia_ctx *ctx, const float *img_hwc, const uint8_t *mask, int H, int W, int C,
+                                   const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
+                                   obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out);
+int obia_tiled_slic_seeded_f32(obia_ctx *ctx, const float *img_hwc, const uint8_t *mask, int H, int W, int C,
+                               const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
+                               obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out);
+
 /* ---- B3, sharded: the same tile loops as a session, for slabs of a raster spread over several GPUs --------
  * The caller holds rows [row0, row0 + H_local) of a (H_global, W) raster on this GPU: its slab plus the halo
  * rows its white windows reach (`buffer` rows, +1 label row so that "segment continues beyond the halo" can be
@@ -393,6 +419,9 @@ int obia_tiler_set_segments(obia_tiler *t, int first_id, int count, const uint32
 int obia_tiler_get_alive(obia_tiler *t, uint8_t *alive_out_dev, int count);
 int obia_tiler_set_alive(obia_tiler *t, const uint8_t *alive_in_dev, int count);
 int obia_tiler_finalize(obia_tiler *t, int64_t *n_segments_out);
+/* Seeding rule of the session's later passes (OBIA_SEEDING_*, see obia_tiled_slic_seeded_f32_dev); `picks` and `picks_user`
+ * must outlive the session.  Every rank draws its own tiles' picks: they depend on (n_valid, n_segments) only.            */
+int obia_tiler_set_seeding(obia_tiler *t, int seeding, obia_pick_fn picks, void *picks_user);
 /* Import of a seam (round 4): the boundary label rows a neighbouring rank sent, as wire codes, become local ids in ONE call --
  * the step between `ncclRecv` and the next pass (semantic anchor obia/utils/tiling.py:289-290: one id space).
  *   codes_dev [n]        int32: (owner_rank + 1) << 24 | the owner's local id; 0 = no segment

@@ -58,6 +58,10 @@ class Forest(ctypes.Structure):
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
+SEEDING_GRID, SEEDING_SKIMAGE = 0, 1   # OBIA_SEEDING_* (include/obia_hip.h)
+# obia_pick_fn: (user, n_valid, n_segments, &idx, &n_idx, &dense, &n_dense) -> 0
+PickFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
+                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64))
 _SIGNATURES = {
     "obia_abi_version": (ctypes.c_int, []),
     "obia_last_error": (ctypes.c_char_p, []),
@@ -109,6 +113,11 @@ _SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int64)]),
     "obia_tiled_slic_f32": (_I, [_P, _P, _P, _I, _I, _I, ctypes.POINTER(TilingParams), ctypes.POINTER(SlicParams), _P,
                                  ctypes.POINTER(ctypes.c_int64)]),
+    "obia_tiled_slic_seeded_f32_dev": (_I, [_P, _P, _P, _I, _I, _I, ctypes.POINTER(TilingParams), ctypes.POINTER(SlicParams), _I, PickFn, _P,
+                                            _P, ctypes.POINTER(ctypes.c_int64)]),
+    "obia_tiled_slic_seeded_f32": (_I, [_P, _P, _P, _I, _I, _I, ctypes.POINTER(TilingParams), ctypes.POINTER(SlicParams), _I, PickFn, _P,
+                                        _P, ctypes.POINTER(ctypes.c_int64)]),
+    "obia_tiler_set_seeding": (_I, [_P, _I, PickFn, _P]),
     "obia_tiler_create": (_P, [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(TilingParams), ctypes.POINTER(SlicParams), _P, _I]),
     "obia_tiler_destroy": (None, [_P]),
     "obia_tiler_run": (_I, [_P, _I, _I, _I, _I]),

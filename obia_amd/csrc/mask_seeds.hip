@@ -184,34 +184,51 @@ __global__ __launch_bounds__(MS_THREADS) void ms_nearest_kernel(const double2 *_
     if (live) closest[i] = bj;
 }
 
+// ---- a tile of a batch: seeds and steps stay on the device -----------------------------------------------------------------------
+// One workgroup.  seeds_out[k] = the centroid as the float32 pair the sweeps start from (segments.astype(float32)); steps_out[0..1] =
+// abs(centroids - centroids[closest]).mean(0) of the row and column axes.  NumPy reduces axis 0 of the C-ordered (K, 3) array row by
+// row, one running sum per column, then divides by K: the terms are computed by all lanes, MS_CHUNK at a time into LDS, and ONE lane
+// adds them up in index order -- the order of the host loop in mask_centroids_dev, bit for bit.
+__global__ __launch_bounds__(MS_THREADS) void ms_emit_kernel(const double2 *__restrict__ book, const int *__restrict__ closest, int K,
+                                                             float2 *__restrict__ seeds_out, double *__restrict__ steps_out) {
+    __shared__ double2 sd[MS_CHUNK];
+    double sy = 0.0, sx = 0.0;
+    for (int c0 = 0; c0 < K; c0 += MS_CHUNK) {
+        const int m = min(MS_CHUNK, K - c0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < m; t += MS_THREADS) {
+            const double2 a = book[c0 + t];
+            const int j = closest[c0 + t];                                      // (0 <= j < K: ms_nearest_kernel)
+            const double2 o = book[j];
+            sd[t] = make_double2(fabs(a.x - o.x), fabs(a.y - o.y));
+            seeds_out[c0 + t] = make_float2((float)a.x, (float)a.y);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int t = 0; t < m; ++t) { sy += sd[t].x; sx += sd[t].y; }
+    }
+    if (threadIdx.x == 0) { steps_out[0] = sy / (double)K; steps_out[1] = sx / (double)K; }
+}
+
 }  // namespace
 
-int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int K, const int64_t *dense, long long n_dense,
-                       int iters, double *centroids_yx_out, double *steps_zyx_out) {
+// rank of every row's first valid pixel: rowoff[0 .. H], rowoff[H] = n_valid
+static int ms_rank_rows(obia_ctx *ctx, const uint8_t *mask, int H, int W, long long **rowoff_out) {
     Arena &A = ctx->arena;
-    A.reset();
     int *rowcnt = A.get<int>((size_t)H);
     long long *rowoff = A.get<long long>((size_t)H + 1);
     if (!rowcnt || !rowoff) return OBIA_E_NOMEM;
     hipLaunchKernelGGL(ms_row_count_kernel, dim3(H), dim3(MS_THREADS), 0, ctx->stream, mask, W, rowcnt);
     hipLaunchKernelGGL(ms_row_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, rowcnt, H, rowoff);
     OBIA_HIP_TRY(hipGetLastError());
-    long long n_valid = 0;
-    OBIA_TRY(read_back(ctx, &n_valid, rowoff + H, sizeof(long long)));
-    // the picks are sorted (checked by the caller): the last one bounds them all
-    if (picks[K - 1] >= n_valid) {
-        set_error("mask centroids: pick %lld out of range, the mask has %lld valid pixels", (long long)picks[K - 1], n_valid);
-        return OBIA_E_INVALID;
-    }
-    if (dense && dense[n_dense - 1] >= n_valid) {
-        set_error("mask centroids: dense pick %lld out of range, the mask has %lld valid pixels", (long long)dense[n_dense - 1], n_valid);
-        return OBIA_E_INVALID;
-    }
-    const long long n_pts = dense ? n_dense : n_valid;
-    if ((double)n_pts * (double)std::max(H, W) >= 9007199254740992.0) {   // coordinate sums must stay exact as float64
-        set_error("mask centroids: %lld points on a (%d, %d) raster overflow the exact sums", n_pts, H, W);
-        return OBIA_E_UNSUPPORTED;
-    }
+    *rowoff_out = rowoff;
+    return OBIA_OK;
+}
+
+// picks -> k-means -> nearest other centroid, queued on the context's stream; book / closest: K entries each, in the arena
+static int ms_kmeans(obia_ctx *ctx, const uint8_t *mask, int H, int W, const long long *rowoff, const int64_t *picks, int K, const int64_t *dense,
+                     long long n_dense, long long n_pts, int iters, double2 **book_out, int **closest_out) {
+    Arena &A = ctx->arena;
     long long *d_picks = A.get<long long>((size_t)K);
     long long *d_dense = dense ? A.get<long long>((size_t)n_dense) : nullptr;
     int2 *seeds = A.get<int2>((size_t)K);
@@ -233,6 +250,36 @@ int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const i
     }
     hipLaunchKernelGGL(ms_nearest_kernel, kgrid, dim3(MS_THREADS), 0, ctx->stream, book, K, closest);
     OBIA_HIP_TRY(hipGetLastError());
+    *book_out = book;
+    *closest_out = closest;
+    return OBIA_OK;
+}
+
+int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int K, const int64_t *dense, long long n_dense,
+                       int iters, double *centroids_yx_out, double *steps_zyx_out) {
+    Arena &A = ctx->arena;
+    A.reset();
+    long long *rowoff = nullptr;
+    OBIA_TRY(ms_rank_rows(ctx, mask, H, W, &rowoff));
+    long long n_valid = 0;
+    OBIA_TRY(read_back(ctx, &n_valid, rowoff + H, sizeof(long long)));
+    // the picks are sorted (checked by the caller): the last one bounds them all
+    if (picks[K - 1] >= n_valid) {
+        set_error("mask centroids: pick %lld out of range, the mask has %lld valid pixels", (long long)picks[K - 1], n_valid);
+        return OBIA_E_INVALID;
+    }
+    if (dense && dense[n_dense - 1] >= n_valid) {
+        set_error("mask centroids: dense pick %lld out of range, the mask has %lld valid pixels", (long long)dense[n_dense - 1], n_valid);
+        return OBIA_E_INVALID;
+    }
+    const long long n_pts = dense ? n_dense : n_valid;
+    if ((double)n_pts * (double)std::max(H, W) >= 9007199254740992.0) {   // coordinate sums must stay exact as float64
+        set_error("mask centroids: %lld points on a (%d, %d) raster overflow the exact sums", n_pts, H, W);
+        return OBIA_E_UNSUPPORTED;
+    }
+    double2 *book = nullptr;
+    int *closest = nullptr;
+    OBIA_TRY(ms_kmeans(ctx, mask, H, W, rowoff, picks, K, dense, n_dense, n_pts, iters, &book, &closest));
     std::vector<int> h_closest((size_t)K);
     OBIA_HIP_TRY(hipMemcpyAsync(centroids_yx_out, book, sizeof(double2) * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
     OBIA_TRY(read_back(ctx, h_closest.data(), closest, sizeof(int) * (size_t)K));
@@ -247,6 +294,27 @@ int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const i
     steps_zyx_out[0] = 0.0;
     steps_zyx_out[1] = sy / (double)K;
     steps_zyx_out[2] = sx / (double)K;
+    return OBIA_OK;
+}
+
+int mask_centroids_queue(obia_ctx *ctx, const uint8_t *mask, int h, int w, long long n_valid, const int64_t *picks, int K, const int64_t *dense,
+                         long long n_dense, int iters, float *seeds_out_dev, double *steps_out_dev) {
+    if (!mask || !picks || K < 1 || h <= 0 || w <= 0 || n_valid < K || n_valid > (long long)h * w || (dense && (n_dense < 1 || n_dense > n_valid)) ||
+        !seeds_out_dev || !steps_out_dev) {
+        set_error("mask centroids (tile): bad arguments");
+        return OBIA_E_INVALID;
+    }
+    Arena &A = ctx->arena;
+    const Arena::Mark mk = A.mark();
+    long long *rowoff = nullptr;
+    OBIA_TRY(ms_rank_rows(ctx, mask, h, w, &rowoff));
+    const long long n_pts = dense ? n_dense : n_valid;   // without the dense draw every valid pixel is a point
+    double2 *book = nullptr;
+    int *closest = nullptr;
+    OBIA_TRY(ms_kmeans(ctx, mask, h, w, rowoff, picks, K, dense, n_dense, n_pts, iters, &book, &closest));
+    hipLaunchKernelGGL(ms_emit_kernel, dim3(1), dim3(MS_THREADS), 0, ctx->stream, book, closest, K, reinterpret_cast<float2 *>(seeds_out_dev), steps_out_dev);
+    OBIA_HIP_TRY(hipGetLastError());
+    A.rewind(mk);   // (reused in stream order by whatever the caller queues next)
     return OBIA_OK;
 }
 

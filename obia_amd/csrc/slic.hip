@@ -809,7 +809,9 @@ int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid) {
 int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_segments, const std::vector<int> *nvalid_in,
                        const ExternalSeeds *ext) {
     const int np = b.nprob;
-    if (ext && (np != 1 || ext->n < 1 || !ext->yx)) { set_error("external seeds need one raster and at least one seed"); return OBIA_E_INVALID; }
+    if (ext)   // (a single-raster caller has checked that its one set holds a seed: check_seeds; in a batch n = 0 marks a skipped tile)
+        for (int p = 0; p < np; ++p)
+            if (ext[p].n < 0 || (ext[p].n > 0 && !ext[p].yx && !ext[p].d_yx)) { set_error("external seeds of problem %d: bad set", p); return OBIA_E_INVALID; }
     Arena &A = ctx->arena;
     // problems carry H, W and their offsets already (slic_batch_layout); upload a first version for the
     // counting / seeding kernels
@@ -821,7 +823,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     // caller-supplied seeds on a mask without a valid pixel: the reference raises before seeding (mask.sum() == 0).  Refused
     // here, BEFORE anything is sized or uploaded: the seed arrays below would hold one dummy record while the upload wrote
     // ext->n of them
-    if (ext && nvalid[0] <= 0) { set_error("the mask has no valid pixel"); return OBIA_E_EMPTY; }
+    if (ext && np == 1 && ext->n > 0 && nvalid[0] <= 0) { set_error("the mask has no valid pixel"); return OBIA_E_EMPTY; }
     std::vector<SeedGrid> grids(np);
     std::vector<double> stepmax(np);
     b.step.assign(np, 1.0f);
@@ -831,14 +833,15 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
         P.n_valid = nvalid[p];
         SeedGrid &g = grids[p];
         g.cent_off = cent_off; g.slots = 0;
-        if (ext && nvalid[p] > 0) {   // seeds given by the caller: K = their number, step = max(steps) of the seeding
-            g.start_y = g.start_x = 0; g.step_y = g.step_x = 1; g.ny = 1; g.nx = ext->n;
-            stepmax[p] = ext->step < 1.0 ? 1.0 : ext->step;
+        if (ext && ext[p].n > 0 && nvalid[p] > 0) {   // seeds given by the caller: K = their number, step = max(steps) of the seeding
+            if ((long long)cent_off + ext[p].n > 0x7fff0000LL) { set_error("too many centroids in one batch"); return OBIA_E_INVALID; }
+            g.start_y = g.start_x = 0; g.step_y = g.step_x = 1; g.ny = 1; g.nx = ext[p].n;
+            stepmax[p] = ext[p].step < 1.0 ? 1.0 : ext[p].step;
             P.cent_off = cent_off;
-            cent_off += ext->n;
+            cent_off += ext[p].n;
             continue;
         }
-        if (nvalid[p] <= 0 || n_segments[p] <= 0) {   // empty problem: no centroids, every pixel stays masked
+        if (ext || nvalid[p] <= 0 || n_segments[p] <= 0) {   // empty problem (or one without external seeds): no centroids, every pixel stays masked
             g.start_y = g.start_x = 0; g.step_y = g.step_x = 1; g.ny = g.nx = 0;
             stepmax[p] = 1.0;
             P.cent_off = cent_off;
@@ -872,11 +875,23 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     OBIA_TRY(upload_async(ctx, d_grids, grids.data(), sizeof(SeedGrid) * np));
     std::vector<int> K(np);
     if (ext) {
-        std::vector<float> hs((size_t)ext->n * 2);
-        for (size_t i = 0; i < hs.size(); ++i) hs[i] = (float)ext->yx[i];   // segments.astype(float32): centroids are float
-        OBIA_HIP_TRY(hipMemsetAsync(b.d_cent_prob, 0, sizeof(int) * b.total_cent, ctx->stream));
-        OBIA_TRY(upload_async(ctx, b.d_seed, hs.data(), sizeof(float) * hs.size()));
-        K[0] = nvalid[0] > 0 ? ext->n : 0;
+        // every problem's set behind the one before it (grids[p].cent_off); the centroid -> problem table from the host
+        std::vector<int> hp((size_t)b.total_cent, 0);
+        std::vector<float> hs;
+        for (int p = 0; p < np; ++p) {
+            K[p] = grids[p].ny * grids[p].nx;   // (0 for a problem without seeds or without a valid pixel)
+            if (K[p] <= 0) continue;
+            float *dst = b.d_seed + 2 * (size_t)grids[p].cent_off;
+            for (int k = 0; k < K[p]; ++k) hp[(size_t)grids[p].cent_off + k] = p;
+            if (ext[p].d_yx) {
+                OBIA_HIP_TRY(hipMemcpyAsync(dst, ext[p].d_yx, sizeof(float) * 2 * (size_t)K[p], hipMemcpyDeviceToDevice, ctx->stream));
+            } else {
+                hs.resize((size_t)K[p] * 2);
+                for (size_t i = 0; i < hs.size(); ++i) hs[i] = (float)ext[p].yx[i];   // segments.astype(float32): centroids are float
+                OBIA_TRY(upload_async(ctx, dst, hs.data(), sizeof(float) * hs.size()));
+            }
+        }
+        OBIA_TRY(upload_async(ctx, b.d_cent_prob, hp.data(), sizeof(int) * hp.size()));
     } else if (b.masked) {
         int *d_K = A.get<int>(np);
         if (!d_K) return OBIA_E_NOMEM;

@@ -172,9 +172,12 @@ inline std::pair<int, int> slic_cc_sizes(double min_size_factor, double max_size
 // Seeds (grid or masked grid), fills K / steps / bins in b.probs, uploads descriptors.
 // n_segments[p] = requested segments of problem p.
 // nvalid (nullable): valid-pixel counts already known to the caller.
-// ext (nullable, single-problem batches only): externally supplied initial centroids -- scikit-image's own
-// _get_mask_centroids output (slic_superpixels.py:14-68) -- instead of the grid rule; step = max(steps).
-struct ExternalSeeds { const double *yx; int n; double step; };
+// ext (nullable): externally supplied initial centroids -- scikit-image's own _get_mask_centroids output
+// (slic_superpixels.py:14-68) -- instead of the grid rule; step = max(steps).  One entry per problem of the batch (a single-raster
+// call passes the address of one); n = 0 marks a problem without centroids, which is skipped like an empty one.  The positions
+// come from the host (yx, float64, converted like segments.astype(float32)) or, when d_yx is set, from device memory as the
+// float32 pairs themselves (the tiler's per-tile seeding leaves them there: mask_centroids_queue).
+struct ExternalSeeds { const double *yx; int n; double step; const float *d_yx = nullptr; };
 int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_segments,
                        const std::vector<int> *nvalid = nullptr, const ExternalSeeds *ext = nullptr);
 // valid (unmasked) pixels per problem: mask.sum() (tiling.py:133, slic_superpixels.py:322)
@@ -200,6 +203,14 @@ int slic_stage_outputs(obia_ctx *ctx, const SlicBatch &b, float *features, float
 // has checked them -- picks sorted and >= 0, K >= 1, n_dense >= 1 when dense is given).  mask: device; everything else: host.
 int mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int K, const int64_t *dense, long long n_dense,
                        int iters, double *centroids_yx_out, double *steps_zyx_out);
+// The same seeding for one tile of a batch, queued on the context's stream WITHOUT a host synchronisation: `mask` is the tile's
+// dense (h, w) window inside the batch's mask (SlicBatch::d_mask + pix_off -- the tiler's mask kernel built it), the picks are ranks
+// among its n_valid valid pixels in the window's row-major order (the caller has counted them and checked the picks against the count).  The
+// centroids land in seeds_out_dev as K float32 (y, x) pairs -- what the sweeps start from -- and the row / column means of
+// |centroid - nearest other centroid| in steps_out_dev[0..1]; the caller reads the steps of all its tiles back at once.  The
+// workspace is taken from the arena and given back before returning: the next tile's kernels reuse it in stream order.
+int mask_centroids_queue(obia_ctx *ctx, const uint8_t *mask, int h, int w, long long n_valid, const int64_t *picks, int K, const int64_t *dense,
+                         long long n_dense, int iters, float *seeds_out_dev, double *steps_out_dev);
 
 // Connectivity enforcement on a batch of dense label maps laid out back to back (pix_off); labels come
 // out consecutive over the whole batch, in problem order then raster order of each component's first pixel.

@@ -333,6 +333,9 @@ struct TileState {
     obia_tiling_params tp;
     obia_slic_params sp;
     SlicBatch settings;    // slic_batch_settings of (sp, C): every batch of the tiler, and the white prefetch, starts as a copy
+    int seeding = OBIA_SEEDING_GRID;       // OBIA_SEEDING_*: how every tile is seeded (obia_tiler_set_seeding)
+    obia_pick_fn pick_fn = nullptr;        // OBIA_SEEDING_SKIMAGE: the caller's source of the random picks
+    void *pick_user = nullptr;
     // features of ALL white tiles, prepared in one batch (they depend on the raster only): windows in processing order,
     // one dense buffer, keys read back once before the white pass
     struct PreFeat {
@@ -359,6 +362,69 @@ static int grid_rows(const std::vector<TileWin> &wins) {   // row-walking kernel
 
 // One batch of tiles: mask -> features -> plan -> sweeps -> connectivity -> scatter.
 static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside = false);
+
+// OBIA_SEEDING_SKIMAGE: every tile of the batch is seeded as scikit-image seeds maskSLIC, from its own window of the batch's mask
+// (b.d_mask + pix_off: dense (h, w), for a white tile what tile_mask_kernel left of the input mask).  A tile with n < 2 or fewer
+// than two valid pixels is skipped (nseg[p] = 0): scikit-image ends with a zero step there and raises, the reference's tile loop
+// prints "empty tile" (tiling.py:149-150).  The tiles are queued one after the other on the context's stream with no host
+// synchronisation in between -- the host fetches and checks the picks of tile p + 1 while the kernels of tile p run -- and the steps
+// of all tiles come back in ONE read-back; the centroids never leave the device (ext[p].d_yx).
+static int seed_tiles_skimage(obia_ctx *ctx, TileState &S, const SlicBatch &b, const std::vector<int> &nvalid, std::vector<int> &nseg,
+                              std::vector<ExternalSeeds> &ext) {
+    const int np = b.nprob;
+    if (!S.pick_fn) { set_error("seeding = skimage needs a pick function"); return OBIA_E_INVALID; }
+    Arena &A = ctx->arena;
+    ext.assign(np, ExternalSeeds{nullptr, 0, 1.0, nullptr});
+    std::vector<long long> off(np, 0);
+    long long total = 0;
+    for (int p = 0; p < np; ++p) {
+        if (nseg[p] < 2 || nvalid[p] < 2) { nseg[p] = 0; continue; }
+        off[p] = total;
+        total += std::min(nseg[p], nvalid[p]);   // K = min(n, n_valid) exactly
+    }
+    if (total == 0) return OBIA_OK;
+    if (total > 0x7fff0000LL) { set_error("too many centroids in one batch"); return OBIA_E_INVALID; }
+    float *d_seeds = A.get<float>(2 * (size_t)total);
+    double *d_steps = A.get<double>(2 * (size_t)np);
+    if (!d_seeds || !d_steps) return OBIA_E_NOMEM;
+    OBIA_HIP_TRY(hipMemsetAsync(d_steps, 0, sizeof(double) * 2 * (size_t)np, ctx->stream));
+    auto ascending_below = [](const int64_t *v, long long n, long long bound) {
+        if (v[0] < 0 || v[n - 1] >= bound) return false;
+        for (long long i = 1; i < n; ++i) if (v[i] <= v[i - 1]) return false;
+        return true;
+    };
+    for (int p = 0; p < np; ++p) {
+        if (nseg[p] == 0) continue;
+        const int K = std::min(nseg[p], nvalid[p]);
+        const int64_t *idx = nullptr, *dense = nullptr;
+        int32_t n_idx = 0;
+        int64_t n_dense = 0;
+        if (S.pick_fn(S.pick_user, (int64_t)nvalid[p], (int32_t)nseg[p], &idx, &n_idx, &dense, &n_dense) != 0) {
+            set_error("the pick function failed for a tile with %d valid pixels and n_segments = %d", nvalid[p], nseg[p]);
+            return OBIA_E_INVALID;
+        }
+        if (!idx || n_idx != K || !ascending_below(idx, K, nvalid[p]) ||
+            (dense && (n_dense < 1 || n_dense > nvalid[p] || !ascending_below(dense, n_dense, nvalid[p])))) {
+            set_error("the pick function returned bad picks for a tile with %d valid pixels and n_segments = %d: %d strictly ascending ranks below the "
+                      "valid count are needed", nvalid[p], nseg[p], K);
+            return OBIA_E_INVALID;
+        }
+        const SlicProblem &P = b.probs[p];
+        OBIA_TRY(mask_centroids_queue(ctx, b.d_mask + P.pix_off, P.H, P.W, nvalid[p], idx, K, dense, dense ? (long long)n_dense : 0, 5,
+                                      d_seeds + 2 * off[p], d_steps + 2 * (size_t)p));
+        ext[p].n = K;
+        ext[p].d_yx = d_seeds + 2 * off[p];
+    }
+    std::vector<double> steps(2 * (size_t)np);
+    OBIA_TRY(read_back(ctx, steps.data(), d_steps, sizeof(double) * steps.size()));
+    for (int p = 0; p < np; ++p) {
+        if (ext[p].n == 0) continue;
+        const double st = std::max(steps[2 * (size_t)p], steps[2 * (size_t)p + 1]);   // step = max(steps); the depth axis contributes 0
+        if (!(st >= 0.0) || !(st < 1e9)) { set_error("tile seeding: steps are not finite"); return OBIA_E_INVALID; }
+        ext[p].step = st;
+    }
+    return OBIA_OK;
+}
 
 static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &wins, bool white) {
     const int np = (int)wins.size();
@@ -441,7 +507,9 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
             n = std::nearbyint((double)nvalid[p] * pixel_area / crown_area);   // Python round(): half to even
         nseg[p] = (skip[p] || n < 1.0) ? 0 : (n > 2.0e9 ? 2000000000 : (int)n);   // empty tile -> skipped (tiling.py:149-150)
     }
-    OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid));
+    std::vector<ExternalSeeds> ext;
+    if (S.seeding == OBIA_SEEDING_SKIMAGE) OBIA_TRY(seed_tiles_skimage(ctx, S, b, nvalid, nseg, ext));
+    OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid, ext.empty() ? nullptr : ext.data()));
     debug_sync(ctx, "tiler: plan_and_seed");
     if (!white && S.pf.b.d_feat && !S.pf.launched) OBIA_TRY(prefetch_white_launch(ctx, S, true));
     const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
@@ -599,7 +667,8 @@ static int tiler_init(obia_ctx *ctx, TileState &S, const float *img, const uint8
     const long long wh = (long long)(T + 2 * B) * (T + 2 * B);
     double n = sp->n_segments > 0 ? (double)sp->n_segments * (double)wh / ((double)T * T) : (double)wh * pixel_area / crown_area;
     if (n < 1) n = 1;
-    // masked seeding lays a grid for n_eff ~ n over the window; rounding of the step can add ~(1 + 1/S)^2
+    // masked seeding lays a grid for n_eff ~ n over the window; rounding of the step can add ~(1 + 1/S)^2.  (OBIA_SEEDING_SKIMAGE: a tile
+    // has K = min(n, n_valid) <= n + 1/2 centroids, n_valid at most the grown window's pixels: inside the same bound.)
     long long cap = (long long)(n * 1.5 + 64.0) * (long long)ntx * nty + 16 + extra_ids;
     if (cap > 0x7ffffff0LL) { set_error("too many segments for int32 ids"); return OBIA_E_INVALID; }
     S.H = H; S.W = W; S.C = C; S.Hg = Hg; S.row0 = row0; S.img = img; S.inmask = mask; S.G = labels; S.tp = *tp; S.sp = *sp;
@@ -781,11 +850,19 @@ static int tiler_finalize(obia_ctx *ctx, TileState &S, int64_t *n_segments_out) 
     return OBIA_OK;
 }
 
+static int check_seeding(int seeding, obia_pick_fn picks) {
+    if (seeding != OBIA_SEEDING_GRID && seeding != OBIA_SEEDING_SKIMAGE) { set_error("seeding must be OBIA_SEEDING_GRID or OBIA_SEEDING_SKIMAGE (got %d)", seeding); return OBIA_E_INVALID; }
+    if (seeding == OBIA_SEEDING_SKIMAGE && !picks) { set_error("seeding = skimage needs a pick function"); return OBIA_E_INVALID; }
+    return OBIA_OK;
+}
+
 static int tiled_slic_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
-                          const obia_tiling_params *tp, const obia_slic_params *sp, int32_t *labels_out,
-                          int64_t *n_segments_out) {
+                          const obia_tiling_params *tp, const obia_slic_params *sp, int seeding, obia_pick_fn picks, void *picks_user,
+                          int32_t *labels_out, int64_t *n_segments_out) {
     TileState S;
+    OBIA_TRY(check_seeding(seeding, picks));
     OBIA_TRY(tiler_init(ctx, S, img, mask, H, W, C, H, 0, tp, sp, labels_out, 0));
+    S.seeding = seeding; S.pick_fn = picks; S.pick_user = picks_user;
     OBIA_HIP_TRY(hipMemsetAsync(labels_out, 0, sizeof(int32_t) * (size_t)H * W, ctx->stream));
     const int nty = cdiv(H, tp->tile_size);
     OBIA_TRY(prefetch_white_plan(ctx, S, tp->white_order));               // features of all white tiles: one batch
@@ -858,6 +935,13 @@ int obia_tiler_run(obia_tiler *t, int white, int tile_row_lo, int tile_row_hi, i
 }
 
 int obia_tiler_next_id(obia_tiler *t) { return t ? t->S.next_id : -1; }
+
+int obia_tiler_set_seeding(obia_tiler *t, int seeding, obia_pick_fn picks, void *picks_user) {
+    if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
+    OBIA_TRY(check_seeding(seeding, picks));
+    t->S.seeding = seeding; t->S.pick_fn = picks; t->S.pick_user = picks_user;
+    return OBIA_OK;
+}
 
 int obia_tiler_set_segments(obia_tiler *t, int first_id, int count, const uint32_t *sizes_dev) {
     if (!t || !sizes_dev || first_id < 1 || count < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
@@ -935,9 +1019,9 @@ int obia_tiler_finalize(obia_tiler *t, int64_t *n_segments_out) {
     return rc == OBIA_OK ? rc : fail_quiesced(t->ctx, rc);
 }
 
-int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
-                            const obia_tiling_params *tiling, const obia_slic_params *params, int32_t *labels_out,
-                            int64_t *n_segments_out) {
+int obia_tiled_slic_seeded_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
+                                   const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
+                                   obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out) {
     if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
     if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     ctx->arena.reset();
@@ -945,7 +1029,7 @@ int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask
     int rc;
     {
         ScopedSpan total(ctx, T_TOTAL);
-        rc = tiled_slic_dev(ctx, img, mask, H, W, C, tiling, params, labels_out, n_segments_out);
+        rc = tiled_slic_dev(ctx, img, mask, H, W, C, tiling, params, seeding, picks, picks_user, labels_out, n_segments_out);
     }
     if (rc != OBIA_OK) return fail_quiesced(ctx, rc);
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -953,11 +1037,18 @@ int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask
     return OBIA_OK;
 }
 
-int obia_tiled_slic_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
-                        const obia_tiling_params *tiling, const obia_slic_params *params, int32_t *labels_out,
-                        int64_t *n_segments_out) {
+int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
+                            const obia_tiling_params *tiling, const obia_slic_params *params, int32_t *labels_out,
+                            int64_t *n_segments_out) {
+    return obia_tiled_slic_seeded_f32_dev(ctx, img, mask, H, W, C, tiling, params, OBIA_SEEDING_GRID, nullptr, nullptr, labels_out, n_segments_out);
+}
+
+int obia_tiled_slic_seeded_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
+                               const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
+                               obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out) {
     if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
     if (!img || !labels_out || H <= 0 || W <= 0 || C <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
+    OBIA_TRY(check_seeding(seeding, picks));
     if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     const size_t npix = (size_t)H * W;
     float *d_img = nullptr; uint8_t *d_mask = nullptr; int32_t *d_lab = nullptr;
@@ -970,7 +1061,7 @@ int obia_tiled_slic_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, in
     if (rc == OBIA_OK && hipMemcpyAsync(d_img, img, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
     if (rc == OBIA_OK && mask && hipMemcpyAsync(d_mask, mask, npix, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
     if (rc == OBIA_E_HIP) set_error("host->device copy failed in obia_tiled_slic_f32");
-    if (rc == OBIA_OK) rc = obia_tiled_slic_f32_dev(ctx, d_img, d_mask, H, W, C, tiling, params, d_lab, n_segments_out);
+    if (rc == OBIA_OK) rc = obia_tiled_slic_seeded_f32_dev(ctx, d_img, d_mask, H, W, C, tiling, params, seeding, picks, picks_user, d_lab, n_segments_out);
     if (rc == OBIA_OK && hipMemcpyAsync(labels_out, d_lab, npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
         set_error("device->host copy failed in obia_tiled_slic_f32");
         rc = OBIA_E_HIP;
@@ -978,6 +1069,12 @@ int obia_tiled_slic_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, in
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_img); (void)hipFree(d_lab); (void)hipFree(d_mask);
     return rc;
+}
+
+int obia_tiled_slic_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
+                        const obia_tiling_params *tiling, const obia_slic_params *params, int32_t *labels_out,
+                        int64_t *n_segments_out) {
+    return obia_tiled_slic_seeded_f32(ctx, img, mask, H, W, C, tiling, params, OBIA_SEEDING_GRID, nullptr, nullptr, labels_out, n_segments_out);
 }
 
 }  // extern "C"

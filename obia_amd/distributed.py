@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .segmentation import make_params
+from .segmentation import make_params, MaskSeedPickSource, check_seeding
 
 CODE_SHIFT = 24                      # a segment travels as the int32 code (owner_rank + 1) << 24 | owner_local_id
 ID_MASK = (1 << CODE_SHIFT) - 1
@@ -42,6 +42,10 @@ class HipTilerEngine:
         assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
         self.img, self.mask = img, mask
         H, W, C = img.shape
+        # ``seeding`` rides with the SLIC keywords (create_tiled_segments' argument): "grid", or "skimage" -- every tile seeded as
+        # scikit-image seeds maskSLIC.  Every rank draws its own tiles' picks: they depend on (valid pixels, n) only, nothing is exchanged.
+        slic_kwargs = dict(slic_kwargs)
+        rule = check_seeding(slic_kwargs.pop("seeding", "grid"))
         self.G = torch.zeros((H, W), dtype=torch.int32, device=img.device)
         n_seg = slic_kwargs.get("n_segments", None)
         self.params = make_params(n_segments=0 if n_seg is None else n_seg, compactness=slic_kwargs.get("compactness", 10.0),
@@ -68,10 +72,20 @@ class HipTilerEngine:
                                             self.G.data_ptr(), int(extra_ids))
         if not self.h:
             raise ValueError(_lib.last_error())
+        self.picks = None
+        if rule == _lib.SEEDING_SKIMAGE:
+            self.picks = MaskSeedPickSource()      # (kept alive for the session's lifetime: the library calls it from every pass)
+            rc = self.lib.obia_tiler_set_seeding(self.h, rule, self.picks.fn, None)
+            if rc != _lib.OBIA_OK:
+                self.close()
+                _lib.check(rc)
 
     def run(self, white, tr_lo, tr_hi, parity=-1):
         torch.cuda.current_stream(self.G.device).synchronize()
-        _lib.check(self.lib.obia_tiler_run(self.h, int(bool(white)), int(tr_lo), int(tr_hi), int(parity)))
+        rc = self.lib.obia_tiler_run(self.h, int(bool(white)), int(tr_lo), int(tr_hi), int(parity))
+        if self.picks is not None:
+            self.picks.reraise()
+        _lib.check(rc)
 
     def next_id(self):
         return int(self.lib.obia_tiler_next_id(self.h))
@@ -260,6 +274,7 @@ class ShardedTiler:
     def __init__(self, slab, mask_slab, global_rows, tile_rows_per_rank, tile_size, buffer, crown_radius=5,
                  pixel_size=(1.0, 1.0), engine_factory=None, group=None, ctx=None, ext_image=None, ext_mask=None, comm=None,
                  **slic_kwargs):
+        check_seeding(slic_kwargs.get("seeding", "grid"))      # (ValueError before anything is exchanged or allocated)
         self.clock = _PhaseClock(slic_kwargs.pop("profile", False), slab.device)
         self.clock.start()
         self.comm = comm if comm is not None else TorchComm(group)

@@ -110,6 +110,52 @@ def _mask_seed_picks(n_valid, n_segments):
     return np.ascontiguousarray(idx, np.int64), None if dense is None else np.ascontiguousarray(dense, np.int64)
 
 
+class MaskSeedPickSource:
+    """:func:`_mask_seed_picks` behind the library's pick-function interface (``obia_pick_fn``, include/obia_hip.h): the tiled
+    drivers ask it for the two draws of every tile they seed with ``seeding="skimage"``.  ``fn`` is the C callable; the object must
+    stay alive as long as the library can call it (a one-shot call, or a tiler session).  The arrays of the last answers are kept --
+    the library reads them until the next call -- and full tiles of one raster share their (n_valid, n_segments), so the few most
+    recent draws are reused.  An exception inside the callback cannot cross the C frames: it is parked in ``error`` and the call
+    fails with OBIA_E_INVALID; :meth:`reraise` hands it on."""
+
+    def __init__(self, keep=8):
+        self.error = None
+        self.calls = 0
+        self._keep = int(keep)
+        self._recent = {}
+        self.fn = _lib.PickFn(self._answer)
+
+    def _answer(self, user, n_valid, n_segments, idx_out, n_idx_out, dense_out, n_dense_out):
+        try:
+            key = (int(n_valid), int(n_segments))
+            got = self._recent.pop(key, None)
+            if got is None:
+                got = _mask_seed_picks(*key)
+            self._recent[key] = got                     # (most recent last)
+            while len(self._recent) > self._keep:
+                self._recent.pop(next(iter(self._recent)))
+            idx, dense = got
+            idx_out[0], n_idx_out[0] = idx.ctypes.data, len(idx)
+            dense_out[0], n_dense_out[0] = (None, 0) if dense is None else (dense.ctypes.data, len(dense))
+            self.calls += 1
+            return 0
+        except BaseException as e:  # noqa: BLE001  (parked: see the class docstring)
+            self.error = e
+            return 1
+
+    def reraise(self):
+        if self.error is not None:
+            e, self.error = self.error, None
+            raise e
+
+
+def check_seeding(seeding):
+    """The tiled drivers' ``seeding`` argument -> OBIA_SEEDING_*; ValueError like :func:`slic` for anything else."""
+    if seeding not in _SEEDINGS:
+        raise ValueError(f'seeding must be "grid" or "skimage" (got {seeding!r})')
+    return _lib.SEEDING_SKIMAGE if seeding == "skimage" else _lib.SEEDING_GRID
+
+
 def mask_centroids(mask, n_segments, ctx=None):
     """scikit-image's ``_get_mask_centroids(mask[np.newaxis], n_segments, True)`` (0.18: slic_superpixels.py:14-68), bit for bit, on the
     GPU: the seeds maskSLIC starts from.  ``mask``: (H, W) NumPy array or CUDA tensor, non-zero = valid.  Returns

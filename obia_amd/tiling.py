@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .segmentation import make_params, _is_torch, _SLIC_KWARGS
+from .segmentation import make_params, _is_torch, _SLIC_KWARGS, MaskSeedPickSource, check_seeding
 
 try:
     import torch
@@ -53,7 +53,7 @@ def write_segments_gpkg(labels, output_dir, affine_transformation=None, crs=None
 
 def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method="slic", tile_size=200, buffer=30,
                           crown_radius=5, pixel_size=None, white_order="raster", affine_transformation=None, crs=None, ctx=None,
-                          **kwargs):
+                          seeding="grid", **kwargs):
     """Tiled SLIC over a large raster.
 
     input_raster : path (GDAL), object with ``img_data``, (H,W,C) NumPy array, or CUDA tensor.
@@ -68,6 +68,12 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
         geometry + segment_id), from either entry (NumPy array or CUDA tensor).  ``affine_transformation`` ([a, b, d, e,
         xoff, yoff], obia ``Image.affine_transformation``; taken from the geotransform for paths, default: pixel size and
         a north-up origin at (0, 0)) and ``crs`` ("EPSG:xxxx") place the polygons.
+    seeding      : ``"grid"`` (default): every tile is seeded by the deterministic masked-grid rule.  ``"skimage"``: every
+        tile is seeded as scikit-image 0.18 seeds maskSLIC -- what every tile of the reference goes through -- from the tile's own mask
+        (for a white tile the input mask minus kept segments and corner squares): ``RandomState(123)`` picks drawn here per tile,
+        k-means and steps in the library, bit for bit (:func:`obia_amd.segmentation.mask_centroids`).  K = min(n, valid pixels); a tile
+        with n < 2 or fewer than two valid pixels is skipped like an empty tile (scikit-image raises there and the reference's tile
+        loop prints "empty tile").  The step is not divided by ``spacing``, as in ``slic(seeding="skimage")``.  Anything else: ValueError.
     kwargs       : SLIC keyword arguments (scikit-image names).  ``n_segments`` (which the reference
         cannot accept: duplicate keyword TypeError, tiling.py:126,137-143) is taken per full tile and
         scaled by the tile's valid area.
@@ -75,6 +81,7 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
     """
     if method != "slic":
         raise ValueError("Currently, only the 'slic' method is supported for segmentation.")
+    rule = check_seeding(seeding)
     unknown = [k for k in kwargs if k not in _SLIC_KWARGS]
     if unknown:
         raise TypeError(f"slic() got an unexpected keyword argument '{unknown[0]}'")
@@ -113,6 +120,15 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
     tp.crown_radius, tp.pixel_width, tp.pixel_height = float(crown_radius), float(pw), float(ph)
     lib = _lib.load()
     n_out = ctypes.c_int64(0)
+    picks = MaskSeedPickSource() if rule == _lib.SEEDING_SKIMAGE else None      # (alive until the call has returned)
+
+    def run(plain, seeded, *args):
+        """the one-shot call: (..., labels, n) of the grid rule, or its *_seeded flavour with (rule, pick function, user) before them"""
+        if picks is None:
+            return _lib.check(plain(*args))
+        rc = seeded(*args[:-2], rule, picks.fn, None, *args[-2:])
+        picks.reraise()
+        _lib.check(rc)
     if _is_torch(img):
         if not img.is_cuda:
             raise ValueError("torch inputs must live on the GPU")
@@ -127,8 +143,8 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
         c = ctx or _lib.default_context(dev)
         torch.cuda.current_stream(dev).synchronize()
         out = torch.empty((H, W), dtype=torch.int32, device=x.device)
-        _lib.check(lib.obia_tiled_slic_f32_dev(c.handle, x.data_ptr(), m.data_ptr() if m is not None else None, H, W, C,
-                                               ctypes.byref(tp), ctypes.byref(params), out.data_ptr(), ctypes.byref(n_out)))
+        run(lib.obia_tiled_slic_f32_dev, lib.obia_tiled_slic_seeded_f32_dev, c.handle, x.data_ptr(), m.data_ptr() if m is not None else None, H, W, C,
+            ctypes.byref(tp), ctypes.byref(params), out.data_ptr(), ctypes.byref(n_out))
         if output_dir is not None:
             write_segments_gpkg(out, output_dir, affine_transformation or [pw, 0.0, 0.0, -ph, 0.0, 0.0], crs, ctx=c)
         return out, int(n_out.value)
@@ -143,8 +159,8 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
             raise ValueError("image and mask should have the same shape.")
     c = ctx or _lib.default_context(0)
     out = np.empty((H, W), np.int32)
-    _lib.check(lib.obia_tiled_slic_f32(c.handle, _lib.np_ptr(x), _lib.np_ptr(m), H, W, C, ctypes.byref(tp),
-                                       ctypes.byref(params), _lib.np_ptr(out), ctypes.byref(n_out)))
+    run(lib.obia_tiled_slic_f32, lib.obia_tiled_slic_seeded_f32, c.handle, _lib.np_ptr(x), _lib.np_ptr(m), H, W, C, ctypes.byref(tp),
+        ctypes.byref(params), _lib.np_ptr(out), ctypes.byref(n_out))
     if output_dir is not None:
         write_segments_gpkg(out, output_dir, affine_transformation or [pw, 0.0, 0.0, -ph, 0.0, 0.0], crs, ctx=c)
     return out, int(n_out.value)
