@@ -512,6 +512,34 @@ int obia_table_scale_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int
 int obia_forest_predict_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest,
                             const uint8_t *acceptable, double *proba_out, int32_t *pred_out, double *margin_out);
 
+/* ---- a fitted MLPClassifier on the whole segment table (scikit-learn's _forward_pass_fast, then class filter and margin) ----
+ * obia_table_scale_f64_dev : obia_table_scale_dev without the cast: the same mean_out / scale_out bit for bit (the same partial
+ *                        sums), scaled_out (n_rows, n_features) float64 = (x - mean) / scale.  What MLPClassifier is handed.
+ * obia_mlp_predict_dev : x (n_rows, n_features) float64, n_features = layer_sizes[0].  All arithmetic in float64, every product
+ *                        and every sum rounded on its own (no fma): per layer and unit j,
+ *                        z_j = ((...((0.0 + a_0 W[0,j]) + a_1 W[1,j]) + ...) + a_{n-1} W[n-1,j]) + b_j, inputs in ascending order.
+ *                        Hidden activation: 0 identity, 1 relu (z > 0 ? z : 0.0), 2 tanh(z), 3 logistic 1 / (1 + exp(-z)).
+ *                        Output: 0 softmax -- m = max_k z_k, e_k = exp(z_k - m), s = the e_k added in ascending k, p_k = e_k / s;
+ *                        1 binary logistic -- p = 1 / (1 + exp(-z_0)), proba = [1 - p, p] (n_out = 1, n_classes = 2).
+ *                        acceptable / proba_out / pred_out / margin_out: as in obia_forest_predict_dev, the same selection rule.
+ *                        logits_out (n_rows, n_out) float64, nullable: the last layer before the output activation.
+ *                        A NaN or an infinity in x: OBIA_E_INVALID, "Input X contains NaN or infinity" (outputs unspecified).
+ *                        More than 8 weight matrices, 4096 features, 64 classes or 512 units in a hidden layer: OBIA_E_UNSUPPORTED.
+ * obia_mlp: weights = coefs_[0], coefs_[1], ... each row-major (n_in, n_out), one after the other; biases = intercepts_ likewise. */
+typedef struct obia_mlp {
+    const double *weights;        /* device */
+    const double *biases;         /* device */
+    const int32_t *layer_sizes;   /* HOST: n_layers + 1 values: n_features, hidden widths ..., n_out (K, or 1 for binary logistic) */
+    int32_t n_layers;             /* number of weight matrices */
+    int32_t hidden_activation;    /* 0 identity, 1 relu, 2 tanh, 3 logistic */
+    int32_t out_activation;       /* 0 softmax, 1 logistic (binary) */
+    int32_t n_classes;
+} obia_mlp;
+int obia_mlp_predict_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_features, const obia_mlp *mlp, const uint8_t *acceptable,
+                         double *proba_out, int32_t *pred_out, double *margin_out, double *logits_out);
+int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
+                             double *scaled_out);
+
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
  * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of

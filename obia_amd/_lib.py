@@ -56,6 +56,12 @@ class Forest(ctypes.Structure):
                 ("value", ctypes.c_void_p), ("n_nodes", ctypes.c_int64), ("n_trees", ctypes.c_int32), ("n_classes", ctypes.c_int32)]
 
 
+class Mlp(ctypes.Structure):
+    """obia_mlp (include/obia_hip.h): the flat weights and biases of a multi-layer perceptron."""
+    _fields_ = [("weights", ctypes.c_void_p), ("biases", ctypes.c_void_p), ("layer_sizes", ctypes.c_void_p), ("n_layers", ctypes.c_int32),
+                ("hidden_activation", ctypes.c_int32), ("out_activation", ctypes.c_int32), ("n_classes", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 SEEDING_GRID, SEEDING_SKIMAGE = 0, 1   # OBIA_SEEDING_* (include/obia_hip.h)
@@ -130,6 +136,8 @@ _SIGNATURES = {
                                     ctypes.POINTER(ctypes.c_int)]),
     "obia_table_scale_dev": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
     "obia_forest_predict_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Forest), _P, _P, _P, _P]),
+    "obia_mlp_predict_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Mlp), _P, _P, _P, _P, _P]),
+    "obia_table_scale_f64_dev": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
     "obia_set_profiling": (_I, [_P, _I]),
     "obia_last_timing": (ctypes.c_double, [_P, _I]),
 }

@@ -4,11 +4,16 @@ Training stays scikit-learn on the host: it sees a few hundred labelled rows and
 the whole segment table runs on the device (libobia_hip.so, csrc/classify.hip):
 
     standard_scale  ``StandardScaler().fit(x).transform(x)`` of classify.py:126-129 plus the forest's cast to float32
+                    (``dtype=np.float64``: without the cast, what ``MLPClassifier`` is handed)
     forest_predict  the ``segments.iterrows()`` loop of :135-158 -- ``predict_proba`` / ``predict`` row by row, the class filter
                     and the margin -- as one tree walk per (row, tree) for all rows at once
+    mlp_predict     the same loop for a fitted ``MLPClassifier``: the forward pass of all rows, class filter and margin in one
+                    kernel (csrc/mlp.hip)
+    predict_segments  the back half of ``classify`` for a classifier fitted earlier (forest or MLP)
 
-The arithmetic is scikit-learn's: ``proba`` is bit-identical to ``RandomForestClassifier.predict_proba`` with
-``n_jobs=None``.  There is no CPU path.
+The forest's arithmetic is scikit-learn's: ``proba`` is bit-identical to
+``RandomForestClassifier.predict_proba`` with ``n_jobs=None``.  The MLP's is an order of our own in float64:
+scikit-learn's own bits depend on the BLAS call.  There is no CPU path.
 """
 import ctypes
 import struct
@@ -25,6 +30,10 @@ except Exception:  # pragma: no cover
 MAX_CLASSES, MAX_FEATURES, MAX_TREES = 64, 4096, 65536
 _FOREST_ARRAYS = ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset", "value")
 _DROPPED = ["feature_class", "geometry", "segment_id"]
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 8, 512
+_MLP_ARRAYS = ("weights", "biases", "layer_sizes")
+_HIDDEN_ACTIVATIONS = ("identity", "relu", "tanh", "logistic")     # obia_mlp.hidden_activation
+_OUT_ACTIVATIONS = ("softmax", "logistic")                         # obia_mlp.out_activation
 
 
 def _is_torch(x):
@@ -128,13 +137,87 @@ class Forest:
         return d
 
 
-def standard_scale(table, ctx=None):
+class MLP:
+    """A fitted multi-layer perceptron as flat arrays: ``weights`` float64 = ``coefs_[0]``, ``coefs_[1]``, ... each row-major
+    (n_in, n_out), one after the other; ``biases`` float64 = ``intercepts_`` likewise; ``layer_sizes`` int32 = n_features, hidden
+    widths ..., n_out (the number of classes, or 1 for the binary logistic output); ``hidden_activation`` one of identity / relu /
+    tanh / logistic; ``out_activation`` softmax or logistic; ``classes_`` (K,)."""
+
+    def __init__(self, weights, biases, layer_sizes, hidden_activation, out_activation, classes_):
+        self.weights = np.ascontiguousarray(weights, np.float64)
+        self.biases = np.ascontiguousarray(biases, np.float64)
+        self.layer_sizes = np.ascontiguousarray(layer_sizes, np.int32)
+        self.hidden_activation, self.out_activation = str(hidden_activation), str(out_activation)
+        self.classes_ = np.asarray(classes_)
+        if self.classes_.dtype == object:
+            raise ValueError("classes_ must be numbers or strings, not Python objects")
+        if self.hidden_activation not in _HIDDEN_ACTIVATIONS:
+            raise ValueError(f"hidden_activation must be one of {_HIDDEN_ACTIVATIONS}, got {self.hidden_activation!r}")
+        if self.out_activation not in _OUT_ACTIVATIONS:
+            raise ValueError(f"out_activation must be one of {_OUT_ACTIVATIONS}, got {self.out_activation!r}")
+        ls = self.layer_sizes
+        if ls.ndim != 1 or ls.shape[0] < 2 or (ls <= 0).any():
+            raise ValueError("layer_sizes must hold n_features, the hidden widths and n_out, all positive")
+        n_w = int((ls[:-1].astype(np.int64) * ls[1:]).sum())
+        if self.weights.shape != (n_w,) or self.biases.shape != (int(ls[1:].sum()),):
+            raise ValueError(f"layer_sizes {ls.tolist()} need {n_w} weights and {int(ls[1:].sum())} biases, flat")
+        if self.classes_.ndim != 1 or len(self.classes_) != (int(ls[-1]) if self.out_activation == "softmax" else 2) or \
+                (self.out_activation == "logistic" and ls[-1] != 1):
+            raise ValueError("softmax needs one output per class; the logistic output is one unit for two classes")
+        self._dev = {}
+
+    n_features = property(lambda self: int(self.layer_sizes[0]))
+    n_layers = property(lambda self: int(self.layer_sizes.shape[0]) - 1)
+    n_classes = property(lambda self: int(len(self.classes_)))
+
+    @classmethod
+    def from_sklearn(cls, clf):
+        """Read a fitted ``MLPClassifier``.  float32 ``coefs_`` become float64, as NumPy promotes them against a float64 table."""
+        if clf.out_activation_ == "logistic" and clf.n_outputs_ > 1:
+            raise NotImplementedError("multilabel MLPClassifier (several logistic outputs) is not supported")
+        ls = [int(clf.coefs_[0].shape[0])] + [int(w.shape[1]) for w in clf.coefs_]
+        return cls(np.concatenate([np.asarray(w, np.float64).ravel() for w in clf.coefs_]),
+                   np.concatenate([np.asarray(b, np.float64).ravel() for b in clf.intercepts_]), ls, clf.activation, clf.out_activation_,
+                   np.asarray(clf.classes_))
+
+    def layers(self):
+        """[(W (n_in, n_out), b (n_out,)), ...] as views of the flat arrays."""
+        out, wo, bo = [], 0, 0
+        for n_in, n_out in zip(self.layer_sizes[:-1].tolist(), self.layer_sizes[1:].tolist()):
+            out.append((self.weights[wo:wo + n_in * n_out].reshape(n_in, n_out), self.biases[bo:bo + n_out]))
+            wo, bo = wo + n_in * n_out, bo + n_out
+        return out
+
+    def save(self, path):
+        """Plain ``.npz`` of the arrays, the two activation names and ``classes_``; nothing pickled."""
+        np.savez(path, classes_=self.classes_, hidden_activation=np.str_(self.hidden_activation),
+                 out_activation=np.str_(self.out_activation), **{k: getattr(self, k) for k in _MLP_ARRAYS})
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(classes_=z["classes_"], hidden_activation=str(z["hidden_activation"]), out_activation=str(z["out_activation"]),
+                       **{k: z[k] for k in _MLP_ARRAYS})
+
+    def _on(self, device):
+        d = self._dev.get(str(device))
+        if d is None:
+            d = self._dev[str(device)] = {k: torch.as_tensor(getattr(self, k), device=device) for k in ("weights", "biases")}
+        return d
+
+
+def standard_scale(table, ctx=None, dtype=np.float32):
     """``StandardScaler().fit(table).transform(table)`` followed by the forest's cast: returns ``(X32, mean, scale)`` with X32
     (N, F) float32 and ``mean`` / ``scale`` (F,) float64 (obia_table_scale_dev).  Per column the NaNs are left out of the count,
     the mean and the two-pass variance; a column scikit-learn treats as constant gets scale 1; an all-NaN column stays NaN.
-    NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    ``dtype=np.float64``: the table without the cast, as ``MLPClassifier`` is handed it (obia_table_scale_f64_dev; ``mean`` and
+    ``scale`` are the same bits).  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
     if torch is None:
         raise ImportError("obia_amd.classify needs torch for device memory")
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be numpy.float32 or numpy.float64")
     is_t = _is_torch(table)
     if is_t and not table.is_cuda:
         raise ValueError("torch inputs must live on the GPU")
@@ -154,9 +237,11 @@ def standard_scale(table, ctx=None):
     N, F = shape
     mean = torch.empty((F,), dtype=torch.float64, device=t.device)
     scale = torch.empty_like(mean)
-    out = torch.empty((N, F), dtype=torch.float32, device=t.device)
+    wide = dtype == np.dtype(np.float64)
+    out = torch.empty((N, F), dtype=torch.float64 if wide else torch.float32, device=t.device)
     torch.cuda.current_stream(dev).synchronize()
-    _lib.check(lib.obia_table_scale_dev(c.handle, t.data_ptr(), N, F, mean.data_ptr(), scale.data_ptr(), out.data_ptr()))
+    entry = lib.obia_table_scale_f64_dev if wide else lib.obia_table_scale_dev
+    _lib.check(entry(c.handle, t.data_ptr(), N, F, mean.data_ptr(), scale.data_ptr(), out.data_ptr()))
     if is_t:
         return out, mean, scale
     return out.cpu().numpy(), mean.cpu().numpy(), scale.cpu().numpy()
@@ -226,6 +311,68 @@ def forest_predict(forest, X32, acceptable=None, ctx=None):
     if is_t:
         return pred, margin, proba
     return pred.cpu().numpy(), margin.cpu().numpy(), proba.cpu().numpy()
+
+
+def _mlp_plan(layer_sizes):
+    """(rows a workgroup takes, features of the input layer staged at a time) of obia_mlp_predict_dev for these layer sizes: the
+    same few lines as in csrc/mlp.hip, for the tests that walk the kernel's thresholds.  64 KB of LDS hold two activation buffers
+    of (widest layer output) x rows doubles and the staging buffer of features x (rows + 1)."""
+    ls = [int(v) for v in layer_sizes]
+    wmax, rows = max(ls[1:]), 64
+    while 2 * wmax * rows + 8 * (rows + 1) > 8192:
+        rows //= 2
+    return rows, min(ls[0], (8192 - 2 * wmax * rows) // (rows + 1))
+
+
+def mlp_predict(mlp, X, acceptable=None, ctx=None, _logits=False):
+    """Prediction of ``mlp`` for every row of ``X`` (N, F) float64: returns ``(pred, margin, proba)``.
+
+    ``proba`` (N, K) float64 is ``MLPClassifier.predict_proba`` in the summation order of DESIGN.md 3.5j (inputs in ascending
+    order, every product and sum rounded on its own), never filtered; it agrees with scikit-learn's to a few units of the last
+    place of 1.  ``acceptable`` / ``pred`` / ``margin``: as in :func:`forest_predict`.  A NaN or an infinity in ``X`` raises
+    ValueError, as scikit-learn does.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  ``_logits=True`` appends the
+    last layer before its activation, (N, n_out) (test hook)."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    if not isinstance(mlp, MLP):
+        raise TypeError("mlp must be an obia_amd.classify.MLP (MLP.from_sklearn(clf))")
+    is_t = _is_torch(X)
+    if is_t and not X.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(X.shape)
+    if len(shape) != 2:
+        raise ValueError("X must be (rows, features)")
+    N, F = shape
+    if N == 0:
+        raise ValueError("the table has no rows")
+    if F != mlp.n_features:
+        raise ValueError(f"the network takes {mlp.n_features} features, the table has {F} columns")
+    K, ls = mlp.n_classes, mlp.layer_sizes
+    if mlp.n_layers > MLP_MAX_LAYERS or F > MAX_FEATURES or K > MAX_CLASSES or (mlp.n_layers > 1 and int(ls[1:-1].max()) > MLP_MAX_WIDTH):
+        raise NotImplementedError(f"mlp_predict supports at most {MLP_MAX_LAYERS} weight matrices, {MAX_FEATURES} features, {MAX_CLASSES} "
+                                  f"classes and {MLP_MAX_WIDTH} units in a hidden layer (layer sizes {ls.tolist()}, {K} classes)")
+    _check_candidates(acceptable, N, K)
+    lib = _lib.load()
+    if is_t:
+        x = X.to(torch.float64).contiguous()
+    else:
+        c0 = ctx or _lib.default_context(0)
+        x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device=f"cuda:{c0.device}")
+    dev = x.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    mask = None if acceptable is None else _lib.mask_bytes(acceptable, device=x.device)
+    d = mlp._on(x.device)
+    ms = _lib.Mlp(d["weights"].data_ptr(), d["biases"].data_ptr(), ls.ctypes.data, mlp.n_layers,
+                  _HIDDEN_ACTIVATIONS.index(mlp.hidden_activation), _OUT_ACTIVATIONS.index(mlp.out_activation), K)
+    proba = torch.empty((N, K), dtype=torch.float64, device=x.device)
+    pred = torch.empty((N,), dtype=torch.int32, device=x.device)
+    margin = torch.empty((N,), dtype=torch.float64, device=x.device)
+    logits = torch.empty((N, int(ls[-1])), dtype=torch.float64, device=x.device) if _logits else None
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_mlp_predict_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(ms), None if mask is None else mask.data_ptr(),
+                                        proba.data_ptr(), pred.data_ptr(), margin.data_ptr(), None if logits is None else logits.data_ptr()))
+    out = (pred, margin, proba) + ((logits,) if _logits else ())
+    return out if is_t else tuple(t.cpu().numpy() for t in out)
 
 
 class ClassifiedImage:
@@ -332,14 +479,14 @@ def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf
 
     ``acceptable``: (N, K) boolean mask in ``classes_`` order, or ``acceptable_classes_gdf`` (see :func:`acceptable_mask`; needs
     ``segments.attrs["labels"]`` or ``labels=``, and ``affine_transformation=`` when the zones are in map coordinates).
-    ``method='mlp'`` and ``compute_shap=True`` are not implemented."""
+    ``method='mlp'`` is refused here (fit the ``MLPClassifier`` yourself and call :func:`predict_segments`); ``compute_shap=True``
+    is not implemented."""
     if method == 'mlp':
-        raise NotImplementedError("method='mlp' is not implemented: only the random forest predicts on the GPU")
+        raise NotImplementedError("method='mlp' is not switched on in classify(): fit the MLPClassifier and call predict_segments")
     if method != 'rf':
         raise ValueError('An unsupported classification algorithm was requested')
     if compute_shap:
         raise NotImplementedError("compute_shap=True is not implemented")
-    import pandas as pd
     from sklearn.ensemble import RandomForestClassifier
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
@@ -357,21 +504,50 @@ def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf
         cm = confusion_matrix(y_test, y_pred)
         report = classification_report(y_test, y_pred)
 
+    res = predict_segments(classifier, segments, acceptable_classes_gdf, acceptable=acceptable, labels=labels,
+                           affine_transformation=affine_transformation, start_label=start_label, ctx=ctx)
+    res.confusion_matrix, res.report = cm, report
+    return res
+
+
+def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, acceptable=None, labels=None, affine_transformation=None,
+                     start_label=1, ctx=None):
+    """The back half of :func:`classify` (classify.py:125-175) for a classifier fitted earlier, so that a second raster or tile
+    does not pay for training again.
+
+    ``classifier``: a fitted ``RandomForestClassifier`` or ``MLPClassifier``, a :class:`Forest` or an :class:`MLP`.  The three
+    non-feature columns are dropped, the rest scaled with :func:`standard_scale` -- float32 for a forest, float64 for an MLP --
+    and predicted with :func:`forest_predict` / :func:`mlp_predict`.  ``segments`` gains ``predicted_class`` and
+    ``prediction_margin`` and is returned inside a :class:`ClassifiedImage` whose ``params`` are the estimator's ``get_params()``
+    ({} for a Forest or an MLP).  The acceptable-class arguments are those of :func:`classify`."""
+    import pandas as pd
+    params = {}
+    if isinstance(classifier, (Forest, MLP)):
+        model = classifier
+    else:
+        params = classifier.get_params()
+        if hasattr(classifier, "coefs_"):
+            model = MLP.from_sklearn(classifier)
+        elif hasattr(classifier, "estimators_"):
+            model = Forest.from_sklearn(classifier)
+        else:
+            raise TypeError("classifier must be a fitted RandomForestClassifier or MLPClassifier, a Forest or an MLP")
     x_pred = segments.drop(_DROPPED, axis=1, errors='ignore')
-    forest = Forest.from_sklearn(classifier)
     if acceptable is None and acceptable_classes_gdf is not None:
         if labels is None:
             labels = getattr(segments, "attrs", {}).get("labels")
         if labels is None:
             raise ValueError("acceptable_classes_gdf needs the label raster: segments.attrs['labels'] or labels=")
-        acceptable = acceptable_mask(acceptable_classes_gdf, forest.classes_, labels, affine_transformation=affine_transformation,
+        acceptable = acceptable_mask(acceptable_classes_gdf, model.classes_, labels, affine_transformation=affine_transformation,
                                      start_label=start_label, ctx=ctx)
         if acceptable.shape[0] != len(segments):
             raise ValueError(f"the label raster holds {acceptable.shape[0]} segments, the table {len(segments)} rows")
-    X32, _, _ = standard_scale(np.ascontiguousarray(x_pred.to_numpy(dtype=np.float64)), ctx=ctx)
-    pred, margin, _ = forest_predict(forest, X32, acceptable=None if acceptable is None else np.asarray(acceptable), ctx=ctx)
+    is_mlp = isinstance(model, MLP)
+    X, _, _ = standard_scale(np.ascontiguousarray(x_pred.to_numpy(dtype=np.float64)), ctx=ctx, dtype=np.float64 if is_mlp else np.float32)
+    pred, margin, _ = (mlp_predict if is_mlp else forest_predict)(model, X, acceptable=None if acceptable is None else np.asarray(acceptable),
+                                                                  ctx=ctx)
 
-    segments['predicted_class'] = forest.classes_[pred]
+    segments['predicted_class'] = model.classes_[pred]
     segments['prediction_margin'] = margin
     for col in segments.columns:                      # classify.py:165-173
         if col == 'geometry' or not isinstance(segments[col].dtype, np.dtype):
@@ -380,4 +556,4 @@ def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf
             segments[col] = segments[col].astype(pd.Int64Dtype())
         elif np.issubdtype(segments[col].dtype, np.floating):
             segments[col] = segments[col].astype(float)
-    return ClassifiedImage(segments, cm, report, None, None, None, classifier.get_params())
+    return ClassifiedImage(segments, None, None, None, None, None, params)

@@ -101,11 +101,13 @@ __global__ __launch_bounds__(64) void scale_var_kernel(const double *__restrict_
     }
 }
 
+// OUT = float: the table the forest wants; OUT = double: what MLPClassifier is handed (no cast)
+template <typename OUT>
 __global__ __launch_bounds__(256) void scale_transform_kernel(const double *__restrict__ x, long long total, int F, const double *__restrict__ mean,
-                                                              const double *__restrict__ scale, float *__restrict__ out) {
+                                                              const double *__restrict__ scale, OUT *__restrict__ out) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % F);
-        out[i] = (float)((x[i] - mean[c]) / scale[c]);
+        out[i] = (OUT)((x[i] - mean[c]) / scale[c]);
     }
 }
 
@@ -285,10 +287,9 @@ __global__ __launch_bounds__(256) void forest_predict_kernel(const float *__rest
 
 using namespace obia;
 
-extern "C" {
-
-int obia_table_scale_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
-                         float *scaled_out) {
+template <typename OUT>
+static int table_scale(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
+                       OUT *scaled_out) {
     if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
     if (!table || !mean_out || !scale_out || !scaled_out || n_features <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (n_rows <= 0) { set_error("the table has no rows"); return OBIA_E_INVALID; }
@@ -310,10 +311,22 @@ int obia_table_scale_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int
     hipLaunchKernelGGL(scale_var_kernel, dim3(F), dim3(64), 0, ctx->stream, p1, p2, B, F, mean_out, cnt, scale_out);
     const long long total = (long long)n_rows * F;
     const int tb = (int)(cdiv(total, 256) < 2048 ? cdiv(total, 256) : 2048);
-    hipLaunchKernelGGL(scale_transform_kernel, dim3(tb), dim3(256), 0, ctx->stream, table, total, F, mean_out, scale_out, scaled_out);
+    hipLaunchKernelGGL(scale_transform_kernel<OUT>, dim3(tb), dim3(256), 0, ctx->stream, table, total, F, mean_out, scale_out, scaled_out);
     OBIA_HIP_TRY(hipGetLastError());
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return OBIA_OK;
+}
+
+extern "C" {
+
+int obia_table_scale_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
+                         float *scaled_out) {
+    return table_scale<float>(ctx, table, n_rows, n_features, mean_out, scale_out, scaled_out);
+}
+
+int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
+                             double *scaled_out) {
+    return table_scale<double>(ctx, table, n_rows, n_features, mean_out, scale_out, scaled_out);
 }
 
 int obia_forest_predict_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest,
