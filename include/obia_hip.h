@@ -552,6 +552,8 @@ int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows,
  * 6 are sums of the kernels' own start-to-end times, as a rocprofv3 kernel trace reports them.
  * 12 = batches of the call whose sweeps ran a second time with every sweep storing its labels (a valid pixel that no window
  * reached keeps the label of the sweep before: DESIGN.md 3.2 item 5) -- counted whether profiling is on or not.
+ * 13 = the part of 8 that no sweep evaluated: pre-pass pixel-sweeps of problems whose class representative ran them (DESIGN.md 3.2,
+ * "One pre-pass per class of identical tiles"); 8 counts them as covered.
  * `enabled`: 0 off, 1 every class, 2 only the colour sweeps (an event pair costs ~2.5 us of stream time: with all classes on,
  * a step of the headline workload records ~420 pairs = 1.1 ms; bench.py times its steps in mode 2).                       */
 int obia_set_profiling(obia_ctx *ctx, int enabled);

@@ -55,6 +55,7 @@ class Arena {
 struct Timing {
     double assign_ms = 0, prepass_ms = 0, feat_ms = 0, cc_ms = 0, zonal_ms = 0, total_ms = 0;
     double assign_px = 0, prepass_px = 0;   // pixels processed by the timed colour / pre-pass sweeps (sum over launches)
+    double prepass_shared_px = 0;           // ... of prepass_px that no sweep evaluated: covered by a class representative's sweeps (shared pre-pass)
     double assign_store_px = 0;             // ... of the colour sweeps that also stored their labels (the last sweep of a batch)
     int sweeps = 0;
     int batch_repeats = 0;                  // batches whose sweeps ran again with every sweep storing its labels (a valid pixel no window reached)
@@ -74,6 +75,7 @@ struct obia_ctx {
     size_t pinned_bytes = 0;
     unsigned long long *defer_buf = nullptr;   // pinned landing area of a read-back that is looked at after a LATER synchronisation
     bool defer_pending = false;                // (slic_run_sweeps: the orphan flag and pixel counters of the sweeps)
+    double defer_shared_px = 0;                // (and the pixel-sweeps a shared pre-pass covered without evaluating them)
     // visited map of the connectivity stage's component walks (cc.hip): every walk clears its own marks, so the map is all zero
     // between calls and is cleared as a whole only when it grows or after a call that did not complete (cc_visited_dirty)
     int32_t *cc_visited = nullptr;

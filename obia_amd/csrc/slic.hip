@@ -827,6 +827,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     std::vector<SeedGrid> grids(np);
     std::vector<double> stepmax(np);
     b.step.assign(np, 1.0f);
+    b.grid_n.assign(np, 0);
     int cent_off = 0;
     for (int p = 0; p < np; ++p) {
         SlicProblem &P = b.probs[p];
@@ -852,6 +853,7 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
             double ne = std::nearbyint((double)n_segments[p] * ((double)P.H * (double)P.W) / (double)nvalid[p]);
             n_eff = ne < 1.0 ? 1 : (long long)ne;
         }
+        b.grid_n[p] = n_eff;
         long long gr[4];
         regular_grid_hw(P.H, P.W, n_eff, gr);
         g.start_y = (int)gr[0]; g.step_y = gr[1] ? (int)gr[1] : 1; g.ny = (int)slice_len(P.H, gr[0], gr[1]);

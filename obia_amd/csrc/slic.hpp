@@ -121,7 +121,39 @@ struct SlicBatch {
     bool prepass_only = false;         // stage entry only (obia_slic_stages::prepass_only): a masked batch stops after its spatial pre-pass
     int prepass_iter = 0;              // stage entry only (obia_slic_stages::prepass_iters): sweeps of the pre-pass, 0 = max_iter
     std::vector<float> step;           // per problem: `step` of _slic_cython, max(steps) of the seeding grid (slic_plan_and_seed)
+    std::vector<long long> grid_n;     // per problem: the n its seeds were laid out for by the grid rule (regular_grid((1,H,W), n)); 0: no
+                                       // centroids or seeds from the caller (slic_plan_and_seed; read by slic_prepass_classes)
 };
+
+// Classes of problems whose spatial pre-pass is ONE computation (slic_sweep.hip, "shared pre-pass").  The pre-pass sweeps but the
+// last read a problem's shape, its seeds and its mask and nothing else, so two problems of a masked batch with the same shape, the
+// same grid seeds (same H, W and n: same K, steps, bins and weight) and a mask that hides nothing run the same sweeps bit for bit.
+// rep[p] = the first problem of p's class, p itself for a representative and for every problem that shares with nobody.  Returns the
+// number of problems that have another problem as representative.  A pure function of the problem table.
+inline int slic_prepass_classes(const std::vector<SlicProblem> &probs, const std::vector<long long> &grid_n, std::vector<int> &rep) {
+    const int np = (int)probs.size();
+    rep.resize(np);
+    std::vector<int> reps;   // representatives so far (a handful: interior, edge and corner shapes)
+    int members = 0;
+    for (int p = 0; p < np; ++p) {
+        const SlicProblem &P = probs[p];
+        rep[p] = p;
+        if ((int)grid_n.size() != np || grid_n[p] <= 0 || P.K <= 0 || P.direct) continue;
+        if ((long long)P.n_valid != (long long)P.H * (long long)P.W) continue;
+        bool found = false;
+        for (int r : reps) {
+            const SlicProblem &R = probs[r];
+            if (R.H == P.H && R.W == P.W && R.K == P.K && grid_n[r] == grid_n[p] && R.sy == P.sy && R.sx == P.sx && R.ncy == P.ncy &&
+                R.ncx == P.ncx && R.tiles_x == P.tiles_x && R.tiles_y == P.tiles_y && R.spatial_w == P.spatial_w && R.sp_y == P.sp_y &&
+                R.sp_x == P.sp_x) {
+                rep[p] = r; ++members; found = true;
+                break;
+            }
+        }
+        if (!found) reps.push_back(p);
+    }
+    return members;
+}
 
 // Feature preparation for every problem of the batch: per-band min/max of its window, then
 // normalise (optional) -> Lab (optional) -> * 1/compactness into d_feat.  `src` is the caller's

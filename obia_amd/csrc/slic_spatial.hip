@@ -335,11 +335,12 @@ __device__ __forceinline__ void slic_spatial_tile(const SlicProblem &P, int gtil
 
 // the pre-pass sweeps that fold no colours and store no labels (and keep no fixed-point cache): runs where the tile has a list
 template <int CP>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, LEAN_WAVES))) void slic_spatial_kernel(OBIA_ASSIGN_PARAMS) {
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, LEAN_WAVES))) void slic_spatial_kernel(OBIA_ASSIGN_PARAMS, const int *__restrict__ act_tiles) {
     // (the tile of this workgroup and its list state: as in slic_assign_body)
     constexpr int XG = OBIA_XCD_GROUP;
-    const int gtile = tile_base + (((int)(blockIdx.x >> 3) / XG) * 8 + (int)(blockIdx.x & 7)) * XG + (int)(blockIdx.x >> 3) % XG;
-    if (gtile >= total_tiles_all) return;
+    const int gslot = tile_base + (((int)(blockIdx.x >> 3) / XG) * 8 + (int)(blockIdx.x & 7)) * XG + (int)(blockIdx.x >> 3) % XG;
+    if (gslot >= total_tiles_all) return;
+    const int gtile = act_tiles ? act_tiles[gslot] : gslot;
     const int l_n = tl_meta[2 * (size_t)gtile], l_bw = tl_meta[2 * (size_t)gtile + 1], l_req = tl_req[gtile];
     const int prob_i = tiles_per_prob > 0 ? gtile / tiles_per_prob : tile_prob[gtile];
     const SlicProblem P = probs[prob_i];
@@ -347,5 +348,5 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, 
     if (listed && accumulate && !store_labels && !P.direct && P.spatial_w >= RUN_W_LO && P.spatial_w <= RUN_W_HI)   // workgroup-uniform
         slic_spatial_tile<CP>(P, gtile, gtile - P.tile_off, l_n, mask4, cent, acc, RQ, px_counter, orphan_flag, tl_k, tl_fp);
     else
-        slic_assign_body<CP, true, true, false, false, true, false>(OBIA_ASSIGN_ARGS);
+        slic_assign_body<CP, true, true, false, false, true, false>(OBIA_ASSIGN_ARGS, act_tiles);
 }

@@ -247,7 +247,8 @@ __global__ __launch_bounds__(64) void slic_prep_lane_kernel(const SlicProblem *_
                                                              float *__restrict__ cent, int *__restrict__ head,
                                                              int *__restrict__ head_other,
                                                              int total_cells, int *__restrict__ bin_stamp, int sweep_id,
-                                                             int cell_base, float *__restrict__ ref, int *__restrict__ tl_req) {
+                                                             int cell_base, float *__restrict__ ref, int *__restrict__ tl_req,
+                                                             const int *__restrict__ act_probs) {
     constexpr int RS = CENT_REC + CP;
     constexpr int NQ = (CP + 3 + 1) / 2;   // 16-byte pairs of the accumulator record that are in use: colours | n | sum_y | sum_x
     {   // the bins of the NEXT sweep (see slic_prep_kernel)
@@ -256,7 +257,9 @@ __global__ __launch_bounds__(64) void slic_prep_lane_kernel(const SlicProblem *_
     }
     // grid = (blocks of 64 centroids, problems of the group): the problem descriptor is workgroup-uniform (scalar loads that depend
     // on nothing), so the chain of dependent round trips is descriptor -> records -> bin head
-    const SlicProblem P = probs[p_base + blockIdx.y];
+    // (act_probs: the launch covers the problems the table names -- the representatives of a shared pre-pass -- instead of a span;
+    // the bins above are reset for the whole batch either way)
+    const SlicProblem P = probs[act_probs ? act_probs[blockIdx.y] : p_base + (int)blockIdx.y];
     const int kl = blockIdx.x * blockDim.x + threadIdx.x;
     if (kl >= P.K) return;
     const int k = P.cent_off + kl;
@@ -339,6 +342,43 @@ __global__ __launch_bounds__(64) void slic_prep_lane_kernel(const SlicProblem *_
     hrec[1] = make_float4(__int_as_float((int)fx0), __int_as_float((int)fx1), __int_as_float(link), mdc);
     if (bin_stamp && moved) bin_stamp[P.cell_off + by * P.ncx + bx] = sweep_id;   // the bin it enters (or changed in)
     list_margin_check(P, k, cy, cx, (int)fy0, (int)fy1, (int)fx0, (int)fx1, first != 0, ref, tl_req, sweep_id);
+}
+
+// ---- shared pre-pass -----------------------------------------------------------------------------------------------------
+// The spatial pre-pass sweeps of a problem -- all of its pass but the last, which folds the colours -- read its shape, its seeds and
+// its mask and nothing else.  Problems of a masked batch with the same shape, the same grid seeds and a mask that hides nothing
+// (slic.hpp: slic_prepass_classes; every interior black tile of the tiler) run the same sweeps bit for bit, so only the first of
+// a class, its representative, runs them: the sweeps and the centroid steps between them are launched for the representatives and
+// the problems that share with nobody (a span or a table of their tiles / problems).  In front of the centroid step of the last
+// pre-pass sweep this kernel hands every other member what its representative's last shared sweep left -- n, sum_y, sum_x of every
+// centroid -- and that step and that sweep run on the whole batch as they always did.  What a member needs beyond the sums:
+//   * its accumulator record in the state the step expects: the three words set, the colour words zero (they are: the records
+//     are cleared when the batch is planned and no spatial-only sweep adds colours);
+//   * the header of its centroid record (position and window of the representative's; no link: the member is in no bin).  The
+//     step overwrites it from the sums -- also for a centroid without pixels, whose position turns NaN -- but reads it first;
+//   * the reference position its margin is measured from (list_margin_check) = the position that step is about to compute, with
+//     the same operations: invariant (A) holds from the member's first list build on, which is the next sweep (its tiles have no
+//     list, tl_meta = -1, as in the first sweep of a batch), and (B) is what a build establishes;
+//   * bins: a member's cells of the buffer the step fills were reset by the steps before it, which reset the whole batch.
+// grid = (blocks of 64 centroids, members); member_rep: pairs {member, representative}.
+__global__ __launch_bounds__(64) void slic_prepass_broadcast_kernel(const SlicProblem *__restrict__ probs, const int *__restrict__ member_rep,
+                                                                     int CP, int RQ, unsigned long long *__restrict__ acc,
+                                                                     float *__restrict__ cent, float *__restrict__ ref) {
+    const SlicProblem P = probs[member_rep[2 * blockIdx.y]], R = probs[member_rep[2 * blockIdx.y + 1]];
+    const int kl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (kl >= P.K || kl >= R.K) return;
+    const size_t km = (size_t)P.cent_off + kl, kr = (size_t)R.cent_off + kl;
+    const int RS = CENT_REC + CP;
+    const unsigned long long n = acc[kr * RQ + CP], sy = acc[kr * RQ + CP + 1], sx = acc[kr * RQ + CP + 2];
+    acc[km * RQ + CP] = n; acc[km * RQ + CP + 1] = sy; acc[km * RQ + CP + 2] = sx;
+    const float4 *src = reinterpret_cast<const float4 *>(cent + kr * RS);
+    float4 *dst = reinterpret_cast<float4 *>(cent + km * RS);
+    const float4 h0 = src[0], h1 = src[1];
+    dst[0] = h0;
+    dst[1] = make_float4(h1.x, h1.y, __int_as_float(-1), h1.w);
+    // (uint64 -> float by way of double: see slic_prep_lane_kernel)
+    const float fn = (float)(double)n;
+    reinterpret_cast<float2 *>(ref)[km] = make_float2((float)(double)sy / fn, (float)(double)sx / fn);
 }
 
 // float feature -> 32-bit fixed point.  fs is a power of two chosen in slic_features_finish so that |f * fs| < 2^29:
@@ -481,7 +521,8 @@ __device__ __forceinline__ void slic_assign_body(
     int *__restrict__ cache_k, unsigned long long *__restrict__ cache_q, int sweep_id, int use_cache,
     unsigned long long *__restrict__ px_counter, const int *__restrict__ tile_prob, int total_tiles_all,
     int *__restrict__ orphan_flag, int tiles_per_prob, const float *__restrict__ fbox, int tile_base, int nch_arg,
-    int *__restrict__ tl_k, unsigned *__restrict__ tl_fp, int *__restrict__ tl_meta, const int *__restrict__ tl_req) {
+    int *__restrict__ tl_k, unsigned *__restrict__ tl_fp, int *__restrict__ tl_meta, const int *__restrict__ tl_req,
+    const int *__restrict__ act_tiles) {
     // channels that exist: a compile-time constant in the variants compiled per padding (NCH < CP), the launch argument in the
     // others (NCH == CP: the last pre-pass sweep, SLIC-zero, the fixed-point variant).  The planes of the padded channels are NOT
     // written by the feature pass since round 3 (nine bands: 36 instead of 48 bytes per pixel): nobody may read them.
@@ -507,9 +548,11 @@ __device__ __forceinline__ void slic_assign_body(
 #define OBIA_XCD_GROUP 2
 #endif
     constexpr int XG = OBIA_XCD_GROUP;   // consecutive tiles that share an XCD
-    // (a launch covers the tiles [tile_base, total_tiles_all) of the batch; slic_run_sweeps launches them all: tile_base = 0)
-    const int gtile = tile_base + (((int)(blockIdx.x >> 3) / XG) * 8 + (int)(blockIdx.x & 7)) * XG + (int)(blockIdx.x >> 3) % XG;
-    if (gtile >= total_tiles_all) return;
+    // (a launch covers the tiles [tile_base, total_tiles_all) of the batch: all of them, or the span of one representative of a
+    // shared pre-pass; with act_tiles -- the lean kernels only, null at compile time in the others -- the tiles that table names)
+    const int gslot = tile_base + (((int)(blockIdx.x >> 3) / XG) * 8 + (int)(blockIdx.x & 7)) * XG + (int)(blockIdx.x >> 3) % XG;
+    if (gslot >= total_tiles_all) return;
+    const int gtile = act_tiles ? act_tiles[gslot] : gslot;   // workgroup-uniform (a scalar load)
     // the tile's list state (scalar loads that depend on the block index alone: in flight beside the problem descriptor)
     // (meta: {entries | -1 no list yet | -2 not listed,  sweep of the build | short-lived builds in a row << 16})
     const int l_n = tl_meta[2 * (size_t)gtile], l_bw = tl_meta[2 * (size_t)gtile + 1], l_req = tl_req[gtile];
@@ -1289,19 +1332,19 @@ __device__ __forceinline__ void slic_assign_body(
 // the colour sweeps and the last pre-pass sweep
 template <int CP, bool MASKED, bool IGNORE_COLOR, bool FIXPT, bool SLICZERO, int NCH = CP>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ASSIGN_WAVES, ASSIGN_WAVES))) void slic_assign_kernel(OBIA_ASSIGN_PARAMS) {
-    slic_assign_body<CP, MASKED, IGNORE_COLOR, FIXPT, SLICZERO, false, false, NCH>(OBIA_ASSIGN_ARGS);
+    slic_assign_body<CP, MASKED, IGNORE_COLOR, FIXPT, SLICZERO, false, false, NCH>(OBIA_ASSIGN_ARGS, nullptr);
 }
 
 // the colour sweeps at low compactness: with the colour-box bound (one more LDS table, a few more registers)
 template <int CP, bool MASKED, int NCH = CP>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void slic_assign_collb_kernel(OBIA_ASSIGN_PARAMS) {
-    slic_assign_body<CP, MASKED, false, false, false, false, true, NCH>(OBIA_ASSIGN_ARGS);
+    slic_assign_body<CP, MASKED, false, false, false, false, true, NCH>(OBIA_ASSIGN_ARGS, nullptr);
 }
 
 // the pre-pass sweeps that fold no colours: no feature registers, 4 KB of LDS
 template <int CP, bool MASKED, bool FIXPT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, LEAN_WAVES))) void slic_prepass_kernel(OBIA_ASSIGN_PARAMS) {
-    slic_assign_body<CP, MASKED, true, FIXPT, false, true, false>(OBIA_ASSIGN_ARGS);
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LEAN_WAVES, LEAN_WAVES))) void slic_prepass_kernel(OBIA_ASSIGN_PARAMS, const int *__restrict__ act_tiles) {
+    slic_assign_body<CP, MASKED, true, FIXPT, false, true, false>(OBIA_ASSIGN_ARGS, act_tiles);
 }
 
 #include "slic_spatial.hip"   // slic_spatial_kernel: the same sweeps decided by runs on pixel rows
@@ -1341,6 +1384,9 @@ __global__ __launch_bounds__(256) void slic_maxdist_kernel(const SlicProblem *__
         }
 }
 
+// The tiles a sweep launch covers: all of the batch, a span [base, end) of them, or the `end` tiles a device table names.
+struct TileSubset { const int *table = nullptr; int base = 0, end = -1; };
+
 struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; null when the option is off)
     int *bin_stamp = nullptr, *tile_lp = nullptr, *cache_k = nullptr;
     unsigned long long *cache_q = nullptr;
@@ -1349,18 +1395,23 @@ struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; 
 template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
-                          const KernelSpan &span, const int *head_cur, bool prepass_visits) {
+                          const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset()) {
     constexpr int XGH = OBIA_XCD_GROUP;
-    const int ntiles = (int)b.total_tiles_all;
-    dim3 grid(8 * XGH * (unsigned)((ntiles + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
+    // (a subset -- the lean kernels of a shared pre-pass only -- is grouped over the XCDs like the whole batch)
+    const int ntiles = sub.end >= 0 ? sub.end : (int)b.total_tiles_all, tbase = sub.end >= 0 ? sub.base : 0;
+    dim3 grid(8 * XGH * (unsigned)((ntiles - tbase + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
     const int RQ = acc_record_qwords(CP);
     int tpp = b.probs.empty() ? 0 : b.probs[0].tiles_x * b.probs[0].tiles_y;   // tiles per problem if all problems agree, else 0
     for (auto &P : b.probs) if (P.tiles_x * P.tiles_y != tpp) tpp = 0;
+#define LAUNCH_ARGS_                                                                                                 \
+    b.d_probs, b.d_feat, b.d_mask, b.d_mask4, b.d_cent, head_cur, b.d_labels, b.d_acc, RQ, accumulate, store_labels, b.start_label,      \
+        (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
+        b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, tbase, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req
 #define LAUNCH_K_(...)                                                                                               \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, b.d_probs, b.d_feat,   \
-                          b.d_mask, b.d_mask4, b.d_cent, head_cur, b.d_labels, b.d_acc, RQ, accumulate, store_labels, b.start_label,      \
-                          (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
-                          b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, 0, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req)
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_)
+    // (the lean kernels: the spatial-only pre-pass sweeps, which a shared pre-pass launches for a subset of the tiles)
+#define LAUNCH_KL_(...)                                                                                              \
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_, sub.table)
     // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
     // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
     const int pad = CP - b.C;
@@ -1381,7 +1432,7 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
         else if (pad == 3) LAUNCH_K_(slic_assign_collb_kernel<CP, M, CP - 3>);                                       \
         else LAUNCH_K_(slic_assign_collb_kernel<CP, M>);                                                             \
     } while (0)
-#define LAUNCH_LEAN_(M, F) LAUNCH_K_(slic_prepass_kernel<CP, M, F>)
+#define LAUNCH_LEAN_(M, F) LAUNCH_KL_(slic_prepass_kernel<CP, M, F>)
     // a spatial-only sweep that stores no labels and keeps no fixed-point cache is decided by runs (slic_spatial.hip); the others,
     // and all of them under the developer switch, by the pixel-by-pixel kernel
 #define LAUNCH_ASSIGN(M, I)                                                                                          \
@@ -1389,7 +1440,7 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
         if ((I) && !accum_color) {                                                                                   \
             if (fp.bin_stamp) LAUNCH_LEAN_(M, true);                                                                 \
             else if (store_labels || prepass_visits) LAUNCH_LEAN_(M, false);                                         \
-            else LAUNCH_K_(slic_spatial_kernel<CP>);                                                                 \
+            else LAUNCH_KL_(slic_spatial_kernel<CP>);                                                                \
         }                                                                                                            \
         else if (b.slic_zero && !(I)) LAUNCH_ASSIGN_(M, false, false, true);                                         \
         else if (fp.bin_stamp) LAUNCH_ASSIGN_(M, I, true, false);                                                    \
@@ -1405,6 +1456,8 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
 #undef LAUNCH_COLLB_
 #undef LAUNCH_MAIN_
 #undef LAUNCH_K_
+#undef LAUNCH_KL_
+#undef LAUNCH_ARGS_
 }
 
 // d_mask -> d_mask4 (slic.hpp): dword (q, x) = the mask bytes of the rows 4q .. 4q+3 at column x.  Once per batch; every sweep then
@@ -1467,17 +1520,23 @@ static void fill_labels(obia_ctx *ctx, SlicBatch &b) {
     hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, n, b.start_label - 1);
 }
 
-// h: the 513 slots of the sweeps' pixel counters (slic_run_sweeps); the profiling totals of the batch
-static void fold_counters(obia_ctx *ctx, const unsigned long long *h) {
-    if (ctx->profiling)
+// h: the 513 slots of the sweeps' pixel counters (slic_run_sweeps); the profiling totals of the batch.  shared_px: pixel-sweeps of
+// the pre-pass that were covered by a class representative's sweeps and not evaluated (they count as covered, and on their own)
+static void fold_counters(obia_ctx *ctx, const unsigned long long *h, double shared_px) {
+    if (ctx->profiling) {
         for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
+        ctx->timing.prepass_px += shared_px;
+        ctx->timing.prepass_shared_px += shared_px;
+    }
 }
 
 // Queues every sweep of the batch on the context's stream.  repeat: the batch runs again from the seeds with every sweep storing
 // its labels (slic_rerun_storing).  *d_px_out: the pixel counters of the sweeps, 256 slots each for the colour and the pre-pass
 // sweeps, and in slot 512 the orphan flag of the sweeps that do not store their labels; null when the batch has no sweep.
-static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long long **d_px_out) {
+// *shared_px_out: the pixel-sweeps a shared pre-pass covered without evaluating them (0 when nothing was shared).
+static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long long **d_px_out, double *shared_px_out) {
     *d_px_out = nullptr;
+    *shared_px_out = 0.0;
     if (std::getenv("OBIA_DEBUG_SYNC"))
         for (size_t p = 0; p < b.probs.size(); ++p) {
             const SlicProblem &P = b.probs[p];
@@ -1546,6 +1605,59 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     if (repeat) OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
     const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
     const bool prepass_visits = std::getenv("OBIA_PREPASS_VISITS") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prepass_runs.py): the spatial pre-pass by pixel visits, not runs
+    // Shared pre-pass (slic_prepass_broadcast_kernel): the sweeps of the pre-pass but the last, and the centroid steps between them,
+    // run for the first problem of every class only.  Not when every sweep stores its labels (the repeat, exit_on_fixed_point,
+    // SLIC-zero), with a `spacing`, for the stage entry's pre-pass variants, or when no class has a second member: the path
+    // without sharing, unchanged.  External seeds (seeding="skimage" among them) form no class.  OBIA_PREPASS_SHARE=0: developer switch (A/B timing,
+    // tests/test_gpu_prepass_share.py).
+    std::vector<int> share_rep;
+    int n_shared = 0;
+    {
+        const char *e = std::getenv("OBIA_PREPASS_SHARE");
+        const bool off = e && e[0] == '0';
+        if (!off && b.masked && passes == 2 && pre_iter >= 2 && b.prepass_iter <= 0 && !store_all && !b.direct && !prep_grouped)
+            n_shared = slic_prepass_classes(b.probs, b.grid_n, share_rep);
+    }
+    TileSubset act_tiles;                 // tiles of the problems that run the shared sweeps
+    const int *d_act_probs = nullptr;     // those problems: a table, or the span [act_p_base, act_p_base + n_act)
+    const int *d_member_rep = nullptr;    // {member, representative} of every problem that does not
+    int act_p_base = 0, n_act = b.nprob, kmax_act = kmax, kmax_mem = 1;
+    if (n_shared > 0) {
+        std::vector<int> ap, at, mr;
+        double spx = 0.0;
+        kmax_act = 1;
+        for (int p = 0; p < b.nprob; ++p) {
+            const SlicProblem &P = b.probs[p];
+            if (share_rep[p] == p) {
+                ap.push_back(p);
+                for (int t = 0; t < P.tiles_x * P.tiles_y; ++t) at.push_back(P.tile_off + t);
+                if (P.K > kmax_act) kmax_act = P.K;
+            } else {
+                mr.push_back(p); mr.push_back(share_rep[p]);
+                if (P.K > kmax_mem) kmax_mem = P.K;
+                spx += (double)P.H * (double)P.W * (double)(pre_iter - 1);
+            }
+        }
+        n_act = (int)ap.size();
+        act_p_base = ap.front();
+        const bool span = ap.back() - ap.front() + 1 == n_act;   // consecutive problems: consecutive tiles, no table in front of a tile
+        int *d_mr = A.get<int>(mr.size());
+        if (!d_mr) return OBIA_E_NOMEM;
+        OBIA_TRY(upload_async(ctx, d_mr, mr.data(), sizeof(int) * mr.size()));
+        d_member_rep = d_mr;
+        if (span) {
+            act_tiles.base = b.probs[ap.front()].tile_off;
+            act_tiles.end = b.probs[ap.back()].tile_off + b.probs[ap.back()].tiles_x * b.probs[ap.back()].tiles_y;
+        } else {
+            int *d_ap = A.get<int>(ap.size()), *d_at = A.get<int>(at.size() ? at.size() : 1);
+            if (!d_ap || !d_at) return OBIA_E_NOMEM;
+            OBIA_TRY(upload_async(ctx, d_ap, ap.data(), sizeof(int) * ap.size()));
+            if (!at.empty()) OBIA_TRY(upload_async(ctx, d_at, at.data(), sizeof(int) * at.size()));
+            d_act_probs = d_ap;
+            act_tiles.table = d_at; act_tiles.base = 0; act_tiles.end = (int)at.size();
+        }
+        *shared_px_out = spx;
+    }
     OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
     OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
     // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
@@ -1572,10 +1684,21 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             ++sweep_no;   // sweep ids start at 1
             // SLIC-zero: the per-cluster colour scale restarts at 1 with the colour pass and is carried afterwards
             const int zmode = (b.slic_zero && !ignore_color) ? (it == 0 ? 2 : 1) : 0;
+            // shared pre-pass: this sweep and the step in front of it run for the representatives only; in front of the step of the
+            // last pre-pass sweep the other members receive what they skipped
+            const bool shared_sweep = n_shared > 0 && ignore_color && it < iters - 1;
+            if (n_shared > 0 && ignore_color && it == iters - 1) {
+                hipLaunchKernelGGL(slic_prepass_broadcast_kernel, dim3(cdiv(kmax_mem, 64), n_shared), dim3(64), 0, ctx->stream, b.d_probs,
+                                   d_member_rep, b.CP, RQ, b.d_acc, b.d_cent, b.d_ref);
+                debug_sync(ctx, "sweeps: pre-pass broadcast");
+            }
+            const dim3 prep_grid(cdiv(shared_sweep ? kmax_act : kmax, 64), shared_sweep ? n_act : b.nprob);
+            const int prep_base = shared_sweep ? act_p_base : 0;
+            const int *prep_table = shared_sweep ? d_act_probs : nullptr;
 #define LAUNCH_PREP_LANE(CPV)                                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), dim3(cdiv(kmax, 64), b.nprob), dim3(64), 0, ctx->stream, \
-                       b.d_probs, 0, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
-                       b.total_cells, fp.bin_stamp, sweep_no, 0, b.d_ref, b.d_tl_req)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), prep_grid, dim3(64), 0, ctx->stream, \
+                       b.d_probs, prep_base, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
+                       b.total_cells, fp.bin_stamp, sweep_no, 0, b.d_ref, b.d_tl_req, prep_table)
             if (!prep_grouped) {
                 switch (b.CP) {
                     case 4: LAUNCH_PREP_LANE(4); break;
@@ -1622,14 +1745,15 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             const int use_cache = (ignore_color && it == iters - 1) ? 0 : 1;
             {
                 KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
+                const TileSubset sub = shared_sweep ? act_tiles : TileSubset();
                 unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
                 if (ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
                 switch (b.CP) {
-                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
+                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
 #ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
-                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
-                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
-                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits); break;
+                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
+                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
+                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
 #endif
                     default: set_error("bad CP"); return OBIA_E_INVALID;
                 }
@@ -1645,7 +1769,8 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
 int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b) {
     ctx->defer_pending = false;   // (also when this call fails: a settle after it finds nothing to look at)
     unsigned long long *d_px = nullptr;
-    OBIA_TRY(queue_sweeps(ctx, b, false, &d_px));
+    ctx->defer_shared_px = 0.0;
+    OBIA_TRY(queue_sweeps(ctx, b, false, &d_px, &ctx->defer_shared_px));
     if (!d_px) return OBIA_OK;
     // the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle
     if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(unsigned long long) * 513, hipHostMallocDefault));
@@ -1661,18 +1786,19 @@ int slic_sweeps_settle(obia_ctx *ctx, bool *repeat) {
     ctx->defer_pending = false;
     const unsigned long long *h = ctx->defer_buf;
     if ((h[512] & 0xffffffffull) != 0ull) { *repeat = true; return OBIA_OK; }   // (the repeat counts its own pixels)
-    fold_counters(ctx, h);
+    fold_counters(ctx, h, ctx->defer_shared_px);
     return OBIA_OK;
 }
 
 int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b) {
     ctx->timing.batch_repeats += 1;
     unsigned long long *d_px = nullptr;
-    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px));
+    double shared_px = 0.0;   // (a repeat stores labels in every sweep: nothing is shared)
+    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px, &shared_px));
     if (!d_px) return OBIA_OK;
     unsigned long long h[513];
     OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
-    fold_counters(ctx, h);
+    fold_counters(ctx, h, shared_px);
     return OBIA_OK;
 }
 

@@ -349,10 +349,12 @@ struct TileState {
     } pf;
 };
 
-// The feature pass of the white tiles (bound by HBM, few vector instructions) runs on a side stream beside the black batch's
-// sweeps, whose first nine launches -- the spatial pre-pass -- are bound by vector issue and move no data: 46.62 / 46.48 ->
-// 46.10 / 46.00 ms per step (two pairs on one box; the pre-pass gives back 0.4 ms of the 2.7 ms hidden).  Round 2 had measured the
-// same idea as a loss on the round-1 kernels.
+// The feature pass of the white tiles (bound by HBM, few vector instructions) ran on a side stream beside the black batch's
+// sweeps while their first nine launches -- the spatial pre-pass, bound by vector issue, no data moved -- covered the whole batch:
+// 46.62 / 46.48 -> 46.10 / 46.00 ms per step then.  Since the black tiles of a class share one pre-pass (slic_sweep.hip) there is little
+// left to run beside, and the pass is queued on the context's stream in front of the black sweeps: 37.8 - 38.1 ms per step against
+// 38.1 - 38.5 beside (five alternating runs each, profiles/prepass_share_notes.md).  Batches that never share -- exit_on_fixed_point,
+// SLIC-zero: every sweep stores its labels -- keep the side stream; OBIA_PREFETCH_BESIDE=1 builds that form for every batch.
 
 static int grid_rows(const std::vector<TileWin> &wins) {   // row-walking kernels: one block per row (capped)
     int g = 1;
@@ -361,6 +363,9 @@ static int grid_rows(const std::vector<TileWin> &wins) {   // row-walking kernel
 }
 
 // One batch of tiles: mask -> features -> plan -> sweeps -> connectivity -> scatter.
+#ifndef OBIA_PREFETCH_BESIDE
+#define OBIA_PREFETCH_BESIDE 0   /* developer builds: 1 = the white feature pass runs on a side stream beside the black sweeps */
+#endif
 static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside = false);
 
 // OBIA_SEEDING_SKIMAGE: every tile of the batch is seeded as scikit-image seeds maskSLIC, from its own window of the batch's mask
@@ -511,7 +516,9 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     if (S.seeding == OBIA_SEEDING_SKIMAGE) OBIA_TRY(seed_tiles_skimage(ctx, S, b, nvalid, nseg, ext));
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid, ext.empty() ? nullptr : ext.data()));
     debug_sync(ctx, "tiler: plan_and_seed");
-    if (!white && S.pf.b.d_feat && !S.pf.launched) OBIA_TRY(prefetch_white_launch(ctx, S, true));
+    // (a batch whose sweeps all store their labels never shares its pre-pass: the whole black pre-pass is there to run beside, as before)
+    if (!white && S.pf.b.d_feat && !S.pf.launched)
+        OBIA_TRY(prefetch_white_launch(ctx, S, OBIA_PREFETCH_BESIDE != 0 || b.exit_on_fixed_point || b.slic_zero));
     const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
     unsigned *const mask4 = b.d_mask4;        // (null: the sweeps pack the mask above the mark)
     OBIA_TRY(slic_run_sweeps(ctx, b));   // (the orphan flag is looked at after the connectivity stage's own synchronisation)
