@@ -540,6 +540,25 @@ int obia_mlp_predict_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_f
 int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
                              double *scaled_out);
 
+/* ---- SHAP values of a tree ensemble (what shap.TreeExplainer(forest).shap_values(x) computes without background data) -----
+ * obia_forest_shap_dev : x (n_rows, n_features) float32 and forest as in obia_forest_predict_dev, the same walk rule.  cover
+ *                        [n_nodes] float64, device: the weight of the training rows that reached the node (scikit-learn's
+ *                        weighted_n_node_samples), finite and positive.  v_t(S) from the root of tree t: value[leaf] at a leaf;
+ *                        at a node whose feature is in S the value of the child the row follows; otherwise
+ *                        z_left v(left) + z_right v(right), z_child = cover[child] / cover[node].  phi_out (n_rows, n_features,
+ *                        n_classes) float64 = the Shapley value of every feature under (1 / T) sum_t v_t; a feature no tree tests
+ *                        gets exactly 0.  base_out [n_classes] float64 = v(empty set).  sum_f phi + base = proba of
+ *                        obia_forest_predict_dev up to rounding.  Path-dependent TreeSHAP per root-to-leaf path with the splits
+ *                        of one feature merged; all float64, no floating-point atomics, additions in an order the forest alone
+ *                        fixes (trees ascending, leaves in ascending node index): two calls agree bit for bit and a row's result
+ *                        does not depend on the other rows.  The stream is synchronised before the call returns.
+ *                        More than 64 classes, 4096 features, 65536 trees or 2^31 - 1 nodes, or a path that tests more than 32
+ *                        distinct features: OBIA_E_UNSUPPORTED.  A node whose feature or children point outside their range, a
+ *                        node that is not reached from its tree's root exactly once, or a cover that is not finite and positive:
+ *                        OBIA_E_INVALID; every walk is bounded by its tree's node count.                                        */
+int obia_forest_shap_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest, const double *cover,
+                         double *phi_out, double *base_out);
+
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
  * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of

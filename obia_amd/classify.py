@@ -9,6 +9,8 @@ the whole segment table runs on the device (libobia_hip.so, csrc/classify.hip):
                     and the margin -- as one tree walk per (row, tree) for all rows at once
     mlp_predict     the same loop for a fitted ``MLPClassifier``: the forward pass of all rows, class filter and margin in one
                     kernel (csrc/mlp.hip)
+    forest_shap     ``shap.TreeExplainer(classifier).shap_values(x)`` of :113-118 for the whole table: path-dependent TreeSHAP,
+                    one (row, root-to-leaf path) pair at a time (csrc/shap.hip)
     predict_segments  the back half of ``classify`` for a classifier fitted earlier (forest or MLP)
 
 The forest's arithmetic is scikit-learn's: ``proba`` is bit-identical to
@@ -46,10 +48,11 @@ class Forest:
     ``threshold`` (n,) float64, ``feature`` (n,) int32, ``left`` / ``right`` (n,) int32 -- indices within the node's own tree, -1 at
     a leaf, as scikit-learn's ``children_left`` / ``children_right`` -- ``missing_go_to_left`` (n,) uint8, ``tree_offset`` (T,) int64
     (the first node of every tree, its root), ``value`` (n, K) float64 (what a leaf adds to ``proba`` before the division by T:
-    the tree's own ``predict_proba`` row) and ``classes_`` (K,).
+    the tree's own ``predict_proba`` row) and ``classes_`` (K,).  ``cover`` (n,) float64, optional: the weight of the training
+    rows that reached every node (scikit-learn's ``weighted_n_node_samples``); only :func:`forest_shap` needs it.
     """
 
-    def __init__(self, threshold, feature, left, right, missing_go_to_left, tree_offset, value, classes_, n_features=None):
+    def __init__(self, threshold, feature, left, right, missing_go_to_left, tree_offset, value, classes_, n_features=None, cover=None):
         self.threshold = np.ascontiguousarray(threshold, np.float64)
         self.feature = np.ascontiguousarray(feature, np.int32)
         self.left = np.ascontiguousarray(left, np.int32)
@@ -80,6 +83,9 @@ class Forest:
         self.n_features = int(n_features) if n_features is not None else (int(self.feature[inner].max()) + 1 if inner.any() else 1)
         if inner.any() and int(self.feature[inner].max()) >= self.n_features:
             raise ValueError("a node tests a feature beyond n_features")
+        self.cover = None if cover is None else np.ascontiguousarray(cover, np.float64)
+        if self.cover is not None and self.cover.shape != (n,):
+            raise ValueError(f"cover must hold one entry per node ({n})")
         self._dev = {}
 
     n_nodes = property(lambda self: int(self.threshold.shape[0]))
@@ -91,6 +97,7 @@ class Forest:
         """Read a fitted ``RandomForestClassifier`` (or any ensemble whose ``estimators_`` are single-output
         ``DecisionTreeClassifier``\\ s that vote by averaging ``predict_proba``)."""
         parts = {k: [] for k in _FOREST_ARRAYS}
+        cover = []
         offset = 0
         for est in rf.estimators_:
             t = est.tree_
@@ -113,27 +120,37 @@ class Forest:
             parts["missing_go_to_left"].append(np.zeros(n, np.uint8) if mgl is None else np.asarray(mgl, np.uint8))
             parts["tree_offset"].append(offset)
             parts["value"].append(v)
+            cover.append(np.asarray(t.weighted_n_node_samples, np.float64))
             offset += n
         if not parts["value"]:
             raise ValueError("the ensemble has no trees")
         cat = {k: np.concatenate(v) for k, v in parts.items() if k != "tree_offset"}
         return cls(tree_offset=np.asarray(parts["tree_offset"], np.int64), classes_=np.asarray(rf.classes_),
-                   n_features=int(rf.n_features_in_), **cat)
+                   n_features=int(rf.n_features_in_), cover=np.concatenate(cover), **cat)
 
     def save(self, path):
-        """Plain ``.npz`` of the arrays and ``classes_``; nothing pickled."""
-        np.savez(path, classes_=self.classes_, n_features=np.int64(self.n_features), **{k: getattr(self, k) for k in _FOREST_ARRAYS})
+        """Plain ``.npz`` of the arrays and ``classes_`` (and ``cover`` when there is one); nothing pickled."""
+        extra = {} if self.cover is None else {"cover": self.cover}
+        np.savez(path, classes_=self.classes_, n_features=np.int64(self.n_features), **{k: getattr(self, k) for k in _FOREST_ARRAYS}, **extra)
         return path
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            return cls(classes_=z["classes_"], n_features=int(z["n_features"]), **{k: z[k] for k in _FOREST_ARRAYS})
+            return cls(classes_=z["classes_"], n_features=int(z["n_features"]), cover=z["cover"] if "cover" in z.files else None,
+                       **{k: z[k] for k in _FOREST_ARRAYS})
 
     def _on(self, device):
         d = self._dev.get(str(device))
         if d is None:
             d = self._dev[str(device)] = {k: torch.as_tensor(getattr(self, k), device=device) for k in _FOREST_ARRAYS}
+        return d
+
+    def _cover_on(self, device):
+        """``cover`` on the device, uploaded once (kept apart from :meth:`_on`: prediction does not need it)."""
+        d = self._dev.get(("cover", str(device)))
+        if d is None:
+            d = self._dev[("cover", str(device))] = torch.as_tensor(self.cover, device=device)
         return d
 
 
@@ -313,6 +330,62 @@ def forest_predict(forest, X32, acceptable=None, ctx=None):
     return pred.cpu().numpy(), margin.cpu().numpy(), proba.cpu().numpy()
 
 
+def forest_shap(forest, X32, ctx=None):
+    """SHAP values of ``forest`` for every row of ``X32`` (N, F) float32: returns ``(phi, base)``.
+
+    ``phi`` (N, F, K) float64 -- the layout ``shap.TreeExplainer(rf).shap_values(x)`` returns for a multi-class forest -- is the
+    Shapley value of every feature for every class under the forest's path-dependent value function (no background data: a
+    feature outside the coalition is averaged out with ``cover[child] / cover[node]``); ``base`` (K,) float64 is the
+    cover-weighted mean of the leaves, the explainer's ``expected_value``.  ``phi.sum(1) + base`` is ``proba`` of
+    :func:`forest_predict` up to rounding, and a feature no tree tests gets exactly 0.  The rows are walked as
+    :func:`forest_predict` walks them (cast to float32, NaN by ``missing_go_to_left``), which is where this departs from the
+    ``shap`` package.  Float64 throughout, no floating-point atomics: two calls agree bit for bit, and a row's
+    result does not depend on the other rows.  A path may test at most 32 distinct features.
+
+    The output takes N * F * K * 8 bytes: 1.9 GB for 489 480 x 96 x 5.  ``forest`` needs ``cover`` (``Forest.from_sklearn``
+    fills it).  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    if not isinstance(forest, Forest):
+        raise TypeError("forest must be an obia_amd.classify.Forest (Forest.from_sklearn(rf))")
+    if forest.cover is None:
+        raise ValueError("forest_shap needs the nodes' cover: build the forest with Forest.from_sklearn(rf) or pass cover=")
+    is_t = _is_torch(X32)
+    if is_t and not X32.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(X32.shape)
+    if len(shape) != 2:
+        raise ValueError("X32 must be (rows, features)")
+    N, F = shape
+    if N == 0:
+        raise ValueError("the table has no rows")
+    if F < forest.n_features:
+        raise ValueError(f"the forest tests feature {forest.n_features - 1}, the table has {F} columns")
+    K = forest.n_classes
+    if K > MAX_CLASSES or F > MAX_FEATURES or forest.n_trees > MAX_TREES or forest.n_nodes >= 2 ** 31:
+        raise NotImplementedError(f"forest_shap supports at most {MAX_CLASSES} classes, {MAX_FEATURES} features, {MAX_TREES} trees "
+                                  f"and 2^31 - 1 nodes (got {K}, {F}, {forest.n_trees}, {forest.n_nodes})")
+    lib = _lib.load()
+    if is_t:
+        x = X32.to(torch.float32).contiguous()
+    else:
+        c0 = ctx or _lib.default_context(0)
+        x = torch.as_tensor(np.ascontiguousarray(X32, dtype=np.float32), device=f"cuda:{c0.device}")
+    dev = x.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    d = forest._on(x.device)
+    fs = _lib.Forest(*(d[k].data_ptr() for k in ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset")),
+                     forest.tree_offset.ctypes.data, d["value"].data_ptr(), forest.n_nodes, forest.n_trees, K)
+    phi = torch.empty((N, F, K), dtype=torch.float64, device=x.device)
+    base = torch.empty((K,), dtype=torch.float64, device=x.device)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(lib.obia_forest_shap_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(fs), forest._cover_on(x.device).data_ptr(),
+                                        phi.data_ptr(), base.data_ptr()))
+    if is_t:
+        return phi, base
+    return phi.cpu().numpy(), base.cpu().numpy()
+
+
 def _mlp_plan(layer_sizes):
     """(rows a workgroup takes, features of the input layer staged at a time) of obia_mlp_predict_dev for these layer sizes: the
     same few lines as in csrc/mlp.hip, for the tests that walk the kernel's thresholds.  64 KB of LDS hold two activation buffers
@@ -377,7 +450,8 @@ def mlp_predict(mlp, X, acceptable=None, ctx=None, _logits=False):
 
 class ClassifiedImage:
     """The reference's result object (classify.py:12-65): ``classified`` (the segment table with ``predicted_class`` and
-    ``prediction_margin``), ``confusion_matrix``, ``report``, ``shap_values``, ``transform``, ``crs``, ``params``."""
+    ``prediction_margin``), ``confusion_matrix``, ``report``, ``shap_values``, ``transform``, ``crs``, ``params``.  ``shap_base_values`` (not in the
+    reference) is the explainer's ``expected_value`` that goes with ``shap_values``; both are None unless they were asked for."""
 
     def __init__(self, classified, confusion_matrix, report, shap_values, transform, crs, params):
         self.classified = classified
@@ -387,6 +461,7 @@ class ClassifiedImage:
         self.params = params
         self.transform = transform
         self.crs = crs
+        self.shap_base_values = None
 
     def to_raster(self, labels, start_label=1, fill=0):
         """Class per pixel: a gather of ``predicted_class`` through the label raster.  The table's rows are the labels that
@@ -479,14 +554,15 @@ def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf
 
     ``acceptable``: (N, K) boolean mask in ``classes_`` order, or ``acceptable_classes_gdf`` (see :func:`acceptable_mask`; needs
     ``segments.attrs["labels"]`` or ``labels=``, and ``affine_transformation=`` when the zones are in map coordinates).
-    ``method='mlp'`` is refused here (fit the ``MLPClassifier`` yourself and call :func:`predict_segments`); ``compute_shap=True``
-    is not implemented."""
+    ``method='mlp'`` and ``compute_shap=True`` are refused here: fit the classifier yourself and call :func:`predict_segments`
+    (``compute_shap=True`` there, or :func:`forest_shap`)."""
     if method == 'mlp':
         raise NotImplementedError("method='mlp' is not switched on in classify(): fit the MLPClassifier and call predict_segments")
     if method != 'rf':
         raise ValueError('An unsupported classification algorithm was requested')
     if compute_shap:
-        raise NotImplementedError("compute_shap=True is not implemented")
+        raise NotImplementedError("compute_shap=True is not switched on in classify(): fit the forest and call "
+                                  "predict_segments(..., compute_shap=True) or forest_shap")
     from sklearn.ensemble import RandomForestClassifier
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
@@ -511,7 +587,7 @@ def classify(segments, training_classes, acceptable_classes_gdf=None, method='rf
 
 
 def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, acceptable=None, labels=None, affine_transformation=None,
-                     start_label=1, ctx=None):
+                     start_label=1, ctx=None, **options):
     """The back half of :func:`classify` (classify.py:125-175) for a classifier fitted earlier, so that a second raster or tile
     does not pay for training again.
 
@@ -519,8 +595,16 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
     non-feature columns are dropped, the rest scaled with :func:`standard_scale` -- float32 for a forest, float64 for an MLP --
     and predicted with :func:`forest_predict` / :func:`mlp_predict`.  ``segments`` gains ``predicted_class`` and
     ``prediction_margin`` and is returned inside a :class:`ClassifiedImage` whose ``params`` are the estimator's ``get_params()``
-    ({} for a Forest or an MLP).  The acceptable-class arguments are those of :func:`classify`."""
+    ({} for a Forest or an MLP).  The acceptable-class arguments are those of :func:`classify`.
+
+    One more keyword, ``compute_shap=False`` (taken through ``**options`` so that the listed keywords, which a test pins, stay
+    as they are; any other name raises TypeError).  ``compute_shap=True``, forests only: ``shap_values`` is ``phi`` (rows,
+    features, classes) of :func:`forest_shap` on the scaled table and ``shap_base_values`` its ``base``; mind the size, rows x
+    features x classes x 8 bytes."""
     import pandas as pd
+    compute_shap = bool(options.pop("compute_shap", False))
+    if options:
+        raise TypeError(f"predict_segments() got an unexpected keyword argument {sorted(options)[0]!r}")
     params = {}
     if isinstance(classifier, (Forest, MLP)):
         model = classifier
@@ -543,6 +627,8 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
         if acceptable.shape[0] != len(segments):
             raise ValueError(f"the label raster holds {acceptable.shape[0]} segments, the table {len(segments)} rows")
     is_mlp = isinstance(model, MLP)
+    if compute_shap and is_mlp:
+        raise NotImplementedError("compute_shap=True explains forests only (TreeSHAP); there is no explainer for an MLP")
     X, _, _ = standard_scale(np.ascontiguousarray(x_pred.to_numpy(dtype=np.float64)), ctx=ctx, dtype=np.float64 if is_mlp else np.float32)
     pred, margin, _ = (mlp_predict if is_mlp else forest_predict)(model, X, acceptable=None if acceptable is None else np.asarray(acceptable),
                                                                   ctx=ctx)
@@ -556,4 +642,7 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
             segments[col] = segments[col].astype(pd.Int64Dtype())
         elif np.issubdtype(segments[col].dtype, np.floating):
             segments[col] = segments[col].astype(float)
-    return ClassifiedImage(segments, None, None, None, None, None, params)
+    res = ClassifiedImage(segments, None, None, None, None, None, params)
+    if compute_shap:
+        res.shap_values, res.shap_base_values = forest_shap(model, X, ctx=ctx)
+    return res
