@@ -559,6 +559,29 @@ int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows,
 int obia_forest_shap_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest, const double *cover,
                          double *phi_out, double *base_out);
 
+/* ---- exact Shapley values of a fitted MLP against a background table (shap.KernelExplainer with every coalition enumerated) ----
+ * obia_mlp_coalition_dev : x (n_rows, n_features), background (n_background, n_features) float64, mlp as in obia_mlp_predict_dev.
+ *                        masks (n_masks, n_features) bytes, non-zero = the feature comes from x; NULL = all 2^F coalitions in
+ *                        binary order (coalition m holds feature f iff bit f of m is set; n_masks must be 2^F, F <= 16).
+ *                        values_out (n_rows, n_masks, n_classes) float64:
+ *                        values[n, m] = (...((0.0 + p(h_0)) + p(h_1)) + ... + p(h_{B-1})) / B, h_b[f] = x[n, f] where the coalition
+ *                        holds f, else background[b, f]; p = proba of obia_mlp_predict_dev for that row, the same bits.  The
+ *                        background rows are added in ascending order from 0.0 and the sum is divided once by B; the empty and
+ *                        the full coalition follow the same rule.  No floating-point atomics.  A NaN or an infinity in x or in
+ *                        background: OBIA_E_INVALID ("Input X ..." / "Input background contains NaN or infinity").  The limits
+ *                        of obia_mlp_predict_dev, fewer than 2^31 background rows and (row, coalition) pairs: OBIA_E_UNSUPPORTED;
+ *                        n_background < 1 or n_masks < 1: OBIA_E_INVALID.
+ * obia_shapley_combine_dev : values (n_rows, 2^F, n_classes) float64 in binary coalition order, size_weights [F] float64 on the
+ *                        HOST, w[s] = s! (F - 1 - s)! / F!.  phi_out (n_rows, F, n_classes) float64:
+ *                        phi[n, f, k] = the sum over the coalitions m without bit f, in ascending m from 0.0, of
+ *                        w[popcount(m)] * (values[n, m | 1 << f, k] - values[n, m, k]); every difference, product and sum is
+ *                        rounded on its own.  F > 16 or more than 64 classes: OBIA_E_UNSUPPORTED.  The stream is synchronised
+ *                        before the call returns.                                                                            */
+int obia_mlp_coalition_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_features, const obia_mlp *mlp, const double *background,
+                           int64_t n_background, const uint8_t *masks, int64_t n_masks, double *values_out);
+int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows, int n_features, int n_classes, const double *size_weights,
+                             double *phi_out);
+
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
  * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of

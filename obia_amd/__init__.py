@@ -8,5 +8,6 @@ from .geopackage import write_geopackage, read_geopackage  # noqa: F401
 from .seeds import make_chm_seeds, make_density_seeds, make_canonical_seeds  # noqa: F401
 from .classify import classify, ClassifiedImage, Forest, standard_scale, forest_predict, acceptable_mask  # noqa: F401
 from .classify import MLP, mlp_predict, predict_segments, forest_shap  # noqa: F401
+from .classify import mlp_shap, mlp_coalition_values, shapley_combine  # noqa: F401
 
 __version__ = "0.1.0"

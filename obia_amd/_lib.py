@@ -139,6 +139,8 @@ _SIGNATURES = {
     "obia_mlp_predict_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Mlp), _P, _P, _P, _P, _P]),
     "obia_table_scale_f64_dev": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
     "obia_forest_shap_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Forest), _P, _P, _P]),
+    "obia_mlp_coalition_dev": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(Mlp), _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
+    "obia_shapley_combine_dev": (_I, [_P, _P, ctypes.c_int64, _I, _I, _P, _P]),
     "obia_set_profiling": (_I, [_P, _I]),
     "obia_last_timing": (ctypes.c_double, [_P, _I]),
 }

@@ -11,6 +11,9 @@ the whole segment table runs on the device (libobia_hip.so, csrc/classify.hip):
                     kernel (csrc/mlp.hip)
     forest_shap     ``shap.TreeExplainer(classifier).shap_values(x)`` of :113-118 for the whole table: path-dependent TreeSHAP,
                     one (row, root-to-leaf path) pair at a time (csrc/shap.hip)
+    mlp_shap        ``shap.KernelExplainer(classifier.predict_proba, background).shap_values(x)`` of :108-115 for a table of at
+                    most 16 features, where every coalition is enumerated: the exact interventional Shapley value of the
+                    network against the background rows (csrc/mlp_shap.hip: mlp_coalition_values, then shapley_combine)
     predict_segments  the back half of ``classify`` for a classifier fitted earlier (forest or MLP)
 
 The forest's arithmetic is scikit-learn's: ``proba`` is bit-identical to
@@ -18,7 +21,9 @@ The forest's arithmetic is scikit-learn's: ``proba`` is bit-ide
 scikit-learn's own bits depend on the BLAS call.  There is no CPU path.
 """
 import ctypes
+import math
 import struct
+from fractions import Fraction
 
 import numpy as np
 
@@ -36,6 +41,8 @@ MLP_MAX_LAYERS, MLP_MAX_WIDTH = 8, 512
 _MLP_ARRAYS = ("weights", "biases", "layer_sizes")
 _HIDDEN_ACTIVATIONS = ("identity", "relu", "tanh", "logistic")     # obia_mlp.hidden_activation
 _OUT_ACTIVATIONS = ("softmax", "logistic")                         # obia_mlp.out_activation
+SHAP_MAX_FEATURES = 16                                             # mlp_shap enumerates all 2^F coalitions
+_SHAP_VALUES_BYTES = 256 << 20                                     # mlp_shap: the (rows, 2^F, K) coalition values of one piece at most
 
 
 def _is_torch(x):
@@ -448,6 +455,171 @@ def mlp_predict(mlp, X, acceptable=None, ctx=None, _logits=False):
     return out if is_t else tuple(t.cpu().numpy() for t in out)
 
 
+def _check_mlp_table(mlp, X, name, who):
+    """The argument checks of :func:`mlp_predict` for one table; returns ``(is_torch, rows)``."""
+    if not isinstance(mlp, MLP):
+        raise TypeError("mlp must be an obia_amd.classify.MLP (MLP.from_sklearn(clf))")
+    is_t = _is_torch(X)
+    if is_t and not X.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(X.shape)
+    if len(shape) != 2:
+        raise ValueError(f"{name} must be (rows, features)")
+    if shape[1] != mlp.n_features:
+        raise ValueError(f"the network takes {mlp.n_features} features, {name} has {shape[1]} columns")
+    K, ls = mlp.n_classes, mlp.layer_sizes
+    if mlp.n_layers > MLP_MAX_LAYERS or shape[1] > MAX_FEATURES or K > MAX_CLASSES or (mlp.n_layers > 1 and int(ls[1:-1].max()) > MLP_MAX_WIDTH):
+        raise NotImplementedError(f"{who} supports at most {MLP_MAX_LAYERS} weight matrices, {MAX_FEATURES} features, {MAX_CLASSES} "
+                                  f"classes and {MLP_MAX_WIDTH} units in a hidden layer (layer sizes {ls.tolist()}, {K} classes)")
+    return is_t, shape[0]
+
+
+def _mlp_struct(mlp, device):
+    d = mlp._on(device)
+    return _lib.Mlp(d["weights"].data_ptr(), d["biases"].data_ptr(), mlp.layer_sizes.ctypes.data, mlp.n_layers,
+                    _HIDDEN_ACTIVATIONS.index(mlp.hidden_activation), _OUT_ACTIVATIONS.index(mlp.out_activation), mlp.n_classes)
+
+
+def _coalition_inputs(mlp, X, background, who, ctx):
+    """Checks both tables (before the library is loaded), loads it and puts them on one device: ``(x, bg, context, is_torch)``."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    is_t, N = _check_mlp_table(mlp, X, "X", who)
+    bg_t, B = _check_mlp_table(mlp, background, "background", who)
+    if N == 0:
+        raise ValueError("the table has no rows")
+    if B == 0:
+        raise ValueError("the background has no rows")
+    _lib.load()
+    if is_t:
+        x = X.to(torch.float64).contiguous()
+        device = x.device
+    else:
+        device = background.device if bg_t else torch.device(f"cuda:{(ctx or _lib.default_context(0)).device}")
+        x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device=device)
+    if bg_t:
+        bg = background.to(device=device, dtype=torch.float64).contiguous()
+    else:
+        bg = torch.as_tensor(np.ascontiguousarray(background, dtype=np.float64), device=device)
+    return x, bg, ctx or _lib.default_context(device.index or 0), is_t
+
+
+def mlp_coalition_values(mlp, X, background, masks, ctx=None):
+    """Coalition values of ``mlp`` for every row of ``X`` (N, F) float64 against ``background`` (B, F) float64 under ``masks``
+    (M, F) boolean: returns ``values`` (N, M, K) float64,
+
+        ``values[n, m] = (...((0.0 + p(h_0)) + p(h_1)) + ... + p(h_{B-1})) / B``,
+
+    where ``h_b[f] = X[n, f]`` if ``masks[m, f]`` else ``background[b, f]`` and ``p`` is ``proba`` of :func:`mlp_predict` for that
+    row, the same bits: the background rows are added in ascending order from 0.0 and the sum is divided once
+    by B; the empty and the full mask follow the same rule.  This is the game whose Shapley values :func:`mlp_shap` returns, and
+    what a sampled KernelSHAP for wider tables would evaluate.  A NaN or an infinity in ``X`` or ``background`` raises
+    ValueError.  The limits of :func:`mlp_predict`; B >= 1, M >= 1.  NumPy in -> NumPy out, CUDA tensor ``X`` in -> CUDA tensor out."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    if not _is_torch(masks):
+        masks = np.asarray(masks)
+    if isinstance(mlp, MLP) and (len(tuple(masks.shape)) != 2 or masks.shape[1] != mlp.n_features or masks.shape[0] == 0):
+        raise ValueError(f"masks must be (coalitions, features) = (M >= 1, {mlp.n_features}), got {tuple(masks.shape)}")
+    x, bg, c, is_t = _coalition_inputs(mlp, X, background, "mlp_coalition_values", ctx)
+    mk = _lib.mask_bytes(masks, device=x.device)
+    N, M, K = x.shape[0], mk.shape[0], mlp.n_classes
+    values = torch.empty((N, M, K), dtype=torch.float64, device=x.device)
+    ms = _mlp_struct(mlp, x.device)
+    torch.cuda.current_stream(x.device.index or 0).synchronize()
+    _lib.check(_lib.load().obia_mlp_coalition_dev(c.handle, x.data_ptr(), N, x.shape[1], ctypes.byref(ms), bg.data_ptr(), bg.shape[0],
+                                                  mk.data_ptr(), M, values.data_ptr()))
+    return values if is_t else values.cpu().numpy()
+
+
+def _check_shap_width(mlp):
+    if isinstance(mlp, MLP) and mlp.n_features > SHAP_MAX_FEATURES:
+        raise NotImplementedError(f"mlp_shap enumerates all 2^F coalitions and supports at most {SHAP_MAX_FEATURES} features (the network "
+                                  f"takes {mlp.n_features}); for a wider table evaluate chosen coalitions with mlp_coalition_values")
+
+
+def _size_weights(F):
+    """w[s] = s! (F - 1 - s)! / F! for s = 0 .. F - 1, each the correctly rounded float64 of the rational."""
+    return np.array([float(Fraction(math.factorial(s) * math.factorial(F - 1 - s), math.factorial(F))) for s in range(F)], np.float64)
+
+
+def _combine(lib, c, values, F, K, phi):
+    w = _size_weights(F)
+    _lib.check(lib.obia_shapley_combine_dev(c.handle, values.data_ptr(), phi.shape[0], F, K, w.ctypes.data, phi.data_ptr()))
+
+
+def shapley_combine(values, ctx=None):
+    """Shapley values from the values of all coalitions: ``values`` (N, 2^F, K) float64, row m the coalition whose bit f says that
+    feature f is in it; returns ``phi`` (N, F, K) float64,
+
+        ``phi[n, f, k] = sum over the m without bit f of w[popcount(m)] * (values[n, m | 1 << f, k] - values[n, m, k])``,
+
+    ``w[s] = s! (F - 1 - s)! / F!`` rounded correctly from the rational.  The coalitions are taken in ascending m from 0.0; every
+    difference, product and sum is rounded on its own, so two calls agree bit for bit.  F <= 16.  NumPy in -> NumPy out, CUDA
+    tensor in -> CUDA tensor out."""
+    if torch is None:
+        raise ImportError("obia_amd.classify needs torch for device memory")
+    is_t = _is_torch(values)
+    if is_t and not values.is_cuda:
+        raise ValueError("torch inputs must live on the GPU")
+    shape = tuple(values.shape)
+    if len(shape) != 3 or shape[1] < 2 or shape[1] & (shape[1] - 1) or shape[2] == 0:
+        raise ValueError("values must be (rows, 2^F coalitions, classes) with F >= 1")
+    N, M, K = shape
+    F = M.bit_length() - 1
+    if N == 0:
+        raise ValueError("the table has no rows")
+    if F > SHAP_MAX_FEATURES or K > MAX_CLASSES:
+        raise NotImplementedError(f"shapley_combine supports at most {SHAP_MAX_FEATURES} features and {MAX_CLASSES} classes (got {F}, {K})")
+    lib = _lib.load()
+    if is_t:
+        v = values.to(torch.float64).contiguous()
+    else:
+        c0 = ctx or _lib.default_context(0)
+        v = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float64), device=f"cuda:{c0.device}")
+    dev = v.device.index or 0
+    c = ctx or _lib.default_context(dev)
+    phi = torch.empty((N, F, K), dtype=torch.float64, device=v.device)
+    torch.cuda.current_stream(dev).synchronize()
+    _combine(lib, c, v, F, K, phi)
+    return phi if is_t else phi.cpu().numpy()
+
+
+def mlp_shap(mlp, X, background, ctx=None):
+    """Exact Shapley values of ``mlp`` for every row of ``X`` (N, F) float64 against ``background`` (B, F) float64: returns
+    ``(phi, base)``.
+
+    The game is ``v(S) = mean over the background rows b of predict_proba(x on the features in S, background[b] elsewhere)`` --
+    what ``shap.KernelExplainer(clf.predict_proba, background).shap_values(X)`` fits when its budget covers every coalition (up
+    to 11 features with the default budget); here all 2^F coalitions are evaluated for up to 16 features, with no sampling
+    (DESIGN.md 3.5l, 5).  ``phi`` (N, F, K) float64 is the layout ``shap_values[:, :, class_ind]`` indexes; ``base`` (K,) float64
+    is the value of the empty coalition, the explainer's ``expected_value``.  ``phi.sum(1) + base`` is ``proba`` of
+    :func:`mlp_predict` up to rounding, and a feature on which a row equals every background row gets exactly +0.0.
+    :func:`mlp_coalition_values` on all coalitions in binary order, then :func:`shapley_combine`, a piece of rows at a time so
+    that the coalition values stay under ``_SHAP_VALUES_BYTES``; a row's result does not depend on the piece it fell in.
+    The work is N * 2^F * B forward passes.  NumPy in -> NumPy out, CUDA tensor ``X`` in -> CUDA tensors out."""
+    _check_shap_width(mlp)
+    x, bg, c, is_t = _coalition_inputs(mlp, X, background, "mlp_shap", ctx)
+    lib = _lib.load()
+    N, F = x.shape
+    K, M = mlp.n_classes, 1 << F
+    rows = max(1, min(N, _SHAP_VALUES_BYTES // (M * K * 8)))
+    values = torch.empty((rows, M, K), dtype=torch.float64, device=x.device)
+    phi = torch.empty((N, F, K), dtype=torch.float64, device=x.device)
+    base = None
+    ms = _mlp_struct(mlp, x.device)
+    torch.cuda.current_stream(x.device.index or 0).synchronize()
+    for r0 in range(0, N, rows):
+        n = min(rows, N - r0)
+        _lib.check(lib.obia_mlp_coalition_dev(c.handle, x[r0:r0 + n].data_ptr(), n, F, ctypes.byref(ms), bg.data_ptr(), bg.shape[0], None, M,
+                                              values.data_ptr()))
+        _combine(lib, c, values, F, K, phi[r0:r0 + n])
+        if base is None:
+            base = values[0, 0].clone()                # the empty coalition does not depend on the row
+            torch.cuda.current_stream(x.device.index or 0).synchronize()   # copied before the next piece overwrites it
+    return (phi, base) if is_t else (phi.cpu().numpy(), base.cpu().numpy())
+
+
 class ClassifiedImage:
     """The reference's result object (classify.py:12-65): ``classified`` (the segment table with ``predicted_class`` and
     ``prediction_margin``), ``confusion_matrix``, ``report``, ``shap_values``, ``transform``, ``crs``, ``params``.  ``shap_base_values`` (not in the
@@ -600,9 +772,14 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
     One more keyword, ``compute_shap=False`` (taken through ``**options`` so that the listed keywords, which a test pins, stay
     as they are; any other name raises TypeError).  ``compute_shap=True``, forests only: ``shap_values`` is ``phi`` (rows,
     features, classes) of :func:`forest_shap` on the scaled table and ``shap_base_values`` its ``base``; mind the size, rows x
-    features x classes x 8 bytes."""
+    features x classes x 8 bytes.  ``compute_shap=True, shap_background=B`` (a second key taken the same way), MLPs only: ``B``
+    (rows, features) is a background table in the scaled feature space, and ``shap_values`` / ``shap_base_values`` are ``phi`` /
+    ``base`` of :func:`mlp_shap` on the float64 scaled table against it (at most 16 features).  Without a background an MLP is
+    refused; a background given with a forest, whose explainer takes none, or without ``compute_shap=True`` raises
+    ValueError."""
     import pandas as pd
     compute_shap = bool(options.pop("compute_shap", False))
+    shap_background = options.pop("shap_background", None)
     if options:
         raise TypeError(f"predict_segments() got an unexpected keyword argument {sorted(options)[0]!r}")
     params = {}
@@ -627,8 +804,12 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
         if acceptable.shape[0] != len(segments):
             raise ValueError(f"the label raster holds {acceptable.shape[0]} segments, the table {len(segments)} rows")
     is_mlp = isinstance(model, MLP)
-    if compute_shap and is_mlp:
+    if compute_shap and is_mlp and shap_background is None:
         raise NotImplementedError("compute_shap=True explains forests only (TreeSHAP); there is no explainer for an MLP")
+    if shap_background is not None and not (compute_shap and is_mlp):
+        raise ValueError("shap_background goes with compute_shap=True and an MLP: forest_shap takes no background data")
+    if shap_background is not None:
+        _check_shap_width(model)
     X, _, _ = standard_scale(np.ascontiguousarray(x_pred.to_numpy(dtype=np.float64)), ctx=ctx, dtype=np.float64 if is_mlp else np.float32)
     pred, margin, _ = (mlp_predict if is_mlp else forest_predict)(model, X, acceptable=None if acceptable is None else np.asarray(acceptable),
                                                                   ctx=ctx)
@@ -644,5 +825,5 @@ def predict_segments(classifier, segments, acceptable_classes_gdf=None, *, accep
             segments[col] = segments[col].astype(float)
     res = ClassifiedImage(segments, None, None, None, None, None, params)
     if compute_shap:
-        res.shap_values, res.shap_base_values = forest_shap(model, X, ctx=ctx)
+        res.shap_values, res.shap_base_values = mlp_shap(model, X, shap_background, ctx=ctx) if is_mlp else forest_shap(model, X, ctx=ctx)
     return res
