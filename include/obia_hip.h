@@ -596,6 +596,8 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
  * reached keeps the label of the sweep before: DESIGN.md 3.2 item 5) -- counted whether profiling is on or not.
  * 13 = the part of 8 that no sweep evaluated: pre-pass pixel-sweeps of problems whose class representative ran them (DESIGN.md 3.2,
  * "One pre-pass per class of identical tiles"); 8 counts them as covered.
+ * 14 = pixels whose feature planes were written by the last pre-pass sweep from the raster (the fused feature pass)
+ * instead of the feature pass: all pixels of every batch that fused, 0 when none did -- counted whether profiling is on or not.
  * `enabled`: 0 off, 1 every class, 2 only the colour sweeps (an event pair costs ~2.5 us of stream time: with all classes on,
  * a step of the headline workload records ~420 pairs = 1.1 ms; bench.py times its steps in mode 2).                       */
 int obia_set_profiling(obia_ctx *ctx, int enabled);

@@ -57,6 +57,7 @@ struct Timing {
     double assign_px = 0, prepass_px = 0;   // pixels processed by the timed colour / pre-pass sweeps (sum over launches)
     double prepass_shared_px = 0;           // ... of prepass_px that no sweep evaluated: covered by a class representative's sweeps (shared pre-pass)
     double assign_store_px = 0;             // ... of the colour sweeps that also stored their labels (the last sweep of a batch)
+    double feat_fused_px = 0;               // pixels whose feature planes were written by a sweep (fused feature pass) instead of the feature pass
     int sweeps = 0;
     int batch_repeats = 0;                  // batches whose sweeps ran again with every sweep storing its labels (a valid pixel no window reached)
     // time during which at least one colour (pre-pass) sweep was running: the sweeps run one after the other, so this equals

@@ -334,6 +334,7 @@ double obia_last_timing(obia_ctx *ctx, int what) {
         case 11: return ctx->timing.prepass_busy_ms;
         case 12: return (double)ctx->timing.batch_repeats;
         case 13: return ctx->timing.prepass_shared_px;
+        case 14: return ctx->timing.feat_fused_px;
         default: return -1.0;
     }
 }

@@ -15,6 +15,7 @@
 // global integer atomic per (tile, centroid, field); colour sums are 64-bit fixed point, so the sums
 // (and therefore the whole segmentation) do not depend on the order of the atomics.
 #include "slic.hpp"
+#include "slic_features.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -67,14 +68,7 @@ static long long slice_len(long long L, long long start, long long step) {
 // ------------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned f2key(float f) {   // order-preserving float -> uint
-    unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-    unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
+// (f2key / key2f, the order-preserving float <-> uint of the min / max keys: slic_features.hpp)
 
 constexpr int FP_NT = 256;
 
@@ -198,11 +192,7 @@ __device__ __forceinline__ float feature_pixel(const float *__restrict__ px, int
     }
     if (normalize) {
 #pragma unroll
-        for (int c = 0; c < CP; ++c) {
-            float t = (v[c] - bmn[c]) / bden[c];
-            if (!(fabsf(t) <= 3.0e38f)) t = 0.0f;   // constant / non-finite band: the problem is rejected on the host
-            v[c] = t;
-        }
+        for (int c = 0; c < CP; ++c) v[c] = feature_normalized(v[c], bmn[c], bden[c]);   // (slic_features.hpp: shared with the sweep that normalises on the fly)
     } else {
 #pragma unroll
         for (int c = 0; c < CP; ++c) if (!(fabsf(v[c]) <= 3.0e38f)) v[c] = 0.0f;
@@ -227,11 +217,7 @@ __device__ __forceinline__ void feature_band_params(const unsigned *__restrict__
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
         bmn[c] = 0.0f; bden[c] = 1.0f;
-        if (normalize && c < C) {
-            const float mn = key2f(keys[((long long)p * C + c) * 2 + 0]);
-            const float mx = key2f(keys[((long long)p * C + c) * 2 + 1]);
-            bmn[c] = mn; bden[c] = mx - mn;     // (band - min) / (max - min), segment_boundaries.py:16
-        }
+        if (normalize && c < C) feature_band_param(keys, p, C, c, bmn[c], bden[c]);
     }
 }
 
@@ -455,7 +441,8 @@ int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, int CP, i
 
 // Launch half of the feature pass on `stream`: min / max of every band of every window, then the features.
 // d_keys layout for np windows: keys[np][C][2] (min, max as ordered uints) | nonfinite[np] | max|feature| bits [np].
-int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth) {
+int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth,
+                         bool minmax_only) {
     const int C = b.C, CP = b.CP, np = b.nprob, maxh = b.maxh, normalize = b.normalize, to_lab = b.to_lab;
     const SrcWindow *d_windows = b.d_windows;
     const float ratio = b.feat_ratio;
@@ -478,6 +465,8 @@ int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *sr
             hipLaunchKernelGGL(HIP_KERNEL_NAME(band_minmax_kernel<1>), dim3(gx, np), dim3(FP_NT), 0, stream, src, Ws, C, d_windows,
                                d_keys, (int *)d_nonfinite);
     }
+    // fused feature pass (slic_fuse_features): the last pre-pass sweep reads the raster, normalises with these keys and writes the planes
+    if (minmax_only) { OBIA_HIP_TRY(hipGetLastError()); return OBIA_OK; }
     const bool box = planes && d_fbox != nullptr;   // colour boxes from the same pass (a block walks footprint bands of 16 rows)
     const int rows = box ? (maxh + 15) / 16 : (planes ? (maxh + 3) / 4 : maxh);
     dim3 grid(rows < 4096 ? rows : 4096, np);
@@ -555,15 +544,31 @@ int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *non
             }
         }
     }
+    // fused feature pass: the planes do not exist yet, so neither does max|feature|.  With the prescale in the ratio a normalised band
+    // reaches exactly 1 * feat_ratio (its maximum is (max - min) / (max - min)), and nothing larger (slic_prescale): the scale follows
+    // from the ratio.  (Constant / non-finite bands were rejected or skipped above, from the flags of the min / max pass.)
+    if (b.fuse_features) { b.fscale = slic_fscale(b.feat_ratio); return OBIA_OK; }
     float maxabs = 0.0f;
     for (int p = 0; p < np; ++p) {
         float v; memcpy(&v, &maxabs_bits[p], 4);
         if (!(v <= 3.0e38f)) { set_error("non-finite feature values"); return OBIA_E_NONFINITE; }
         if (v > maxabs) maxabs = v;
     }
-    // fixed-point scale for the colour sums (to_fixed32 in slic_sweep.hip): a power of two with |feature| * 2^s < 2^29, so
-    // that the scaling is exact, the four pixels of a lane's strip add up in an int32 and the total over a cluster of up to
-    // 2^31 pixels stays below 2^60
+    b.fscale = slic_fscale(maxabs);
+    // what the fused pass relies on, checked wherever max|feature| is known: all zeros (every window skipped) or exactly the ratio
+    // (not behind the Gaussian smoothing, which lowers the maximum; such a batch never fuses)
+    const bool smoothed = b.sigma[0] > 1e-15 || b.sigma[1] > 1e-15 || b.sigma[2] > 1e-15;
+    if (b.prescale != 1.0f && !smoothed && maxabs > 0.0f && b.fscale != slic_fscale(b.feat_ratio)) {
+        set_error("largest feature %g of normalised bands is not the ratio %g", (double)maxabs, (double)b.feat_ratio);
+        return OBIA_E_INVALID;
+    }
+    return OBIA_OK;
+}
+
+// fixed-point scale for the colour sums (to_fixed32 in slic_sweep.hip): a power of two with |feature| * 2^s < 2^29, so
+// that the scaling is exact, the four pixels of a lane's strip add up in an int32 and the total over a cluster of up to
+// 2^31 pixels stays below 2^60
+double slic_fscale(float maxabs) {
     int s = 0;
     if (maxabs > 0.0f) {
         int e = 0;
@@ -572,8 +577,28 @@ int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *non
     }
     if (s > 100) s = 100;
     if (s < -90) s = -90;
-    b.fscale = std::ldexp(1.0, s);
-    return OBIA_OK;
+    return std::ldexp(1.0, s);
+}
+
+// On by default: bit-identical (tests/test_gpu_fused_features.py) and 1.4 ms per headline step faster than the separate pass, ranges
+// apart (profiles/feature_fuse_notes.md).
+#ifndef OBIA_FUSE_FEATURES_DEFAULT
+#define OBIA_FUSE_FEATURES_DEFAULT 1
+#endif
+bool slic_fuse_features(const SlicBatch &b, const float *src, int Ws) {
+    // OBIA_FUSE_FEATURES, read per call: 1 = fuse wherever the rules below allow it, 0 = the separate pass (A/B timing,
+    // tests/test_gpu_fused_features.py).  Unset: OBIA_FUSE_FEATURES_DEFAULT
+    const char *e = std::getenv("OBIA_FUSE_FEATURES");
+    if (e ? e[0] == '0' : !OBIA_FUSE_FEATURES_DEFAULT) return false;
+    if (!b.feat_planes || !b.normalize || b.to_lab || b.slic_zero || b.prescale == 1.0f) return false;
+    if (b.sigma[0] > 1e-15 || b.sigma[1] > 1e-15 || b.sigma[2] > 1e-15) return false;   // the smoothing passes read the normalised bands
+    if (!b.masked || b.max_iter < 1) return false;   // a pre-pass of at least one sweep (its last one folds the colours), and it runs
+    if (b.direct || b.exit_on_fixed_point) return false;
+    if (b.col_lb) return false;                      // the colour boxes of low compactness come out of the feature pass
+    if (b.C % 4 != 0 || (reinterpret_cast<uintptr_t>(src) & 15) != 0) return false;   // float4 reads of a pixel's bands
+    if (b.CP > 12) return false;   // 16 bands: the sweep holds 130 vector registers (3 waves per SIMD) before it normalises anything; not built, not measured
+    if ((double)Ws * b.C * 4.0 * 20.0 >= 4294967296.0) return false;   // 32-bit lane offsets into a footprint's 16 raster rows
+    return true;
 }
 
 float slic_prescale(float ratio, int normalize, int to_lab, bool slic_zero) {
@@ -638,7 +663,9 @@ int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Ws,
     SmoothSpec sm;
     for (int i = 0; i < 3; ++i) sm.sigma[i] = b.sigma[i];
     OBIA_TRY(smooth_prepare(ctx, sm, b.total_pix, b.CP, np));
-    OBIA_TRY(slic_features_launch(ctx->stream, b, src, Ws, d_keys, &sm));
+    b.fuse_features = slic_fuse_features(b, src, Ws);
+    if (b.fuse_features) { b.raw_src = src; b.raw_ws = Ws; b.d_keys = d_keys; }
+    OBIA_TRY(slic_features_launch(ctx->stream, b, src, Ws, d_keys, &sm, b.fuse_features));
     // one read-back: min/max keys (constant-band check), non-finite flags, max|feature| per window
     std::vector<unsigned> host(ntot);
     OBIA_TRY(read_back(ctx, host.data(), d_keys, ntot * sizeof(unsigned)));

@@ -92,6 +92,12 @@ struct SlicBatch {
     float *d_fbox = nullptr;           // footprint colour boxes (feat_boxes), or null
     bool col_lb = false;               // the sweeps add the colour-box bound to the spatial one (see slic_use_colour_bound)
     float *d_feat = nullptr;           // quad-row planes, 4 * total_feat_f4 floats (pixel-major [total_pix][CP] when !feat_planes)
+    // fused feature pass (slic_fuse_features): the feature step ran the min / max pass only; the last sweep of the spatial pre-pass
+    // reads the caller's raster, normalises with the keys and writes d_feat on its way (slic_sweep.hip: RAWIN)
+    bool fuse_features = false;
+    const float *raw_src = nullptr;    // the caller's raster (rows of raw_ws pixels, C bands) the windows lie in
+    int raw_ws = 0;
+    const unsigned *d_keys = nullptr;  // [nprob][C][2] min / max keys of the batch's windows (band_minmax_kernel)
     bool feat_planes = true;           // false: pixel-major features (quickshift reads them per pixel)
     double sigma[3] = {0.0, 0.0, 0.0};   // Gaussian pre-smoothing (z, y, x), 0 = none (obia_slic_params::sigma_zyx)
     double spacing[3] = {1.0, 1.0, 1.0}; // obia_slic_params::spacing_zyx
@@ -175,7 +181,16 @@ struct SmoothSpec {
 int smooth_prepare(obia_ctx *ctx, SmoothSpec &sm, long long total_pix, int CP, int np);
 int gaussian_weights_host(double sigma, bool sigma_is_f32, std::vector<double> &w);   // returns the radius; w[0] = centre weight
 // (b.d_fbox, plane layout only: the footprints' colour boxes come out of the same pass)
-int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth = nullptr);
+// minmax_only: the fused form -- keys and flags only, no planes
+int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *src, int Ws, unsigned *d_keys, const SmoothSpec *smooth = nullptr,
+                         bool minmax_only = false);
+// Does the batch (settings filled) take the fused feature pass on this raster?  Plane layout; normalised bands with the prescale in
+// the ratio (no Lab, no SLIC-zero); no smoothing; masked with at least one sweep (the last pre-pass sweep folds colours: it is the
+// first reader of the planes); not direct, exit_on_fixed_point or the colour-box bound; 4, 8 or 12 bands and a 16-byte aligned raster.
+// The default where it applies; OBIA_FUSE_FEATURES=0 (developer switch, read per call) forces the separate pass, 1 asks for the fused one.
+bool slic_fuse_features(const SlicBatch &b, const float *src, int Ws);
+// The fixed-point scale of the colour sums from the largest |feature| (SlicBatch::fscale)
+double slic_fscale(float maxabs);
 int slic_features_finish(SlicBatch &b, const unsigned *keys, const unsigned *nonfinite, const unsigned *maxabs_bits, std::vector<int> *skip);
 int slic_prepare_features(obia_ctx *ctx, SlicBatch &b, const float *src, int Ws, std::vector<int> *skip = nullptr);
 // The part of the fixed-point scale of the colour sums that is known BEFORE the features are computed -- normalised bands times

@@ -33,6 +33,7 @@
 // A tile that meets more candidates than fit in LDS (tiny S, clustered centroids) takes slow_tile(), which
 // reads the bins directly; correctness never depends on the LDS capacity.
 #include "slic.hpp"
+#include "slic_features.hpp"
 
 #include <type_traits>
 #include <hip/hip_ext.h>
@@ -442,16 +443,58 @@ __device__ __forceinline__ bool orphan_needs_repeat(int store_labels, int sweep_
     return store_labels == 0 || (store_labels == 1 && sweep_id > 1);
 }
 
+// ---- fused feature pass (RAWIN) ------------------------------------------------------------------------------------------
+// The last sweep of the spatial pre-pass is the first reader of the feature planes, and all it does with a colour is fold it into
+// the centroid sums.  With RAWIN it reads the caller's raster instead (the same 16 bytes per four bands and pixel), normalises in
+// registers with the window's min / max keys (slic_features.hpp: the arithmetic of the feature pass, bit for bit), writes the
+// planes for the colour sweeps that follow and folds from the registers: the planes are written once and not read back, and the
+// feature pass of such a batch is its min / max pass alone (slic.hpp: slic_fuse_features).  Every float4 of the planes of every
+// problem is written -- masked pixels and the zeros outside a window inside its last quad row / column block included -- by
+// the footprint that holds it, or by rawin_write_tile for a tile that takes slow_tile().
+struct RawInput {
+    const float *src = nullptr;          // the caller's raster: rows of Ws pixels, CP (= C) bands
+    int Ws = 0;
+    const SrcWindow *wins = nullptr;     // window of every problem in the raster
+    const unsigned *keys = nullptr;      // [problem][C][2] min / max keys (band_minmax_kernel)
+    float ratio = 0.0f;                  // SlicBatch::feat_ratio
+    float *planes = nullptr;             // SlicBatch::d_feat
+};
+
+// the planes of one sweep tile, written by its workgroup (a thread: the four pixels of one column of one quad row at a time)
+template <int CP>
+__device__ void rawin_write_tile(const SlicProblem &P, int prob_i, int ty0, int tx0, const RawInput &ri, const float *__restrict__ rsrc) {
+    float4 *__restrict__ planes = reinterpret_cast<float4 *>(ri.planes) + P.feat_off;
+    for (int i = threadIdx.x; i < (SWEEP_TH / 4) * SWEEP_TW; i += blockDim.x) {
+        const int y = ty0 + 4 * (i / SWEEP_TW), x = tx0 + i % SWEEP_TW;
+        if (y >= P.H || (x >> 4) >= P.XB) continue;   // no such quad row / column block
+        float4 *dst = planes + ((long long)(y >> 2) * P.XB + (x >> 4)) * (CP * 16) + (x & 15);
+#pragma unroll
+        for (int ch = 0; ch < CP; ++ch) {
+            float mn, den;
+            feature_band_param(ri.keys, prob_i, CP, ch, mn, den);
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[j] = (y + j < P.H && x < P.W) ? feature_normalized(rsrc[((long long)(y + j) * ri.Ws + x) * CP + ch], mn, den) * ri.ratio : 0.0f;
+            dst[ch * 16] = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+
 // Fallback for a tile whose candidate set does not fit the LDS slots: every lane scans the bins around
 // each of its pixels directly in global memory.  Same arithmetic, no staging.
-template <int CP, bool MASKED, bool IGNORE_COLOR, bool SLICZERO>
+// RAWIN: the tile's planes are written first (rawin_write_tile); a pixel's features are computed from the raster again rather than
+// read back from planes another thread wrote.
+template <int CP, bool MASKED, bool IGNORE_COLOR, bool SLICZERO, bool RAWIN = false>
 __device__ void slow_tile(const SlicProblem &P, int ty0, int tx0, const float *__restrict__ feat,
                           const uint8_t *__restrict__ mask, const float *__restrict__ cent,
                           const int *__restrict__ head, int32_t *__restrict__ labels,
                           unsigned long long *__restrict__ acc, int RQ, int accumulate, int accum_color, int start_label,
-                          float fs, int store_labels, int *__restrict__ orphan_flag, int sweep_id, int nch) {
+                          float fs, int store_labels, int *__restrict__ orphan_flag, int sweep_id, int nch,
+                          int prob_i = 0, const RawInput &ri = RawInput(), const float *__restrict__ rsrc = nullptr) {
     constexpr int RS = CENT_REC + CP;
     const float w = P.spatial_w;
+    if (RAWIN) rawin_write_tile<CP>(P, prob_i, ty0, tx0, ri, rsrc);
     for (int i = threadIdx.x; i < SWEEP_TW * SWEEP_TH; i += NT) {
         const int y = ty0 + i / SWEEP_TW, x = tx0 + i % SWEEP_TW;
         if (y >= P.H || x >= P.W) continue;
@@ -459,7 +502,15 @@ __device__ void slow_tile(const SlicProblem &P, int ty0, int tx0, const float *_
         if (MASKED && mask[pix] == 0) { labels[pix] = start_label - 1; continue; }
         float f[CP];
 #pragma unroll
-        for (int ch = 0; ch < CP; ++ch) f[ch] = ch < nch ? feat_at(feat, P, CP, y, x, ch) : 0.0f;   // (padded planes are not written)
+        for (int ch = 0; ch < CP; ++ch) {
+            if (RAWIN) {
+                float mn, den;
+                feature_band_param(ri.keys, prob_i, CP, ch, mn, den);
+                f[ch] = feature_normalized(rsrc[((long long)y * ri.Ws + x) * CP + ch], mn, den) * ri.ratio;
+            } else {
+                f[ch] = ch < nch ? feat_at(feat, P, CP, y, x, ch) : 0.0f;   // (padded planes are not written)
+            }
+        }
         int by_lo = (y - 2 * P.sy - 2) / P.sy; if (y - 2 * P.sy - 2 < 0) by_lo = 0;
         int by_hi = (y + 2 * P.sy + 2) / P.sy; if (by_hi > P.ncy - 1) by_hi = P.ncy - 1;
         int bx_lo = (x - 2 * P.sx - 2) / P.sx; if (x - 2 * P.sx - 2 < 0) bx_lo = 0;
@@ -512,7 +563,8 @@ __device__ void slow_tile(const SlicProblem &P, int ty0, int tx0, const float *_
 // NCH: the channels that exist (C <= CP).  Planes, records and accumulators come in groups of four channels; the padded ones
 // hold zeros in the features and in every centroid, so a body compiled with NCH < CP neither loads them nor adds their
 // (0 - 0)^2 = +0 to the colour distance: same bits, a quarter less traffic and colour arithmetic for 9 bands run as 12.
-template <int CP, bool MASKED, bool IGNORE_COLOR, bool FIXPT, bool SLICZERO, bool LEAN, bool COLLB, int NCH = CP>
+// RAWIN: the last pre-pass sweep of a batch with the fused feature pass (above); IGNORE_COLOR without LEAN only.
+template <int CP, bool MASKED, bool IGNORE_COLOR, bool FIXPT, bool SLICZERO, bool LEAN, bool COLLB, int NCH = CP, bool RAWIN = false>
 __device__ __forceinline__ void slic_assign_body(
     const SlicProblem *__restrict__ probs, const float *__restrict__ feat, const uint8_t *__restrict__ mask,
     const unsigned *__restrict__ mask4, const float *__restrict__ cent, const int *__restrict__ head,
@@ -522,7 +574,8 @@ __device__ __forceinline__ void slic_assign_body(
     unsigned long long *__restrict__ px_counter, const int *__restrict__ tile_prob, int total_tiles_all,
     int *__restrict__ orphan_flag, int tiles_per_prob, const float *__restrict__ fbox, int tile_base, int nch_arg,
     int *__restrict__ tl_k, unsigned *__restrict__ tl_fp, int *__restrict__ tl_meta, const int *__restrict__ tl_req,
-    const int *__restrict__ act_tiles) {
+    const int *__restrict__ act_tiles, const RawInput &ri = RawInput()) {
+    static_assert(!RAWIN || (IGNORE_COLOR && !LEAN && !FIXPT && !SLICZERO && !COLLB && NCH == CP), "RAWIN: the last pre-pass sweep only");
     // channels that exist: a compile-time constant in the variants compiled per padding (NCH < CP), the launch argument in the
     // others (NCH == CP: the last pre-pass sweep, SLIC-zero, the fixed-point variant).  The planes of the padded channels are NOT
     // written by the feature pass since round 3 (nine bands: 36 instead of 48 bytes per pixel): nobody may read them.
@@ -564,6 +617,12 @@ __device__ __forceinline__ void slic_assign_body(
     const int prob_i = tiles_per_prob > 0 ? gtile / tiles_per_prob : tile_prob[gtile];
     const SlicProblem P = probs[prob_i];
     const int tile = gtile - P.tile_off;
+    // RAWIN: first pixel of the problem's window in the caller's raster (workgroup-uniform: scalar registers)
+    const float *rsrc = nullptr;
+    if (RAWIN) {
+        const int wy0 = ri.wins[prob_i].y0, wx0 = ri.wins[prob_i].x0;
+        rsrc = ri.src + ((long long)wy0 * ri.Ws + wx0) * CP;
+    }
     constexpr int AQ = LEAN ? 1 : CP + 1;       // qwords of an LDS accumulator: colours (not in the lean kernel), then one packed word
     constexpr int PWI = LEAN ? 0 : CP;          // index of the packed word
                                                 //   n | sum(y - ty0) << 16 | sum(x - tx0) << 40   (a 64x64 tile: n <= 4096 < 2^16,
@@ -604,8 +663,8 @@ __device__ __forceinline__ void slic_assign_body(
     const int ty1 = min(ty0 + SWEEP_TH, P.H), tx1 = min(tx0 + SWEEP_TW, P.W);
     if (P.direct) {   // anisotropic `spacing`: every tile takes the direct path (same arithmetic with the scaled differences; the staged
                       // path's bounds and packed distance code assume unit spacing).  Workgroup-uniform.
-        slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
-                                                      accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt);
+        slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO, RAWIN>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
+                                                      accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt, prob_i, ri, rsrc);
         return;
     }
 
@@ -646,7 +705,25 @@ __device__ __forceinline__ void slic_assign_body(
         } else {
             mbw = 0x01010101u;
         }
-        if (!LEAN && want_feat) {
+        if (RAWIN) {
+            // the lane's four pixels from the caller's raster: rows yb .. yb+3 of column xx, CP / 4 loads of 16 bytes per pixel (for
+            // eight bands the same 8 loads and the same 32 registers as the plane loads below); a wave-uniform base (the footprint's
+            // first pixel) plus a 32-bit lane offset (slic_fuse_features limits the row pitch).  A pixel outside the window reads
+            // the footprint's first pixel: its value is replaced by zero where the planes are written.
+            const char *rb = reinterpret_cast<const char *>(rsrc + ((long long)fy0 * ri.Ws + fx0) * CP);   // wave-uniform
+            const unsigned rowb = (unsigned)ri.Ws * (unsigned)(CP * 4);
+            const unsigned lob = (unsigned)(PPT * (lane_o >> 4)) * rowb + (unsigned)(lane_o & 15) * (unsigned)(CP * 4);
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) {
+                const unsigned off = (real && (yb + j < P.H) && (xx < P.W)) ? lob + (unsigned)j * rowb : 0u;
+#pragma unroll
+                for (int q = 0; q < (LEAN ? 0 : CP / 4); ++q) {
+                    const float4 t = ld_stream_f4(rb + (size_t)off + 16 * q);
+                    if (j & 1) { f2[4 * q][j >> 1].y = t.x; f2[4 * q + 1][j >> 1].y = t.y; f2[4 * q + 2][j >> 1].y = t.z; f2[4 * q + 3][j >> 1].y = t.w; }
+                    else { f2[4 * q][j >> 1].x = t.x; f2[4 * q + 1][j >> 1].x = t.y; f2[4 * q + 2][j >> 1].x = t.z; f2[4 * q + 3][j >> 1].x = t.w; }
+                }
+            }
+        } else if (!LEAN && want_feat) {
             // quad-row blocks (slic.hpp): ONE 16-byte load per channel brings that channel of the lane's four pixels, the
             // channels are 256 bytes apart (immediate offsets), a quarter wave reads 256 contiguous bytes and the footprint's
             // quad row is one contiguous block (fy0 and fx0 are multiples of 16: the lane's strip is one quad row of one block)
@@ -810,8 +887,8 @@ __device__ __forceinline__ void slic_assign_body(
             if (nc > MAXC) {   // workgroup-uniform
                 if (g > 0) { g = 0; listable = false; continue; }
                 if (tid == 0) { tl_meta[2 * (size_t)gtile] = -2; tl_meta[2 * (size_t)gtile + 1] = sweep_id & 0xffff; }
-                slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
-                                                              accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt);
+                slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO, RAWIN>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
+                                                              accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt, prob_i, ri, rsrc);
                 return;
             }
             // rank of every slot = number of staged candidates with a smaller k (all distinct).  Thread t ranks slot t against the
@@ -870,8 +947,8 @@ __device__ __forceinline__ void slic_assign_body(
             if (__syncthreads_or(ovf ? 1 : 0)) {   // (a footprint meets more than 64 candidates: clustered centroids)
                 if (g > 0) { g = 0; listable = false; continue; }
                 if (tid == 0) { tl_meta[2 * (size_t)gtile] = -2; tl_meta[2 * (size_t)gtile + 1] = sweep_id & 0xffff; }
-                slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
-                                                              accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt);
+                slow_tile<CP, MASKED, IGNORE_COLOR, SLICZERO, RAWIN>(P, ty0, tx0, feat, mask, cent, head, labels, acc, RQ, accumulate,
+                                                              accum_color, start_label, fs, store_labels, orphan_flag, sweep_id, nch_rt, prob_i, ri, rsrc);
                 return;
             }
             break;
@@ -1138,6 +1215,33 @@ __device__ __forceinline__ void slic_assign_body(
         }
         STAMP(4)   // labels
 
+        if (RAWIN) {
+            // normalise and store: the registers hold raw band values; from here on they hold what the planes hold.  The lane writes
+            // the float4 of every channel of its quad row -- exactly the addresses the plain fetch() reads -- whatever the mask says
+            // (the colour sweeps load masked pixels' features too); pixels outside the window get the zeros of the feature pass.  A
+            // lane whose quad row lies below the window has nothing to write.  The band parameters are workgroup-uniform: scalar
+            // loads and scalar arithmetic, fetched here so that they hold no registers across the visits.
+            const unsigned *kp = ri.keys + (size_t)prob_i * (2 * CP);
+            asm volatile("" : "+s"(kp));
+            char *pb = reinterpret_cast<char *>(reinterpret_cast<float4 *>(ri.planes) +
+                                                (P.feat_off + ((long long)(fy0 >> 2) * P.XB + (fx0 >> 4)) * (CP * 16)));   // wave-uniform
+            const unsigned fob = ((unsigned)(lane_i >> 4) * (unsigned)(CP * 16 * P.XB) + (unsigned)(lane_i & 15)) * 16u;
+            const bool in_x = x < P.W;
+#pragma unroll
+            for (int ch = 0; ch < (LEAN ? 0 : CP); ++ch) {
+                const float mn = key2f(kp[2 * ch]), den = key2f(kp[2 * ch + 1]) - mn;
+                float v[PPT];
+#pragma unroll
+                for (int j = 0; j < PPT; ++j) {
+                    const float r = (j & 1) ? f2[ch][j >> 1].y : f2[ch][j >> 1].x;
+                    v[j] = (in_x && (yb_i + j < P.H)) ? feature_normalized(r, mn, den) * ri.ratio : 0.0f;
+                }
+                f2[ch][0] = (v2f){v[0], v[1]};
+                f2[ch][1] = (v2f){v[2], v[3]};
+                if (yb_i < P.H)
+                    __builtin_nontemporal_store((obia_v4f){v[0], v[1], v[2], v[3]}, reinterpret_cast<obia_v4f *>(pb + (size_t)fob + ch * 256));
+            }
+        }
         // ---- 3. fused centroid update ------------------------------------------------------------------------------------
         // LDS atomics on one address are executed one lane after the other, and a footprint only holds three or four slots:
         // sixty-four lanes adding their sums directly cost 11 % of the sweep (measured: OBIA_FOLD_LAYERS = 0 vs 1).  So the
@@ -1335,6 +1439,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ASSIGN_WAVES
     slic_assign_body<CP, MASKED, IGNORE_COLOR, FIXPT, SLICZERO, false, false, NCH>(OBIA_ASSIGN_ARGS, nullptr);
 }
 
+// the last pre-pass sweep of a batch with the fused feature pass: reads the raster, writes the planes (RawInput)
+template <int CP>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ASSIGN_WAVES, ASSIGN_WAVES))) void slic_assign_rawin_kernel(OBIA_ASSIGN_PARAMS, RawInput ri) {
+    slic_assign_body<CP, true, true, false, false, false, false, CP, true>(OBIA_ASSIGN_ARGS, nullptr, ri);
+}
+
 // the colour sweeps at low compactness: with the colour-box bound (one more LDS table, a few more registers)
 template <int CP, bool MASKED, int NCH = CP>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void slic_assign_collb_kernel(OBIA_ASSIGN_PARAMS) {
@@ -1395,7 +1505,8 @@ struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; 
 template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
-                          const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset()) {
+                          const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset(),
+                          bool rawin = false) {
     constexpr int XGH = OBIA_XCD_GROUP;
     // (a subset -- the lean kernels of a shared pre-pass only -- is grouped over the XCDs like the whole batch)
     const int ntiles = sub.end >= 0 ? sub.end : (int)b.total_tiles_all, tbase = sub.end >= 0 ? sub.base : 0;
@@ -1415,6 +1526,13 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
     // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
     // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
     const int pad = CP - b.C;
+    if constexpr (CP <= 12) if (rawin) {   // fused feature pass: the batch's last pre-pass sweep (queue_sweeps)
+        RawInput ri;
+        ri.src = b.raw_src; ri.Ws = b.raw_ws; ri.wins = b.d_windows; ri.keys = b.d_keys; ri.ratio = b.feat_ratio; ri.planes = b.d_feat;
+        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(slic_assign_rawin_kernel<CP>), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_, ri);
+        ctx->timing.feat_fused_px += (double)b.total_pix;
+        return;
+    }
 #define LAUNCH_ASSIGN_(M, I, F, Z) LAUNCH_K_(slic_assign_kernel<CP, M, I, F, Z>)
 #define LAUNCH_MAIN_(M)                                                                                              \
     do {                                                                                                             \
@@ -1549,6 +1667,10 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     for (auto &P : b.probs)
         if (P.W >= (1 << 22)) { set_error("rasters / tile windows wider than 4194303 pixels are not supported (got %d)", P.W); return OBIA_E_UNSUPPORTED; }
     const int passes = (b.masked && !b.prepass_only) ? 2 : 1;   // maskSLIC: spatial-only pre-pass first (slic_superpixels.py:310-314)
+    if (b.fuse_features && (!b.masked || b.exit_on_fixed_point || b.slic_zero || b.direct || b.col_lb || b.C != b.CP || b.CP > 12 || !b.raw_src || !b.d_keys)) {
+        set_error("fused feature pass on a batch that cannot take it");   // (slic_fuse_features decides; nothing else may set the flag)
+        return OBIA_E_INVALID;
+    }
     // sweeps of the pre-pass: max_iter like every pass, unless the stage entry asks for another count (obia_slic_stages::prepass_iters)
     const int pre_iter = (b.masked && b.prepass_iter > 0) ? b.prepass_iter : b.max_iter;
     const int total_sweeps = b.masked ? pre_iter + (passes - 1) * b.max_iter : b.max_iter;
@@ -1743,17 +1865,20 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             // the last pre-pass sweep is the only one of its pass that folds colours (they seed the main pass): the
             // caches written by the earlier pre-pass sweeps hold no colour sums, so it evaluates every tile
             const int use_cache = (ignore_color && it == iters - 1) ? 0 : 1;
+            // fused feature pass: this sweep -- the first reader of the planes -- writes them from the raster (RAWIN).  Not in the
+            // repeat: the first run has written them
+            const bool rawin = b.fuse_features && !repeat && ignore_color && it == iters - 1;
             {
                 KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
                 const TileSubset sub = shared_sweep ? act_tiles : TileSubset();
                 unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
                 if (ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
                 switch (b.CP) {
-                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
+                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
 #ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
-                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
-                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
-                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;
+                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
+                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
+                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;   // (never fused: slic_fuse_features)
 #endif
                     default: set_error("bad CP"); return OBIA_E_INVALID;
                 }

@@ -338,9 +338,14 @@ struct TileState {
     void *pick_user = nullptr;
     // features of ALL white tiles, prepared in one batch (they depend on the raster only): windows in processing order,
     // one dense buffer, keys read back once before the white pass
+    // Batches that take the fused feature pass (slic.hpp: slic_fuse_features) need the min / max keys only: the prefetch is then the
+    // min / max pass of all white windows with its one read-back, no planes are allocated for the set (4.85 GB at the headline
+    // size), and every white batch takes its planes from its own scope of the arena, where its last pre-pass sweep writes them.
     struct PreFeat {
         bool ready = false;
-        SlicBatch b;                     // windows, layout and feature buffers of the whole set (b.d_feat null: no prefetch)
+        bool planned = false;            // there is a prefetch (windows, keys; planes unless fused)
+        bool fused = false;              // keys only: the white batches fuse their feature pass into their sweeps
+        SlicBatch b;                     // windows, layout and feature buffers of the whole set
         std::vector<unsigned> host;      // keys | nonfinite | max|feature| of all windows
         unsigned *d_keys = nullptr;
         bool launched = false;
@@ -453,9 +458,17 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         const SrcWindow *a = &pb.windows[S.pf.cursor];
         for (int p = 0; p < np; ++p)
             if (a[p].y0 != wins[p].y0 || a[p].x0 != wins[p].x0 || a[p].h != wins[p].h || a[p].w != wins[p].w) { set_error("white batch does not match the prefetched windows"); return OBIA_E_INVALID; }
-        // (the batch's feat_off / fb_off values start at 0: offsets from the first window's block in the prefetched set)
-        b.d_feat = pb.d_feat + 4 * (size_t)a[0].feat_off;
-        if (b.col_lb) b.d_fbox = pb.d_fbox + (size_t)a[0].fb_off * 2 * b.CP;
+        if (S.pf.fused) {
+            // keys only: the planes come from this batch's scope of the arena, its last pre-pass sweep writes them
+            b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
+            b.fuse_features = true;
+            b.raw_src = S.img; b.raw_ws = S.W;
+            b.d_keys = S.pf.d_keys + S.pf.cursor * (size_t)S.C * 2;
+        } else {
+            // (the batch's feat_off / fb_off values start at 0: offsets from the first window's block in the prefetched set)
+            b.d_feat = pb.d_feat + 4 * (size_t)a[0].feat_off;
+            if (b.col_lb) b.d_fbox = pb.d_fbox + (size_t)a[0].fb_off * 2 * b.CP;
+        }
     } else {
         b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
         if (b.col_lb) {
@@ -517,7 +530,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid, ext.empty() ? nullptr : ext.data()));
     debug_sync(ctx, "tiler: plan_and_seed");
     // (a batch whose sweeps all store their labels never shares its pre-pass: the whole black pre-pass is there to run beside, as before)
-    if (!white && S.pf.b.d_feat && !S.pf.launched)
+    if (!white && S.pf.planned && !S.pf.launched)
         OBIA_TRY(prefetch_white_launch(ctx, S, OBIA_PREFETCH_BESIDE != 0 || b.exit_on_fixed_point || b.slic_zero));
     const Arena::Mark sweeps_mk = A.mark();   // a repeat of the sweeps reuses their workspace
     unsigned *const mask4 = b.d_mask4;        // (null: the sweeps pack the mask above the mark)
@@ -749,26 +762,30 @@ static int prefetch_white_plan(obia_ctx *ctx, TileState &S, int white_order) {
     const size_t NP = b.windows.size();
     if (NP == 0) return OBIA_OK;
     // too big to hold: per-batch features
-    if (slic_batch_layout(b) != OBIA_OK || (double)b.total_feat_f4 * 16.0 > 32.0 * 1024 * 1024 * 1024) return OBIA_OK;
+    if (slic_batch_layout(b) != OBIA_OK) return OBIA_OK;
+    pf.fused = slic_fuse_features(b, S.img, S.W);
+    if (!pf.fused && (double)b.total_feat_f4 * 16.0 > 32.0 * 1024 * 1024 * 1024) return OBIA_OK;
     Arena &A = ctx->arena;
     const size_t ntot = NP * (size_t)S.C * 2 + 2 * NP;
     b.d_windows = A.get<SrcWindow>(NP);
     pf.d_keys = A.get<unsigned>(ntot);
-    b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
-    if (!b.d_windows || !pf.d_keys || !b.d_feat) return OBIA_E_NOMEM;
+    if (!pf.fused) b.d_feat = A.get<float>(4 * (size_t)b.total_feat_f4);
+    if (!b.d_windows || !pf.d_keys || (!pf.fused && !b.d_feat)) return OBIA_E_NOMEM;
     if (b.col_lb) {
         b.d_fbox = A.get<float>((size_t)b.total_boxes * 2 * b.CP);
         if (!b.d_fbox) return OBIA_E_NOMEM;
     }
     pf.host.resize(ntot);
     pf.b = std::move(b);
+    pf.planned = true;
     return OBIA_OK;
 }
 
 static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside) {
     TileState::PreFeat &pf = S.pf;
-    if (pf.launched || !pf.b.d_feat) return OBIA_OK;
+    if (pf.launched || !pf.planned) return OBIA_OK;
     pf.launched = true;
+    if (pf.fused) beside = false;   // (the side stream stays for the unfused batches that have it: exit_on_fixed_point, SLIC-zero)
     OBIA_TRY(upload_async(ctx, pf.b.d_windows, pf.b.windows.data(), sizeof(SrcWindow) * pf.b.windows.size()));
     if (beside) {
         // `beside`: on a side stream, forked here and joined in prefetch_white_fetch -- the caller queues the black batch's
@@ -777,18 +794,18 @@ static int prefetch_white_launch(obia_ctx *ctx, TileState &S, bool beside) {
         hipStream_t side = ctx->side;
         OBIA_HIP_TRY(hipEventRecord(ctx->aux_fork, ctx->stream));
         OBIA_HIP_TRY(hipStreamWaitEvent(side, ctx->aux_fork, 0));
-        OBIA_TRY(slic_features_launch(side, pf.b, S.img, S.W, pf.d_keys));
+        OBIA_TRY(slic_features_launch(side, pf.b, S.img, S.W, pf.d_keys, nullptr, false));
         OBIA_HIP_TRY(hipEventRecord(ctx->aux_join, side));
         pf.on_side = true;
         return OBIA_OK;
     }
     ScopedSpan span(ctx, T_FEAT);
-    OBIA_TRY(slic_features_launch(ctx->stream, pf.b, S.img, S.W, pf.d_keys));
+    OBIA_TRY(slic_features_launch(ctx->stream, pf.b, S.img, S.W, pf.d_keys, nullptr, pf.fused));
     return OBIA_OK;
 }
 
 static int prefetch_white_fetch(obia_ctx *ctx, TileState &S) {
-    if (!S.pf.b.d_feat) return OBIA_OK;
+    if (!S.pf.planned) return OBIA_OK;
     OBIA_TRY(prefetch_white_launch(ctx, S));
     if (S.pf.on_side) { OBIA_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0)); S.pf.on_side = false; }
     OBIA_TRY(read_back(ctx, S.pf.host.data(), S.pf.d_keys, S.pf.host.size() * sizeof(unsigned)));
