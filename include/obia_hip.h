@@ -19,6 +19,14 @@
  *     Functions without the suffix take HOST pointers and do H2D / D2H themselves.
  *   - images are (H, W, C) float32, band-interleaved, C-contiguous -- the layout of
  *     obia.handlers.geotif.Image.img_data (geotif.py:100, tiling.py:47).  Labels are int32.
+ *   - alignment: a buffer only has to be aligned to its ELEMENT (4 bytes for float32 / int32, 8 for float64 / int64, 1 for
+ *     uint8 masks), so a contiguous view at any element offset of an allocation -- `flat[1:]`, a row slab `img[r0:r1]` -- is
+ *     a valid argument, for inputs and outputs alike, and gives the result the aligned buffer gives (the wide-load kernels
+ *     are chosen per call from the pointers; tests/test_gpu_pointer_alignment.py, DESIGN.md "Buffer alignment").  The
+ *     exceptions say so where they are declared and need 16 bytes: `hwc8` of obia_cost_bands_f32_dev, `plane` of
+ *     obia_cost_select_dev and the flag plane of obia_seeds_peaks_dev / obia_seeds_peaks_gather_dev; they refuse a
+ *     misaligned pointer with OBIA_E_INVALID before anything is launched.  The Python side never sends one: obia_amd.cost
+ *     copies a misaligned raster or plane to an aligned buffer first, and obia_amd.seeds allocates the flag plane itself.
  */
 #ifndef OBIA_HIP_H
 #define OBIA_HIP_H
@@ -278,7 +286,8 @@ int obia_sample_labels_i32_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, i
  *                              and 1 - ndvi(R, N1), float32, in one pass.
  * obia_cost_ndvi_f32_dev     : clip((nir - red) / (nir + red + 1e-9), -1, 1), float32.
  * obia_cost_sobel_f32_dev    : hypot(sobel(chm, axis=1), sobel(chm, axis=0)), mode "nearest", float32.
- * obia_cost_select_dev       : exact order statistics of the non-NaN values of a float32 (is_f64 = 0) or float64 plane:
+ * obia_cost_select_dev       : exact order statistics of the non-NaN values of a float32 (is_f64 = 0) or float64 plane
+ *                              (16-byte aligned):
  *                              n_valid_out and bits4_out (HOST) = the float's bits of the values of rank floor(v), floor(v)+1
  *                              at v = (n_valid - 1) * q_lo, then at q_hi (both neighbours are the last value when v >= n_valid
  *                              - 1); np.nanpercentile's interpolation is left to the caller.  1 <= n < 2^32.

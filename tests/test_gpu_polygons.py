@@ -30,6 +30,13 @@ def oracle_grouped(lab, start_label):
 @pytest.mark.parametrize("case", ["rect", "donut", "diag", "inv", "salt", "border"])
 def test_rings_equal_the_oracle_on_small_maps(case):
     from obia_amd.polygons import polygonize
+    lab, start = small_map(case)
+    tab = polygonize(lab, start_label=start)
+    assert rings_as_tuples(tab) == oracle_grouped(lab, start)
+
+
+def small_map(case):
+    """(labels, start_label) of the small maps above"""
     rs = np.random.RandomState(11)
     if case == "rect":
         lab = np.zeros((4, 5), np.int32); lab[1:3, 1:4] = 7
@@ -43,9 +50,7 @@ def test_rings_equal_the_oracle_on_small_maps(case):
         lab = rs.randint(-1, 4, (37, 53)).astype(np.int32)
     else:
         lab = np.full((70, 130), 5, np.int32); lab[10:60, 10:120] = 6; lab[20:30, 20:30] = 5; lab[69, 129] = -1
-    start = 0 if case == "salt" else 1
-    tab = polygonize(lab, start_label=start)
-    assert rings_as_tuples(tab) == oracle_grouped(lab, start)
+    return lab, 0 if case == "salt" else 1
 
 
 @pytest.mark.parametrize("name", ["c2s_256x256x4_c10", "mask_128x160x4_c10", "ragged_200x333x5"])

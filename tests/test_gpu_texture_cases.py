@@ -72,17 +72,21 @@ def test_nan_subsets_16_bands_start0_out_of_range():
     check(raw, lab + 1, bands=[15, 3, 5, 0], n_labels=n + 7)
 
 
-@pytest.mark.parametrize("hw", [(64, 64), (1, 4096), (4096, 1), (17, 241), (1, 4097), (4097, 1), (65, 63)])
-def test_bbox_4096_4097(hw):
-    """Bounding boxes of exactly 4096 pixels (LDS path) and 4097 (dense path), as squares and strips."""
-    h, w = hw
+def bbox_inputs(h, w):
+    """(raw, labels): label 1 fills an h x w box, with a hole row of another label inside it"""
     rs = np.random.RandomState(h * 7 + w)
     raw = rs.uniform(0, 1000, (h + 4, w + 4, 2)).astype(np.float32)
     lab = np.zeros((h + 4, w + 4), np.int32)
     lab[2:2 + h, 2:2 + w] = 1
     lab[2 + h // 2, 2:2 + w] = 2 if h > 2 else 1            # a hole row (another label) inside the box
     lab[0, 0] = 3
-    check(raw, lab)
+    return raw, lab
+
+
+@pytest.mark.parametrize("hw", [(64, 64), (1, 4096), (4096, 1), (17, 241), (1, 4097), (4097, 1), (65, 63)])
+def test_bbox_4096_4097(hw):
+    """Bounding boxes of exactly 4096 pixels (LDS path) and 4097 (dense path), as squares and strips."""
+    check(*bbox_inputs(*hw))
 
 
 def test_lds_table_sizes_full_of_noise():
@@ -129,7 +133,7 @@ def test_more_than_65536_labels_and_crowded_blocks():
     check(rs.uniform(0, 100, (200, 200, 1)).astype(np.float32), lab2)
 
 
-def test_thin_strips():
+def thin_strips_inputs():
     rs = np.random.RandomState(6)
     H, W = 40, 60
     raw = rs.uniform(0, 100, (H, W, 2)).astype(np.float32)
@@ -139,7 +143,11 @@ def test_thin_strips():
     lab[0, 5:] = 3                                          # h = 1
     lab[2:4, 5:] = 4                                        # h = 2
     lab[5:, 5:] = blocks(H - 5, W - 5, 7) + 4
-    check(raw, lab)
+    return raw, lab
+
+
+def test_thin_strips():
+    check(*thin_strips_inputs())
 
 
 @pytest.mark.parametrize("den", [1.0, 3.0, 7.0, 100.0, 255.0, 1000.0, 4095.0, 65535.0])
