@@ -27,6 +27,12 @@
  *     obia_cost_select_dev and the flag plane of obia_seeds_peaks_dev / obia_seeds_peaks_gather_dev; they refuse a
  *     misaligned pointer with OBIA_E_INVALID before anything is launched.  The Python side never sends one: obia_amd.cost
  *     copies a misaligned raster or plane to an aligned buffer first, and obia_amd.seeds allocates the flag plane itself.
+ *   - outputs: a call that returns OBIA_OK has written EVERY element of every non-null output buffer it documents -- the caller need
+ *     not clear them, and what they held before does not reach the result -- and has written nothing outside them and nothing to
+ *     its inputs.  The elements a call leaves as they were are named where the output is declared (rows at and above K of the stage
+ *     buffers, entries at and above the returned counts of the polygon buffers, `smooth_out` with sigma == 0); a refused call writes
+ *     nothing outside its outputs and promises nothing about their contents (tests/test_gpu_output_guards.py, DESIGN.md "Output
+ *     buffers").
  */
 #ifndef OBIA_HIP_H
 #define OBIA_HIP_H
@@ -172,7 +178,8 @@ int obia_mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, co
  *              are the centroids of sweep N and labels_pre the labels of sweep N; the sums are integers, so a run with another N
  *              reproduces the earlier sweeps exactly.  Needs max_num_iter >= 1.
  *   labels_pre (H, W) int32: labels before connectivity
- *   centroid_capacity  rows that seeds_yx / centroids hold (K above it is OBIA_E_INVALID; H * W always suffices)
+ *   centroid_capacity  rows that seeds_yx / centroids hold (K above it is OBIA_E_INVALID; H * W always suffices); rows at and above K
+ *              are not written
  *   prepass_only  1 with a mask: stop after the spatial-only pre-pass, so that centroids / labels_pre are those of its last sweep
  *              (sweep max_num_iter, or prepass_iters when that is given) (labels_pre: what that sweep assigns; the full run never stores them).  The centroids the colour pass
  *              starts from are `centroids` of a full run with max_num_iter = 1.
@@ -218,7 +225,9 @@ int obia_zonal_stats_f32_dev(obia_ctx *ctx, const float *raw_hwc, const int32_t 
  * bias=True, fisher=True; NaN for nearly constant data as scipy >= 1.9 does, with float32 eps).  Second pass over
  * (labels, raw) with the per-label means as pivots (central power sums in float64).
  *   var_out (may be NULL): receives the central m2 of this pass -- the variance about the first pass's mean, which
- *   replaces the first pass's variance (same value within float64 rounding, no shift conversions)
+ *   replaces the first pass's variance (same value within float64 rounding, no shift conversions) -- at EVERY entry: NaN
+ *   for an empty label and for a band without a valid pixel, like skew_out and kurt_out, so a fresh buffer is as good as
+ *   the first pass's table
  *   _dev : mean_dev = the mean table of obia_zonal_stats_f32_dev [n_labels*n_bands]; outputs on the device
  *   host : runs both passes itself; outputs [n_labels*n_bands] float64 on the host                              */
 int obia_zonal_moments_f32_dev(obia_ctx *ctx, const float *raw_hwc, const int32_t *labels_hw, int H, int W, int C,
@@ -239,7 +248,8 @@ int obia_zonal_moments_f32(obia_ctx *ctx, const float *raw_hwc, const int32_t *l
  *               direction changes; first vertex repeated at the end.  Map coordinates = affine * (x, y).
  *   ring_label  label of the ring; ring_is_hole 1 for an interior ring of that label.
  * Two calls: _count returns the sizes, _rings fills caller-allocated DEVICE buffers of at least that capacity
- * (ring_offset holds n_rings + 1 entries).  A label is one 4-connected component (the output of B1 / B3).          */
+ * (ring_offset holds n_rings + 1 entries; entries at and above the returned counts are not written, and a capacity below
+ * the count is OBIA_E_NOMEM before anything is written).  A label is one 4-connected component (the output of B1 / B3). */
 int obia_polygon_count_i32_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, int W, int start_label,
                                int64_t *n_rings_out, int64_t *n_vertices_out);
 int obia_polygon_rings_i32_dev(obia_ctx *ctx, const int32_t *labels_hw, int H, int W, int start_label,
@@ -497,7 +507,8 @@ int obia_seeds_pair_matrix_dev(obia_ctx *ctx, const double *xs, const double *ys
  *                        acceptable (n_rows, n_classes) uint8, nullable: 1 = the class is a candidate for that row (NULL: all).
  *                        Outputs, each nullable: proba_out (n_rows, n_classes) float64, never filtered; pred_out [n_rows] int32 =
  *                        the first maximum of proba over the candidates (-1 when there is none); margin_out [n_rows] float64 =
- *                        the largest minus the second largest candidate value (0 on a tie at the top).
+ *                        the largest minus the second largest candidate value (0 on a tie at the top); written for every row, its
+ *                        value unspecified for a row with fewer than two candidates.
  *                        More than 64 classes, 4096 features, 65536 trees or 2^31 - 1 nodes: OBIA_E_UNSUPPORTED.  A node whose
  *                        feature or children point outside [0, n_features) / its own tree: OBIA_E_INVALID (no walk follows it).
  * obia_forest: the trees' nodes one after the other.  left / right are indices within the node's OWN tree (scikit-learn's

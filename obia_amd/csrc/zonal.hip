@@ -480,6 +480,7 @@ __global__ void zonal_moments_finalize_kernel(const unsigned *__restrict__ g_n, 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const unsigned c = g_n[i];
         double sk = NAN, ku = NAN;
+        if (var && c == 0) var[i] = NAN;                               // no valid pixel: every entry of var_out is written
         if (c > 0) {
             const double m2 = g_s2[i] / (double)c, m3 = g_s3[i] / (double)c, m4 = g_s4[i] / (double)c;
             if (var) var[i] = m2;                                      // the central m2: the variance with no cancellation
