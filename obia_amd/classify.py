@@ -27,7 +27,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:
     import torch
@@ -43,10 +43,6 @@ _HIDDEN_ACTIVATIONS = ("identity", "relu", "tanh", "logistic")     # obia_mlp.hi
 _OUT_ACTIVATIONS = ("softmax", "logistic")                         # obia_mlp.out_activation
 SHAP_MAX_FEATURES = 16                                             # mlp_shap enumerates all 2^F coalitions
 _SHAP_VALUES_BYTES = 256 << 20                                     # mlp_shap: the (rows, 2^F, K) coalition values of one piece at most
-
-
-def _is_torch(x):
-    return torch is not None and isinstance(x, torch.Tensor)
 
 
 class Forest:
@@ -237,38 +233,27 @@ def standard_scale(table, ctx=None, dtype=np.float32):
     the mean and the two-pass variance; a column scikit-learn treats as constant gets scale 1; an all-NaN column stays NaN.
     ``dtype=np.float64``: the table without the cast, as ``MLPClassifier`` is handed it (obia_table_scale_f64_dev; ``mean`` and
     ``scale`` are the same bits).  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
+    _device.need_torch("obia_amd.classify")
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise ValueError("dtype must be numpy.float32 or numpy.float64")
-    is_t = _is_torch(table)
-    if is_t and not table.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
+    is_t = _device.is_torch(table)
+    dev = _device.device_of(ctx, table)
     shape = tuple(table.shape)
     if len(shape) != 2 or shape[1] == 0:
         raise ValueError("table must be (rows, features)")
     if shape[0] == 0:
         raise ValueError("the table has no rows")
-    lib = _lib.load()
-    if is_t:
-        t = table.to(torch.float64).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        t = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float64), device=f"cuda:{c0.device}")
-    dev = t.device.index or 0
-    c = ctx or _lib.default_context(dev)
+    t = _device.as_dev(table, torch.float64, dev)
     N, F = shape
     mean = torch.empty((F,), dtype=torch.float64, device=t.device)
     scale = torch.empty_like(mean)
     wide = dtype == np.dtype(np.float64)
     out = torch.empty((N, F), dtype=torch.float64 if wide else torch.float32, device=t.device)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     entry = lib.obia_table_scale_f64_dev if wide else lib.obia_table_scale_dev
     _lib.check(entry(c.handle, t.data_ptr(), N, F, mean.data_ptr(), scale.data_ptr(), out.data_ptr()))
-    if is_t:
-        return out, mean, scale
-    return out.cpu().numpy(), mean.cpu().numpy(), scale.cpu().numpy()
+    return _device.out((out, mean, scale), is_t)
 
 
 def _check_candidates(acceptable, n_rows, n_classes):
@@ -282,25 +267,15 @@ def _check_candidates(acceptable, n_rows, n_classes):
         raise ValueError(f"acceptable must be (rows, classes) = ({n_rows}, {n_classes}), got {tuple(acceptable.shape)}")
     few = (acceptable != 0).sum(1) < 2
     if bool(few.any()):
-        first = int(few.nonzero()[0][0]) if not _is_torch(few) else int(few.nonzero()[0, 0])
+        first = int(few.nonzero()[0][0]) if not _device.is_torch(few) else int(few.nonzero()[0, 0])
         raise ValueError(f"row {first} has fewer than two acceptable classes among classes_")
 
 
-def forest_predict(forest, X32, acceptable=None, ctx=None):
-    """Prediction of ``forest`` for every row of ``X32`` (N, F) float32: returns ``(pred, margin, proba)``.
-
-    ``proba`` (N, K) float64 is ``RandomForestClassifier.predict_proba`` bit for bit (leaf rows added in float64 in tree order,
-    divided by the number of trees), never filtered.  ``acceptable``: optional (N, K) boolean mask in ``classes_`` order;
-    ``pred`` (N,) int32 is the index into ``classes_`` of the first maximum of ``proba`` over the row's acceptable classes
-    (all classes without a mask), ``margin`` (N,) float64 the largest minus the second largest of those values.  A row with
-    fewer than two candidates raises ValueError.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
+def _check_forest_table(forest, X32, who):
+    """The argument checks :func:`forest_predict` and :func:`forest_shap` share; returns ``(is_torch, rows, columns)``."""
     if not isinstance(forest, Forest):
         raise TypeError("forest must be an obia_amd.classify.Forest (Forest.from_sklearn(rf))")
-    is_t = _is_torch(X32)
-    if is_t and not X32.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
+    _device.device_of(None, X32)                       # (a CPU tensor is refused here)
     shape = tuple(X32.shape)
     if len(shape) != 2:
         raise ValueError("X32 must be (rows, features)")
@@ -311,30 +286,40 @@ def forest_predict(forest, X32, acceptable=None, ctx=None):
         raise ValueError(f"the forest tests feature {forest.n_features - 1}, the table has {F} columns")
     K = forest.n_classes
     if K > MAX_CLASSES or F > MAX_FEATURES or forest.n_trees > MAX_TREES or forest.n_nodes >= 2 ** 31:
-        raise NotImplementedError(f"forest_predict supports at most {MAX_CLASSES} classes, {MAX_FEATURES} features, {MAX_TREES} trees "
+        raise NotImplementedError(f"{who} supports at most {MAX_CLASSES} classes, {MAX_FEATURES} features, {MAX_TREES} trees "
                                   f"and 2^31 - 1 nodes (got {K}, {F}, {forest.n_trees}, {forest.n_nodes})")
+    return _device.is_torch(X32), N, F
+
+
+def _forest_struct(forest, device):
+    d = forest._on(device)
+    return _lib.Forest(*(d[k].data_ptr() for k in ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset")),
+                       forest.tree_offset.ctypes.data, d["value"].data_ptr(), forest.n_nodes, forest.n_trees, forest.n_classes)
+
+
+def forest_predict(forest, X32, acceptable=None, ctx=None):
+    """Prediction of ``forest`` for every row of ``X32`` (N, F) float32: returns ``(pred, margin, proba)``.
+
+    ``proba`` (N, K) float64 is ``RandomForestClassifier.predict_proba`` bit for bit (leaf rows added in float64 in tree order,
+    divided by the number of trees), never filtered.  ``acceptable``: optional (N, K) boolean mask in ``classes_`` order;
+    ``pred`` (N,) int32 is the index into ``classes_`` of the first maximum of ``proba`` over the row's acceptable classes
+    (all classes without a mask), ``margin`` (N,) float64 the largest minus the second largest of those values.  A row with
+    fewer than two candidates raises ValueError.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    _device.need_torch("obia_amd.classify")
+    is_t, N, F = _check_forest_table(forest, X32, "forest_predict")
+    K = forest.n_classes
     _check_candidates(acceptable, N, K)
-    lib = _lib.load()
-    if is_t:
-        x = X32.to(torch.float32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        x = torch.as_tensor(np.ascontiguousarray(X32, dtype=np.float32), device=f"cuda:{c0.device}")
-    dev = x.device.index or 0
-    c = ctx or _lib.default_context(dev)
+    dev = _device.device_of(ctx, X32, acceptable)
+    x = _device.as_dev(X32, torch.float32, dev)
     mask = None if acceptable is None else _lib.mask_bytes(acceptable, device=x.device)
-    d = forest._on(x.device)
-    fs = _lib.Forest(*(d[k].data_ptr() for k in ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset")),
-                     forest.tree_offset.ctypes.data, d["value"].data_ptr(), forest.n_nodes, forest.n_trees, K)
+    fs = _forest_struct(forest, x.device)
     proba = torch.empty((N, K), dtype=torch.float64, device=x.device)
     pred = torch.empty((N,), dtype=torch.int32, device=x.device)
     margin = torch.empty((N,), dtype=torch.float64, device=x.device)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     _lib.check(lib.obia_forest_predict_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(fs), None if mask is None else mask.data_ptr(),
                                            proba.data_ptr(), pred.data_ptr(), margin.data_ptr()))
-    if is_t:
-        return pred, margin, proba
-    return pred.cpu().numpy(), margin.cpu().numpy(), proba.cpu().numpy()
+    return _device.out((pred, margin, proba), is_t)
 
 
 def forest_shap(forest, X32, ctx=None):
@@ -351,46 +336,20 @@ def forest_shap(forest, X32, ctx=None):
 
     The output takes N * F * K * 8 bytes: 1.9 GB for 489 480 x 96 x 5.  ``forest`` needs ``cover`` (``Forest.from_sklearn``
     fills it).  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
-    if not isinstance(forest, Forest):
-        raise TypeError("forest must be an obia_amd.classify.Forest (Forest.from_sklearn(rf))")
-    if forest.cover is None:
+    _device.need_torch("obia_amd.classify")
+    if isinstance(forest, Forest) and forest.cover is None:
         raise ValueError("forest_shap needs the nodes' cover: build the forest with Forest.from_sklearn(rf) or pass cover=")
-    is_t = _is_torch(X32)
-    if is_t and not X32.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
-    shape = tuple(X32.shape)
-    if len(shape) != 2:
-        raise ValueError("X32 must be (rows, features)")
-    N, F = shape
-    if N == 0:
-        raise ValueError("the table has no rows")
-    if F < forest.n_features:
-        raise ValueError(f"the forest tests feature {forest.n_features - 1}, the table has {F} columns")
+    is_t, N, F = _check_forest_table(forest, X32, "forest_shap")
     K = forest.n_classes
-    if K > MAX_CLASSES or F > MAX_FEATURES or forest.n_trees > MAX_TREES or forest.n_nodes >= 2 ** 31:
-        raise NotImplementedError(f"forest_shap supports at most {MAX_CLASSES} classes, {MAX_FEATURES} features, {MAX_TREES} trees "
-                                  f"and 2^31 - 1 nodes (got {K}, {F}, {forest.n_trees}, {forest.n_nodes})")
-    lib = _lib.load()
-    if is_t:
-        x = X32.to(torch.float32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        x = torch.as_tensor(np.ascontiguousarray(X32, dtype=np.float32), device=f"cuda:{c0.device}")
-    dev = x.device.index or 0
-    c = ctx or _lib.default_context(dev)
-    d = forest._on(x.device)
-    fs = _lib.Forest(*(d[k].data_ptr() for k in ("threshold", "feature", "left", "right", "missing_go_to_left", "tree_offset")),
-                     forest.tree_offset.ctypes.data, d["value"].data_ptr(), forest.n_nodes, forest.n_trees, K)
+    dev = _device.device_of(ctx, X32)
+    x = _device.as_dev(X32, torch.float32, dev)
+    fs = _forest_struct(forest, x.device)
     phi = torch.empty((N, F, K), dtype=torch.float64, device=x.device)
     base = torch.empty((K,), dtype=torch.float64, device=x.device)
-    torch.cuda.current_stream(dev).synchronize()
-    _lib.check(lib.obia_forest_shap_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(fs), forest._cover_on(x.device).data_ptr(),
-                                        phi.data_ptr(), base.data_ptr()))
-    if is_t:
-        return phi, base
-    return phi.cpu().numpy(), base.cpu().numpy()
+    cover = forest._cover_on(x.device)
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_forest_shap_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(fs), cover.data_ptr(), phi.data_ptr(), base.data_ptr()))
+    return _device.out((phi, base), is_t)
 
 
 def _mlp_plan(layer_sizes):
@@ -412,13 +371,11 @@ def mlp_predict(mlp, X, acceptable=None, ctx=None, _logits=False):
     place of 1.  ``acceptable`` / ``pred`` / ``margin``: as in :func:`forest_predict`.  A NaN or an infinity in ``X`` raises
     ValueError, as scikit-learn does.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  ``_logits=True`` appends the
     last layer before its activation, (N, n_out) (test hook)."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
+    _device.need_torch("obia_amd.classify")
     if not isinstance(mlp, MLP):
         raise TypeError("mlp must be an obia_amd.classify.MLP (MLP.from_sklearn(clf))")
-    is_t = _is_torch(X)
-    if is_t and not X.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
+    is_t = _device.is_torch(X)
+    _device.device_of(None, X)                         # (a CPU tensor is refused here)
     shape = tuple(X.shape)
     if len(shape) != 2:
         raise ValueError("X must be (rows, features)")
@@ -432,36 +389,25 @@ def mlp_predict(mlp, X, acceptable=None, ctx=None, _logits=False):
         raise NotImplementedError(f"mlp_predict supports at most {MLP_MAX_LAYERS} weight matrices, {MAX_FEATURES} features, {MAX_CLASSES} "
                                   f"classes and {MLP_MAX_WIDTH} units in a hidden layer (layer sizes {ls.tolist()}, {K} classes)")
     _check_candidates(acceptable, N, K)
-    lib = _lib.load()
-    if is_t:
-        x = X.to(torch.float64).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device=f"cuda:{c0.device}")
-    dev = x.device.index or 0
-    c = ctx or _lib.default_context(dev)
+    dev = _device.device_of(ctx, X, acceptable)
+    x = _device.as_dev(X, torch.float64, dev)
     mask = None if acceptable is None else _lib.mask_bytes(acceptable, device=x.device)
-    d = mlp._on(x.device)
-    ms = _lib.Mlp(d["weights"].data_ptr(), d["biases"].data_ptr(), ls.ctypes.data, mlp.n_layers,
-                  _HIDDEN_ACTIVATIONS.index(mlp.hidden_activation), _OUT_ACTIVATIONS.index(mlp.out_activation), K)
+    ms = _mlp_struct(mlp, x.device)
     proba = torch.empty((N, K), dtype=torch.float64, device=x.device)
     pred = torch.empty((N,), dtype=torch.int32, device=x.device)
     margin = torch.empty((N,), dtype=torch.float64, device=x.device)
     logits = torch.empty((N, int(ls[-1])), dtype=torch.float64, device=x.device) if _logits else None
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     _lib.check(lib.obia_mlp_predict_dev(c.handle, x.data_ptr(), N, F, ctypes.byref(ms), None if mask is None else mask.data_ptr(),
                                         proba.data_ptr(), pred.data_ptr(), margin.data_ptr(), None if logits is None else logits.data_ptr()))
-    out = (pred, margin, proba) + ((logits,) if _logits else ())
-    return out if is_t else tuple(t.cpu().numpy() for t in out)
+    return _device.out((pred, margin, proba) + ((logits,) if _logits else ()), is_t)
 
 
 def _check_mlp_table(mlp, X, name, who):
     """The argument checks of :func:`mlp_predict` for one table; returns ``(is_torch, rows)``."""
     if not isinstance(mlp, MLP):
         raise TypeError("mlp must be an obia_amd.classify.MLP (MLP.from_sklearn(clf))")
-    is_t = _is_torch(X)
-    if is_t and not X.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
+    _device.device_of(None, X)                         # (a CPU tensor is refused here)
     shape = tuple(X.shape)
     if len(shape) != 2:
         raise ValueError(f"{name} must be (rows, features)")
@@ -471,7 +417,7 @@ def _check_mlp_table(mlp, X, name, who):
     if mlp.n_layers > MLP_MAX_LAYERS or shape[1] > MAX_FEATURES or K > MAX_CLASSES or (mlp.n_layers > 1 and int(ls[1:-1].max()) > MLP_MAX_WIDTH):
         raise NotImplementedError(f"{who} supports at most {MLP_MAX_LAYERS} weight matrices, {MAX_FEATURES} features, {MAX_CLASSES} "
                                   f"classes and {MLP_MAX_WIDTH} units in a hidden layer (layer sizes {ls.tolist()}, {K} classes)")
-    return is_t, shape[0]
+    return _device.is_torch(X), shape[0]
 
 
 def _mlp_struct(mlp, device):
@@ -480,28 +426,17 @@ def _mlp_struct(mlp, device):
                     _HIDDEN_ACTIVATIONS.index(mlp.hidden_activation), _OUT_ACTIVATIONS.index(mlp.out_activation), mlp.n_classes)
 
 
-def _coalition_inputs(mlp, X, background, who, ctx):
-    """Checks both tables (before the library is loaded), loads it and puts them on one device: ``(x, bg, context, is_torch)``."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
+def _coalition_inputs(mlp, X, background, who, ctx, masks=None):
+    """Checks both tables (before the library is loaded) and puts them on one device: ``(x, bg, device index, is_torch)``."""
+    _device.need_torch("obia_amd.classify")
     is_t, N = _check_mlp_table(mlp, X, "X", who)
-    bg_t, B = _check_mlp_table(mlp, background, "background", who)
+    _, B = _check_mlp_table(mlp, background, "background", who)
     if N == 0:
         raise ValueError("the table has no rows")
     if B == 0:
         raise ValueError("the background has no rows")
-    _lib.load()
-    if is_t:
-        x = X.to(torch.float64).contiguous()
-        device = x.device
-    else:
-        device = background.device if bg_t else torch.device(f"cuda:{(ctx or _lib.default_context(0)).device}")
-        x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device=device)
-    if bg_t:
-        bg = background.to(device=device, dtype=torch.float64).contiguous()
-    else:
-        bg = torch.as_tensor(np.ascontiguousarray(background, dtype=np.float64), device=device)
-    return x, bg, ctx or _lib.default_context(device.index or 0), is_t
+    dev = _device.device_of(ctx, X, background, masks)
+    return _device.as_dev(X, torch.float64, dev), _device.as_dev(background, torch.float64, dev), dev, is_t
 
 
 def mlp_coalition_values(mlp, X, background, masks, ctx=None):
@@ -515,21 +450,20 @@ def mlp_coalition_values(mlp, X, background, masks, ctx=None):
     by B; the empty and the full mask follow the same rule.  This is the game whose Shapley values :func:`mlp_shap` returns, and
     what a sampled KernelSHAP for wider tables would evaluate.  A NaN or an infinity in ``X`` or ``background`` raises
     ValueError.  The limits of :func:`mlp_predict`; B >= 1, M >= 1.  NumPy in -> NumPy out, CUDA tensor ``X`` in -> CUDA tensor out."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
-    if not _is_torch(masks):
+    _device.need_torch("obia_amd.classify")
+    if not _device.is_torch(masks):
         masks = np.asarray(masks)
     if isinstance(mlp, MLP) and (len(tuple(masks.shape)) != 2 or masks.shape[1] != mlp.n_features or masks.shape[0] == 0):
         raise ValueError(f"masks must be (coalitions, features) = (M >= 1, {mlp.n_features}), got {tuple(masks.shape)}")
-    x, bg, c, is_t = _coalition_inputs(mlp, X, background, "mlp_coalition_values", ctx)
+    x, bg, dev, is_t = _coalition_inputs(mlp, X, background, "mlp_coalition_values", ctx, masks)
     mk = _lib.mask_bytes(masks, device=x.device)
     N, M, K = x.shape[0], mk.shape[0], mlp.n_classes
     values = torch.empty((N, M, K), dtype=torch.float64, device=x.device)
     ms = _mlp_struct(mlp, x.device)
-    torch.cuda.current_stream(x.device.index or 0).synchronize()
-    _lib.check(_lib.load().obia_mlp_coalition_dev(c.handle, x.data_ptr(), N, x.shape[1], ctypes.byref(ms), bg.data_ptr(), bg.shape[0],
-                                                  mk.data_ptr(), M, values.data_ptr()))
-    return values if is_t else values.cpu().numpy()
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_mlp_coalition_dev(c.handle, x.data_ptr(), N, x.shape[1], ctypes.byref(ms), bg.data_ptr(), bg.shape[0], mk.data_ptr(), M,
+                                          values.data_ptr()))
+    return _device.out(values, is_t)
 
 
 def _check_shap_width(mlp):
@@ -557,11 +491,9 @@ def shapley_combine(values, ctx=None):
     ``w[s] = s! (F - 1 - s)! / F!`` rounded correctly from the rational.  The coalitions are taken in ascending m from 0.0; every
     difference, product and sum is rounded on its own, so two calls agree bit for bit.  F <= 16.  NumPy in -> NumPy out, CUDA
     tensor in -> CUDA tensor out."""
-    if torch is None:
-        raise ImportError("obia_amd.classify needs torch for device memory")
-    is_t = _is_torch(values)
-    if is_t and not values.is_cuda:
-        raise ValueError("torch inputs must live on the GPU")
+    _device.need_torch("obia_amd.classify")
+    is_t = _device.is_torch(values)
+    dev = _device.device_of(ctx, values)
     shape = tuple(values.shape)
     if len(shape) != 3 or shape[1] < 2 or shape[1] & (shape[1] - 1) or shape[2] == 0:
         raise ValueError("values must be (rows, 2^F coalitions, classes) with F >= 1")
@@ -571,18 +503,11 @@ def shapley_combine(values, ctx=None):
         raise ValueError("the table has no rows")
     if F > SHAP_MAX_FEATURES or K > MAX_CLASSES:
         raise NotImplementedError(f"shapley_combine supports at most {SHAP_MAX_FEATURES} features and {MAX_CLASSES} classes (got {F}, {K})")
-    lib = _lib.load()
-    if is_t:
-        v = values.to(torch.float64).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        v = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float64), device=f"cuda:{c0.device}")
-    dev = v.device.index or 0
-    c = ctx or _lib.default_context(dev)
+    v = _device.as_dev(values, torch.float64, dev)
     phi = torch.empty((N, F, K), dtype=torch.float64, device=v.device)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     _combine(lib, c, v, F, K, phi)
-    return phi if is_t else phi.cpu().numpy()
+    return _device.out(phi, is_t)
 
 
 def mlp_shap(mlp, X, background, ctx=None):
@@ -599,8 +524,7 @@ def mlp_shap(mlp, X, background, ctx=None):
     that the coalition values stay under ``_SHAP_VALUES_BYTES``; a row's result does not depend on the piece it fell in.
     The work is N * 2^F * B forward passes.  NumPy in -> NumPy out, CUDA tensor ``X`` in -> CUDA tensors out."""
     _check_shap_width(mlp)
-    x, bg, c, is_t = _coalition_inputs(mlp, X, background, "mlp_shap", ctx)
-    lib = _lib.load()
+    x, bg, dev, is_t = _coalition_inputs(mlp, X, background, "mlp_shap", ctx)
     N, F = x.shape
     K, M = mlp.n_classes, 1 << F
     rows = max(1, min(N, _SHAP_VALUES_BYTES // (M * K * 8)))
@@ -608,7 +532,7 @@ def mlp_shap(mlp, X, background, ctx=None):
     phi = torch.empty((N, F, K), dtype=torch.float64, device=x.device)
     base = None
     ms = _mlp_struct(mlp, x.device)
-    torch.cuda.current_stream(x.device.index or 0).synchronize()
+    lib, c = _device.begin(dev, ctx)
     for r0 in range(0, N, rows):
         n = min(rows, N - r0)
         _lib.check(lib.obia_mlp_coalition_dev(c.handle, x[r0:r0 + n].data_ptr(), n, F, ctypes.byref(ms), bg.data_ptr(), bg.shape[0], None, M,
@@ -616,8 +540,8 @@ def mlp_shap(mlp, X, background, ctx=None):
         _combine(lib, c, values, F, K, phi[r0:r0 + n])
         if base is None:
             base = values[0, 0].clone()                # the empty coalition does not depend on the row
-            torch.cuda.current_stream(x.device.index or 0).synchronize()   # copied before the next piece overwrites it
-    return (phi, base) if is_t else (phi.cpu().numpy(), base.cpu().numpy())
+            torch.cuda.current_stream(dev).synchronize()   # copied before the next piece overwrites it
+    return _device.out((phi, base), is_t)
 
 
 class ClassifiedImage:
@@ -639,8 +563,7 @@ class ClassifiedImage:
         """Class per pixel: a gather of ``predicted_class`` through the label raster.  The table's rows are the labels that
         exist, in ascending order (as create_objects numbers them); pixels below ``start_label`` get ``fill``.  Classes must be
         integers.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out (int32)."""
-        if torch is None:
-            raise ImportError("obia_amd.classify needs torch for device memory")
+        _device.need_torch("obia_amd.classify")
         cls = np.asarray(self.classified["predicted_class"])
         try:
             cls_i = cls.astype(np.int64)
@@ -649,11 +572,8 @@ class ClassifiedImage:
             exact = False
         if not exact or (cls_i.size and (cls_i.min() < -2 ** 31 or cls_i.max() >= 2 ** 31)):
             raise ValueError("to_raster needs integer classes that fit int32")
-        is_t = _is_torch(labels)
-        if is_t:
-            lab = labels.to(torch.int64)
-        else:
-            lab = torch.as_tensor(np.ascontiguousarray(labels), device=f"cuda:{_lib.default_context(0).device}").to(torch.int64)
+        is_t = _device.is_torch(labels)
+        lab = _device.as_dev(labels, torch.int64, _device.device_of(None, labels))
         valid = lab >= start_label
         present = torch.unique(lab[valid])
         if present.numel() != len(cls_i):
@@ -662,7 +582,7 @@ class ClassifiedImage:
         lut = torch.full((n + 1,), int(fill), dtype=torch.int32, device=lab.device)       # (last entry: pixels below start_label)
         lut[present - start_label] = torch.as_tensor(cls_i, device=lab.device).to(torch.int32)
         out = lut[torch.where(valid, lab - start_label, torch.full_like(lab, n))]
-        return out if is_t else out.cpu().numpy()
+        return _device.out(out, is_t)
 
 
 def _zone_wkb(geom):
@@ -694,7 +614,7 @@ def acceptable_mask(acceptable_classes_gdf, classes_, labels, affine_transformat
     nz = len(geoms)
     if nz >= 2 ** 24:
         raise NotImplementedError("2^24 or more zones are not supported")
-    lab = labels if _is_torch(labels) else np.asarray(labels)
+    lab = labels if _device.is_torch(labels) else np.asarray(labels)
     H, W = (int(v) for v in lab.shape)
     classes_ = np.asarray(classes_)
     zone_rows = np.stack([np.isin(classes_, np.asarray(list(w))) for w in wanted]) if nz else np.zeros((0, len(classes_)), bool)
@@ -703,7 +623,7 @@ def acceptable_mask(acceptable_classes_gdf, classes_, labels, affine_transformat
                    values=order.astype(np.int32), fill=-1, ctx=ctx, as_tensor=True)
     plane = zr.to(torch.float32)
     plane[zr < 0] = float("nan")                       # zonal_stats drops NaN pixels: no zone here
-    lab_t = lab if _is_torch(lab) else torch.as_tensor(np.ascontiguousarray(lab, dtype=np.int32), device=zr.device)
+    lab_t = lab if _device.is_torch(lab) else torch.as_tensor(np.ascontiguousarray(lab, dtype=np.int32), device=zr.device)
     st = zonal_stats(plane[:, :, None].contiguous(), lab_t, start_label=start_label, ctx=ctx)
     present = (st["count"] > 0).cpu().numpy()
     zone = st["min"][:, 0].cpu().numpy()[present]

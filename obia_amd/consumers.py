@@ -7,7 +7,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:
     import torch
@@ -32,22 +32,14 @@ def slic_edge(label_img, ctx=None):
     percentile, rescale, NaN -> 0): on a 0/1 image the percentiles follow from the number of edge pixels, which the
     kernel returns with the raster (obia_label_edges_u8_dev).  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out.
     """
-    if torch is None:
-        raise ImportError("obia_amd.consumers needs torch for device memory")
-    lib = _lib.load()
-    is_t = isinstance(label_img, torch.Tensor)
-    if is_t:
-        if not label_img.is_cuda:
-            raise ValueError("torch inputs must live on the GPU")
-        lab = label_img.to(torch.int32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        lab = torch.as_tensor(np.ascontiguousarray(label_img, dtype=np.int32), device=f"cuda:{c0.device}")
+    _device.need_torch("obia_amd.consumers")
+    is_t = _device.is_torch(label_img)
+    dev = _device.device_of(ctx, label_img)
+    lab = _device.as_dev(label_img, torch.int32, dev)
     if lab.dim() != 2:
         raise ValueError("label_img must be (H, W)")
     H, W = lab.shape
-    c = ctx or _lib.default_context(lab.device.index or 0)
-    torch.cuda.current_stream(lab.device.index or 0).synchronize()
+    lib, c = _device.begin(dev, ctx)
     edge = torch.empty((H, W), dtype=torch.uint8, device=lab.device)
     n_edge = ctypes.c_int64(0)
     _lib.check(lib.obia_label_edges_u8_dev(c.handle, lab.data_ptr(), H, W, edge.data_ptr(), ctypes.byref(n_edge)))
@@ -59,12 +51,13 @@ def slic_edge(label_img, ctx=None):
         out = torch.zeros_like(e)                         # (x - lo) / 0 -> NaN -> 0 (np.nan_to_num)
     else:
         out = (e.clamp(lo, hi) - lo) / (hi - lo)
-    return out if is_t else out.cpu().numpy()
+    return _device.out(out, is_t)
 
 
 def invert_affine(affine_transformation):
     """Inverse of the reference's ``image.affine_transformation`` [a, b, d, e, xoff, yoff] (x' = a x + b y + xoff,
-    y' = d x + e y + yoff), in the same layout."""
+    y' = d x + e y + yoff), in the same layout: what obia_sample_labels_i32_dev takes.  Not :func:`obia_amd.seeds.invert_affine`,
+    which returns the affine package's (a, b, c, d, e, f) and rounds as that package does (``e * (1 / det)``, here ``e / det``)."""
     a, b, d, e, xoff, yoff = [float(v) for v in affine_transformation]
     det = a * e - b * d
     if det == 0.0:
@@ -76,22 +69,16 @@ def invert_affine(affine_transformation):
 def sample_labels(labels, affine_transformation, points_xy, outside=-1, ctx=None):
     """Label under every point: map coordinates -> pixel (floor of the pixel-corner coordinates) -> label; ``outside``
     for points that fall off the raster.  labels: (H, W) NumPy or CUDA tensor; points_xy: (n, 2) map coordinates."""
-    if torch is None:
-        raise ImportError("obia_amd.consumers needs torch for device memory")
-    lib = _lib.load()
-    if isinstance(labels, torch.Tensor):
-        lab = labels.to(torch.int32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        lab = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32), device=f"cuda:{c0.device}")
+    _device.need_torch("obia_amd.consumers")
+    dev = _device.device_of(ctx, labels)
+    lab = _device.as_dev(labels, torch.int32, dev)
     H, W = lab.shape
     pts = np.ascontiguousarray(points_xy, dtype=np.float64).reshape(-1, 2)
     n = pts.shape[0]
-    c = ctx or _lib.default_context(lab.device.index or 0)
     d_pts = torch.as_tensor(pts, device=lab.device)
     out = torch.full((max(n, 1),), int(outside), dtype=torch.int32, device=lab.device)
     inv = (ctypes.c_double * 6)(*invert_affine(affine_transformation))
-    torch.cuda.current_stream(lab.device.index or 0).synchronize()
+    lib, c = _device.begin(dev, ctx)
     _lib.check(lib.obia_sample_labels_i32_dev(c.handle, lab.data_ptr(), H, W, inv, d_pts.data_ptr(), n, int(outside),
                                               out.data_ptr()))
     return out[:n].cpu().numpy()

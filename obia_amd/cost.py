@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:
     import torch
@@ -29,21 +29,11 @@ _TCOLS = 32
 
 
 def _need_torch():
-    if torch is None:
-        raise ImportError("obia_amd.cost needs torch for device memory")
+    _device.need_torch("obia_amd.cost")
 
 
 def _is_path(x):
     return isinstance(x, (str, bytes, os.PathLike))
-
-
-def _device_of(ctx, *xs):
-    for x in xs:
-        if torch is not None and isinstance(x, torch.Tensor):
-            if not x.is_cuda:
-                raise ValueError("torch inputs must live on the GPU")
-            return x.device.index or 0
-    return ctx.device if ctx is not None else 0
 
 
 def _shape(x):
@@ -52,25 +42,7 @@ def _shape(x):
 
 def _as_dev(x, dtype, dev):
     """Contiguous, 16-byte aligned device tensor of ``dtype`` (NumPy's astype for other dtypes)."""
-    if isinstance(x, torch.Tensor):
-        t = x.to(device=f"cuda:{dev}", dtype=dtype).contiguous()
-    else:
-        npdt = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32}[dtype]
-        t = torch.as_tensor(np.ascontiguousarray(np.asarray(x).astype(npdt, copy=False)), device=f"cuda:{dev}")
-    if t.data_ptr() % 16:
-        t = t.clone()
-    return t
-
-
-def _begin(dev, ctx):
-    lib = _lib.load()
-    c = ctx or _lib.default_context(dev)
-    torch.cuda.current_stream(dev).synchronize()     # inputs written by torch are complete before the context's stream reads them
-    return lib, c
-
-
-def _end(lib, c):
-    _lib.check(lib.obia_synchronize(c.handle))       # outputs are complete before torch (or the host) sees them
+    return _device.as_dev(x, dtype, dev, align16=True)
 
 
 def _lerp(n, a, b, dtype):
@@ -147,7 +119,7 @@ def _plane(x, dev, name):
 
 def _float_plane(x, dev):
     """float32 / float64 planes are kept as they are; any other dtype is cast to float32."""
-    if isinstance(x, torch.Tensor):
+    if _device.is_torch(x):
         dt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
     else:
         dt = torch.float64 if np.asarray(x).dtype == np.float64 else torch.float32
@@ -164,23 +136,19 @@ def _normalise_dev(lib, c, plane):
     return out
 
 
-def _out(t, is_t):
-    return t if is_t else t.cpu().numpy()
-
-
 def normalise(arr, ctx=None):
     """np.nan_to_num((np.clip(arr, lo, hi) - lo) / (hi - lo)) with lo, hi = np.nanpercentile(arr, (2, 98)): float64 out for
     a float32 or float64 plane (other dtypes are taken as float32).  Constant or all-NaN input gives zeros."""
     _need_torch()
-    is_t = isinstance(arr, torch.Tensor)
-    dev = _device_of(ctx, arr)
+    is_t = _device.is_torch(arr)
+    dev = _device.device_of(ctx, arr)
     x = _float_plane(arr, dev)
     if x.numel() == 0:
         raise ValueError("normalise of an empty array")
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     out = _normalise_dev(lib, c, x)
-    _end(lib, c)
-    return _out(out.reshape(_shape(arr)), is_t)
+    _device.end(lib, c)
+    return _device.out(out.reshape(_shape(arr)), is_t)
 
 
 def _sobel_dev(lib, c, chm):
@@ -195,16 +163,16 @@ def chm_gradient(chm, ctx=None, _raw=False):
     spoil their 3 x 3 neighbourhood and end as 0.  ``_raw=True`` returns the float32 hypot plane before normalise."""
     _need_torch()
     chm = _plane(chm, None, "chm")
-    is_t = isinstance(chm, torch.Tensor)
+    is_t = _device.is_torch(chm)
     if 0 in _shape(chm):
         raise ValueError("chm is empty")
-    dev = _device_of(ctx, chm)
+    dev = _device.device_of(ctx, chm)
     x = _as_dev(chm, torch.float32, dev)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     g = _sobel_dev(lib, c, x)
     out = g if _raw else _normalise_dev(lib, c, g)
-    _end(lib, c)
-    return _out(out, is_t)
+    _device.end(lib, c)
+    return _device.out(out, is_t)
 
 
 def ndvi(red, nir, ctx=None):
@@ -212,15 +180,15 @@ def ndvi(red, nir, ctx=None):
     _need_torch()
     if _shape(red) != _shape(nir):
         raise ValueError(f"red and nir differ in shape: {_shape(red)} vs {_shape(nir)}")
-    is_t = isinstance(red, torch.Tensor) or isinstance(nir, torch.Tensor)
-    dev = _device_of(ctx, red, nir)
+    is_t = _device.is_torch(red) or _device.is_torch(nir)
+    dev = _device.device_of(ctx, red, nir)
     r, n = _as_dev(red, torch.float32, dev), _as_dev(nir, torch.float32, dev)
     out = torch.empty(r.shape, dtype=torch.float32, device=r.device)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     if r.numel():
         _lib.check(lib.obia_cost_ndvi_f32_dev(c.handle, r.data_ptr(), n.data_ptr(), r.numel(), out.data_ptr()))
-    _end(lib, c)
-    return _out(out, is_t)
+    _device.end(lib, c)
+    return _device.out(out, is_t)
 
 
 def _entropy_dev(lib, c, pan, lo, hi):
@@ -237,17 +205,17 @@ def texture_entropy(pan, ctx=None, _raw=False):
     normalise."""
     _need_torch()
     pan = _plane(pan, None, "pan")
-    is_t = isinstance(pan, torch.Tensor)
+    is_t = _device.is_torch(pan)
     if 0 in _shape(pan):
         raise ValueError("pan is empty")
-    dev = _device_of(ctx, pan)
+    dev = _device.device_of(ctx, pan)
     x = _as_dev(pan, torch.float32, dev)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     lo, hi, _ = _select(lib, c, x)
     e = _entropy_dev(lib, c, x, lo, hi)
     out = e if _raw else _normalise_dev(lib, c, e)
-    _end(lib, c)
-    return _out(out, is_t)
+    _device.end(lib, c)
+    return _device.out(out, is_t)
 
 
 # ------------------------------------------------------------------------------------------- segments.gpkg -> label raster
@@ -419,13 +387,13 @@ def make_cost_surface(wv3, chm, out=None, slic=None, weights=(0.5, 0.25, 0.25, 0
         raise ValueError(f"slic shape {_shape(slic)} does not match the raster's {(H, W)}")
     if slic is None:
         warnings.warn("No SLIC provided – cost built from 3 terms only.")
-    is_t = isinstance(wv3, torch.Tensor)
-    dev = _device_of(ctx, wv3, chm, slic)
+    is_t = _device.is_torch(wv3)
+    dev = _device.device_of(ctx, wv3, chm, slic)
 
     img = _as_dev(wv3, torch.float32, dev)
     chm_d = _as_dev(chm, torch.float32, dev)
     lab = _as_dev(slic, torch.int32, dev) if slic is not None else None
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     pan = torch.empty((H, W), dtype=torch.float32, device=img.device)
     gap = torch.empty((H, W), dtype=torch.float32, device=img.device)
     _lib.check(lib.obia_cost_bands_f32_dev(c.handle, img.data_ptr(), H * W, pan.data_ptr(), gap.data_ptr()))
@@ -440,10 +408,10 @@ def make_cost_surface(wv3, chm, out=None, slic=None, weights=(0.5, 0.25, 0.25, 0
     _lib.check(lib.obia_cost_combine_dev(c.handle, grad.data_ptr(), gap.data_ptr(), tex.data_ptr(),
                                          lab.data_ptr() if lab is not None else None, H, W, d4(*[p[0] for p in lohi]),
                                          d4(*[p[1] for p in lohi]), d4(*w), cost.data_ptr()))
-    _end(lib, c)
+    _device.end(lib, c)
     if _layers is not None:
         _layers.update(pan=(lo_c, hi_c), grad=lohi[0], gap=lohi[1], tex=lohi[2], edge=lohi[3] if lab is not None else None,
                        weights=tuple(w))
     if out is not None:
         _write_cost(out, cost.cpu().numpy(), like)
-    return cost if is_t else cost.cpu().numpy()
+    return _device.out(cost, is_t)

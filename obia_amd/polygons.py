@@ -13,7 +13,7 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:
     import torch
@@ -126,22 +126,13 @@ def polygonize(labels, affine_transformation=None, start_label=0, ctx=None):
     ``image.affine_transformation`` = [a, b, d, e, xoff, yoff] (x' = a*x + b*y + xoff, y' = d*x + e*y + yoff applied to
     pixel-corner coordinates); None keeps pixel-corner coordinates.  Returns a :class:`PolygonTable`.
     """
-    if torch is None:
-        raise ImportError("obia_amd.polygons needs torch for device memory")
-    lib = _lib.load()
-    if isinstance(labels, torch.Tensor):
-        if not labels.is_cuda:
-            raise ValueError("torch inputs must live on the GPU")
-        lab = labels.to(torch.int32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        lab = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32), device=f"cuda:{c0.device}")
+    _device.need_torch("obia_amd.polygons")
+    lab = _device.as_dev(labels, torch.int32, _device.device_of(ctx, labels))
     if lab.dim() != 2:
         raise ValueError("labels must be (H, W)")
     H, W = lab.shape
     dev = lab.device
-    c = ctx or _lib.default_context(dev.index or 0)
-    torch.cuda.current_stream(dev.index or 0).synchronize()
+    lib, c = _device.begin(dev.index, ctx)
     n_r, n_v = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(lib.obia_polygon_count_i32_dev(c.handle, lab.data_ptr(), H, W, int(start_label), ctypes.byref(n_r),
                                               ctypes.byref(n_v)))
@@ -252,12 +243,8 @@ def _rings_of_wkb(wkbs):
     return xy, off, np.asarray(shape, np.int32)
 
 
-def _is_tensor(x):
-    return torch is not None and isinstance(x, torch.Tensor)
-
-
 def _host(x):
-    return x.cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    return x.cpu().numpy() if _device.is_torch(x) else np.asarray(x)
 
 
 def rasterize(shapes, out_shape, affine_transformation=None, values=None, fill=0, ctx=None, as_tensor=False):
@@ -292,8 +279,8 @@ def rasterize(shapes, out_shape, affine_transformation=None, values=None, fill=0
         default_values = shapes.labels
     elif isinstance(shapes, tuple) and len(shapes) == 3 and not isinstance(shapes[0], (bytes, bytearray, memoryview)):
         xy, off, rshape = shapes
-        on_device = any(_is_tensor(t) for t in shapes)
-        if on_device and not all(_is_tensor(t) and t.is_cuda for t in shapes):
+        on_device = any(_device.is_torch(t) for t in shapes)
+        if on_device and not all(_device.is_torch(t) and t.is_cuda for t in shapes):
             raise ValueError("ring arrays must be all NumPy arrays or all CUDA tensors")
         if not on_device:
             xy, off, rshape = np.asarray(xy), np.asarray(off), np.asarray(rshape)
@@ -333,15 +320,9 @@ def rasterize(shapes, out_shape, affine_transformation=None, values=None, fill=0
     if affine_transformation is not None or not on_device:
         xy = to_pixel(_host(xy), affine_transformation)       # (raises ValueError for a singular or malformed transform)
 
-    if torch is None:
-        raise ImportError("obia_amd.polygons needs torch for device memory")
-    lib = _lib.load()
-    if on_device:
-        dev = shapes[0].device.index or 0
-        c = ctx or _lib.default_context(dev)
-    else:
-        c = ctx or _lib.default_context(0)
-        dev = c.device
+    _device.need_torch("obia_amd.polygons")
+    _lib.load()                                               # (a library that is not built is reported before anything is uploaded)
+    dev = _device.device_of(ctx, *(shapes if on_device else ()))
     d = f"cuda:{dev}"
     xy_d = torch.as_tensor(xy, device=d).to(torch.float64).contiguous()
     if on_device and not bool(torch.isfinite(xy_d).all()):
@@ -350,7 +331,7 @@ def rasterize(shapes, out_shape, affine_transformation=None, values=None, fill=0
     rs_d = torch.as_tensor(rshape_h.astype(np.int32), device=d)
     val_d = torch.as_tensor(np.ascontiguousarray(values, dtype=np.int32), device=d)
     out = torch.empty((H, W), dtype=torch.int32, device=d)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     _lib.check(lib.obia_rasterize_polygons_dev(c.handle, xy_d.data_ptr() if xy_d.numel() else None, off_d.data_ptr(),
                                                int(rs_d.numel()), rs_d.data_ptr() if rs_d.numel() else None,
                                                val_d.data_ptr() if val_d.numel() else None, n_shapes, H, W, int(fill),

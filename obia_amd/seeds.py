@@ -16,8 +16,8 @@ import struct
 
 import numpy as np
 
-from . import _lib
-from .cost import _as_dev, _begin, _device_of, _end, _is_path, _need_torch, _plane, _shape
+from . import _device, _lib
+from .cost import _as_dev, _is_path, _need_torch, _plane, _shape
 
 try:
     import torch
@@ -67,14 +67,14 @@ def detect_peaks(arr, v_min, min_dist_px, sigma=0, ctx=None, _smooth=False):
     ``_smooth=True`` appends the smoothed plane (test hook)."""
     _need_torch()
     _check_peak_args("arr", _shape(arr), min_dist_px, sigma)
-    is_t = isinstance(arr, torch.Tensor)
-    dev = _device_of(ctx, arr)
+    is_t = _device.is_torch(arr)
+    dev = _device.device_of(ctx, arr)
     x = _as_dev(arr, torch.float32, dev)
     H, W = x.shape
     n = H * W
     nchunks = -(-n // _CHUNK)
     sigma = float(sigma)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     smooth = torch.empty((H, W), dtype=torch.float32, device=x.device) if sigma > 0 else x
     flags = torch.empty(nchunks * _CHUNK, dtype=torch.uint8, device=x.device)
     offsets = torch.empty(nchunks + 1, dtype=torch.int32, device=x.device)
@@ -89,9 +89,9 @@ def detect_peaks(arr, v_min, min_dist_px, sigma=0, ctx=None, _smooth=False):
     rval = torch.empty(k, dtype=torch.float32, device=x.device)
     _lib.check(lib.obia_seeds_peaks_gather_dev(c.handle, x.data_ptr(), smooth.data_ptr(), flags.data_ptr(), offsets.data_ptr(), H, W, k,
                                                rows.data_ptr(), cols.data_ptr(), gval.data_ptr(), rval.data_ptr()))
-    _end(lib, c)
+    _device.end(lib, c)
     out = (rows, cols, gval, rval) + ((smooth,) if _smooth else ())
-    return out if is_t else tuple(t.cpu().numpy() for t in out)
+    return _device.out(out, is_t)
 
 
 def _table_name(path):
@@ -105,7 +105,7 @@ def _point_wkb(x, y):
 def write_seed_points(path, seeds, table=None, srs_epsg=None):
     """One point layer: every key of ``seeds`` other than x / y / row / col becomes a column."""
     from .geopackage import write_geopackage
-    host = {k: (v.cpu().numpy() if torch is not None and isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in seeds.items()}
+    host = {k: (v.cpu().numpy() if _device.is_torch(v) else np.asarray(v)) for k, v in seeds.items()}
     wkbs = [_point_wkb(x, y) for x, y in zip(host["x"], host["y"])]
     cols = {k: v for k, v in host.items() if k not in ("x", "y", "row", "col")}
     d = os.path.dirname(os.path.abspath(os.fspath(path)))
@@ -137,7 +137,7 @@ def read_seed_points(path):
 def _make_seeds(raster, seeds_gpkg, v_min, min_dist_px, gauss_sigma, affine_transformation, ctx, name, column, empty_message):
     _need_torch()
     raster = _plane(raster, None, name)
-    is_t = isinstance(raster, torch.Tensor)
+    is_t = _device.is_torch(raster)
     rows, cols, _, raw = detect_peaks(raster if is_t else np.asarray(raster), v_min, min_dist_px, gauss_sigma, ctx=ctx)
     if len(rows) == 0:
         raise SystemExit(empty_message)
@@ -193,14 +193,14 @@ def pair_distances(xs, ys, cost, inv6, weight, xy_thresh, samples=SAMPLES, ctx=N
     """_build_distance_matrix (seeds.py:139-165) as a full float32 (n, n) matrix, n <= 512: a test hook of the pair function."""
     _need_torch()
     _check_pair_args(xs, ys, cost, inv6)
-    is_t = isinstance(xs, torch.Tensor)
-    dev = _device_of(ctx, xs, ys, cost)
+    is_t = _device.is_torch(xs)
+    dev = _device.device_of(ctx, xs, ys, cost)
     x, y, cst = _as_dev(xs, torch.float64, dev), _as_dev(ys, torch.float64, dev), _as_dev(cost, torch.float32, dev)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     D = torch.empty((x.numel(), x.numel()), dtype=torch.float32, device=x.device)
     _lib.check(_pair_call(lib.obia_seeds_pair_matrix_dev, c, x, y, cst, inv6, weight, xy_thresh, samples, D.data_ptr()))
-    _end(lib, c)
-    return D if is_t else D.cpu().numpy()
+    _device.end(lib, c)
+    return _device.out(D, is_t)
 
 
 def merge_clusters(xs, ys, cost, inv6, weight, xy_thresh, eps, samples=SAMPLES, prune=None, ctx=None):
@@ -209,17 +209,17 @@ def merge_clusters(xs, ys, cost, inv6, weight, xy_thresh, eps, samples=SAMPLES, 
     when weight >= 0 and the cost has no negative value; False = evaluate every pair (same result)."""
     _need_torch()
     _check_pair_args(xs, ys, cost, inv6)
-    is_t = isinstance(xs, torch.Tensor)
-    dev = _device_of(ctx, xs, ys, cost)
+    is_t = _device.is_torch(xs)
+    dev = _device.device_of(ctx, xs, ys, cost)
     x, y, cst = _as_dev(xs, torch.float64, dev), _as_dev(ys, torch.float64, dev), _as_dev(cost, torch.float32, dev)
     nonneg = False if prune is False else bool(float(weight) >= 0 and bool((cst >= 0).all()))
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     cl = torch.empty(x.numel(), dtype=torch.int32, device=x.device)
     ncl = ctypes.c_int(0)
     _lib.check(_pair_call(lib.obia_seeds_pair_link_dev, c, x, y, cst, inv6, weight, xy_thresh, samples, float(eps), int(nonneg),
                           cl.data_ptr(), ctypes.byref(ncl)))
-    _end(lib, c)
-    return cl if is_t else cl.cpu().numpy()
+    _device.end(lib, c)
+    return _device.out(cl, is_t)
 
 
 def pair_stats(xs, ys, cost, inv6, weight, xy_thresh, samples=SAMPLES, ctx=None):
@@ -229,13 +229,13 @@ def pair_stats(xs, ys, cost, inv6, weight, xy_thresh, samples=SAMPLES, ctx=None)
     _check_pair_args(xs, ys, cost, inv6)
     if _shape(xs)[0] < 2:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
-    dev = _device_of(ctx, xs, ys, cost)
+    dev = _device.device_of(ctx, xs, ys, cost)
     x, y, cst = _as_dev(xs, torch.float64, dev), _as_dev(ys, torch.float64, dev), _as_dev(cost, torch.float32, dev)
-    lib, c = _begin(dev, ctx)
+    lib, c = _device.begin(dev, ctx)
     st = (ctypes.c_float * 4)()
     n_nan = ctypes.c_int64(0)
     _lib.check(_pair_call(lib.obia_seeds_pair_stats_dev, c, x, y, cst, inv6, weight, xy_thresh, samples, st, ctypes.byref(n_nan)))
-    _end(lib, c)
+    _device.end(lib, c)
     v = np.array(list(st), np.float32)
     return v[0], np.mean(v[1:3]), v[3]
 
@@ -288,8 +288,8 @@ def make_canonical_seeds(chm_seeds, den_seeds, cost_surface, out_path=None, merg
     cost_surface = _plane(cost_surface, None, "cost_surface")
     if 0 in _shape(cost_surface):
         raise ValueError("cost_surface is empty")
-    is_t = isinstance(cost_surface, torch.Tensor)
-    dev = _device_of(ctx, cost_surface, cx, dx)
+    is_t = _device.is_torch(cost_surface)
+    dev = _device.device_of(ctx, cost_surface, cx, dx)
     xs = torch.cat([_as_dev(cx, torch.float64, dev), _as_dev(dx, torch.float64, dev)])
     ys = torch.cat([_as_dev(cy, torch.float64, dev), _as_dev(dy, torch.float64, dev)])
     hs = torch.cat([_as_dev(ch, torch.float32, dev), _as_dev(dh, torch.float32, dev)])
@@ -307,8 +307,7 @@ def make_canonical_seeds(chm_seeds, den_seeds, cost_surface, out_path=None, merg
     cl = merge_clusters(xs, ys, cost, inv6, cost_weight, xy_thresh, merge_radius, SAMPLES, ctx=ctx)
     origin = np.array(["chm"] * n_chm + ["density"] * (n - n_chm))
     out = {"id": torch.arange(n, dtype=torch.int64, device=xs.device), "cluster": cl, "ch_max": hs, "origin": origin, "x": xs, "y": ys}
-    if not is_t:
-        out = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+    out = _device.out(out, is_t)
     if out_path is not None:
         write_seed_points(out_path, out, table="canonical_seeds")
         print(f"✓ canonical seeds: {n:,}  →  {out_path}")

@@ -12,7 +12,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:  # torch is plumbing only: device tensors in, device tensors out
     import torch
@@ -23,10 +23,7 @@ _SLIC_KWARGS = ("n_segments", "compactness", "max_num_iter", "max_iter", "sigma"
                 "enforce_connectivity", "min_size_factor", "max_size_factor", "slic_zero", "start_label", "mask",
                 "channel_axis", "multichannel", "exit_on_fixed_point")
 _SEEDINGS = ("grid", "skimage")
-
-
-def _is_torch(x):
-    return torch is not None and isinstance(x, torch.Tensor)
+_HOST_HINT = "; pass a NumPy array for host data"
 
 
 def make_params(n_segments=100, compactness=10.0, max_num_iter=10, convert2lab=None, enforce_connectivity=True,
@@ -165,14 +162,12 @@ def mask_centroids(mask, n_segments, ctx=None):
     the nearest-other-centroid search and ``steps`` run in the library (obia_mask_centroids_dev): brute force,
     points x centroids float64 distances per iteration.  ValueError with fewer than two valid pixels or ``n_segments < 2`` (the
     reference ends up with a zero step there and divides by it)."""
-    if torch is None:
-        raise ImportError("mask_centroids needs torch (device plumbing)")
+    _device.need_torch("mask_centroids", "(device plumbing)")
     n_segments = int(n_segments)
     if n_segments < 2:
         raise ValueError("mask_centroids: n_segments must be at least 2")
-    if _is_torch(mask):
-        if not mask.is_cuda:
-            raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
+    dev = _device.device_of(ctx, mask, hint=_HOST_HINT)
+    if _device.is_torch(mask):
         m = _lib.mask_bytes(mask)
     else:
         m = np.asarray(mask)
@@ -180,7 +175,6 @@ def mask_centroids(mask, n_segments, ctx=None):
             raise ValueError("mask must be (H, W)")
         if np.count_nonzero(m) < 2:      # (before anything touches the device)
             raise ValueError("mask_centroids: the mask needs at least two valid pixels")
-        dev = ctx.device if ctx is not None else 0
         m = torch.as_tensor(np.ascontiguousarray(m != 0).view(np.uint8), device=f"cuda:{dev}")
     if m.dim() != 2:
         raise ValueError("mask must be (H, W)")
@@ -191,11 +185,9 @@ def mask_centroids(mask, n_segments, ctx=None):
     idx, dense = _mask_seed_picks(n_valid, n_segments)
     yx = np.empty((len(idx), 2), np.float64)
     steps = np.empty(3, np.float64)
-    dev = m.device.index or 0
-    c = ctx or _lib.default_context(dev)
-    torch.cuda.current_stream(dev).synchronize()
-    _lib.check(_lib.load().obia_mask_centroids_dev(c.handle, m.data_ptr(), H, W, _lib.np_ptr(idx), len(idx), _lib.np_ptr(dense),
-                                                   0 if dense is None else len(dense), 5, _lib.np_ptr(yx), _lib.np_ptr(steps)))
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_mask_centroids_dev(c.handle, m.data_ptr(), H, W, _lib.np_ptr(idx), len(idx), _lib.np_ptr(dense),
+                                           0 if dense is None else len(dense), 5, _lib.np_ptr(yx), _lib.np_ptr(steps)))
     return np.concatenate([np.zeros((len(yx), 1)), yx], 1), steps
 
 
@@ -207,25 +199,22 @@ def _slic_skimage_seeding(image, mask, seeds, n_segments, ctx, kw):
         raise ValueError('seeding="skimage" computes the seeds: do not pass seeds= with it')
     if int(n_segments) < 2:
         raise ValueError('seeding="skimage" needs n_segments >= 2')
-    if torch is None:
-        raise ImportError('seeding="skimage" needs torch (device plumbing)')
-    if _is_torch(image) and not image.is_cuda:
-        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
-    img = image if _is_torch(image) else np.asarray(image)
+    _device.need_torch('seeding="skimage"', "(device plumbing)")
+    dev = _device.device_of(ctx, image, mask, hint=_HOST_HINT)
+    img = image if _device.is_torch(image) else np.asarray(image)
     if len(img.shape) not in (2, 3):
         raise ValueError("image must be (H,W) or (H,W,C)")
-    if not _is_torch(mask):
+    if not _device.is_torch(mask):
         mask = np.asarray(mask) != 0
         if np.count_nonzero(mask) < 2:      # (before anything touches the device)
             raise ValueError('seeding="skimage" needs at least two valid pixels in the mask')
     if tuple(mask.shape) != tuple(img.shape[:2]):
         raise ValueError("image and mask should have the same shape.")
-    dev_img = img if _is_torch(img) else torch.as_tensor(np.ascontiguousarray(img, dtype=np.float32),
-                                                         device=f"cuda:{ctx.device if ctx is not None else 0}")
-    m = _lib.mask_bytes(mask if _is_torch(mask) else np.ascontiguousarray(mask), device=dev_img.device)
+    dev_img = _device.as_dev(img, torch.float32, dev)
+    m = _lib.mask_bytes(mask if _device.is_torch(mask) else np.ascontiguousarray(mask), device=dev_img.device)
     cent, steps = mask_centroids(m, n_segments, ctx=ctx)
     out = slic(dev_img, n_segments=n_segments, mask=m, seeds=(cent[:, 1:], steps), ctx=ctx, **kw)
-    return out if _is_torch(image) else out.cpu().numpy().astype(np.int64)
+    return out if _device.is_torch(image) else out.cpu().numpy().astype(np.int64)
 
 
 def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spacing=None, convert2lab=None,
@@ -273,64 +262,50 @@ def slic(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spac
             exit_on_fixed_point=exit_on_fixed_point, _normalize_bands=_normalize_bands, _stage=_stage))
     params = make_params(n_segments, compactness, max_num_iter, convert2lab, enforce_connectivity, min_size_factor,
                          max_size_factor, slic_zero, start_label, _normalize_bands, exit_on_fixed_point, sigma, spacing)
-    lib = _lib.load()
     n_out = ctypes.c_int(0)
-    if _is_torch(image):
-        if not image.is_cuda:
-            raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
-        img = image if image.dim() == 3 else image[..., None]
-        img = img.to(torch.float32).contiguous()
-        H, W, C = img.shape
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=img.device)
-            if tuple(m.shape) != (H, W):
-                raise ValueError("image and mask should have the same shape.")
-            m = _lib.mask_bytes(m)
-        dev = img.device.index or 0
-        c = ctx or _lib.default_context(dev)
-        torch.cuda.current_stream(dev).synchronize()
-        out = torch.empty((H, W), dtype=torch.int32, device=img.device)
-        if seeds is not None:
-            yx = np.ascontiguousarray(seeds[0], np.float64)
-            if yx.ndim != 2 or yx.shape[1] != 2:
-                raise ValueError("seeds[0] must be (K, 2) centroid positions (y, x)")
-            st = [float(v) for v in np.ravel(seeds[1])]
-            if len(st) == 2:
-                st = [1.0] + st
-            if len(st) != 3:
-                raise ValueError("seeds[1] must hold 2 (y, x) or 3 (z, y, x) steps")
-            sd = _lib.SlicSeeds()
-            sd.yx, sd.n = yx.ctypes.data, yx.shape[0]
-            sd.steps_zyx[:] = st
-            _lib.check(lib.obia_slic_seeded_f32_dev(c.handle, img.data_ptr(), H, W, C, m.data_ptr() if m is not None else None,
-                                                    ctypes.byref(params), ctypes.byref(sd), {"full": 0, "pre": 1}[_stage],
-                                                    out.data_ptr(), ctypes.byref(n_out)))
-            return out
-        fn = {"full": lib.obia_slic_f32_dev, "pre": lib.obia_slic_assign_only_f32_dev}[_stage]
-        _lib.check(fn(c.handle, img.data_ptr(), H, W, C, m.data_ptr() if m is not None else None,
-                      ctypes.byref(params), out.data_ptr(), ctypes.byref(n_out)))
-        return out
-    img = np.asarray(image)
-    if img.ndim == 2:
-        img = img[..., None]
-    if img.ndim != 3:
-        raise ValueError("image must be (H,W) or (H,W,C)")
-    img = np.ascontiguousarray(img, dtype=np.float32)
+    is_t = _device.is_torch(image)
+    dev = _device.device_of(ctx, image, mask, hint=_HOST_HINT)
+    if is_t:
+        img = _device.as_dev(image if image.dim() == 3 else image[..., None], torch.float32, dev)
+        ptr = torch.Tensor.data_ptr
+    else:
+        img = np.asarray(image)
+        if img.ndim == 2:
+            img = img[..., None]
+        if img.ndim != 3:
+            raise ValueError("image must be (H,W) or (H,W,C)")
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        ptr = _lib.np_ptr
     H, W, C = img.shape
     m = None
     if mask is not None:
-        m = np.asarray(mask)
-        if m.shape != (H, W):
+        m = torch.as_tensor(mask, device=img.device) if is_t else np.asarray(mask)
+        if tuple(m.shape) != (H, W):
             raise ValueError("image and mask should have the same shape.")
-        m = np.ascontiguousarray(m != 0, dtype=np.uint8)
-    c = ctx or _lib.default_context(0)
-    out = np.empty((H, W), np.int32)
-    if _stage != "full" or seeds is not None:
+        m = _lib.mask_bytes(m) if is_t else np.ascontiguousarray(m != 0, dtype=np.uint8)
+    if not is_t and (_stage != "full" or seeds is not None):
         raise ValueError("stage-level and seeded calls need device tensors")
-    _lib.check(lib.obia_slic_f32(c.handle, _lib.np_ptr(img), H, W, C, _lib.np_ptr(m), ctypes.byref(params),
-                                 _lib.np_ptr(out), ctypes.byref(n_out)))
-    return out.astype(np.int64)
+    lib, c = _device.begin(dev, ctx, host=not is_t)
+    out = torch.empty((H, W), dtype=torch.int32, device=img.device) if is_t else np.empty((H, W), np.int32)
+    if seeds is not None:
+        yx = np.ascontiguousarray(seeds[0], np.float64)
+        if yx.ndim != 2 or yx.shape[1] != 2:
+            raise ValueError("seeds[0] must be (K, 2) centroid positions (y, x)")
+        st = [float(v) for v in np.ravel(seeds[1])]
+        if len(st) == 2:
+            st = [1.0] + st
+        if len(st) != 3:
+            raise ValueError("seeds[1] must hold 2 (y, x) or 3 (z, y, x) steps")
+        sd = _lib.SlicSeeds()
+        sd.yx, sd.n = yx.ctypes.data, yx.shape[0]
+        sd.steps_zyx[:] = st
+        _lib.check(lib.obia_slic_seeded_f32_dev(c.handle, ptr(img), H, W, C, ptr(m) if m is not None else None,
+                                                ctypes.byref(params), ctypes.byref(sd), {"full": 0, "pre": 1}[_stage],
+                                                ptr(out), ctypes.byref(n_out)))
+        return out
+    fn = {"full": lib.obia_slic_f32_dev if is_t else lib.obia_slic_f32, "pre": lib.obia_slic_assign_only_f32_dev}[_stage]
+    _lib.check(fn(c.handle, ptr(img), H, W, C, ptr(m) if m is not None else None, ctypes.byref(params), ptr(out), ctypes.byref(n_out)))
+    return out if is_t else out.astype(np.int64)
 
 
 def _slic_stages(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma=0, spacing=None, convert2lab=None,
@@ -345,17 +320,13 @@ def _slic_stages(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma
     the pre-pass M sweeps whatever ``max_num_iter`` is (0: ``max_num_iter``, as ``slic`` runs it)."""
     params = make_params(n_segments, compactness, max_num_iter, convert2lab, False, 0.5, 3, slic_zero, start_label, _normalize_bands,
                          exit_on_fixed_point, sigma, spacing)
-    lib = _lib.load()
-    if not _is_torch(image):
-        image = torch.as_tensor(np.ascontiguousarray(image, np.float32), device="cuda")
-    if not image.is_cuda:
-        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
-    img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
+    img = _device.as_dev(image, torch.float32, _device.device_of(ctx, image, hint=_HOST_HINT))
+    img = img if img.dim() == 3 else img[..., None]
     H, W, C = img.shape
     dev = img.device
     m = None
     if mask is not None:
-        m = _lib.mask_bytes(torch.as_tensor(np.asarray(mask) != 0 if not _is_torch(mask) else mask, device=dev))
+        m = _lib.mask_bytes(torch.as_tensor(np.asarray(mask) != 0 if not _device.is_torch(mask) else mask, device=dev))
         if tuple(m.shape) != (H, W):
             raise ValueError("image and mask should have the same shape.")
     sd = None
@@ -375,8 +346,7 @@ def _slic_stages(image, n_segments=100, compactness=10.0, max_num_iter=10, sigma
     s.features, s.seeds_yx, s.labels_pre = out["features"].data_ptr(), out["seeds_yx"].data_ptr(), out["labels_pre"].data_ptr()
     s.centroids = out["centroids"].data_ptr() if params.max_num_iter >= 1 else None
     s.centroid_capacity, s.prepass_only, s.prepass_iters = cap, int(bool(prepass_only)), int(prepass_iters)
-    c = ctx or _lib.default_context(dev.index or 0)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev.index, ctx)
     _lib.check(lib.obia_slic_stages_f32_dev(c.handle, img.data_ptr(), H, W, C, m.data_ptr() if m is not None else None,
                                             ctypes.byref(params), ctypes.byref(sd) if sd is not None else None, ctypes.byref(s)))
     out["seeds_yx"], out["centroids"] = out["seeds_yx"][:s.K], out["centroids"][:s.K]
@@ -409,9 +379,8 @@ def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, 
         raise ValueError("`kernel_size` should be >= 1.")
     # any band count up to 16 and any kernel_size: 1 / 3 / 4 bands with kernel_size <= 5 take the LDS-staged kernel, other
     # calls the same arithmetic on global memory (csrc/quickshift.hip)
-    lib = _lib.load()
     n_out = ctypes.c_int(0)
-    is_t = _is_torch(image)
+    is_t = _device.is_torch(image)
     shape = tuple(image.shape)
     H, W = shape[0], shape[1]
     C = 1 if len(shape) == 2 else shape[2]
@@ -421,15 +390,12 @@ def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, 
     if device_noise and not is_t:
         raise ValueError('rng="device" needs a CUDA tensor input')
     noise = None if device_noise else _quickshift_host_noise(H, W, rng, random_seed)
+    dev = _device.device_of(ctx, image, hint=_HOST_HINT)
     if is_t:
-        if not image.is_cuda:
-            raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
-        img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
-        dev = img.device.index or 0
-        c = ctx or _lib.default_context(dev)
+        img = _device.as_dev(image if image.dim() == 3 else image[..., None], torch.float32, dev)
         nz = _quickshift_device_noise(H, W, img.device) if device_noise else torch.as_tensor(noise, device=img.device)
         out = torch.empty((H, W), dtype=torch.int32, device=img.device)
-        torch.cuda.current_stream(dev).synchronize()
+        lib, c = _device.begin(dev, ctx)
         _lib.check(lib.obia_quickshift_f32_dev(c.handle, img.data_ptr(), H, W, C, float(ratio), float(kernel_size),
                                                float(max_dist), float(sigma), int(bool(convert2lab)), nz.data_ptr(),
                                                int(bool(_normalize_bands)), out.data_ptr(), ctypes.byref(n_out)))
@@ -438,7 +404,7 @@ def quickshift(image, ratio=1.0, kernel_size=5, max_dist=10, return_tree=False, 
     if img.ndim == 2:
         img = img[..., None]
     img = np.ascontiguousarray(img, dtype=np.float32)
-    c = ctx or _lib.default_context(0)
+    lib, c = _device.begin(dev, ctx, host=True)
     out = np.empty((H, W), np.int32)
     _lib.check(lib.obia_quickshift_f32(c.handle, _lib.np_ptr(img), H, W, C, float(ratio), float(kernel_size), float(max_dist),
                                        float(sigma), int(bool(convert2lab)), _lib.np_ptr(noise), int(bool(_normalize_bands)),
@@ -471,12 +437,8 @@ def _quickshift_stages(image, ratio=1.0, kernel_size=5, max_dist=10, sigma=0, co
         raise ValueError("sigma: a number >= 0 (the width of the Gaussian pre-smoothing on both raster axes)")
     if kernel_size < 1:
         raise ValueError("`kernel_size` should be >= 1.")
-    lib = _lib.load()
-    if not _is_torch(image):
-        image = torch.as_tensor(np.ascontiguousarray(image, np.float32), device="cuda")
-    if not image.is_cuda:
-        raise ValueError("torch inputs must live on the GPU; pass a NumPy array for host data")
-    img = (image if image.dim() == 3 else image[..., None]).to(torch.float32).contiguous()
+    img = _device.as_dev(image, torch.float32, _device.device_of(ctx, image, hint=_HOST_HINT))
+    img = img if img.dim() == 3 else img[..., None]
     H, W, C = img.shape
     if convert2lab and C != 3:
         raise ValueError("Only RGB images can be converted to Lab space.")
@@ -490,9 +452,8 @@ def _quickshift_stages(image, ratio=1.0, kernel_size=5, max_dist=10, sigma=0, co
     out = {"image": torch.empty((C, H, W), **f64), "noise": torch.empty((H, W), **f64), "dens": torch.empty((H, W), **f64),
            "parent": torch.empty((H, W), **i32), "dist_parent": torch.empty((H, W), **f64), "roots": torch.empty((H, W), **i32),
            "labels": torch.empty((H, W), **i32)}
-    c = ctx or _lib.default_context(dev.index or 0)
     n_out = ctypes.c_int(0)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev.index, ctx)
     _lib.check(lib.obia_quickshift_stages_f32_dev(c.handle, img.data_ptr(), H, W, C, float(ratio), float(kernel_size), float(max_dist),
                                                   float(sigma), int(bool(convert2lab)), nz.data_ptr(), int(bool(_normalize_bands)),
                                                   out["labels"].data_ptr(), ctypes.byref(n_out), out["image"].data_ptr(),
@@ -504,17 +465,16 @@ def _quickshift_stages(image, ratio=1.0, kernel_size=5, max_dist=10, sigma=0, co
 
 def enforce_connectivity(labels, min_size, max_size, start_label=1, ctx=None):
     """Connectivity enforcement alone on an int32 CUDA label tensor (stage-level parity hook)."""
-    if not _is_torch(labels) or not labels.is_cuda:
+    if not _device.is_torch(labels) or not labels.is_cuda:
         raise ValueError("enforce_connectivity needs an int32 CUDA tensor")
-    lab = labels.to(torch.int32).contiguous()
+    dev = _device.device_of(ctx, labels)
+    lab = _device.as_dev(labels, torch.int32, dev)
     H, W = lab.shape
-    dev = lab.device.index or 0
-    c = ctx or _lib.default_context(dev)
-    torch.cuda.current_stream(dev).synchronize()
+    lib, c = _device.begin(dev, ctx)
     out = torch.empty_like(lab)
     n = ctypes.c_int(0)
-    _lib.check(_lib.load().obia_enforce_connectivity_i32_dev(c.handle, lab.data_ptr(), H, W, int(min_size), int(max_size),
-                                                              int(start_label), out.data_ptr(), ctypes.byref(n)))
+    _lib.check(lib.obia_enforce_connectivity_i32_dev(c.handle, lab.data_ptr(), H, W, int(min_size), int(max_size), int(start_label),
+                                                     out.data_ptr(), ctypes.byref(n)))
     return out, n.value
 
 
@@ -573,7 +533,7 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
             raise IndexError(f"Band index {band} out of range. Available bands indices: 0 to {num_bands - 1}.")
     if method not in ("slic", "quickshift"):
         raise Exception("An unknown segmentation method was requested.")
-    if _is_torch(img_data):
+    if _device.is_torch(img_data):
         sel = img_data[:, :, list(segmentation_bands)]
     else:
         sel = np.asarray(img_data)[:, :, list(segmentation_bands)]
@@ -587,7 +547,7 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
         if unknown:
             raise TypeError(f"quickshift() got an unexpected keyword argument '{unknown[0]}'")
         segments = quickshift(sel, ctx=ctx, _normalize_bands=True, **kwargs)
-        if inplace_normalize and not _is_torch(img_data):
+        if inplace_normalize and not _device.is_torch(img_data):
             for i in range(num_bands):
                 img_data[:, :, i] = normalize_band(img_data[:, :, i])
         return segments_table(segments, image, start_label=0, ctx=ctx) if as_table else segments
@@ -597,12 +557,12 @@ def create_segments(image, segmentation_bands=None, method="slic", inplace_norma
     kwargs.setdefault("start_label", 1)   # scikit-image >= 0.19 default (pyproject.toml:23 pins >= 0.23.2)
     # normalisation is per band, so selecting first and normalising the selected bands is identical
     segments = slic(sel, ctx=ctx, seeding=seeding, _normalize_bands=True, **kwargs)
-    if inplace_normalize and not _is_torch(img_data):
+    if inplace_normalize and not _device.is_torch(img_data):
         for i in range(num_bands):
             img_data[:, :, i] = normalize_band(img_data[:, :, i])
     mask = kwargs.get("mask", None)
     if mask is not None:
-        if _is_torch(segments):
+        if _device.is_torch(segments):
             segments[torch.as_tensor(mask, device=segments.device) == 0] = -1
         else:
             segments[np.asarray(mask) == 0] = -1

@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 
 try:
     import torch
@@ -18,8 +18,29 @@ except Exception:  # pragma: no cover
     torch = None
 
 
-def _is_torch(x):
-    return torch is not None and isinstance(x, torch.Tensor)
+def _band_list(bands, C):
+    bl = list(range(C)) if bands is None else [int(b) for b in bands]
+    for b in bl:
+        if b < 0 or b >= C:
+            raise IndexError(f"Band index {b} out of range. Available bands indices: 0 to {C - 1}.")
+    return bl
+
+
+def _n_labels(n_labels, lab, start_label):
+    """``n_labels`` as given, or what the largest label of ``lab`` implies; never negative."""
+    if n_labels is None:
+        empty = isinstance(lab, np.ndarray) and lab.size == 0      # (an empty tensor is refused by its own max())
+        n_labels = 0 if empty else int(lab.max()) - start_label + 1
+    return max(int(n_labels), 0)
+
+
+def _buffer(like, shape, dtype, fill=None):
+    """An output beside ``like``.  A tensor is left unwritten unless ``fill`` is given (the device kernels write every entry);
+    an array for the host entry points starts at ``fill``, or at 0 / NaN."""
+    if _device.is_torch(like):
+        dt = getattr(torch, np.dtype(dtype).name)
+        return torch.empty(shape, dtype=dt, device=like.device) if fill is None else torch.full(shape, fill, dtype=dt, device=like.device)
+    return np.full(shape, fill if fill is not None else (0 if np.dtype(dtype).kind == "i" else np.nan), dtype)
 
 
 def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None, moments=False):
@@ -28,85 +49,45 @@ def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None,
     Returns a dict: ``count`` (N,), ``mean``/``variance`` (N,B) float64, ``min``/``max`` (N,B) float32, with
     N = n_labels (default: max label - start_label + 1) and B = len(bands).  Labels outside
     [start_label, start_label+N) -- e.g. the -1 / 0 of masked pixels -- are ignored; NaN pixels are dropped
-    per band; empty segments give NaN (segment_statistics.py:145-162).  NumPy in -> NumPy out; CUDA
-    tensors in -> CUDA tensors out.
+    per band; empty segments give NaN (segment_statistics.py:145-162).  NumPy in -> NumPy out (the host entry points:
+    torch is not needed); CUDA tensors in -> CUDA tensors out.
 
     ``moments=True`` adds ``skewness`` and ``kurtosis`` (N,B) float64: scipy.stats.skew / kurtosis with their defaults
     (segment_statistics.py:173-175), computed by a second pass with the per-label means as pivots
     (obia_zonal_moments_f32_dev); ``variance`` is then that pass's central m2.  The first pass alone sums about a pivot
     pixel of each segment (zonal.hip), so both stay accurate on bright, nearly flat segments.
     """
-    lib = _lib.load()
-    if _is_torch(raw):
-        if not raw.is_cuda:
-            raise ValueError("torch inputs must live on the GPU")
-        r = raw.to(torch.float32).contiguous()
-        H, W, C = r.shape
-        lab = torch.as_tensor(labels, device=r.device).to(torch.int32).contiguous()
-        if tuple(lab.shape) != (H, W):
-            raise ValueError("labels must have the raster's (H,W) shape")
-        if n_labels is None:
-            n_labels = int(lab.max().item()) - start_label + 1
-        n_labels = max(int(n_labels), 0)
-        bl = list(range(C)) if bands is None else [int(b) for b in bands]
-        for b in bl:
-            if b < 0 or b >= C:
-                raise IndexError(f"Band index {b} out of range. Available bands indices: 0 to {C - 1}.")
-        B = len(bl)
-        barr = np.ascontiguousarray(bl, np.int32)
-        dev = r.device
-        # (zonal_finalize_kernel writes every entry -- NaN for an empty label -- so the outputs need no fill)
-        cnt = torch.empty((n_labels,), dtype=torch.int64, device=dev)
-        mean = torch.empty((n_labels, B), dtype=torch.float64, device=dev)
-        var = torch.empty_like(mean)
-        mn = torch.empty((n_labels, B), dtype=torch.float32, device=dev)
-        mx = torch.empty_like(mn)
-        c = ctx or _lib.default_context(dev.index or 0)
-        torch.cuda.current_stream(dev.index or 0).synchronize()
-        _lib.check(lib.obia_zonal_stats_f32_dev(c.handle, r.data_ptr(), lab.data_ptr(), H, W, C, _lib.np_ptr(barr), B,
-                                                n_labels, int(start_label), cnt.data_ptr(), mean.data_ptr(),
-                                                var.data_ptr(), mn.data_ptr(), mx.data_ptr()))
-        out = {"count": cnt, "mean": mean, "variance": var, "min": mn, "max": mx, "bands": bl}
-        if moments:
-            skew = torch.full_like(mean, float("nan"))
-            kurt = torch.full_like(mean, float("nan"))
-            _lib.check(lib.obia_zonal_moments_f32_dev(c.handle, r.data_ptr(), lab.data_ptr(), H, W, C, _lib.np_ptr(barr), B,
-                                                      n_labels, int(start_label), mean.data_ptr(), skew.data_ptr(),
-                                                      kurt.data_ptr(), var.data_ptr()))
-            out["skewness"], out["kurtosis"] = skew, kurt
-        return out
-    r = np.ascontiguousarray(raw, dtype=np.float32)
+    is_t = _device.is_torch(raw)
+    dev = _device.device_of(ctx, raw, labels)
+    if is_t:
+        r, lab = _device.as_dev(raw, torch.float32, dev), _device.as_dev(labels, torch.int32, dev)
+        ptr = torch.Tensor.data_ptr
+    else:
+        r, lab = np.ascontiguousarray(raw, dtype=np.float32), np.ascontiguousarray(labels, dtype=np.int32)
+        ptr = _lib.np_ptr
     if r.ndim != 3:
         raise ValueError("raw must be (H,W,C)")
     H, W, C = r.shape
-    lab = np.ascontiguousarray(labels, dtype=np.int32)
-    if lab.shape != (H, W):
+    if tuple(lab.shape) != (H, W):
         raise ValueError("labels must have the raster's (H,W) shape")
-    if n_labels is None:
-        n_labels = int(lab.max()) - start_label + 1 if lab.size else 0
-    n_labels = max(int(n_labels), 0)
-    bl = list(range(C)) if bands is None else [int(b) for b in bands]
-    for b in bl:
-        if b < 0 or b >= C:
-            raise IndexError(f"Band index {b} out of range. Available bands indices: 0 to {C - 1}.")
+    n_labels = _n_labels(n_labels, lab, start_label)
+    bl = _band_list(bands, C)
     B = len(bl)
     barr = np.ascontiguousarray(bl, np.int32)
-    cnt = np.zeros((n_labels,), np.int64)
-    mean = np.full((n_labels, B), np.nan, np.float64)
-    var = np.full((n_labels, B), np.nan, np.float64)
-    mn = np.full((n_labels, B), np.nan, np.float32)
-    mx = np.full((n_labels, B), np.nan, np.float32)
-    c = ctx or _lib.default_context(0)
-    _lib.check(lib.obia_zonal_stats_f32(c.handle, _lib.np_ptr(r), _lib.np_ptr(lab), H, W, C, _lib.np_ptr(barr), B, n_labels,
-                                        int(start_label), _lib.np_ptr(cnt), _lib.np_ptr(mean), _lib.np_ptr(var),
-                                        _lib.np_ptr(mn), _lib.np_ptr(mx)))
+    cnt = _buffer(r, (n_labels,), np.int64)
+    mean, var = _buffer(r, (n_labels, B), np.float64), _buffer(r, (n_labels, B), np.float64)
+    mn, mx = _buffer(r, (n_labels, B), np.float32), _buffer(r, (n_labels, B), np.float32)
+    lib, c = _device.begin(dev, ctx, host=not is_t)
+    stats = lib.obia_zonal_stats_f32_dev if is_t else lib.obia_zonal_stats_f32
+    _lib.check(stats(c.handle, ptr(r), ptr(lab), H, W, C, _lib.np_ptr(barr), B, n_labels, int(start_label), ptr(cnt), ptr(mean),
+                     ptr(var), ptr(mn), ptr(mx)))
     out = {"count": cnt, "mean": mean, "variance": var, "min": mn, "max": mx, "bands": bl}
     if moments:
-        skew = np.full((n_labels, B), np.nan, np.float64)
-        kurt = np.full((n_labels, B), np.nan, np.float64)
-        _lib.check(lib.obia_zonal_moments_f32(c.handle, _lib.np_ptr(r), _lib.np_ptr(lab), H, W, C, _lib.np_ptr(barr), B,
-                                              n_labels, int(start_label), _lib.np_ptr(skew), _lib.np_ptr(kurt),
-                                              _lib.np_ptr(var)))
+        skew, kurt = _buffer(r, (n_labels, B), np.float64, float("nan")), _buffer(r, (n_labels, B), np.float64, float("nan"))
+        pivots = (ptr(mean),) if is_t else ()              # (the host entry point keeps the means of its own first pass)
+        second = lib.obia_zonal_moments_f32_dev if is_t else lib.obia_zonal_moments_f32
+        _lib.check(second(c.handle, ptr(r), ptr(lab), H, W, C, _lib.np_ptr(barr), B, n_labels, int(start_label), *pivots, ptr(skew),
+                          ptr(kurt), ptr(var)))
         out["skewness"], out["kurtosis"] = skew, kurt
     return out
 
@@ -119,39 +100,26 @@ def texture_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=Non
     ASM, energy, correlation (calculate_textural_stats, segment_statistics.py:179-298, on the band plane -- see
     oracle/glcm.py for the one place where this departs from the reference's indexing).  NumPy in -> NumPy out, CUDA
     tensors in -> CUDA tensors out (libobia_hip.so: obia_texture_stats_f32_dev)."""
-    if torch is None:
-        raise ImportError("obia_amd.statistics.texture_stats needs torch for device memory")
-    lib = _lib.load()
-    is_t = _is_torch(raw)
-    if is_t:
-        if not raw.is_cuda:
-            raise ValueError("torch inputs must live on the GPU")
-        r = raw.to(torch.float32).contiguous()
-    else:
-        c0 = ctx or _lib.default_context(0)
-        r = torch.as_tensor(np.ascontiguousarray(raw, dtype=np.float32), device=f"cuda:{c0.device}")
+    _device.need_torch("obia_amd.statistics.texture_stats")
+    is_t = _device.is_torch(raw)
+    dev = _device.device_of(ctx, raw, labels)
+    r = _device.as_dev(raw, torch.float32, dev)
     if r.dim() != 3:
         raise ValueError("raw must be (H,W,C)")
     H, W, C = r.shape
-    lab = torch.as_tensor(labels, device=r.device).to(torch.int32).contiguous()
+    lab = _device.as_dev(labels, torch.int32, dev)
     if tuple(lab.shape) != (H, W):
         raise ValueError("labels must have the raster's (H,W) shape")
-    if n_labels is None:
-        n_labels = int(lab.max().item()) - start_label + 1
-    n_labels = max(int(n_labels), 0)
-    bl = list(range(C)) if bands is None else [int(b) for b in bands]
-    for b in bl:
-        if b < 0 or b >= C:
-            raise IndexError(f"Band index {b} out of range. Available bands indices: 0 to {C - 1}.")
+    n_labels = _n_labels(n_labels, lab, start_label)
+    bl = _band_list(bands, C)
     B = len(bl)
     barr = np.ascontiguousarray(bl, np.int32)
     out = torch.full((6, n_labels, B), float("nan"), dtype=torch.float64, device=r.device)
-    c = ctx or _lib.default_context(r.device.index or 0)
-    torch.cuda.current_stream(r.device.index or 0).synchronize()
+    lib, c = _device.begin(dev, ctx)
     if n_labels > 0 and B > 0:
         _lib.check(lib.obia_texture_stats_f32_dev(c.handle, r.data_ptr(), lab.data_ptr(), H, W, C, _lib.np_ptr(barr), B,
                                                   n_labels, int(start_label), out.data_ptr()))
-    res = {p: (out[i] if is_t else out[i].cpu().numpy()) for i, p in enumerate(TEXTURE_PROPS)}
+    res = {p: _device.out(out[i], is_t) for i, p in enumerate(TEXTURE_PROPS)}
     res["bands"] = bl
     return res
 
@@ -228,8 +196,7 @@ def create_objects(segments, image, ept=None, ept_srs=None, spectral_bands=None,
     spectral_bands, textural_bands = list(spectral_bands), list(textural_bands)
     st = zonal_stats(img_data, labels, bands=spectral_bands, start_label=start_label, ctx=ctx,
                      moments=bool(calc_skewness or calc_kurtosis))
-    if _is_torch(st["count"]):
-        st = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in st.items()}
+    st = _device.out(st, False)
     n = st["count"].shape[0]
     present = st["count"] > 0                      # ids of the table: the labels that exist (np.unique order)
     cols = stats_columns(spectral_bands, textural_bands, calc_mean, calc_variance, calc_min, calc_max, calc_skewness,
@@ -248,7 +215,7 @@ def create_objects(segments, image, ept=None, ept_srs=None, spectral_bands=None,
                                              ("correlation", calc_correlation)) if on]
     if calculate_textural and textural_bands and tex_names:
         tx = texture_stats(img_data, labels, bands=textural_bands, start_label=start_label, n_labels=n, ctx=ctx)
-        tx = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in tx.items()}
+        tx = _device.out(tx, False)
         for j, b in enumerate(textural_bands):
             for name, _ in tex_names:
                 data[f"b{b}_{name}"] = tx[name][present, j]

@@ -10,8 +10,8 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
-from .segmentation import make_params, _is_torch, _SLIC_KWARGS, MaskSeedPickSource, check_seeding
+from . import _device, _lib
+from .segmentation import make_params, _SLIC_KWARGS, MaskSeedPickSource, check_seeding
 
 try:
     import torch
@@ -118,7 +118,6 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
     tp.tile_size, tp.buffer = int(tile_size), int(buffer)
     tp.white_order = 1 if white_order == "parity" else 0
     tp.crown_radius, tp.pixel_width, tp.pixel_height = float(crown_radius), float(pw), float(ph)
-    lib = _lib.load()
     n_out = ctypes.c_int64(0)
     picks = MaskSeedPickSource() if rule == _lib.SEEDING_SKIMAGE else None      # (alive until the call has returned)
 
@@ -129,38 +128,28 @@ def create_tiled_segments(input_raster, output_dir=None, input_mask=None, method
         rc = seeded(*args[:-2], rule, picks.fn, None, *args[-2:])
         picks.reraise()
         _lib.check(rc)
-    if _is_torch(img):
-        if not img.is_cuda:
-            raise ValueError("torch inputs must live on the GPU")
-        x = img.to(torch.float32).contiguous()
-        H, W, C = x.shape
-        m = None
-        if input_mask is not None:
-            m = _lib.mask_bytes(input_mask, x.device)
-            if tuple(m.shape) != (H, W):
-                raise ValueError("image and mask should have the same shape.")
-        dev = x.device.index or 0
-        c = ctx or _lib.default_context(dev)
-        torch.cuda.current_stream(dev).synchronize()
-        out = torch.empty((H, W), dtype=torch.int32, device=x.device)
-        run(lib.obia_tiled_slic_f32_dev, lib.obia_tiled_slic_seeded_f32_dev, c.handle, x.data_ptr(), m.data_ptr() if m is not None else None, H, W, C,
-            ctypes.byref(tp), ctypes.byref(params), out.data_ptr(), ctypes.byref(n_out))
-        if output_dir is not None:
-            write_segments_gpkg(out, output_dir, affine_transformation or [pw, 0.0, 0.0, -ph, 0.0, 0.0], crs, ctx=c)
-        return out, int(n_out.value)
-    x = np.ascontiguousarray(img, dtype=np.float32)
+    is_t = _device.is_torch(img)
+    dev = _device.device_of(ctx, img, input_mask)
+    if is_t:
+        x = _device.as_dev(img, torch.float32, dev)
+        ptr = torch.Tensor.data_ptr
+    else:
+        x = np.ascontiguousarray(img, dtype=np.float32)
+        ptr = _lib.np_ptr
     if x.ndim != 3:
         raise ValueError("raster must be (H,W,C)")
     H, W, C = x.shape
     m = None
     if input_mask is not None:
-        m = np.ascontiguousarray(np.asarray(input_mask) != 0, dtype=np.uint8)
-        if m.shape != (H, W):
+        m = _lib.mask_bytes(input_mask, x.device) if is_t else np.ascontiguousarray(np.asarray(input_mask) != 0, dtype=np.uint8)
+        if tuple(m.shape) != (H, W):
             raise ValueError("image and mask should have the same shape.")
-    c = ctx or _lib.default_context(0)
-    out = np.empty((H, W), np.int32)
-    run(lib.obia_tiled_slic_f32, lib.obia_tiled_slic_seeded_f32, c.handle, _lib.np_ptr(x), _lib.np_ptr(m), H, W, C, ctypes.byref(tp),
-        ctypes.byref(params), _lib.np_ptr(out), ctypes.byref(n_out))
+    lib, c = _device.begin(dev, ctx, host=not is_t)
+    out = torch.empty((H, W), dtype=torch.int32, device=x.device) if is_t else np.empty((H, W), np.int32)
+    plain, seeded = ((lib.obia_tiled_slic_f32_dev, lib.obia_tiled_slic_seeded_f32_dev) if is_t else
+                     (lib.obia_tiled_slic_f32, lib.obia_tiled_slic_seeded_f32))
+    run(plain, seeded, c.handle, ptr(x), ptr(m) if m is not None else None, H, W, C, ctypes.byref(tp), ctypes.byref(params), ptr(out),
+        ctypes.byref(n_out))
     if output_dir is not None:
         write_segments_gpkg(out, output_dir, affine_transformation or [pw, 0.0, 0.0, -ph, 0.0, 0.0], crs, ctx=c)
     return out, int(n_out.value)
