@@ -609,8 +609,8 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
  * 6 = maskSLIC spatial-only pre-pass sweeps (ms), 7 = pixels actually processed by the launches of 0
  * (sum; tiles skipped by exit_on_fixed_point are not counted), 8 = the same for the pre-pass launches,
  * 9 = pixels of the launches of 0 that also stored their labels (only the last sweep of a batch does),
- * 10 / 11 = time during which at least one colour / pre-pass sweep was running (equals 0 / 6: the sweeps run one after the
- * other).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0 and
+ * 10 / 11 = time during which at least one colour / pre-pass sweep was running (10 equals 0: the colour sweeps run one after the
+ * other; 11 is below 6 where a batch's spatial pre-pass ran as two window groups side by side, see 15).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0 and
  * 6 are sums of the kernels' own start-to-end times, as a rocprofv3 kernel trace reports them.
  * 12 = batches of the call whose sweeps ran a second time with every sweep storing its labels (a valid pixel that no window
  * reached keeps the label of the sweep before: DESIGN.md 3.2 item 5) -- counted whether profiling is on or not.
@@ -618,6 +618,8 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
  * "One pre-pass per class of identical tiles"); 8 counts them as covered.
  * 14 = pixels whose feature planes were written by the last pre-pass sweep from the raster (the fused feature pass)
  * instead of the feature pass: all pixels of every batch that fused, 0 when none did -- counted whether profiling is on or not.
+ * 15 = spatial pre-pass sweeps launched for one of two window groups of a batch ("Two window groups in flight"):
+ * 2 per grouped sweep, 0 when no batch was grouped -- counted whether profiling is on or not.
  * `enabled`: 0 off, 1 every class, 2 only the colour sweeps (an event pair costs ~2.5 us of stream time: with all classes on,
  * a step of the headline workload records ~420 pairs = 1.1 ms; bench.py times its steps in mode 2).                       */
 int obia_set_profiling(obia_ctx *ctx, int enabled);

@@ -59,9 +59,11 @@ struct Timing {
     double assign_store_px = 0;             // ... of the colour sweeps that also stored their labels (the last sweep of a batch)
     double feat_fused_px = 0;               // pixels whose feature planes were written by a sweep (fused feature pass) instead of the feature pass
     int sweeps = 0;
+    int prepass_group_launches = 0;         // spatial pre-pass sweeps launched for one of two window groups (slic_sweep.hip: grouped pre-pass)
     int batch_repeats = 0;                  // batches whose sweeps ran again with every sweep storing its labels (a valid pixel no window reached)
-    // time during which at least one colour (pre-pass) sweep was running: the sweeps run one after the other, so this equals
-    // assign_ms (prepass_ms)
+    // time during which at least one colour (pre-pass) sweep was running.  The colour sweeps run one after the other, so
+    // assign_busy_ms equals assign_ms; the sweeps of a grouped pre-pass overlap (two window groups, two streams), so prepass_ms is a
+    // sum of overlapping durations and prepass_busy_ms, their union, is the smaller
     double assign_busy_ms = 0, prepass_busy_ms = 0;
 };
 
@@ -95,6 +97,10 @@ struct obia_ctx {
     // first use
     hipStream_t side = nullptr;
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
+    // grouped spatial pre-pass (slic_sweep.hip: queue_sweeps): the second window group runs on `side` between events of its own -- the
+    // white prefetch may hold aux_fork / aux_join across a batch's sweeps
+    hipEvent_t grp_fork = nullptr, grp_join = nullptr;
+    int spatial_residency[4] = {0, 0, 0, 0};   // workgroups of slic_spatial_kernel<4 (i + 1)> the device holds at once; 0: not asked yet
 };
 
 namespace obia {
@@ -123,7 +129,7 @@ int read_back(obia_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
 // (pageable, short-lived) buffer is free at once; the ring is recycled at the next read_back (everything queued before it
 // has then executed).
 int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
-int side_stream(obia_ctx *ctx);   // makes sure `side` and its events exist
+int side_stream(obia_ctx *ctx);   // makes sure `side` and the events of both its users exist
 // Developer aid (OBIA_DEBUG_SYNC=1): synchronise the stream and report the stage on stderr, so that an asynchronous GPU fault
 // is pinned on the stage that caused it.  A no-op otherwise.
 void debug_sync(obia_ctx *ctx, const char *stage);

@@ -120,6 +120,8 @@ ScopedSpan::~ScopedSpan() {
 int side_stream(obia_ctx *ctx) {
     if (!ctx->aux_fork) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->aux_fork, hipEventDisableTiming));
     if (!ctx->aux_join) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->aux_join, hipEventDisableTiming));
+    if (!ctx->grp_fork) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->grp_fork, hipEventDisableTiming));
+    if (!ctx->grp_join) OBIA_HIP_TRY(hipEventCreateWithFlags(&ctx->grp_join, hipEventDisableTiming));
     if (!ctx->side) OBIA_HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     return OBIA_OK;
 }
@@ -281,6 +283,8 @@ void obia_destroy(obia_ctx *ctx) {
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
     if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
+    if (ctx->grp_fork) (void)hipEventDestroy(ctx->grp_fork);
+    if (ctx->grp_join) (void)hipEventDestroy(ctx->grp_join);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -335,6 +339,7 @@ double obia_last_timing(obia_ctx *ctx, int what) {
         case 12: return (double)ctx->timing.batch_repeats;
         case 13: return ctx->timing.prepass_shared_px;
         case 14: return ctx->timing.feat_fused_px;
+        case 15: return (double)ctx->timing.prepass_group_launches;
         default: return -1.0;
     }
 }

@@ -247,19 +247,20 @@ __global__ __launch_bounds__(64) void slic_prep_lane_kernel(const SlicProblem *_
                                                              unsigned long long *__restrict__ acc, int RQ, double inv_fscale,
                                                              float *__restrict__ cent, int *__restrict__ head,
                                                              int *__restrict__ head_other,
-                                                             int total_cells, int *__restrict__ bin_stamp, int sweep_id,
+                                                             int cell_end, int *__restrict__ bin_stamp, int sweep_id,
                                                              int cell_base, float *__restrict__ ref, int *__restrict__ tl_req,
                                                              const int *__restrict__ act_probs) {
     constexpr int RS = CENT_REC + CP;
     constexpr int NQ = (CP + 3 + 1) / 2;   // 16-byte pairs of the accumulator record that are in use: colours | n | sum_y | sum_x
-    {   // the bins of the NEXT sweep (see slic_prep_kernel)
+    {   // the bins of the NEXT sweep (see slic_prep_kernel): [cell_base, cell_end), the whole batch's unless the launch is one window
+        // group's of a grouped pre-pass (queue_sweeps), whose other group may still be reading ITS bins of that buffer
         const int nthr = gridDim.x * gridDim.y * blockDim.x;
-        for (int i = cell_base + (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < total_cells; i += nthr) head_other[i] = -1;
+        for (int i = cell_base + (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < cell_end; i += nthr) head_other[i] = -1;
     }
     // grid = (blocks of 64 centroids, problems of the group): the problem descriptor is workgroup-uniform (scalar loads that depend
     // on nothing), so the chain of dependent round trips is descriptor -> records -> bin head
     // (act_probs: the launch covers the problems the table names -- the representatives of a shared pre-pass -- instead of a span;
-    // the bins above are reset for the whole batch either way)
+    // the bins above are reset for the whole batch then)
     const SlicProblem P = probs[act_probs ? act_probs[blockIdx.y] : p_base + (int)blockIdx.y];
     const int kl = blockIdx.x * blockDim.x + threadIdx.x;
     if (kl >= P.K) return;
@@ -1506,7 +1507,8 @@ template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
                           const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset(),
-                          bool rawin = false) {
+                          bool rawin = false, const hipStream_t *on = nullptr) {
+    const hipStream_t stream = on ? *on : ctx->stream;   // (on: the side stream, for the second window group of a grouped pre-pass)
     constexpr int XGH = OBIA_XCD_GROUP;
     // (a subset -- the lean kernels of a shared pre-pass only -- is grouped over the XCDs like the whole batch)
     const int ntiles = sub.end >= 0 ? sub.end : (int)b.total_tiles_all, tbase = sub.end >= 0 ? sub.base : 0;
@@ -1519,17 +1521,17 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
         (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
         b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, tbase, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req
 #define LAUNCH_K_(...)                                                                                               \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_)
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_)
     // (the lean kernels: the spatial-only pre-pass sweeps, which a shared pre-pass launches for a subset of the tiles)
 #define LAUNCH_KL_(...)                                                                                              \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_, sub.table)
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_, sub.table)
     // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
     // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
     const int pad = CP - b.C;
     if constexpr (CP <= 12) if (rawin) {   // fused feature pass: the batch's last pre-pass sweep (queue_sweeps)
         RawInput ri;
         ri.src = b.raw_src; ri.Ws = b.raw_ws; ri.wins = b.d_windows; ri.keys = b.d_keys; ri.ratio = b.feat_ratio; ri.planes = b.d_feat;
-        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(slic_assign_rawin_kernel<CP>), grid, dim3(NT), 0, ctx->stream, span.a, span.b, 0, LAUNCH_ARGS_, ri);
+        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(slic_assign_rawin_kernel<CP>), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_, ri);
         ctx->timing.feat_fused_px += (double)b.total_pix;
         return;
     }
@@ -1648,7 +1650,29 @@ static void fold_counters(obia_ctx *ctx, const unsigned long long *h, double sha
     }
 }
 
-// Queues every sweep of the batch on the context's stream.  repeat: the batch runs again from the seeds with every sweep storing
+// Workgroups of slic_spatial_kernel<CP> the device holds at once (occupancy x compute units), asked once per context and CP
+static int spatial_residency(obia_ctx *ctx, int CP) {
+    int &r = ctx->spatial_residency[CP / 4 - 1];
+    if (r > 0) return r;
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipErrorInvalidValue;
+    switch (CP) {
+        case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<8>, NT, 0); break;
+#ifndef OBIA_ONLY_CP8
+        case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<4>, NT, 0); break;
+        case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<12>, NT, 0); break;
+        case 16: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<16>, NT, 0); break;
+#endif
+        default: break;
+    }
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    if (e != hipSuccess || per_cu <= 0 || cus <= 0) { (void)hipGetLastError(); return 0x7fffffff; }   // (unknown: no batch is large enough)
+    r = per_cu * cus;
+    return r;
+}
+
+// Queues every sweep of the batch on the context's stream (a grouped pre-pass: half of its spatial sweeps on the side stream, joined
+// again before this returns).  repeat: the batch runs again from the seeds with every sweep storing
 // its labels (slic_rerun_storing).  *d_px_out: the pixel counters of the sweeps, 256 slots each for the colour and the pre-pass
 // sweeps, and in slot 512 the orphan flag of the sweeps that do not store their labels; null when the batch has no sweep.
 // *shared_px_out: the pixel-sweeps a shared pre-pass covered without evaluating them (0 when nothing was shared).
@@ -1780,6 +1804,37 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
         }
         *shared_px_out = spx;
     }
+    // Two window groups in flight: the spatial-only sweeps of the pre-pass (slic_spatial_kernel) and the centroid steps
+    // in front of them read and write nothing of another problem of the batch -- centroid and accumulator records, bins, candidate
+    // lists, reference positions, rebuild requests and the packed mask are all indexed through the problem; the two batch-wide words
+    // are the pixel counters (integer atomics) and the orphan flag (every writer stores 1).  So the batch's problems are split into
+    // two groups of consecutive problems, balanced by sweep tiles, and each runs its own chain step -> sweep -> step -> ...: group 0
+    // on the context's stream, group 1 on the side stream, forked behind the fills below and joined in front of the step of the last
+    // pre-pass sweep, which runs on the whole batch as always.  A group's centroid step (a launch bound by wave dispatch that leaves
+    // the GPU all but empty) and its launch boundaries then hide behind the other group's sweep.  A step resets the next sweep's bins
+    // of ITS group only: the other group may be one sweep behind and still reading that buffer.  Sweep numbers (list stamps, the
+    // parity of the bin buffers) advance alike in both groups.  Not for a batch that shares its pre-pass (n_shared > 0), not when
+    // every sweep stores its labels (the repeat among them), not under the pre-pass developer switches.  By default only when each
+    // group fills the device at least once (spatial_residency): below that a launch does not fill it and the split buys nothing.
+    // OBIA_PREPASS_GROUPS (developer switch, read per batch: A/B timing, tests/test_gpu_prepass_groups.py): 0 never, 2 at any size.
+    int grp_split = 0;   // > 0: the groups are the problems [0, grp_split) and [grp_split, nprob)
+    {
+        const char *e = std::getenv("OBIA_PREPASS_GROUPS");
+        const int mode = !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1));
+        if (mode != 0 && n_shared == 0 && b.masked && pre_iter >= 2 && !store_all && !prepass_visits && !prep_grouped && !b.direct &&
+            b.nprob >= 2 && !std::getenv("OBIA_DEBUG_SYNC")) {   // (the stage-by-stage synchronisation watches one stream)
+            long long best = -1;
+            for (int p = 1; p < b.nprob; ++p) {
+                const long long t0 = b.probs[p].tile_off, t1 = b.total_tiles_all - t0, d = t0 > t1 ? t0 - t1 : t1 - t0;
+                if (t0 > 0 && t1 > 0 && (best < 0 || d <= best)) { best = d; grp_split = p; }   // (a tie: the later split)
+            }
+            if (grp_split > 0 && mode != 2) {
+                const long long t0 = b.probs[grp_split].tile_off, t1 = b.total_tiles_all - t0;
+                if ((t0 < t1 ? t0 : t1) < (long long)spatial_residency(ctx, b.CP)) grp_split = 0;
+            }
+            if (grp_split > 0) OBIA_TRY(side_stream(ctx));
+        }
+    }
     OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
     OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
     // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
@@ -1817,18 +1872,65 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             const dim3 prep_grid(cdiv(shared_sweep ? kmax_act : kmax, 64), shared_sweep ? n_act : b.nprob);
             const int prep_base = shared_sweep ? act_p_base : 0;
             const int *prep_table = shared_sweep ? d_act_probs : nullptr;
+            // (a launch steps the problems [p_base, p_base + grid.y), or those the table names, and resets the bins [cell_base, cell_end)
+            // of the next sweep's buffer)
 #define LAUNCH_PREP_LANE(CPV)                                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), prep_grid, dim3(64), 0, ctx->stream, \
-                       b.d_probs, prep_base, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
-                       b.total_cells, fp.bin_stamp, sweep_no, 0, b.d_ref, b.d_tl_req, prep_table)
-            if (!prep_grouped) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), pgrid, dim3(64), 0, stream, \
+                       b.d_probs, p_base, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
+                       cell_end, fp.bin_stamp, sweep_no, cell_base, b.d_ref, b.d_tl_req, table)
+            auto prep_lane = [&](hipStream_t stream, dim3 pgrid, int p_base, const int *table, int cell_base, int cell_end) {
                 switch (b.CP) {
                     case 4: LAUNCH_PREP_LANE(4); break;
                     case 8: LAUNCH_PREP_LANE(8); break;
                     case 12: LAUNCH_PREP_LANE(12); break;
                     default: LAUNCH_PREP_LANE(16); break;
                 }
-            } else if (RQ == 16)
+            };
+#undef LAUNCH_PREP_LANE
+            if (grp_split > 0 && ignore_color && it < iters - 1) {
+                // one of the sweeps slic_spatial_kernel decides (see launch_assign: spatial-only, no labels stored), as two groups
+                hipError_t he = hipSuccess;
+                if (it == 0) {   // fork: behind the batch's fills and whatever else this stream holds for the batch
+                    he = hipEventRecord(ctx->grp_fork, ctx->stream);
+                    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->side, ctx->grp_fork, 0);
+                }
+                for (int g = 0; g < 2 && he == hipSuccess; ++g) {
+                    const int p0 = g ? grp_split : 0, p1 = g ? b.nprob : grp_split;
+                    int kmax_g = 1;
+                    for (int p = p0; p < p1; ++p) if (b.probs[p].K > kmax_g) kmax_g = b.probs[p].K;
+                    const hipStream_t st = g ? ctx->side : ctx->stream;
+                    prep_lane(st, dim3(cdiv(kmax_g, 64), p1 - p0), p0, nullptr, b.probs[p0].cell_off, g ? b.total_cells : b.probs[p1].cell_off);
+                    KernelSpan span(ctx, T_PREPASS);
+                    TileSubset sub;
+                    sub.base = b.probs[p0].tile_off;
+                    sub.end = g ? (int)b.total_tiles_all : b.probs[p1].tile_off;
+                    unsigned long long *pxc = ctx->profiling ? d_px + 256 : nullptr;
+                    switch (b.CP) {   // (accumulate, no colours, no labels, lists in use: what the ungrouped launch below passes for this sweep)
+                        case 8: launch_assign<8>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+#ifndef OBIA_ONLY_CP8
+                        case 4: launch_assign<4>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                        case 12: launch_assign<12>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                        case 16: launch_assign<16>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+#endif
+                        default: he = hipErrorInvalidValue; break;
+                    }
+                    ctx->timing.prepass_group_launches += 1;
+                }
+                if (he == hipSuccess && it == iters - 2) {   // join: in front of the whole-batch step of the last pre-pass sweep, before anything else is queued
+                    he = hipEventRecord(ctx->grp_join, ctx->side);
+                    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->grp_join, 0);
+                }
+                if (he != hipSuccess) {   // nothing may be left running on the side stream when the caller gets the error
+                    (void)hipStreamSynchronize(ctx->side);
+                    set_error("grouped pre-pass: %s", hipGetErrorString(he));
+                    return OBIA_E_HIP;
+                }
+                b.d_head_cur = head_cur;
+                first = false;
+                continue;
+            }
+            if (!prep_grouped) prep_lane(ctx->stream, prep_grid, prep_base, prep_table, 0, b.total_cells);
+            else if (RQ == 16)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<16>), dim3(cdiv(b.total_cent * 16LL, 256)), dim3(256), 0,
                                    ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
                                    1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
@@ -1836,7 +1938,6 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<32>), dim3(cdiv(b.total_cent * 32LL, 256)), dim3(256), 0,
                                    ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
                                    1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
-#undef LAUNCH_PREP_LANE
             b.d_head_cur = head_cur;
             debug_sync(ctx, "sweeps: prep");
             first = false;
