@@ -1,4 +1,4 @@
-"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h).
+"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h and include/obia_image.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -145,6 +145,16 @@ _SIGNATURES = {
     "obia_last_timing": (ctypes.c_double, [_P, _I]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# include/obia_image.h: the image-preview entry points, a table of their own (obia_hip.h's is pinned one to one by the
+# guarded-output registry of the test suite; this one by tests/test_image_cpu.py and tests/test_gpu_image_buffers.py)
+_IMAGE_SIGNATURES = {
+    "obia_image_stretch_u8_dev": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
+    "obia_image_gray_hist_dev": (_I, [_P, _P, _I, ctypes.c_int64, _P, _P]),
+    "obia_image_lut_u8_dev": (_I, [_P, _P, ctypes.c_int64, _P, _I, _P]),
+    "obia_image_clahe_u8_dev": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "obia_image_boundaries_dev": (_I, [_P, _P, _I, _I, _P]),
+    "obia_image_mark_u8_dev": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
+}
 
 _lib = None
 
@@ -166,7 +176,7 @@ def load():
             raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

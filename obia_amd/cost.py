@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from . import _device, _lib
+from . import _device, _lib, _percentile
 
 try:
     import torch
@@ -46,34 +46,13 @@ def _as_dev(x, dtype, dev):
 
 
 def _lerp(n, a, b, dtype):
-    """np.nanpercentile(x, (2, 98)) from the order statistics: a[k], b[k] = the values of rank floor(v_k) and floor(v_k) + 1
-    (both the last value when v_k >= n - 1) at the virtual index v_k = (n - 1) * q_k.  NumPy's _lerp: the difference in the
-    input dtype, the weight in float64, the upper half computed from b."""
-    if n == 0:
-        return np.full(2, np.nan, dtype)
-    v = (n - 1) * _Q
-    prev = np.floor(v)
-    prev[v >= n - 1] = -1
-    gamma = v - prev.astype(np.intp)
-    a = np.asarray(a, dtype)
-    b = np.asarray(b, dtype)
-    diff = np.subtract(b, a)
-    out = np.add(a, diff * gamma)
-    np.subtract(b, diff * (1 - gamma), out=out, where=gamma >= 0.5, casting="unsafe", dtype=out.dtype)
-    return out
+    """np.nanpercentile(x, (2, 98)) from the four order statistics (obia_amd._percentile.lerp at q = 0.02, 0.98)."""
+    return _percentile.lerp(n, a, b, dtype, _Q)
 
 
 def _select(lib, c, plane):
     """(lo, hi) = np.nanpercentile(plane, (2, 98)) of a float32 / float64 device plane, and the number of valid values."""
-    f64 = plane.dtype == torch.float64
-    n = ctypes.c_int64(0)
-    bits = (ctypes.c_uint64 * 4)()
-    _lib.check(lib.obia_cost_select_dev(c.handle, plane.data_ptr(), int(f64), plane.numel(), float(_Q[0]), float(_Q[1]),
-                                        ctypes.byref(n), bits))
-    raw = np.array(list(bits), np.uint64)
-    vals = raw.view(np.float64) if f64 else raw.astype(np.uint32).view(np.float32)
-    lohi = _lerp(int(n.value), vals[[0, 2]], vals[[1, 3]], np.float64 if f64 else np.float32)
-    return float(lohi[0]), float(lohi[1]), int(n.value)
+    return _percentile.select(lib, c, plane, _Q)
 
 
 def _edge_lohi(lib, c, lab, H, W):

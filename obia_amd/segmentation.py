@@ -588,6 +588,29 @@ class Segments:
         from .polygons import polygonize
         return polygonize(self._segments, affine_transformation=affine_transformation, start_label=start_label, ctx=ctx)
 
+    def to_segmented_image(self, image, *, as_array=False, ctx=None):
+        """segment.py:41-53: ``(mark_boundaries(np.array(image), self._segments) * 255).astype(uint8)`` -- yellow at the "outer"
+        boundaries of the label raster, background label 0 -- of a PIL image (mode L or RGB) as large as ``_segments``, on the GPU
+        (obia_amd.image.mark_boundaries_u8).  Returns a PIL image; ``as_array=True`` returns the uint8 (H, W, 3) array instead, a
+        CUDA tensor when ``_segments`` is one."""
+        try:
+            from PIL.Image import Image as PILImage, fromarray
+        except Exception:  # pragma: no cover
+            PILImage = ()
+        if not isinstance(image, PILImage):
+            raise TypeError('Input must be a PIL Image')
+        img = np.array(image)
+        seg_shape = tuple(self._segments.shape)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3):
+            raise ValueError(f"to_segmented_image takes an 8-bit grey (L) or RGB image, got mode {image.mode!r}")
+        if img.shape[:2] != seg_shape:
+            raise ValueError(f"the image is {img.shape[0]} x {img.shape[1]}, the label raster {seg_shape[0]} x {seg_shape[1]}")
+        from .image import mark_boundaries_u8
+        out = mark_boundaries_u8(img, self._segments, ctx=ctx)
+        if as_array:
+            return out
+        return fromarray(out.cpu().numpy() if hasattr(out, "cpu") else out)
+
     def write_segments(self, file_path):
         """segment.py:55-60 (``self.segments.to_file(file_path)``): GeoDataFrame.to_file when geopandas is there; else a
         GeoPackage written by obia_amd.geopackage (``.gpkg``) or a CSV without the geometry."""
