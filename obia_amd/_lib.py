@@ -1,4 +1,4 @@
-"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h and include/obia_image.h).
+"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h and include/obia_sharpness.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -155,6 +155,16 @@ _IMAGE_SIGNATURES = {
     "obia_image_boundaries_dev": (_I, [_P, _P, _I, _I, _P]),
     "obia_image_mark_u8_dev": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
 }
+# include/obia_sharpness.h: the sharpness raster, a third table (the first is pinned by the guarded-output registry, the second to its
+# six symbols by tests/test_image_cpu.py; this one by tests/test_sharpness_cpu.py and tests/test_gpu_sharpness_buffers.py)
+SHARP_MAX_WIN = 65536     # OBIA_SHARP_MAX_WIN
+_SHARPNESS_SIGNATURES = {
+    "obia_sharp_gray_lap_dev": (_I, [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P, _P]),
+    "obia_sharp_laplacian_dev": (_I, [_P, _P, _I, _I, _P, _P]),
+    "obia_sharp_box_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "obia_sharp_variance_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "obia_sharp_stretch_f32_dev": (_I, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
+}
 
 _lib = None
 
@@ -176,7 +186,7 @@ def load():
             raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

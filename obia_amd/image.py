@@ -5,13 +5,23 @@ in libobia_hip.so (csrc/image.hip, include/obia_image.h); the host interpolates 
 device selects and builds the 256-entry equalisation table from the histogram the device counts.  NumPy in -> NumPy out, CUDA tensor
 in -> CUDA tensor out.
 
+The sharpness raster of the same module of the reference (obia/utils/image.py:97-136) is here too: ``rgb_to_gray``, ``box_filter``
+(``scipy.ndimage.uniform_filter``), ``variance_of_laplacian`` and ``laplacian`` (csrc/sharpness.hip, include/obia_sharpness.h).
+
 What the results are pinned to:
   * ``rescale_to_8bit``: the reference's three NumPy expressions, evaluated literally;
   * ``find_boundaries`` / ``mark_boundaries_u8``: scikit-image 0.18.3, through committed goldens;
   * ``apply_histogram_equalization`` / ``apply_clahe``: OpenCV's algorithms (cvtColor RGB2GRAY, equalizeHist, CLAHE) RESTATED in
     tests/image_restatement.py.  They are NOT compared with ``cv2`` anywhere: OpenCV is not installed where the tests run.
+  * ``box_filter``: SciPy 1.15.3's ``uniform_filter`` bit for bit, through committed goldens -- a serial running sum in double along
+    every line, which the kernels walk in SciPy's order (DESIGN.md 3.5n);
+  * ``rgb_to_gray`` and the stretch of ``laplacian``: the reference's NumPy expressions, evaluated literally;
+  * the 3 x 3 Laplacian of ``variance_of_laplacian``: ``cv2.Laplacian(gray, CV_32F, ksize=3)`` RESTATED in
+    tests/sharpness_restatement.py (filter2D with [[2, 0, 2], [0, -8, 0], [2, 0, 2]], BORDER_REFLECT_101, float32 accumulation over the
+    taps in row-major order).  It is NOT compared with ``cv2`` anywhere either.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -250,6 +260,168 @@ class Image:
     def to_image(self, bands, p_min=2, p_max=98, stretch_type=None, *, as_array=False, ctx=None):
         """:func:`to_image` of this raster."""
         return to_image(self, bands, p_min=p_min, p_max=p_max, stretch_type=stretch_type, as_array=as_array, ctx=ctx)
+
+    def laplacian(self, win, out_path=None, *, bands=(1, 2, 4), ctx=None):
+        """:func:`laplacian` of this raster."""
+        return laplacian(self, out_path, win, bands=bands, ctx=ctx)
+
+
+# -------------------------------------------------------------------------------------------------------- sharpness raster
+_GRAY_COEFFS = (0.299, 0.587, 0.114)
+
+
+def _check_win(win, who):
+    if isinstance(win, bool) or not isinstance(win, (int, np.integer)) or win < 1:
+        raise ValueError(f"{who}: win must be an integer >= 1, got {win!r}")
+    if win > _lib.SHARP_MAX_WIN:
+        raise NotImplementedError(f"{who}: win {win} is larger than {_lib.SHARP_MAX_WIN}")
+    return int(win)
+
+
+def _check_plane(x, who, what):
+    """shape of a non-empty (H, W) plane of a dtype the module takes as float32"""
+    name = _dtype_name(x)
+    if name not in _FLOAT_IN:
+        raise TypeError(f"{who} takes float32, float64, uint8, uint16 or int16, got {name}")
+    shp = _shape(x)
+    if len(shp) != 2 or 0 in shp:
+        raise ValueError(f"{who} takes a non-empty (H, W) {what}, got shape {shp}")
+    if shp[0] * shp[1] > _MAX_SELECT:
+        raise NotImplementedError(f"{who}: {shp[0] * shp[1]} pixels; the percentile select takes fewer than 2^32 - 1")
+    return shp
+
+
+def _raise_nonfinite(lib, c, counter, who, what):
+    """the one counter a sharpness call reads back"""
+    _device.end(lib, c)
+    bad = int(counter.item())
+    if bad:
+        raise ValueError(f"{who}: {bad} NaN or infinite values in {what} (the reference would write an all-NaN raster)")
+
+
+def rgb_to_gray(rgb):
+    """obia.utils.image.rgb_to_gray: ``(rgb * float32([0.299, 0.587, 0.114])).sum(axis=-1)`` of an (H, W, 3) raster taken as float32,
+    which for three elements is ``(r * 0.299f + g * 0.587f) + b * 0.114f`` with every product and sum rounded to float32.  Plain
+    elementwise torch on the device (one rounding per operation, nothing fused): bit-equal to the NumPy expression."""
+    _need_torch()
+    shp = _shape(rgb)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"rgb_to_gray takes an (H, W, 3) raster, got shape {shp}")
+    name = _dtype_name(rgb)
+    if name not in _FLOAT_IN:
+        raise TypeError(f"rgb_to_gray takes float32, float64, uint8, uint16 or int16, got {name}")
+    is_t = _device.is_torch(rgb)
+    dev = _device.device_of(None, rgb)
+    x = _device.as_dev(rgb, torch.float32, dev)
+    c0, c1, c2 = (float(np.float32(v)) for v in _GRAY_COEFFS)
+    gray = (x[..., 0] * c0 + x[..., 1] * c1) + x[..., 2] * c2
+    return _device.out(gray, is_t)
+
+
+def box_filter(plane, win, ctx=None):
+    """``scipy.ndimage.uniform_filter(plane.astype(float32), size=win)`` (mode "reflect") of an (H, W) plane, bit for bit with SciPy
+    1.15.3: the running sum in double along every column, then along every row of that float32 result, each line walked by one lane
+    in SciPy's order.  Deviation: a NaN or an infinity in the plane raises ValueError."""
+    _need_torch()
+    win = _check_win(win, "box_filter")
+    H, W = _check_plane(plane, "box_filter", "plane")
+    is_t = _device.is_torch(plane)
+    dev = _device.device_of(ctx, plane)
+    x = _device.as_dev(plane, torch.float32, dev)
+    work = torch.empty((H, W), dtype=torch.float32, device=x.device)
+    out = torch.empty((H, W), dtype=torch.float32, device=x.device)
+    bad = torch.empty(1, dtype=torch.int64, device=x.device)
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_sharp_box_dev(c.handle, x.data_ptr(), H, W, win, work.data_ptr(), out.data_ptr(), bad.data_ptr()))
+    _raise_nonfinite(lib, c, bad, "box_filter", "the plane")
+    return _device.out(out, is_t)
+
+
+def _variance_dev(lib, c, lap, win):
+    """variance of the Laplacian from the device plane ``lap``"""
+    H, W = lap.shape
+    work = torch.empty((2, H, W), dtype=torch.float32, device=lap.device)
+    out = torch.empty((H, W), dtype=torch.float32, device=lap.device)
+    _lib.check(lib.obia_sharp_variance_dev(c.handle, lap.data_ptr(), H, W, win, work.data_ptr(), out.data_ptr()))
+    _device.end(lib, c)              # work is still alive here
+    return out
+
+
+def variance_of_laplacian(gray, win, ctx=None):
+    """obia.utils.image.variance_of_laplacian: ``lap = cv2.Laplacian(gray, CV_32F, ksize=3)``, ``mean = uniform_filter(lap, win)``,
+    ``mean2 = uniform_filter(lap * lap, win)``, ``mean2 - mean ** 2`` in float32, of an (H, W) plane taken as float32.  The Laplacian
+    is OpenCV's restated and NOT compared with cv2 anywhere (module docstring).  Deviation: a NaN or an infinity in ``gray`` raises
+    ValueError.  A ``gray`` whose squared Laplacian overflows float32 is not specified."""
+    _need_torch()
+    win = _check_win(win, "variance_of_laplacian")
+    H, W = _check_plane(gray, "variance_of_laplacian", "grey plane")
+    is_t = _device.is_torch(gray)
+    dev = _device.device_of(ctx, gray)
+    x = _device.as_dev(gray, torch.float32, dev)
+    lap = torch.empty((H, W), dtype=torch.float32, device=x.device)
+    bad = torch.empty(1, dtype=torch.int64, device=x.device)
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_sharp_laplacian_dev(c.handle, x.data_ptr(), H, W, lap.data_ptr(), bad.data_ptr()))
+    _raise_nonfinite(lib, c, bad, "variance_of_laplacian", "the grey plane")
+    return _device.out(_variance_dev(lib, c, lap, win), is_t)
+
+
+def laplacian(image, out_path, win, *, bands=(1, 2, 4), ctx=None):
+    """obia.utils.image.laplacian(in_path, out_path, win) at array level: the three ``bands`` (0-based; the default is the reference's
+    1-based [2, 3, 5]) of an (H, W, C) raster -- an array, a CUDA tensor or an :class:`Image` -- as float32, each normalised by
+    ``(x - min) / ((max - min) + 1e-8)``, :func:`rgb_to_gray`, :func:`variance_of_laplacian` with window ``win``, then
+    ``np.clip((sharp - lo) / (hi - lo), 0, 1)`` in float64 between the 2nd and 98th percentiles of ``sharp``, as float32 (H, W).
+    ``hi == lo`` is taken literally: NaN where ``sharp == lo``, 0 below, 1 above (a constant raster gives all NaN).
+
+    ``out_path`` must be None and ``image`` must not be a path: GeoTIFF I/O stays with the caller.  Deviation: a NaN or
+    an infinity in one of the three bands raises ValueError (the reference writes an all-NaN raster)."""
+    _need_torch()
+    if out_path is not None:
+        raise NotImplementedError("laplacian: out_path must be None -- GeoTIFF I/O stays with the caller (DESIGN.md 6); write the "
+                                  "returned raster with rasterio")
+    if isinstance(image, (str, bytes, os.PathLike)):
+        raise NotImplementedError("laplacian takes the raster itself, not a path -- GeoTIFF I/O stays with the caller (DESIGN.md 6); "
+                                  "read it with rasterio and move the bands last")
+    win = _check_win(win, "laplacian")
+    img = image.img_data if hasattr(image, "img_data") else image
+    shp = _shape(img)
+    if not isinstance(bands, (list, tuple)) or len(bands) != 3:
+        raise ValueError("'bands' should be a list or tuple of exactly three elements")
+    if len(shp) != 3:
+        raise ValueError(f"laplacian takes an (H, W, C) raster, got shape {shp}")
+    _check_bands(bands, shp[2], None)
+    if 0 in shp:
+        raise ValueError("laplacian of an empty raster")
+    name = _dtype_name(img)
+    if name not in _FLOAT_IN:
+        raise TypeError(f"laplacian takes float32, float64, uint8, uint16 or int16, got {name}")
+    H, W, C = shp
+    if H * W > _MAX_SELECT:
+        raise NotImplementedError(f"laplacian: {H * W} pixels; the percentile select takes fewer than 2^32 - 1")
+    is_t = _device.is_torch(img)
+    dev = _device.device_of(ctx, img)
+    idx = [int(b) for b in bands]
+    if is_t and img.dtype == torch.float32:
+        x = img.to(device=f"cuda:{dev}").contiguous()         # the kernels pick the bands out of the raster as it is
+    elif is_t:
+        x, idx = img.to(device=f"cuda:{dev}")[:, :, idx].to(torch.float32).contiguous(), [0, 1, 2]
+    else:
+        x = torch.as_tensor(np.ascontiguousarray(np.asarray(img)[:, :, idx], dtype=np.float32), device=f"cuda:{dev}")
+        idx = [0, 1, 2]
+    lap = torch.empty((H, W), dtype=torch.float32, device=x.device)
+    bad = torch.empty(1, dtype=torch.int64, device=x.device)
+    lib, c = _device.begin(dev, ctx)
+    _lib.check(lib.obia_sharp_gray_lap_dev(c.handle, x.data_ptr(), H, W, x.shape[2], (ctypes.c_int32 * 3)(*idx), lap.data_ptr(),
+                                           bad.data_ptr()))
+    _raise_nonfinite(lib, c, bad, "laplacian", f"bands {tuple(int(b) for b in bands)}")
+    del x
+    sharp = _variance_dev(lib, c, lap, win)
+    del lap
+    lo, hi, _ = _percentile.select(lib, c, sharp, _percentile.quantiles(2, 98))
+    out = torch.empty((H, W), dtype=torch.float32, device=sharp.device)
+    _lib.check(lib.obia_sharp_stretch_f32_dev(c.handle, sharp.data_ptr(), H * W, lo, hi, out.data_ptr()))
+    _device.end(lib, c)
+    return _device.out(out, is_t)
 
 
 # ------------------------------------------------------------------------------------------------------------- boundaries
