@@ -8,12 +8,6 @@ using namespace obia;
 
 namespace {
 
-int check_ctx(obia_ctx *ctx) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", ctx->device); return OBIA_E_HIP; }
-    return OBIA_OK;
-}
-
 int check_slic_args(const float *img, int H, int W, int C, const obia_slic_params *p) {
     if (!img || !p) { set_error("null image or params"); return OBIA_E_INVALID; }
     if (H <= 0 || W <= 0 || C <= 0) { set_error("bad image shape (%d,%d,%d)", H, W, C); return OBIA_E_INVALID; }
@@ -97,18 +91,13 @@ static int check_seeds(const obia_slic_seeds *seeds, int H, int W, ExternalSeeds
 // alone) and of obia_slic_stages_f32_dev.
 static int slic_stages_impl(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                             const obia_slic_params *params, const ExternalSeeds *ext, obia_slic_stages *st) {
-    OBIA_TRY(check_ctx(ctx));
     OBIA_TRY(check_slic_args(img, H, W, C, params));
     if (!st) { set_error("null output"); return OBIA_E_INVALID; }
     if (st->prepass_iters < 0) { set_error("prepass_iters must be >= 0"); return OBIA_E_INVALID; }
     if (st->centroids && params->max_num_iter < 1) { set_error("centroids: no sweep ran (max_num_iter = 0)"); return OBIA_E_INVALID; }
-    ctx->arena.reset();
-    begin_timing(ctx);
     SlicBatch b;
-    int rc;
-    {
-        ScopedSpan total(ctx, T_TOTAL);
-        rc = slic_single(ctx, img, H, W, C, mask, params, b, ext, st->prepass_only != 0, st->prepass_iters);
+    OBIA_TRY(call_frame(ctx, FRAME_TOTAL, [&] {
+        int rc = slic_single(ctx, img, H, W, C, mask, params, b, ext, st->prepass_only != 0, st->prepass_iters);
         if (rc == OBIA_OK && (st->seeds_yx || st->centroids) && b.probs[0].K > st->centroid_capacity) {
             set_error("%d centroids, room for %d", b.probs[0].K, st->centroid_capacity);
             rc = OBIA_E_INVALID;
@@ -119,10 +108,8 @@ static int slic_stages_impl(obia_ctx *ctx, const float *img, int H, int W, int C
         }
         if (rc == OBIA_OK && (st->features || st->seeds_yx || st->centroids))
             rc = slic_stage_outputs(ctx, b, st->features, st->seeds_yx, st->centroids);
-    }
-    if (rc != OBIA_OK) return rc;
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
+        return rc;
+    }));
     st->K = b.probs[0].K;
     st->step = (double)b.step[0];
     st->prescale = (double)b.prescale;
@@ -143,48 +130,41 @@ static int slic_assign_only_impl(obia_ctx *ctx, const float *img, int H, int W, 
 
 static int slic_full_impl(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                           const obia_slic_params *params, const ExternalSeeds *ext, int32_t *labels_out, int *n_labels_out) {
-    OBIA_TRY(check_ctx(ctx));
     OBIA_TRY(check_slic_args(img, H, W, C, params));
     if (!labels_out) { set_error("null output"); return OBIA_E_INVALID; }
-    ctx->arena.reset();
-    begin_timing(ctx);
     SlicBatch b;
     int n_labels = 0;
-    int rc;
-    {
-        ScopedSpan total(ctx, T_TOTAL);
-        rc = slic_single(ctx, img, H, W, C, mask, params, b, ext);
-        if (rc == OBIA_OK) {
-            if (params->enforce_connectivity) {
-                const auto [min_size, max_size] = slic_cc_sizes(params->min_size_factor, params->max_size_factor, b.probs[0].n_valid, b.probs[0].K);
-                rc = enforce_connectivity_dev(ctx, b.d_labels, H, W, min_size, max_size, params->start_label, labels_out, &n_labels);
-            } else {
-                hipError_t e = hipMemcpyAsync(labels_out, b.d_labels, sizeof(int32_t) * (size_t)H * W, hipMemcpyDeviceToDevice, ctx->stream);
-                if (e != hipSuccess) { set_error("copy failed: %s", hipGetErrorString(e)); rc = OBIA_E_HIP; }
-                n_labels = b.probs[0].K;
-            }
+    OBIA_TRY(call_frame(ctx, FRAME_TOTAL, [&]() -> int {
+        OBIA_TRY(slic_single(ctx, img, H, W, C, mask, params, b, ext));
+        if (params->enforce_connectivity) {
+            const auto [min_size, max_size] = slic_cc_sizes(params->min_size_factor, params->max_size_factor, b.probs[0].n_valid, b.probs[0].K);
+            return enforce_connectivity_dev(ctx, b.d_labels, H, W, min_size, max_size, params->start_label, labels_out, &n_labels);
         }
-    }
-    if (rc != OBIA_OK) return rc;
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
+        hipError_t e = hipMemcpyAsync(labels_out, b.d_labels, sizeof(int32_t) * (size_t)H * W, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) { set_error("copy failed: %s", hipGetErrorString(e)); return OBIA_E_HIP; }
+        n_labels = b.probs[0].K;
+        return OBIA_OK;
+    }));
     if (n_labels_out) *n_labels_out = n_labels;
     return OBIA_OK;
 }
 
 int obia_slic_assign_only_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                                   const obia_slic_params *params, int32_t *labels_pre_out, int *n_centroids_out) {
+    OBIA_TRY(enter(ctx));
     return slic_assign_only_impl(ctx, img, H, W, C, mask, params, nullptr, labels_pre_out, n_centroids_out);
 }
 
 int obia_slic_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                       const obia_slic_params *params, int32_t *labels_out, int *n_labels_out) {
+    OBIA_TRY(enter(ctx));
     return slic_full_impl(ctx, img, H, W, C, mask, params, nullptr, labels_out, n_labels_out);
 }
 
 int obia_slic_seeded_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                              const obia_slic_params *params, const obia_slic_seeds *seeds, int stage,
                              int32_t *labels_out, int *n_out) {
+    OBIA_TRY(enter(ctx));
     if (H <= 0 || W <= 0) { set_error("bad image shape"); return OBIA_E_INVALID; }
     ExternalSeeds ext{};
     OBIA_TRY(check_seeds(seeds, H, W, ext));
@@ -195,6 +175,7 @@ int obia_slic_seeded_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int 
 
 int obia_slic_stages_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                              const obia_slic_params *params, const obia_slic_seeds *seeds, obia_slic_stages *stages) {
+    OBIA_TRY(enter(ctx));
     if (!seeds) return slic_stages_impl(ctx, img, H, W, C, mask, params, nullptr, stages);
     if (H <= 0 || W <= 0) { set_error("bad image shape"); return OBIA_E_INVALID; }
     ExternalSeeds ext{};
@@ -214,7 +195,7 @@ static int check_picks(const char *what, const int64_t *v, long long n) {
 
 int obia_mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, const int64_t *picks, int32_t n_picks,
                             const int64_t *dense_picks, int64_t n_dense, int iters, double *centroids_yx_out, double *steps_zyx_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!mask || !picks || !centroids_yx_out || !steps_zyx_out) { set_error("mask centroids: null pointer argument"); return OBIA_E_INVALID; }
     if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) { set_error("mask centroids: bad mask shape (%d, %d)", H, W); return OBIA_E_INVALID; }
     if (n_picks < 1) { set_error("mask centroids: need at least one pick (got %d)", n_picks); return OBIA_E_INVALID; }
@@ -228,41 +209,26 @@ int obia_mask_centroids_dev(obia_ctx *ctx, const uint8_t *mask, int H, int W, co
 
 int obia_slic_f32(obia_ctx *ctx, const float *img, int H, int W, int C, const uint8_t *mask,
                   const obia_slic_params *params, int32_t *labels_out, int *n_labels_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     OBIA_TRY(check_slic_args(img, H, W, C, params));
     if (!labels_out) { set_error("null output"); return OBIA_E_INVALID; }
     const size_t npix = (size_t)H * W;
-    float *d_img = nullptr;
-    uint8_t *d_mask = nullptr;
-    int32_t *d_lab = nullptr;
-    int rc = OBIA_OK;
-    // caller-visible buffers are not part of the workspace arena: plain allocations for the call
-    if (hipMalloc(&d_img, npix * C * sizeof(float)) != hipSuccess || hipMalloc(&d_lab, npix * sizeof(int32_t)) != hipSuccess ||
-        (mask && hipMalloc(&d_mask, npix) != hipSuccess)) {
-        set_error("device allocation for host-pointer call failed");
-        rc = OBIA_E_NOMEM;
-    }
-    if (rc == OBIA_OK && hipMemcpyAsync(d_img, img, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK && mask && hipMemcpyAsync(d_mask, mask, npix, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK) rc = obia_slic_f32_dev(ctx, d_img, H, W, C, d_mask, params, d_lab, n_labels_out);
-    if (rc == OBIA_OK && hipMemcpyAsync(labels_out, d_lab, npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc == OBIA_E_HIP) set_error("host<->device copy failed in obia_slic_f32");
-    (void)hipFree(d_img); (void)hipFree(d_lab); (void)hipFree(d_mask);
-    return rc;
+    Staging s(ctx);
+    const float *d_img = s.in(img, npix * C);
+    const uint8_t *d_mask = s.in(mask, npix);
+    int32_t *d_lab = s.out<int32_t>(npix);
+    s.run([&] { return obia_slic_f32_dev(ctx, d_img, H, W, C, d_mask, params, d_lab, n_labels_out); });
+    s.fetch(labels_out, d_lab, npix);
+    return s.finish();
 }
 
 int obia_enforce_connectivity_i32_dev(obia_ctx *ctx, const int32_t *labels_in, int H, int W, int min_size, int max_size,
                                       int start_label, int32_t *labels_out, int *n_labels_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!labels_in || !labels_out || H <= 0 || W <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (start_label != 0 && start_label != 1) { set_error("start_label should be 0 or 1."); return OBIA_E_INVALID; }
-    ctx->arena.reset();
-    begin_timing(ctx);
     int n = 0;
-    OBIA_TRY(enforce_connectivity_dev(ctx, labels_in, H, W, min_size, max_size, start_label, labels_out, &n));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
+    OBIA_TRY(call_frame(ctx, FRAME_TIMING, [&] { return enforce_connectivity_dev(ctx, labels_in, H, W, min_size, max_size, start_label, labels_out, &n); }));
     if (n_labels_out) *n_labels_out = n;
     return OBIA_OK;
 }
@@ -270,102 +236,72 @@ int obia_enforce_connectivity_i32_dev(obia_ctx *ctx, const int32_t *labels_in, i
 int obia_zonal_stats_f32_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                              const int32_t *bands, int n_bands, int n_labels, int start_label, int64_t *count_out,
                              double *mean_out, double *var_out, float *min_out, float *max_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!raw || !labels || !count_out || !mean_out || !var_out || !min_out || !max_out) { set_error("null pointer argument"); return OBIA_E_INVALID; }
-    ctx->arena.reset();
-    begin_timing(ctx);
-    OBIA_TRY(zonal_stats_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, count_out, mean_out, var_out, min_out, max_out));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_TIMING, [&] {
+        return zonal_stats_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, count_out, mean_out, var_out, min_out, max_out);
+    });
 }
 
 int obia_zonal_stats_f32(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                          const int32_t *bands, int n_bands, int n_labels, int start_label, int64_t *count_out,
                          double *mean_out, double *var_out, float *min_out, float *max_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!raw || !labels || H <= 0 || W <= 0 || C <= 0 || n_labels < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     const size_t npix = (size_t)H * W;
     const int nb = bands ? n_bands : C;
     if (nb < 1 || nb > 16) { set_error("n_bands %d out of range (1..16)", nb); return OBIA_E_UNSUPPORTED; }
     const size_t nl = (size_t)(n_labels > 0 ? n_labels : 1), nlb = nl * nb;
-    float *d_raw = nullptr; int32_t *d_lab = nullptr;
-    char *d_out = nullptr;
-    const size_t out_bytes = nl * 8 + nlb * (8 + 8 + 4 + 4);
-    int rc = OBIA_OK;
-    if (hipMalloc(&d_raw, npix * C * sizeof(float)) != hipSuccess || hipMalloc(&d_lab, npix * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&d_out, out_bytes) != hipSuccess) {
-        set_error("device allocation for host-pointer call failed");
-        rc = OBIA_E_NOMEM;
+    Staging s(ctx);
+    const float *d_raw = s.in(raw, npix * C);
+    const int32_t *d_lab = s.in(labels, npix);
+    int64_t *d_cnt = s.out<int64_t>(nl);
+    double *d_mean = s.out<double>(nlb), *d_var = s.out<double>(nlb);
+    float *d_mn = s.out<float>(nlb), *d_mx = s.out<float>(nlb);
+    s.run([&] { return obia_zonal_stats_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_cnt, d_mean, d_var, d_mn, d_mx); });
+    if (n_labels > 0) {
+        s.fetch(count_out, d_cnt, nl);
+        s.fetch(mean_out, d_mean, nlb);
+        s.fetch(var_out, d_var, nlb);
+        s.fetch(min_out, d_mn, nlb);
+        s.fetch(max_out, d_mx, nlb);
     }
-    int64_t *d_cnt = (int64_t *)d_out;
-    double *d_mean = (double *)(d_out + nl * 8), *d_var = d_mean + nlb;
-    float *d_mn = (float *)(d_var + nlb), *d_mx = d_mn + nlb;
-    if (rc == OBIA_OK && hipMemcpyAsync(d_raw, raw, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK && hipMemcpyAsync(d_lab, labels, npix * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK) rc = obia_zonal_stats_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_cnt, d_mean, d_var, d_mn, d_mx);
-    if (rc == OBIA_OK && n_labels > 0) {
-        bool ok = hipMemcpyAsync(count_out, d_cnt, nl * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(mean_out, d_mean, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(var_out, d_var, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(min_out, d_mn, nlb * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(max_out, d_mx, nlb * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        if (!ok) rc = OBIA_E_HIP;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc == OBIA_E_HIP) set_error("host<->device copy failed in obia_zonal_stats_f32");
-    (void)hipFree(d_raw); (void)hipFree(d_lab); (void)hipFree(d_out);
-    return rc;
+    return s.finish();
 }
 
 int obia_zonal_moments_f32_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                                const int32_t *bands, int n_bands, int n_labels, int start_label, const double *mean_dev,
                                double *skew_out, double *kurt_out, double *var_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!raw || !labels || !mean_dev || !skew_out || !kurt_out) { set_error("null pointer argument"); return OBIA_E_INVALID; }
-    ctx->arena.reset();
-    begin_timing(ctx);
-    OBIA_TRY(zonal_moments_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, mean_dev, skew_out, kurt_out, var_out));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_TIMING, [&] {
+        return zonal_moments_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, mean_dev, skew_out, kurt_out, var_out);
+    });
 }
 
 int obia_zonal_moments_f32(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C,
                            const int32_t *bands, int n_bands, int n_labels, int start_label, double *skew_out,
                            double *kurt_out, double *var_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!raw || !labels || !skew_out || !kurt_out || H <= 0 || W <= 0 || C <= 0 || n_labels < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     const size_t npix = (size_t)H * W;
     const int nb = bands ? n_bands : C;
     if (nb < 1 || nb > 16) { set_error("n_bands %d out of range (1..16)", nb); return OBIA_E_UNSUPPORTED; }
     const size_t nl = (size_t)(n_labels > 0 ? n_labels : 1), nlb = nl * nb;
-    float *d_raw = nullptr; int32_t *d_lab = nullptr;
-    char *d_out = nullptr;
-    const size_t out_bytes = nl * 8 + nlb * (8 + 8 + 4 + 4 + 8 + 8);
-    int rc = OBIA_OK;
-    if (hipMalloc(&d_raw, npix * C * sizeof(float)) != hipSuccess || hipMalloc(&d_lab, npix * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&d_out, out_bytes) != hipSuccess) {
-        set_error("device allocation for host-pointer call failed");
-        rc = OBIA_E_NOMEM;
+    Staging s(ctx);
+    const float *d_raw = s.in(raw, npix * C);
+    const int32_t *d_lab = s.in(labels, npix);
+    int64_t *d_cnt = s.out<int64_t>(nl);
+    double *d_mean = s.out<double>(nlb), *d_var = s.out<double>(nlb), *d_skew = s.out<double>(nlb), *d_kurt = s.out<double>(nlb);
+    float *d_mn = s.out<float>(nlb), *d_mx = s.out<float>(nlb);
+    s.run([&] { return obia_zonal_stats_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_cnt, d_mean, d_var, d_mn, d_mx); });
+    s.run([&] { return obia_zonal_moments_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_mean, d_skew, d_kurt, d_var); });
+    if (n_labels > 0) {
+        s.fetch(skew_out, d_skew, nlb);
+        s.fetch(kurt_out, d_kurt, nlb);
+        if (var_out) s.fetch(var_out, d_var, nlb);
     }
-    int64_t *d_cnt = (int64_t *)d_out;
-    double *d_mean = (double *)(d_out + nl * 8), *d_var = d_mean + nlb, *d_skew = d_var + nlb, *d_kurt = d_skew + nlb;
-    float *d_mn = (float *)(d_kurt + nlb), *d_mx = d_mn + nlb;
-    if (rc == OBIA_OK && hipMemcpyAsync(d_raw, raw, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK && hipMemcpyAsync(d_lab, labels, npix * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK) rc = obia_zonal_stats_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_cnt, d_mean, d_var, d_mn, d_mx);
-    if (rc == OBIA_OK) rc = obia_zonal_moments_f32_dev(ctx, d_raw, d_lab, H, W, C, bands, n_bands, n_labels, start_label, d_mean, d_skew, d_kurt, d_var);
-    if (rc == OBIA_OK && n_labels > 0) {
-        bool ok = hipMemcpyAsync(skew_out, d_skew, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  hipMemcpyAsync(kurt_out, d_kurt, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                  (!var_out || hipMemcpyAsync(var_out, d_var, nlb * 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-        if (!ok) rc = OBIA_E_HIP;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc == OBIA_E_HIP) set_error("host<->device copy failed in obia_zonal_moments_f32");
-    (void)hipFree(d_raw); (void)hipFree(d_lab); (void)hipFree(d_out);
-    return rc;
+    return s.finish();
 }
 
 }  // extern "C"

@@ -290,12 +290,11 @@ using namespace obia;
 template <typename OUT>
 static int table_scale(obia_ctx *ctx, const double *table, int64_t n_rows, int n_features, double *mean_out, double *scale_out,
                        OUT *scaled_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!table || !mean_out || !scale_out || !scaled_out || n_features <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (n_rows <= 0) { set_error("the table has no rows"); return OBIA_E_INVALID; }
     const long long B64 = (n_rows + SC_ROWS - 1) / SC_ROWS;
     if (B64 >= (1ll << 31) || n_features > 65535 * 64) { set_error("table too large"); return OBIA_E_UNSUPPORTED; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     const int B = (int)B64, F = n_features;
     ctx->arena.reset();
     double *p1 = ctx->arena.get<double>((size_t)B * F);
@@ -331,7 +330,7 @@ int obia_table_scale_f64_dev(obia_ctx *ctx, const double *table, int64_t n_rows,
 
 int obia_forest_predict_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest,
                             const uint8_t *acceptable, double *proba_out, int32_t *pred_out, double *margin_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!x || !forest || n_features <= 0 || n_rows < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     const obia_forest &f = *forest;
     if (!f.threshold || !f.feature || !f.left || !f.right || !f.tree_offset || !f.tree_offset_host || !f.value || f.n_trees <= 0 ||
@@ -351,7 +350,6 @@ int obia_forest_predict_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n
         if ((t == 0 && lo != 0) || hi <= lo || hi > f.n_nodes) { set_error("tree offsets must start at 0 and increase"); return OBIA_E_INVALID; }
         if (hi - lo > max_nodes) max_nodes = hi - lo;
     }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     if (n_rows == 0) return OBIA_OK;
     ctx->arena.reset();
     NodeRec *rec = ctx->arena.get<NodeRec>((size_t)f.n_nodes);

@@ -1,6 +1,11 @@
 // common.hpp -- context, device workspace arena, error plumbing shared by the HIP translation units.
+//
+// An extern "C" function is its argument checks and its body between three shared pieces (the entry layer, below): enter(), the
+// prologue; call_frame(), for a call that returns with its work done; Staging, for a call that takes host pointers.  A new operator
+// uses them and writes none of its own.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -135,6 +140,59 @@ int side_stream(obia_ctx *ctx);   // makes sure `side` and the events of both it
 void debug_sync(obia_ctx *ctx, const char *stage);
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// Grid of a grid-stride kernel over n elements in workgroups of 256: one workgroup per 256 elements, 8192 at the most, one at the least.
+static inline unsigned flat_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(cdiv(n, 256), 8192)); }
+
+// ---- the entry layer: what every extern "C" function is made of besides its own argument checks and its body ----------------------
+
+// Prologue, the first statement of every entry point that takes a context (the tiler's go through their session's): refuses a null
+// context (OBIA_E_INVALID) before any HIP call and selects the context's device.
+int enter(obia_ctx *ctx);
+
+// Error path of every entry point that returns with its work done: nothing this library queued may still be running when the caller
+// gets the error back -- it is about to free the buffers.  Waits for the context's stream and its side stream, returns rc.
+int quiesce(obia_ctx *ctx, int rc);
+
+// Call frame of those entry points: resets the arena (and, with FRAME_TIMING, the timing record), runs the body (with FRAME_TOTAL
+// inside a T_TOTAL span), then synchronises the stream and resolves the timing -- or, when the body failed, quiesces.
+enum FrameOpts : unsigned { FRAME_PLAIN = 0, FRAME_TIMING = 1, FRAME_TOTAL = 2 | FRAME_TIMING };
+void frame_begin(obia_ctx *ctx, unsigned opts);
+int frame_end(obia_ctx *ctx, unsigned opts, int rc);
+template <typename Body> int call_frame(obia_ctx *ctx, unsigned opts, Body &&body) {
+    frame_begin(ctx, opts);
+    int rc;
+    if ((opts & FRAME_TOTAL) == FRAME_TOTAL) {
+        ScopedSpan total(ctx, T_TOTAL);
+        rc = body();
+    } else {
+        rc = body();
+    }
+    return frame_end(ctx, opts, rc);
+}
+
+// Temporary device buffers of a host-pointer entry point (plain allocations: what the caller sees is not part of the arena).  The
+// first failure sticks -- every later step is skipped -- so a call reads: in() / out() ..., run(the _dev call), fetch() ..., finish().
+class Staging {
+  public:
+    explicit Staging(obia_ctx *ctx) : ctx_(ctx) {}
+    ~Staging() { (void)finish(); }
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    template <typename T> T *in(const T *host, size_t n) { return static_cast<T *>(upload(host, n * sizeof(T))); }   // null stays null
+    template <typename T> T *out(size_t n) { return static_cast<T *>(alloc(n * sizeof(T))); }
+    template <typename T> void fetch(T *host, const T *dev, size_t n) { download(host, dev, n * sizeof(T)); }
+    bool ok() const { return rc_ == OBIA_OK; }
+    template <typename Call> void run(Call &&call) { if (ok()) rc_ = call(); }   // the inner call keeps its own error message
+    int finish();   // synchronises the stream, then frees, on every path; returns the call's status
+  private:
+    void *alloc(size_t bytes);
+    void *upload(const void *host, size_t bytes);
+    void download(void *host, const void *dev, size_t bytes);
+    obia_ctx *ctx_;
+    int rc_ = OBIA_OK;
+    bool open_ = true;
+    std::vector<void *> bufs_;
+};
 
 // Loads of data that ONE workgroup reads ONCE per pass (feature planes in a sweep, the raster in the feature and statistics
 // passes): non-temporal, so the lines do not displace what IS re-read from the caches -- centroid records, bin heads, accumulator

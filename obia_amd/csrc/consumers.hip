@@ -68,9 +68,8 @@ using namespace obia;
 extern "C" {
 
 int obia_label_edges_u8_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, uint8_t *edge_out, int64_t *n_edge_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!labels || !edge_out || H <= 0 || W <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     ctx->arena.reset();
     unsigned long long *d_n = ctx->arena.get<unsigned long long>(1);
     if (!d_n) return OBIA_E_NOMEM;
@@ -85,12 +84,11 @@ int obia_label_edges_u8_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, 
 
 int obia_sample_labels_i32_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, const double *inverse_affine6,
                                const double *points_xy, int64_t n_points, int outside_value, int32_t *labels_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!labels || !inverse_affine6 || H <= 0 || W <= 0 || n_points < 0 || (n_points > 0 && (!points_xy || !labels_out))) {
         set_error("bad arguments");
         return OBIA_E_INVALID;
     }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     if (n_points == 0) return OBIA_OK;
     const double *t = inverse_affine6;
     hipLaunchKernelGGL(sample_labels_kernel, dim3(cdiv(n_points, 256)), dim3(256), 0, ctx->stream, labels, H, W, t[0], t[1], t[2], t[3],

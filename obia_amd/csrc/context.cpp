@@ -1,4 +1,4 @@
-// context.cpp -- context lifetime, workspace arena, error string, timing spans.
+// context.cpp -- context lifetime, workspace arena, error string, timing spans, the entry layer (enter, call frame, Staging).
 #include "common.hpp"
 
 #include <algorithm>
@@ -226,6 +226,69 @@ int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t byte
     OBIA_HIP_TRY(hipMemcpyAsync(dev_dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
     ctx->up_used += (bytes + 63) & ~(size_t)63;
     return OBIA_OK;
+}
+
+int enter(obia_ctx *ctx) {
+    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", ctx->device); return OBIA_E_HIP; }
+    return OBIA_OK;
+}
+
+int quiesce(obia_ctx *ctx, int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
+    return rc;
+}
+
+void frame_begin(obia_ctx *ctx, unsigned opts) {
+    ctx->arena.reset();
+    if (opts & FRAME_TIMING) begin_timing(ctx);
+}
+
+int frame_end(obia_ctx *ctx, unsigned opts, int rc) {
+    if (rc != OBIA_OK) return quiesce(ctx, rc);
+    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (opts & FRAME_TIMING) resolve_timing(ctx);
+    return OBIA_OK;
+}
+
+void *Staging::alloc(size_t bytes) {
+    if (!ok()) return nullptr;
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        set_error("device allocation for host-pointer call failed");
+        rc_ = OBIA_E_NOMEM;
+        return nullptr;
+    }
+    bufs_.push_back(p);
+    return p;
+}
+
+void *Staging::upload(const void *host, size_t bytes) {
+    if (!host) return nullptr;
+    void *p = alloc(bytes);
+    if (p && hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, ctx_->stream) != hipSuccess) {
+        set_error("host->device copy failed in a host-pointer call");
+        rc_ = OBIA_E_HIP;
+    }
+    return p;
+}
+
+void Staging::download(void *host, const void *dev, size_t bytes) {
+    if (ok() && hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx_->stream) != hipSuccess) {
+        set_error("device->host copy failed in a host-pointer call");
+        rc_ = OBIA_E_HIP;
+    }
+}
+
+int Staging::finish() {
+    if (open_) {
+        open_ = false;
+        (void)hipStreamSynchronize(ctx_->stream);
+        for (void *p : bufs_) (void)hipFree(p);
+        bufs_.clear();
+    }
+    return rc_;
 }
 
 }  // namespace obia

@@ -543,12 +543,6 @@ __global__ __launch_bounds__(256) void cost_combine_kernel(const float *__restri
     }
 }
 
-int check_ctx(obia_ctx *ctx) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    return OBIA_OK;
-}
-
 dim3 tile_grid(int H, int W, int tw, int th) { return dim3(cdiv(W, tw), std::min(cdiv(H, th), 65535)); }
 dim3 row_grid(int H, int W) { return dim3(cdiv(W, 256), std::min(H, 65535)); }
 
@@ -560,28 +554,26 @@ using namespace obia;
 extern "C" {
 
 int obia_cost_bands_f32_dev(obia_ctx *ctx, const float *hwc8, int64_t n_pixels, float *pan_out, float *gap_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!hwc8 || !pan_out || !gap_out || n_pixels <= 0 || ((uintptr_t)hwc8 & 15)) {
         set_error("cost bands: bad arguments (the raster must be 16-byte aligned)");
         return OBIA_E_INVALID;
     }
-    hipLaunchKernelGGL(cost_bands_kernel, dim3((unsigned)std::min<long long>(cdiv(n_pixels, 256), 8192)), dim3(256), 0, ctx->stream,
-                       hwc8, (long long)n_pixels, pan_out, gap_out);
+    hipLaunchKernelGGL(cost_bands_kernel, dim3(flat_grid(n_pixels)), dim3(256), 0, ctx->stream, hwc8, (long long)n_pixels, pan_out, gap_out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
 
 int obia_cost_ndvi_f32_dev(obia_ctx *ctx, const float *red, const float *nir, int64_t n, float *out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!red || !nir || !out || n <= 0) { set_error("cost ndvi: bad arguments"); return OBIA_E_INVALID; }
-    hipLaunchKernelGGL(cost_ndvi_kernel, dim3((unsigned)std::min<long long>(cdiv(n, 256), 8192)), dim3(256), 0, ctx->stream, red, nir,
-                       (long long)n, out);
+    hipLaunchKernelGGL(cost_ndvi_kernel, dim3(flat_grid(n)), dim3(256), 0, ctx->stream, red, nir, (long long)n, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
 
 int obia_cost_sobel_f32_dev(obia_ctx *ctx, const float *chm, int H, int W, float *grad_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!chm || !grad_out || H <= 0 || W <= 0) { set_error("cost sobel: bad arguments"); return OBIA_E_INVALID; }
     hipLaunchKernelGGL(cost_sobel_kernel, tile_grid(H, W, SB_TW, SB_TH), dim3(256), 0, ctx->stream, chm, H, W, grad_out);
     OBIA_HIP_TRY(hipGetLastError());
@@ -590,7 +582,7 @@ int obia_cost_sobel_f32_dev(obia_ctx *ctx, const float *chm, int H, int W, float
 
 int obia_cost_select_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n, double q_lo, double q_hi, int64_t *n_valid_out,
                          uint64_t *bits4_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !n_valid_out || !bits4_out || n <= 0 || n >= (int64_t)0xFFFFFFFFll || ((uintptr_t)plane & 15)) {
         set_error("cost select: bad arguments (1 <= n < 2^32 values, 16-byte aligned)");
         return OBIA_E_INVALID;
@@ -601,7 +593,7 @@ int obia_cost_select_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n
 
 int obia_cost_entropy_f32_dev(obia_ctx *ctx, const float *pan, int H, int W, double lo, double hi, const double *table_30x32,
                               double *out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!pan || !table_30x32 || !out || H <= 0 || W <= 0) { set_error("cost entropy: bad arguments"); return OBIA_E_INVALID; }
     hipLaunchKernelGGL(cost_entropy_kernel, tile_grid(H, W, EN_TW, EN_TH), dim3(256), 0, ctx->stream, pan, H, W, lo, hi, table_30x32, out);
     OBIA_HIP_TRY(hipGetLastError());
@@ -609,9 +601,9 @@ int obia_cost_entropy_f32_dev(obia_ctx *ctx, const float *pan, int H, int W, dou
 }
 
 int obia_cost_normalise_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n, double lo, double hi, double *out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !out || n <= 0) { set_error("cost normalise: bad arguments"); return OBIA_E_INVALID; }
-    const dim3 grid((unsigned)std::min<long long>(cdiv(n, 256), 8192));
+    const dim3 grid(flat_grid(n));
     if (is_f64)
         hipLaunchKernelGGL(cost_normalise_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double *)plane, (long long)n, lo, hi, out);
     else
@@ -621,7 +613,7 @@ int obia_cost_normalise_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_
 }
 
 int obia_cost_edge_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int64_t *n_edge_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!labels || !n_edge_out || H <= 0 || W <= 0) { set_error("cost edge count: bad arguments"); return OBIA_E_INVALID; }
     ctx->arena.reset();
     unsigned long long *d_n = ctx->arena.get<unsigned long long>(1);
@@ -640,7 +632,7 @@ int obia_cost_edge_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W,
 
 int obia_cost_combine_dev(obia_ctx *ctx, const float *grad, const float *gap, const double *tex, const int32_t *labels, int H, int W,
                           const double *lo4, const double *hi4, const double *w4, float *out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!grad || !gap || !tex || !lo4 || !hi4 || !w4 || !out || H <= 0 || W <= 0) {
         set_error("cost combine: bad arguments");
         return OBIA_E_INVALID;

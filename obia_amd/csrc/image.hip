@@ -381,13 +381,6 @@ __global__ __launch_bounds__(256) void mark_kernel(const uint8_t *__restrict__ i
     }
 }
 
-int image_ctx(obia_ctx *ctx) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    return OBIA_OK;
-}
-
-unsigned flat_grid(long long chunks) { return (unsigned)std::max<long long>(1, std::min<long long>(cdiv(chunks, 256), 8192)); }
 dim3 rows_grid(int H, long long chunks_per_row) {
     const int gx = (int)std::max<long long>(1, std::min<long long>(cdiv(chunks_per_row, 256), 64));
     return dim3(gx, std::min(H, 65535));
@@ -403,7 +396,7 @@ using namespace obia;
 extern "C" {
 
 int obia_image_stretch_u8_dev(obia_ctx *ctx, const void *plane, int is_f64, int64_t n, double lo, double hi, uint8_t *out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !out || n <= 0 || ((uintptr_t)plane & (is_f64 ? 7 : 3))) {
         set_error("image stretch: bad arguments");
         return OBIA_E_INVALID;
@@ -423,7 +416,7 @@ int obia_image_stretch_u8_dev(obia_ctx *ctx, const void *plane, int is_f64, int6
 }
 
 int obia_image_gray_hist_dev(obia_ctx *ctx, const uint8_t *pixels, int nch, int64_t n, uint8_t *gray_out, int64_t *hist256_out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!pixels || !hist256_out || (nch != 1 && nch != 3) || n <= 0 || n > (int64_t)INT_MAX || ((uintptr_t)hist256_out & 7)) {
         set_error("image gray_hist: bad arguments (nch 1 or 3, 1 <= n < 2^31)");
         return OBIA_E_INVALID;
@@ -436,7 +429,7 @@ int obia_image_gray_hist_dev(obia_ctx *ctx, const uint8_t *pixels, int nch, int6
 }
 
 int obia_image_lut_u8_dev(obia_ctx *ctx, const uint8_t *in, int64_t n, const uint8_t *lut256, int rep, uint8_t *out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!in || !lut256 || !out || n <= 0 || (rep != 1 && rep != 3)) {
         set_error("image lut: bad arguments (rep 1 or 3)");
         return OBIA_E_INVALID;
@@ -451,7 +444,7 @@ int obia_image_lut_u8_dev(obia_ctx *ctx, const uint8_t *in, int64_t n, const uin
 }
 
 int obia_image_clahe_u8_dev(obia_ctx *ctx, const uint8_t *in, int H, int W, int nch, int ch, uint8_t *out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!in || !out || in == out || H < 8 || W < 8 || nch < 1 || nch > 4 || ch < 0 || ch >= nch || W > INT_MAX - 8 || H > INT_MAX - 8) {
         set_error("image clahe: bad arguments (H, W >= 8, 0 <= ch < nch <= 4, out is not in)");
         return OBIA_E_INVALID;
@@ -481,7 +474,7 @@ int obia_image_clahe_u8_dev(obia_ctx *ctx, const uint8_t *in, int H, int W, int 
 }
 
 int obia_image_boundaries_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, uint8_t *out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!labels || !out || H <= 0 || W <= 0 || W > MAX_W) { set_error("image boundaries: bad arguments"); return OBIA_E_INVALID; }
     hipLaunchKernelGGL(boundaries_kernel, rows_grid(H, W / 4 + 2), dim3(256), 0, ctx->stream, labels, H, W, out);
     OBIA_HIP_TRY(hipGetLastError());
@@ -490,7 +483,7 @@ int obia_image_boundaries_dev(obia_ctx *ctx, const int32_t *labels, int H, int W
 
 int obia_image_mark_u8_dev(obia_ctx *ctx, const uint8_t *image, int nch, const int32_t *labels, int H, int W, const uint8_t *table256,
                            const uint8_t *rgb3, uint8_t *out) {
-    OBIA_TRY(image_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!image || !labels || !table256 || !rgb3 || !out || (nch != 1 && nch != 3) || H <= 0 || W <= 0 || W > MAX_W) {
         set_error("image mark: bad arguments (nch 1 or 3)");
         return OBIA_E_INVALID;

@@ -67,7 +67,7 @@ extern "C" {
 
 int obia_mlp_predict_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_features, const obia_mlp *mlp, const uint8_t *acceptable,
                          double *proba_out, int32_t *pred_out, double *margin_out, double *logits_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!x || !mlp || n_features <= 0 || n_rows < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     MlpPlan p;
     OBIA_TRY(mlp_make_plan(mlp, n_features, "mlp_predict", p));
@@ -75,7 +75,6 @@ int obia_mlp_predict_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_f
     const int R = 1 << p.rshift;
     const long long blocks = (n_rows + R - 1) / R;
     if (blocks >= (1ll << 31)) { set_error("table too large"); return OBIA_E_UNSUPPORTED; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     if (n_rows == 0) return OBIA_OK;
     ctx->arena.reset();
     int *bad = ctx->arena.get<int>(1);

@@ -108,7 +108,7 @@ extern "C" {
 
 int obia_mlp_coalition_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n_features, const obia_mlp *mlp, const double *background,
                            int64_t n_background, const uint8_t *masks, int64_t n_masks, double *values_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!x || !mlp || !background || !values_out || n_features <= 0 || n_rows < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (n_background < 1 || n_masks < 1) { set_error("mlp_coalition_values needs at least one background row and one coalition"); return OBIA_E_INVALID; }
     MlpPlan p;
@@ -122,7 +122,6 @@ int obia_mlp_coalition_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n
         set_error("mlp_coalition_values supports fewer than 2^31 background rows and 2^31 (row, coalition) pairs per call");
         return OBIA_E_UNSUPPORTED;
     }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     if (n_rows == 0) return OBIA_OK;
     ctx->arena.reset();
     int *bad = ctx->arena.get<int>(2);
@@ -143,7 +142,7 @@ int obia_mlp_coalition_dev(obia_ctx *ctx, const double *x, int64_t n_rows, int n
 
 int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows, int n_features, int n_classes, const double *size_weights,
                              double *phi_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!values || !size_weights || !phi_out || n_features <= 0 || n_classes <= 0 || n_rows < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (n_features > SHAPLEY_MAX_FEATURES || n_classes > MLP_MAX_CLASSES) {
         set_error("shapley_combine supports at most %d features and %d classes (got %d, %d)", SHAPLEY_MAX_FEATURES, MLP_MAX_CLASSES, n_features,
@@ -152,7 +151,6 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
     }
     const long long total = (long long)n_rows * n_features * n_classes;
     if (n_rows >= (1ll << 31) || total >= (1ll << 31) * 256) { set_error("table too large"); return OBIA_E_UNSUPPORTED; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     if (n_rows == 0) return OBIA_OK;
     ShapleyWeights sw = {};
     for (int s = 0; s < n_features; ++s) sw.w[s] = size_weights[s];

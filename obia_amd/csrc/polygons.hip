@@ -293,26 +293,20 @@ extern "C" {
 
 int obia_polygon_count_i32_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int start_label, int64_t *n_rings_out,
                                int64_t *n_vertices_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!n_rings_out || !n_vertices_out) { set_error("null pointer argument"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    OBIA_TRY(polygon_count_dev(ctx, labels, H, W, start_label, n_rings_out, n_vertices_out));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_PLAIN, [&] { return polygon_count_dev(ctx, labels, H, W, start_label, n_rings_out, n_vertices_out); });
 }
 
 int obia_polygon_rings_i32_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int start_label, int64_t cap_rings,
                                int64_t cap_vertices, int32_t *ring_label, uint8_t *ring_is_hole, int64_t *ring_offset,
                                int32_t *xy, int64_t *n_rings_out, int64_t *n_vertices_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!ring_label || !ring_is_hole || !ring_offset || !xy || !n_rings_out || !n_vertices_out) { set_error("null pointer argument"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    OBIA_TRY(polygon_rings_dev(ctx, labels, H, W, start_label, cap_rings, cap_vertices, ring_label, ring_is_hole, ring_offset, xy,
-                               n_rings_out, n_vertices_out));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_PLAIN, [&] {
+        return polygon_rings_dev(ctx, labels, H, W, start_label, cap_rings, cap_vertices, ring_label, ring_is_hole, ring_offset, xy, n_rings_out,
+                                 n_vertices_out);
+    });
 }
 
 }  // extern "C"

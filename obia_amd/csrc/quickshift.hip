@@ -402,62 +402,41 @@ extern "C" {
 int obia_quickshift_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, double ratio, double kernel_size,
                             double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
                             int32_t *labels_out, int *n_labels_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    begin_timing(ctx);
-    int rc;
-    {
-        ScopedSpan total(ctx, T_TOTAL);
-        rc = quickshift_dev(ctx, img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, tie_noise_hw, normalize_bands,
-                            labels_out, n_labels_out);
-    }
-    if (rc != OBIA_OK) return rc;
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
-    return OBIA_OK;
+    OBIA_TRY(enter(ctx));
+    return call_frame(ctx, FRAME_TOTAL, [&] {
+        return quickshift_dev(ctx, img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, tie_noise_hw, normalize_bands, labels_out,
+                              n_labels_out);
+    });
 }
 
 int obia_quickshift_stages_f32_dev(obia_ctx *ctx, const float *img, int H, int W, int C, double ratio, double kernel_size,
                                    double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
                                    int32_t *labels_out, int *n_labels_out, double *staged_out, double *noise_out, double *dens_out,
                                    int32_t *parent_out, double *dist_parent_out, int32_t *roots_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
+    OBIA_TRY(enter(ctx));
     const QsStages st{staged_out, noise_out, dens_out, parent_out, dist_parent_out, roots_out};
-    const int rc = quickshift_dev(ctx, img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, tie_noise_hw, normalize_bands,
-                                  labels_out, n_labels_out, &st);
-    if (rc != OBIA_OK) return rc;
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_PLAIN, [&] {
+        return quickshift_dev(ctx, img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, tie_noise_hw, normalize_bands, labels_out,
+                              n_labels_out, &st);
+    });
 }
 
 int obia_quickshift_f32(obia_ctx *ctx, const float *img, int H, int W, int C, double ratio, double kernel_size,
                         double max_dist, double sigma, int convert2lab, const double *tie_noise_hw, int normalize_bands,
                         int32_t *labels_out, int *n_labels_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!img || !labels_out || H <= 0 || W <= 0 || C <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     const size_t npix = (size_t)H * W;
-    float *d_img = nullptr; double *d_noise = nullptr; int32_t *d_lab = nullptr;
-    int rc = OBIA_OK;
-    if (hipMalloc(&d_img, npix * C * sizeof(float)) != hipSuccess || hipMalloc(&d_lab, npix * sizeof(int32_t)) != hipSuccess ||
-        (tie_noise_hw && hipMalloc(&d_noise, npix * sizeof(double)) != hipSuccess)) {
-        set_error("device allocation for host-pointer call failed");
-        rc = OBIA_E_NOMEM;
-    }
-    if (rc == OBIA_OK && hipMemcpyAsync(d_img, img, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK && tie_noise_hw && hipMemcpyAsync(d_noise, tie_noise_hw, npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_E_HIP) set_error("host->device copy failed in obia_quickshift_f32");
-    if (rc == OBIA_OK) rc = obia_quickshift_f32_dev(ctx, d_img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, d_noise, normalize_bands, d_lab, n_labels_out);
-    if (rc == OBIA_OK && hipMemcpyAsync(labels_out, d_lab, npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-        set_error("device->host copy failed in obia_quickshift_f32");
-        rc = OBIA_E_HIP;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_img); (void)hipFree(d_lab); (void)hipFree(d_noise);
-    return rc;
+    Staging s(ctx);
+    const float *d_img = s.in(img, npix * C);
+    const double *d_noise = s.in(tie_noise_hw, npix);
+    int32_t *d_lab = s.out<int32_t>(npix);
+    s.run([&] {
+        return obia_quickshift_f32_dev(ctx, d_img, H, W, C, ratio, kernel_size, max_dist, sigma, convert2lab, d_noise, normalize_bands, d_lab,
+                                       n_labels_out);
+    });
+    s.fetch(labels_out, d_lab, npix);
+    return s.finish();
 }
 
 }  // extern "C"

@@ -372,12 +372,10 @@ extern "C" {
 int obia_rasterize_polygons_dev(obia_ctx *ctx, const double *xy_pix, const int64_t *ring_offset, int64_t n_rings,
                                 const int32_t *ring_shape, const int32_t *shape_value, int64_t n_shapes, int H, int W, int32_t fill,
                                 int32_t *out_hw) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    OBIA_TRY(rasterize_polygons_dev(ctx, xy_pix, ring_offset, n_rings, ring_shape, shape_value, n_shapes, H, W, fill, out_hw));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OBIA_OK;
+    OBIA_TRY(enter(ctx));
+    return call_frame(ctx, FRAME_PLAIN, [&] {
+        return rasterize_polygons_dev(ctx, xy_pix, ring_offset, n_rings, ring_shape, shape_value, n_shapes, H, W, fill, out_hw);
+    });
 }
 
 int obia_rasterize_info(int64_t info[4]) {

@@ -15,12 +15,6 @@
 namespace obia {
 namespace {
 
-int check_ctx(obia_ctx *ctx) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    return OBIA_OK;
-}
-
 // scipy's "reflect" (d c b a | a b c d | d c b a), any distance outside
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     const int per = 2 * n;
@@ -462,7 +456,7 @@ extern "C" {
 
 int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double sigma, int min_dist_px, float threshold,
                          float *smooth_out, uint8_t *flags_out, int32_t *offsets_out, int64_t *n_peaks_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !flags_out || !offsets_out || !n_peaks_out || H <= 0 || W <= 0 || ((uintptr_t)flags_out & 15)) {
         set_error("seed peaks: bad arguments (the flag plane must be 16-byte aligned)");
         return OBIA_E_INVALID;
@@ -510,7 +504,7 @@ int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double
 int obia_seeds_peaks_gather_dev(obia_ctx *ctx, const float *plane, const float *smooth, const uint8_t *flags, const int32_t *offsets,
                                 int H, int W, int64_t n_peaks, int32_t *rows_out, int32_t *cols_out, float *smooth_val_out,
                                 float *raw_val_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !smooth || !flags || !offsets || H <= 0 || W <= 0 || n_peaks < 0 || ((uintptr_t)flags & 15)) {
         set_error("seed peaks gather: bad arguments");
         return OBIA_E_INVALID;
@@ -527,7 +521,7 @@ int obia_seeds_peaks_gather_dev(obia_ctx *ctx, const float *plane, const float *
 int obia_seeds_pair_link_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
                              const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host, double eps,
                              int nonneg, int32_t *cluster_out, int *n_clusters_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!cluster_out || !n_clusters_out) { set_error("seed pairs: null output"); return OBIA_E_INVALID; }
     ctx->arena.reset();
     PairArgs P;
@@ -553,7 +547,7 @@ int obia_seeds_pair_link_dev(obia_ctx *ctx, const double *xs, const double *ys, 
 int obia_seeds_pair_stats_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
                               const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host,
                               float *stats4_out, int64_t *n_nan_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!stats4_out || !n_nan_out) { set_error("seed pair stats: null output"); return OBIA_E_INVALID; }
     if (n < 2) { set_error("seed pair stats: fewer than two seeds have no pair"); return OBIA_E_EMPTY; }
     ctx->arena.reset();
@@ -611,7 +605,7 @@ int obia_seeds_pair_stats_dev(obia_ctx *ctx, const double *xs, const double *ys,
 int obia_seeds_pair_matrix_dev(obia_ctx *ctx, const double *xs, const double *ys, int n, const float *cost, int H, int W,
                                const double *inv6, double weight, double xy_thresh, int samples, const double *ts_host,
                                float *matrix_out) {
-    OBIA_TRY(check_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!matrix_out) { set_error("seed pair matrix: null output"); return OBIA_E_INVALID; }
     if (n > 512) { set_error("seed pair matrix: a test hook for n <= 512 (got %d)", n); return OBIA_E_UNSUPPORTED; }
     ctx->arena.reset();

@@ -299,7 +299,7 @@ extern "C" {
 
 int obia_forest_shap_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_features, const obia_forest *forest, const double *cover,
                          double *phi_out, double *base_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!x || !forest || !cover || !phi_out || !base_out || n_features <= 0 || n_rows < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     const obia_forest &f = *forest;
     if (!f.threshold || !f.feature || !f.left || !f.right || !f.tree_offset || !f.tree_offset_host || !f.value || f.n_trees <= 0 ||
@@ -316,7 +316,6 @@ int obia_forest_shap_dev(obia_ctx *ctx, const float *x, int64_t n_rows, int n_fe
         const long long lo = f.tree_offset_host[t], hi = (t + 1 < f.n_trees) ? f.tree_offset_host[t + 1] : f.n_nodes;
         if ((t == 0 && lo != 0) || hi <= lo || hi > f.n_nodes) { set_error("tree offsets must start at 0 and increase"); return OBIA_E_INVALID; }
     }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     const long long n = f.n_nodes;
     const int F = n_features, K = f.n_classes, T = f.n_trees;
     ctx->arena.reset();

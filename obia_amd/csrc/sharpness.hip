@@ -379,12 +379,6 @@ __global__ __launch_bounds__(256) void stretch_f32_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-int sharp_ctx(obia_ctx *ctx) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    return OBIA_OK;
-}
-
 int sharp_shape(const char *who, int H, int W) {
     if (H <= 0 || W <= 0) { set_error("%s: H and W must be positive, got %d x %d", who, H, W); return OBIA_E_INVALID; }
     if ((long long)H * W >= 4294967295LL) {
@@ -399,8 +393,6 @@ int sharp_win(const char *who, int win) {
     if (win > OBIA_SHARP_MAX_WIN) { set_error("%s: win %d is larger than %d", who, win, OBIA_SHARP_MAX_WIN); return OBIA_E_UNSUPPORTED; }
     return OBIA_OK;
 }
-
-unsigned flat_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(cdiv(n, 256), 8192)); }
 
 int clear_counter(obia_ctx *ctx, const char *who, int64_t *counter) {
     if (!counter) return OBIA_OK;
@@ -426,7 +418,7 @@ extern "C" {
 
 int obia_sharp_gray_lap_dev(obia_ctx *ctx, const float *raster, int H, int W, int C, const int32_t *bands3, float *lap_out,
                             int64_t *nonfinite_out) {
-    OBIA_TRY(sharp_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!raster || !bands3 || !lap_out || C < 1 || ((uintptr_t)raster & 3) || ((uintptr_t)lap_out & 3)) {
         set_error("sharp gray_lap: bad arguments");
         return OBIA_E_INVALID;
@@ -453,7 +445,7 @@ int obia_sharp_gray_lap_dev(obia_ctx *ctx, const float *raster, int H, int W, in
 }
 
 int obia_sharp_laplacian_dev(obia_ctx *ctx, const float *gray, int H, int W, float *lap_out, int64_t *nonfinite_out) {
-    OBIA_TRY(sharp_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!gray || !lap_out || gray == lap_out || ((uintptr_t)gray & 3) || ((uintptr_t)lap_out & 3)) {
         set_error("sharp laplacian: bad arguments");
         return OBIA_E_INVALID;
@@ -466,7 +458,7 @@ int obia_sharp_laplacian_dev(obia_ctx *ctx, const float *gray, int H, int W, flo
 }
 
 int obia_sharp_box_dev(obia_ctx *ctx, const float *plane, int H, int W, int win, float *work, float *out, int64_t *nonfinite_out) {
-    OBIA_TRY(sharp_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !work || !out || plane == out || plane == work || work == out || ((uintptr_t)plane & 3) || ((uintptr_t)work & 3) ||
         ((uintptr_t)out & 3)) {
         set_error("sharp box: bad arguments");
@@ -491,7 +483,7 @@ int obia_sharp_box_dev(obia_ctx *ctx, const float *plane, int H, int W, int win,
 }
 
 int obia_sharp_variance_dev(obia_ctx *ctx, const float *lap, int H, int W, int win, float *work, float *out) {
-    OBIA_TRY(sharp_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!lap || !work || !out || lap == out || lap == work || work == out || ((uintptr_t)lap & 3) || ((uintptr_t)work & 3) ||
         ((uintptr_t)out & 3)) {
         set_error("sharp variance: bad arguments");
@@ -513,7 +505,7 @@ int obia_sharp_variance_dev(obia_ctx *ctx, const float *lap, int H, int W, int w
 }
 
 int obia_sharp_stretch_f32_dev(obia_ctx *ctx, const float *plane, int64_t n, double lo, double hi, float *out) {
-    OBIA_TRY(sharp_ctx(ctx));
+    OBIA_TRY(enter(ctx));
     if (!plane || !out || n <= 0 || ((uintptr_t)plane & 3) || ((uintptr_t)out & 3)) {
         set_error("sharp stretch: bad arguments");
         return OBIA_E_INVALID;

@@ -305,13 +305,9 @@ extern "C" {
 
 int obia_texture_stats_f32_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int H, int W, int C, const int32_t *bands,
                                int n_bands, int n_labels, int start_label, double *out6) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!raw || !labels || !out6) { set_error("null pointer argument"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    OBIA_TRY(texture_stats_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, out6));
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OBIA_OK;
+    return call_frame(ctx, FRAME_PLAIN, [&] { return texture_stats_dev(ctx, raw, labels, H, W, C, bands, n_bands, n_labels, start_label, out6); });
 }
 
 }  // extern "C"

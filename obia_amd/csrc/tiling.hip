@@ -914,26 +914,23 @@ struct obia_tiler {
     size_t seam_cap = 0;
 };
 
-// Error path: nothing this library queued may still be running when the caller gets the error back (the white tiles'
-// feature pass runs on a side stream beside the black batch and is joined only when the white pass starts -- a failure in
-// between returned while that pass could still read the caller's raster and write arena memory the next call hands out again).
-static int fail_quiesced(obia_ctx *ctx, int rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
-    return rc;
-}
-
 using namespace obia;
+
+// Prologue of the session's entry points: the null-tiler check, then the context's (common.hpp).  The error path of a session is
+// quiesce(): the white tiles' feature pass runs on the side stream beside the black batch and is joined only when the white pass
+// starts -- a failure in between must not return while that pass can still read the caller's raster and write arena memory.
+static int enter(obia_tiler *t) {
+    if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
+    return enter(t->ctx);
+}
 
 extern "C" {
 
 obia_tiler *obia_tiler_create(obia_ctx *ctx, const float *img_local, const uint8_t *mask_local, int H_local, int W, int C,
                               int H_global, int row0, const obia_tiling_params *tiling, const obia_slic_params *params,
                               int32_t *labels_local, int extra_ids) {
-    if (!ctx) { set_error("null context"); return nullptr; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return nullptr; }
-    ctx->arena.reset();
-    begin_timing(ctx);
+    if (enter(ctx) != OBIA_OK) return nullptr;
+    frame_begin(ctx, FRAME_TIMING);   // the session is one frame: obia_tiler_destroy() ends it
     obia_tiler *t = new obia_tiler();
     t->ctx = ctx;
     if (tiler_init(ctx, t->S, img_local, mask_local, H_local, W, C, H_global, row0, tiling, params, labels_local,
@@ -943,17 +940,17 @@ obia_tiler *obia_tiler_create(obia_ctx *ctx, const float *img_local, const uint8
 
 void obia_tiler_destroy(obia_tiler *t) {
     if (!t) return;
-    (void)fail_quiesced(t->ctx, 0);   // (a session dropped half-way may have left the white feature pass on its side stream)
+    (void)enter(t->ctx);
+    (void)quiesce(t->ctx, 0);   // (a session dropped half-way may have left the white feature pass on its side stream)
     if (t->seam_buf) (void)hipFree(t->seam_buf);
     resolve_timing(t->ctx);
     delete t;
 }
 
 int obia_tiler_run(obia_tiler *t, int white, int tile_row_lo, int tile_row_hi, int row_parity) {
-    if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
-    if (hipSetDevice(t->ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
+    OBIA_TRY(enter(t));
     const int rc = tiler_run(t->ctx, t->S, white != 0, tile_row_lo, tile_row_hi, row_parity);
-    if (rc != OBIA_OK) return fail_quiesced(t->ctx, rc);
+    if (rc != OBIA_OK) return quiesce(t->ctx, rc);
     OBIA_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
     return OBIA_OK;
 }
@@ -961,14 +958,15 @@ int obia_tiler_run(obia_tiler *t, int white, int tile_row_lo, int tile_row_hi, i
 int obia_tiler_next_id(obia_tiler *t) { return t ? t->S.next_id : -1; }
 
 int obia_tiler_set_seeding(obia_tiler *t, int seeding, obia_pick_fn picks, void *picks_user) {
-    if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(t));
     OBIA_TRY(check_seeding(seeding, picks));
     t->S.seeding = seeding; t->S.pick_fn = picks; t->S.pick_user = picks_user;
     return OBIA_OK;
 }
 
 int obia_tiler_set_segments(obia_tiler *t, int first_id, int count, const uint32_t *sizes_dev) {
-    if (!t || !sizes_dev || first_id < 1 || count < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(t));
+    if (!sizes_dev || first_id < 1 || count < 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     if (first_id + count > t->S.id_cap) { set_error("segment id capacity exceeded (%d + %d > %d)", first_id, count, t->S.id_cap); return OBIA_E_NOMEM; }
     if (count == 0) return OBIA_OK;
     OBIA_HIP_TRY(hipMemcpyAsync(t->S.seg_size + first_id, sizes_dev, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToDevice, t->ctx->stream));
@@ -979,14 +977,16 @@ int obia_tiler_set_segments(obia_tiler *t, int first_id, int count, const uint32
 }
 
 int obia_tiler_get_alive(obia_tiler *t, uint8_t *alive_out_dev, int count) {
-    if (!t || !alive_out_dev || count < 0 || count > t->S.id_cap) { set_error("bad arguments"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(t));
+    if (!alive_out_dev || count < 0 || count > t->S.id_cap) { set_error("bad arguments"); return OBIA_E_INVALID; }
     OBIA_HIP_TRY(hipMemcpyAsync(alive_out_dev, t->S.alive, (size_t)count, hipMemcpyDeviceToDevice, t->ctx->stream));
     OBIA_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
     return OBIA_OK;
 }
 
 int obia_tiler_set_alive(obia_tiler *t, const uint8_t *alive_in_dev, int count) {
-    if (!t || !alive_in_dev || count < 0 || count > t->S.id_cap) { set_error("bad arguments"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(t));
+    if (!alive_in_dev || count < 0 || count > t->S.id_cap) { set_error("bad arguments"); return OBIA_E_INVALID; }
     OBIA_HIP_TRY(hipMemcpyAsync(t->S.alive, alive_in_dev, (size_t)count, hipMemcpyDeviceToDevice, t->ctx->stream));
     OBIA_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
     return OBIA_OK;
@@ -995,10 +995,10 @@ int obia_tiler_set_alive(obia_tiler *t, const uint8_t *alive_in_dev, int count) 
 int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int my_rank, int owner_rank,
                            int32_t *fmap_dev, int fmap_cap, int32_t *code_of_dev, int32_t *ids_out_dev,
                            int *first_new_out, int *n_new_out, int *max_owner_id_out) {
-    if (!t || !codes_dev || !fmap_dev || !code_of_dev || !ids_out_dev || n < 0 || fmap_cap < 1 || my_rank < 0 || owner_rank < 0 ||
+    OBIA_TRY(enter(t));
+    if (!codes_dev || !fmap_dev || !code_of_dev || !ids_out_dev || n < 0 || fmap_cap < 1 || my_rank < 0 || owner_rank < 0 ||
         my_rank > 126 || owner_rank > 126 || !first_new_out || !n_new_out || !max_owner_id_out) { set_error("bad arguments"); return OBIA_E_INVALID; }
     obia_ctx *ctx = t->ctx;
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     *first_new_out = t->S.next_id; *n_new_out = 0; *max_owner_id_out = 0;
     if (n == 0) return OBIA_OK;
     // scratch outside the arena (the session's arena holds the tiler's persistent state): one small allocation kept by the session
@@ -1038,27 +1038,18 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
 }
 
 int obia_tiler_finalize(obia_tiler *t, int64_t *n_segments_out) {
-    if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(t));
     const int rc = tiler_finalize(t->ctx, t->S, n_segments_out);
-    return rc == OBIA_OK ? rc : fail_quiesced(t->ctx, rc);
+    return rc == OBIA_OK ? rc : quiesce(t->ctx, rc);
 }
 
 int obia_tiled_slic_seeded_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
                                    const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
                                    obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
-    ctx->arena.reset();
-    begin_timing(ctx);
-    int rc;
-    {
-        ScopedSpan total(ctx, T_TOTAL);
-        rc = tiled_slic_dev(ctx, img, mask, H, W, C, tiling, params, seeding, picks, picks_user, labels_out, n_segments_out);
-    }
-    if (rc != OBIA_OK) return fail_quiesced(ctx, rc);
-    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    resolve_timing(ctx);
-    return OBIA_OK;
+    OBIA_TRY(enter(ctx));
+    return call_frame(ctx, FRAME_TOTAL, [&] {
+        return tiled_slic_dev(ctx, img, mask, H, W, C, tiling, params, seeding, picks, picks_user, labels_out, n_segments_out);
+    });
 }
 
 int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
@@ -1070,29 +1061,19 @@ int obia_tiled_slic_f32_dev(obia_ctx *ctx, const float *img, const uint8_t *mask
 int obia_tiled_slic_seeded_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
                                const obia_tiling_params *tiling, const obia_slic_params *params, int seeding,
                                obia_pick_fn picks, void *picks_user, int32_t *labels_out, int64_t *n_segments_out) {
-    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    OBIA_TRY(enter(ctx));
     if (!img || !labels_out || H <= 0 || W <= 0 || C <= 0) { set_error("bad arguments"); return OBIA_E_INVALID; }
     OBIA_TRY(check_seeding(seeding, picks));
-    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return OBIA_E_HIP; }
     const size_t npix = (size_t)H * W;
-    float *d_img = nullptr; uint8_t *d_mask = nullptr; int32_t *d_lab = nullptr;
-    int rc = OBIA_OK;
-    if (hipMalloc(&d_img, npix * C * sizeof(float)) != hipSuccess || hipMalloc(&d_lab, npix * sizeof(int32_t)) != hipSuccess ||
-        (mask && hipMalloc(&d_mask, npix) != hipSuccess)) {
-        set_error("device allocation for host-pointer call failed");
-        rc = OBIA_E_NOMEM;
-    }
-    if (rc == OBIA_OK && hipMemcpyAsync(d_img, img, npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_OK && mask && hipMemcpyAsync(d_mask, mask, npix, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = OBIA_E_HIP;
-    if (rc == OBIA_E_HIP) set_error("host->device copy failed in obia_tiled_slic_f32");
-    if (rc == OBIA_OK) rc = obia_tiled_slic_seeded_f32_dev(ctx, d_img, d_mask, H, W, C, tiling, params, seeding, picks, picks_user, d_lab, n_segments_out);
-    if (rc == OBIA_OK && hipMemcpyAsync(labels_out, d_lab, npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-        set_error("device->host copy failed in obia_tiled_slic_f32");
-        rc = OBIA_E_HIP;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_img); (void)hipFree(d_lab); (void)hipFree(d_mask);
-    return rc;
+    Staging s(ctx);
+    const float *d_img = s.in(img, npix * C);
+    const uint8_t *d_mask = s.in(mask, npix);
+    int32_t *d_lab = s.out<int32_t>(npix);
+    s.run([&] {
+        return obia_tiled_slic_seeded_f32_dev(ctx, d_img, d_mask, H, W, C, tiling, params, seeding, picks, picks_user, d_lab, n_segments_out);
+    });
+    s.fetch(labels_out, d_lab, npix);
+    return s.finish();
 }
 
 int obia_tiled_slic_f32(obia_ctx *ctx, const float *img, const uint8_t *mask, int H, int W, int C,
