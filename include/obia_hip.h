@@ -620,6 +620,8 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
  * instead of the feature pass: all pixels of every batch that fused, 0 when none did -- counted whether profiling is on or not.
  * 15 = spatial pre-pass sweeps launched for one of two window groups of a batch ("Two window groups in flight"):
  * 2 per grouped sweep, 0 when no batch was grouped -- counted whether profiling is on or not.
+ * 16 / 17 / 18 = small commands the call issued besides its kernels: fills (a memset, or one launch of the clear kernel that
+ * stands for several), host -> device uploads, device -> host read-backs -- counted whether profiling is on or not.
  * `enabled`: 0 off, 1 every class, 2 only the colour sweeps (an event pair costs ~2.5 us of stream time: with all classes on,
  * a step of the headline workload records ~420 pairs = 1.1 ms; bench.py times its steps in mode 2).                       */
 int obia_set_profiling(obia_ctx *ctx, int enabled);

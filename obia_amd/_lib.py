@@ -1,4 +1,5 @@
-"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h and include/obia_sharpness.h).
+"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h and include/obia_sharpness.h; the test suite's
+own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -165,6 +166,10 @@ _SHARPNESS_SIGNATURES = {
     "obia_sharp_variance_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_sharp_stretch_f32_dev": (_I, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
 }
+# include/obia_testing.h: internal pieces driven directly by the test suite, a fourth table (tests/test_gpu_clear_ranges.py)
+_TEST_SIGNATURES = {
+    "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
+}
 
 _lib = None
 
@@ -186,7 +191,7 @@ def load():
             raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items()) + list(_TEST_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError:
@@ -255,7 +260,7 @@ class Context:
         lib = load()
         names = ["assign_ms", "sweeps", "features_ms", "connectivity_ms", "zonal_ms", "total_ms", "prepass_ms", "assign_px",
                  "prepass_px", "assign_store_px", "assign_busy_ms", "prepass_busy_ms", "batch_repeats",
-                 "prepass_shared_px", "feature_fused_px", "prepass_group_launches"]
+                 "prepass_shared_px", "feature_fused_px", "prepass_group_launches", "fills", "uploads", "readbacks"]
         return {n: lib.obia_last_timing(self._h, i) for i, n in enumerate(names)}
 
     def workspace_bytes(self):

@@ -61,6 +61,8 @@ int slic_single(obia_ctx *ctx, const float *img, int H, int W, int C, const uint
         A.rewind(sweeps_mk);
         b.d_mask4 = nullptr;   // (the sweeps packed it above the mark)
         OBIA_TRY(slic_rerun_storing(ctx, b));
+        OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        OBIA_TRY(slic_sweeps_settle(ctx, nullptr));
     }
     return OBIA_OK;
 }

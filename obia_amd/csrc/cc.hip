@@ -895,28 +895,33 @@ __global__ __launch_bounds__(256) void cc_relabel_kernel(const CcResolve R, long
 
 int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &probs, const int32_t *labels_in,
                                long long total_pix, int start_label, int32_t *labels_out, int *h_n_labels_out,
-                               CcResolve *deferred) {
+                               CcResolve *deferred, const CcProblem *d_probs_in) {
     ScopedSpan span(ctx, T_CC);
     Arena &A = ctx->arena;
     const long long n = total_pix;
     const int np = (int)probs.size();
     if (np <= 0 || n <= 0 || n > 0x7fffffffLL) { set_error("label batch of %lld pixels not supported", n); return OBIA_E_INVALID; }
     const int mask_label = start_label - 1;
-    CcProblem *d_probs = A.get<CcProblem>(np);
+    // (d_probs_in: the caller's copy of `probs` on the device, part of an upload it has queued)
+    const CcProblem *d_probs = d_probs_in ? d_probs_in : ctx->plan.add(ctx, probs.data(), (size_t)np);
     int *parent = A.get<int>(n), *size = A.get<int>(n), *newlab = A.get<int>(n);
     const int nb = cdiv(n, SCAN_CHUNK);
     int *block_sums = A.get<int>(3 * (size_t)nb);   // survivors | small components | their pixels (cc_rank_blocksum_kernel)
     unsigned long long *rootbits = A.get<unsigned long long>((size_t)((n + 63) / 64));   // one bit per pixel: root (cc_flatten_kernel)
     if (!rootbits) return OBIA_E_NOMEM;
-    // one bit per pixel: tile-local root (cc_tile_kernel); the eight counters sit in front of the map so that ONE fill clears both
-    unsigned long long *lrbits_block = A.get<unsigned long long>((size_t)((n + 63) / 64) + 4);
+    // one bit per pixel: tile-local root (cc_tile_kernel); the eight counters and the settle rounds' ring of "moved" counters (a ring
+    // of words cleared once: a fill per round was a launch and a gap per round) sit in front of the map so that ONE fill clears all three
+    constexpr int RING = 64;
+    constexpr size_t LR_HEAD = 4 + RING / 2;   // quadwords in front of the map
+    unsigned long long *lrbits_block = A.get<unsigned long long>((size_t)((n + 63) / 64) + LR_HEAD);
     if (!lrbits_block) return OBIA_E_NOMEM;
-    unsigned long long *lrbits = lrbits_block + 4;
+    unsigned long long *lrbits = lrbits_block + LR_HEAD;
+    int *const ring = reinterpret_cast<int *>(lrbits_block + 4);
     const unsigned long long *rb = rootbits;   // the map the ranking passes read; null once the size cut has changed the roots
     int *counters = reinterpret_cast<int *>(lrbits_block);
     if (!d_probs || !parent || !size || !newlab || !block_sums) return OBIA_E_NOMEM;
-    OBIA_TRY(upload_async(ctx, d_probs, probs.data(), sizeof(CcProblem) * np));
-    OBIA_HIP_TRY(hipMemsetAsync(lrbits_block, 0, sizeof(unsigned long long) * ((size_t)((n + 63) / 64) + 4), ctx->stream));
+    OBIA_TRY(ctx->plan.flush(ctx));
+    OBIA_TRY(fill_async(ctx, lrbits_block, 0, sizeof(unsigned long long) * ((size_t)((n + 63) / 64) + LR_HEAD)));
     int gs = cdiv(n, 256 * 4);
     if (gs > 65535 * 4) gs = 65535 * 4;
     {
@@ -939,13 +944,13 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
     hipLaunchKernelGGL(cc_rank_blocksum_bits_kernel, dim3(nb), dim3(64), 0, ctx->stream, d_probs, np, size, n, block_sums, counters, rootbits);
     hipLaunchKernelGGL(cc_rank_scan_kernel, dim3(3), dim3(1024), 0, ctx->stream, block_sums, nb, counters);
     int hc[8];
-    OBIA_TRY(read_back(ctx, hc, counters, sizeof(hc)));   // also orders the pageable `probs` upload
+    OBIA_TRY(read_back(ctx, hc, counters, sizeof(hc)));
     if (hc[6] > 0) {
         // some component reaches max_size: cut it the way the reference's capped BFS does, then count again
         const int n_big = hc[6];
         int *big_root = A.get<int>(n_big), *big_qoff = A.get<int>(n_big), *big_box = A.get<int>(4 * (size_t)n_big);
         if (!big_root || !big_qoff || !big_box) return OBIA_E_NOMEM;
-        OBIA_HIP_TRY(hipMemsetAsync(counters, 0, sizeof(int) * 8, ctx->stream));
+        OBIA_TRY(fill_async(ctx, counters, 0, sizeof(int) * 8));
         hipLaunchKernelGGL(cc_flatten_all_kernel, dim3(gs), dim3(256), 0, ctx->stream, parent, n);
         hipLaunchKernelGGL(cc_big_list_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_probs, np, parent, size, n, newlab,
                            big_root, big_qoff, big_box, counters);
@@ -956,7 +961,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
         hipLaunchKernelGGL(cc_big_mark_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_probs, np, parent, size, n, newlab, big_box);
         hipLaunchKernelGGL(cc_split_kernel, dim3(cdiv(n_big, 64)), dim3(64), 0, ctx->stream, d_probs, np, parent, size, big_root, big_qoff,
                            big_box, n_big, bqueue);
-        OBIA_HIP_TRY(hipMemsetAsync(counters, 0, sizeof(int) * 8, ctx->stream));
+        OBIA_TRY(fill_async(ctx, counters, 0, sizeof(int) * 8));
         rb = nullptr;   // cc_split_kernel made new roots: the ranking passes test parent[] again
         hipLaunchKernelGGL(cc_rank_blocksum_kernel, dim3(nb), dim3(SCAN_NT), 0, ctx->stream, d_probs, np, parent, size, n, block_sums, counters, rb);
         hipLaunchKernelGGL(cc_rank_scan_kernel, dim3(3), dim3(1024), 0, ctx->stream, block_sums, nb, counters);
@@ -984,12 +989,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
         // (developer switch OBIA_CC_CODE_DIV: pixels per small component below which the dense code[] pass and the pixel lists are used)
         static const long long code_div = std::getenv("OBIA_CC_CODE_DIV") ? atoll(std::getenv("OBIA_CC_CODE_DIV")) : 64;
         const bool use_code = (long long)n_small * code_div >= n;
-        // the rounds' "moved" counters: a ring of words cleared once (a fill per round was a launch and a gap per round)
-        constexpr int RING = 64;
-        int *ring = A.get<int>(RING);
-        if (!ring) return OBIA_E_NOMEM;
-        OBIA_HIP_TRY(hipMemsetAsync(ring, 0, sizeof(int) * RING, ctx->stream));
-        long long ring_pos = 0;
+        long long ring_pos = 0;   // (the rounds' "moved" counters: the ring in front of the root map, cleared with it)
         int *code = use_code ? A.get<int>(n) : parent;
         if (!settle || !work_a || !work_b || !tag || !code) return OBIA_E_NOMEM;
         // the walks' visited map: all zero between calls (every walk clears its marks): no 4-byte-per-pixel fill per batch (round 4)
@@ -1002,7 +1002,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                 if (hipMalloc(&ctx->cc_visited, want * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); set_error("out of device memory (visited map of %zu pixels)", want); return OBIA_E_NOMEM; }
                 ctx->cc_visited_px = want;
             }
-            OBIA_HIP_TRY(hipMemsetAsync(ctx->cc_visited, 0, sizeof(int32_t) * ctx->cc_visited_px, ctx->stream));
+            OBIA_TRY(fill_async(ctx, ctx->cc_visited, 0, sizeof(int32_t) * ctx->cc_visited_px));
         }
         ctx->cc_visited_dirty = true;     // until this call has queued its last walk
         visited = ctx->cc_visited;
@@ -1032,10 +1032,10 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
             if (!px_g || !ccur || !px_cn) return OBIA_E_NOMEM;
             int maxh = 1;
             for (auto &P : probs) maxh = std::max(maxh, P.H);
-            OBIA_HIP_TRY(hipMemsetAsync(ccur, 0, sizeof(int) * (size_t)n_small, ctx->stream));
+            OBIA_TRY(fill_async(ctx, ccur, 0, sizeof(int) * (size_t)n_small));
             hipLaunchKernelGGL(cc_small_pixels_kernel, dim3(maxh, np), dim3(256), 0, ctx->stream, d_probs, code, small_qoff, ccur, px_g, px_cn, small_px);
             for (int side = (n_small > 8 * (long long)n_surv ? 1 : 0); side < 2 && !converged; ++side) {
-                OBIA_HIP_TRY(hipMemsetAsync(tag, 0, sizeof(int) * (size_t)n_small, ctx->stream));
+                OBIA_TRY(fill_async(ctx, tag, 0, sizeof(int) * (size_t)n_small));
                 hipLaunchKernelGGL(cc_settle_init_kernel, dim3(cdiv(n_small, 256)), dim3(256), 0, ctx->stream, small_list, n_small, settle, side);
                 int n_items = n_small;
                 const int *work_in = nullptr;
@@ -1043,7 +1043,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                 for (long long round = 0; round <= max_rounds; ++round) {
                     if (std::getenv("OBIA_DEBUG_CC")) fprintf(stderr, "[obia cc]   (lists) side %d round %lld: %d items\n", side, round, n_items);
                     int *cnt = ring + (ring_pos++ % RING);
-                    if (ring_pos > RING && (ring_pos - 1) % RING == 0) OBIA_HIP_TRY(hipMemsetAsync(ring, 0, sizeof(int) * RING, ctx->stream));
+                    if (ring_pos > RING && (ring_pos - 1) % RING == 0) OBIA_TRY(fill_async(ctx, ring, 0, sizeof(int) * RING));
                     hipLaunchKernelGGL(cc_settle_eval_kernel, dim3(cdiv(n_items, 64)), dim3(64), 0, ctx->stream, small_qoff, ccur, px_g, px_cn, small_px,
                                        settle, work_in, n_items, work_a, cnt, tag, (int)(round & 0x3fffffff));
                     int n_next = 0;
@@ -1059,7 +1059,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                                    small_qoff, settle, queue, visited, target, n_small);
         }
         for (int side = (n_small > 8 * (long long)n_surv ? 1 : 0); !dense && side < 2 && !converged; ++side) {
-            OBIA_HIP_TRY(hipMemsetAsync(tag, 0, sizeof(int) * (size_t)n_small, ctx->stream));
+            OBIA_TRY(fill_async(ctx, tag, 0, sizeof(int) * (size_t)n_small));
             hipLaunchKernelGGL(cc_settle_init_kernel, dim3(cdiv(n_small, 256)), dim3(256), 0, ctx->stream, small_list, n_small, settle, side);
             int n_items = n_small;
             const int *work_in = nullptr;
@@ -1069,7 +1069,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
             for (long long round = 0; round <= max_rounds; ++round) {
                 if (std::getenv("OBIA_DEBUG_CC")) fprintf(stderr, "[obia cc]   side %d round %lld: %d items\n", side, round, n_items);
                 int *cnt = ring + (ring_pos++ % RING);
-                if (ring_pos > RING && (ring_pos - 1) % RING == 0) OBIA_HIP_TRY(hipMemsetAsync(ring, 0, sizeof(int) * RING, ctx->stream));
+                if (ring_pos > RING && (ring_pos - 1) % RING == 0) OBIA_TRY(fill_async(ctx, ring, 0, sizeof(int) * RING));
                 if (use_code)
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(cc_small_bfs_kernel<true>), dim3(cdiv(n_items, 64)), dim3(64), 0, ctx->stream, d_probs, np, code,
                                        newlab, small_list, small_qoff, start_label, settle, queue, visited, target, work_in, n_items, work_a,

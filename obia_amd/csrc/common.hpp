@@ -14,6 +14,8 @@
 
 #include "../../include/obia_hip.h"
 
+struct obia_ctx;
+
 namespace obia {
 
 void set_error(const char *fmt, ...);
@@ -57,6 +59,23 @@ class Arena {
     bool failed_ = false;
 };
 
+// The host tables of ONE planning phase -- the host code between two synchronisations -- as ONE upload.  add() copies a table into
+// the blob's slot of the pinned ring and returns where it WILL be on the device: both sides are reserved as one block when the first
+// table arrives (the device side from the arena, so it lives as long as the arena scope it was opened in), every table aligned to 16
+// bytes.  flush() issues the one copy; it must stand in front of the first kernel that reads a table, and a blob is closed by it: the
+// next add() opens another.  read_back() flushes an open blob before it waits, so no table is ever left behind a synchronisation.
+// A table that does not fit into what is left of the block closes it (one more upload, nothing else).
+class PlanBlob {
+  public:
+    template <typename T> T *add(obia_ctx *ctx, const T *host, size_t n) { return static_cast<T *>(add_bytes(ctx, host, n * sizeof(T))); }   // null: failed (the error is set)
+    int flush(obia_ctx *ctx);
+    void drop() { dev_ = host_ = nullptr; cap_ = used_ = 0; }   // forgets an open blob without uploading it
+  private:
+    void *add_bytes(obia_ctx *ctx, const void *host, size_t bytes);
+    char *dev_ = nullptr, *host_ = nullptr;
+    size_t cap_ = 0, used_ = 0;
+};
+
 struct Timing {
     double assign_ms = 0, prepass_ms = 0, feat_ms = 0, cc_ms = 0, zonal_ms = 0, total_ms = 0;
     double assign_px = 0, prepass_px = 0;   // pixels processed by the timed colour / pre-pass sweeps (sum over launches)
@@ -70,6 +89,9 @@ struct Timing {
     // assign_busy_ms equals assign_ms; the sweeps of a grouped pre-pass overlap (two window groups, two streams), so prepass_ms is a
     // sum of overlapping durations and prepass_busy_ms, their union, is the smaller
     double assign_busy_ms = 0, prepass_busy_ms = 0;
+    // small commands issued in the frame, kernels not included: fills (fill_async, clear_ranges: one per launch), host -> device
+    // uploads (upload_async, PlanBlob::flush) and device -> host read-backs (read_back, the sweeps' deferred one)
+    int fills = 0, uploads = 0, readbacks = 0;
 };
 
 }  // namespace obia
@@ -91,6 +113,7 @@ struct obia_ctx {
     bool cc_visited_dirty = false;
     char *up_buf = nullptr;          // pinned ring for small host -> device tables (upload_async): no stream sync per upload
     size_t up_bytes = 0, up_used = 0;
+    obia::PlanBlob plan;             // the open planning phase's tables (one upload per phase)
     int profiling = 0;               // 0 off, 1 every span, 2 only the colour sweeps (obia_set_profiling)
     obia::Timing timing;
     // event pairs recorded around kernels of interest; resolved (one sync) at the end of the call
@@ -134,6 +157,24 @@ int read_back(obia_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
 // (pageable, short-lived) buffer is free at once; the ring is recycled at the next read_back (everything queued before it
 // has then executed).
 int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
+int fill_async(obia_ctx *ctx, void *dev_dst, int byte, size_t bytes);   // hipMemsetAsync on the context's stream
+
+// Fills that stand next to each other in stream order as ONE launch (clear_ranges_kernel, context.cpp): the table of ranges is the
+// kernel's argument, passed by value -- nothing is uploaded.  add() collects (an empty range is dropped; a seventeenth one launches
+// the sixteen held), flush() launches; a set of one range is a plain fill.  Every set is flushed by hand: the destructor launches
+// nothing.
+struct ClearRange { void *p; unsigned long long bytes; unsigned value, pad; };
+struct ClearTable { ClearRange r[16]; int n; };
+class ClearSet {
+  public:
+    explicit ClearSet(obia_ctx *ctx) : ctx_(ctx) { t_.n = 0; }
+    int add(void *dev, int byte, size_t bytes);
+    int flush();
+  private:
+    obia_ctx *ctx_;
+    ClearTable t_;
+};
+
 int side_stream(obia_ctx *ctx);   // makes sure `side` and the events of both its users exist
 // Developer aid (OBIA_DEBUG_SYNC=1): synchronise the stream and report the stage on stderr, so that an asynchronous GPU fault
 // is pinned on the stage that caused it.  A no-op otherwise.

@@ -1,5 +1,6 @@
 // context.cpp -- context lifetime, workspace arena, error string, timing spans, the entry layer (enter, call frame, Staging).
 #include "common.hpp"
+#include "../../include/obia_testing.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -186,7 +187,9 @@ int read_back(obia_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes) 
         OBIA_HIP_TRY(hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault));
         ctx->pinned_bytes = want;
     }
+    OBIA_TRY(ctx->plan.flush(ctx));   // no table stays behind a synchronisation (and the ring is recycled below)
     OBIA_HIP_TRY(hipMemcpyAsync(ctx->pinned, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->timing.readbacks += 1;
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->up_used = 0;   // every upload queued so far has executed: the ring is free again
     memcpy(host_dst, ctx->pinned, bytes);
@@ -201,23 +204,131 @@ void debug_sync(obia_ctx *ctx, const char *stage) {
     fflush(stderr);
 }
 
+int fill_async(obia_ctx *ctx, void *dev_dst, int byte, size_t bytes) {
+    if (bytes == 0) return OBIA_OK;
+    OBIA_HIP_TRY(hipMemsetAsync(dev_dst, byte, bytes, ctx->stream));
+    ctx->timing.fills += 1;
+    return OBIA_OK;
+}
+
+// Every range in turn, all threads of the grid on each: 16-byte stores over the aligned body, single bytes for the at most 15 in
+// front of it and the at most 15 behind it.  Nothing outside [p, p + bytes) is touched.  RAGGED = false: every range of the set
+// starts and ends on a 16-byte boundary (ClearSet::flush looks), the kernel holds no byte store at all.
+template <bool RAGGED> __global__ __launch_bounds__(256) void clear_ranges_kernel(const ClearTable T) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    for (int k = 0; k < T.n; ++k) {
+        unsigned char *p = static_cast<unsigned char *>(T.r[k].p);
+        const size_t n = T.r[k].bytes;
+        const unsigned v = (T.r[k].value & 0xffu) * 0x01010101u;
+        size_t head = RAGGED ? (16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15 : 0;
+        if (head > n) head = n;
+        const size_t nvec = (n - head) / 16, tail0 = head + nvec * 16;
+        uint4 *pv = reinterpret_cast<uint4 *>(p + head);
+        for (size_t i = tid; i < nvec; i += stride) pv[i] = make_uint4(v, v, v, v);
+        if (RAGGED) {
+            if (tid < head) p[tid] = (unsigned char)v;
+            if (tid < n - tail0) p[tail0 + tid] = (unsigned char)v;
+        }
+    }
+}
+
+int ClearSet::add(void *dev, int byte, size_t bytes) {
+    if (bytes == 0) return OBIA_OK;
+    if (t_.n == 16) OBIA_TRY(flush());
+    t_.r[t_.n++] = ClearRange{dev, (unsigned long long)bytes, (unsigned)byte & 0xffu, 0u};
+    return OBIA_OK;
+}
+
+int ClearSet::flush() {
+    const int n = t_.n;
+    t_.n = 0;
+    if (n == 0) return OBIA_OK;
+    if (n == 1) return fill_async(ctx_, t_.r[0].p, (int)t_.r[0].value, (size_t)t_.r[0].bytes);
+    unsigned long long longest = 0;
+    bool ragged = false;
+    for (int k = 0; k < n; ++k) {
+        longest = std::max(longest, t_.r[k].bytes);
+        ragged = ragged || ((reinterpret_cast<uintptr_t>(t_.r[k].p) | (uintptr_t)t_.r[k].bytes) & 15) != 0;
+    }
+    ClearTable t = t_;
+    t.n = n;
+    const dim3 grid(flat_grid((long long)((longest + 15) / 16)));
+    if (ragged) hipLaunchKernelGGL(HIP_KERNEL_NAME(clear_ranges_kernel<true>), grid, dim3(256), 0, ctx_->stream, t);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(clear_ranges_kernel<false>), grid, dim3(256), 0, ctx_->stream, t);
+    OBIA_HIP_TRY(hipGetLastError());
+    ctx_->timing.fills += 1;
+    return OBIA_OK;
+}
+
+constexpr size_t RING = 8u << 20;
+
+static int ring_ready(obia_ctx *ctx) {
+    if (ctx->up_buf) return OBIA_OK;
+    void *p = nullptr;
+    OBIA_HIP_TRY(hipHostMalloc(&p, RING, hipHostMallocDefault));
+    ctx->up_buf = static_cast<char *>(p);
+    ctx->up_bytes = RING;
+    ctx->up_used = 0;
+    return OBIA_OK;
+}
+
+void *PlanBlob::add_bytes(obia_ctx *ctx, const void *host, size_t bytes) {
+    constexpr size_t BLOCK = 64u << 10;
+    const size_t need = (bytes + 15) & ~size_t(15);
+    if (dev_ && used_ + need > cap_ && flush(ctx) != OBIA_OK) return nullptr;
+    if (ring_ready(ctx) != OBIA_OK) return nullptr;
+    if (need > ctx->up_bytes / 2) {   // a table of megabytes: an upload of its own
+        if (flush(ctx) != OBIA_OK) return nullptr;
+        void *d = ctx->arena.alloc(need);
+        return d && upload_async(ctx, d, host, bytes) == OBIA_OK ? d : nullptr;
+    }
+    if (!dev_) {
+        const size_t cap = (std::max(need, BLOCK) + 63) & ~size_t(63);
+        if (ctx->up_used + cap > ctx->up_bytes) {   // ring full: wait for what is queued, start over (no blob is open)
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { set_error("stream synchronisation failed (plan upload)"); return nullptr; }
+            ctx->up_used = 0;
+        }
+        char *d = static_cast<char *>(ctx->arena.alloc(cap));
+        if (!d) return nullptr;
+        dev_ = d;
+        host_ = ctx->up_buf + ctx->up_used;
+        ctx->up_used += cap;
+        cap_ = cap;
+        used_ = 0;
+    }
+    void *d = dev_ + used_;
+    if (bytes) memcpy(host_ + used_, host, bytes);
+    used_ += need;
+    return d;
+}
+
+int PlanBlob::flush(obia_ctx *ctx) {
+    if (!dev_) return OBIA_OK;
+    char *const dev = dev_, *const host = host_;
+    const size_t used = used_, cap = cap_;
+    dev_ = host_ = nullptr;
+    cap_ = used_ = 0;
+    // (the part of the slot nobody wrote goes back to the ring when nothing was taken behind it)
+    if (ctx->up_buf && host + cap == ctx->up_buf + ctx->up_used) ctx->up_used -= cap - ((used + 63) & ~size_t(63));
+    if (used == 0) return OBIA_OK;
+    OBIA_HIP_TRY(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, ctx->stream));
+    ctx->timing.uploads += 1;
+    return OBIA_OK;
+}
+
 int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes) {
     if (bytes == 0) return OBIA_OK;
-    constexpr size_t RING = 8u << 20;
-    if (!ctx->up_buf) {
-        void *p = nullptr;
-        OBIA_HIP_TRY(hipHostMalloc(&p, RING, hipHostMallocDefault));
-        ctx->up_buf = static_cast<char *>(p);
-        ctx->up_bytes = RING;
-        ctx->up_used = 0;
-    }
+    ctx->timing.uploads += 1;
+    OBIA_TRY(ring_ready(ctx));
     if (bytes > ctx->up_bytes) {   // too big for the ring: plain synchronous copy
+        OBIA_TRY(ctx->plan.flush(ctx));   // (its slot of the ring is given up below)
         OBIA_HIP_TRY(hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, ctx->stream));
         OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->up_used = 0;
         return OBIA_OK;
     }
     if (ctx->up_used + bytes > ctx->up_bytes) {   // ring full: wait for what is queued, start over
+        OBIA_TRY(ctx->plan.flush(ctx));
         OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->up_used = 0;
     }
@@ -241,12 +352,14 @@ int quiesce(obia_ctx *ctx, int rc) {
 }
 
 void frame_begin(obia_ctx *ctx, unsigned opts) {
+    ctx->plan.drop();   // (a call that failed may have left tables behind: their device block goes with the arena)
     ctx->arena.reset();
     if (opts & FRAME_TIMING) begin_timing(ctx);
 }
 
 int frame_end(obia_ctx *ctx, unsigned opts, int rc) {
     if (rc != OBIA_OK) return quiesce(ctx, rc);
+    OBIA_TRY(ctx->plan.flush(ctx));
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (opts & FRAME_TIMING) resolve_timing(ctx);
     return OBIA_OK;
@@ -358,6 +471,18 @@ int obia_synchronize(obia_ctx *ctx) {
     return OBIA_OK;
 }
 
+int obia_test_clear_ranges_dev(obia_ctx *ctx, void *const *dev_ptrs, const int64_t *bytes, const int32_t *values, int n) {
+    OBIA_TRY(enter(ctx));
+    if (!dev_ptrs || !bytes || !values || n < 0) { set_error("clear ranges: null array or negative count"); return OBIA_E_INVALID; }
+    for (int i = 0; i < n; ++i)
+        if (bytes[i] < 0 || (bytes[i] > 0 && !dev_ptrs[i])) { set_error("clear ranges: range %d is not a range", i); return OBIA_E_INVALID; }
+    return call_frame(ctx, FRAME_TIMING, [&] {
+        ClearSet clr(ctx);
+        for (int i = 0; i < n; ++i) OBIA_TRY(clr.add(dev_ptrs[i], values[i], (size_t)bytes[i]));
+        return clr.flush();
+    });
+}
+
 int64_t obia_workspace_bytes(obia_ctx *ctx) { return ctx ? (int64_t)ctx->arena.capacity() : 0; }
 
 void obia_slic_default_params(obia_slic_params *p) {
@@ -403,6 +528,9 @@ double obia_last_timing(obia_ctx *ctx, int what) {
         case 13: return ctx->timing.prepass_shared_px;
         case 14: return ctx->timing.feat_fused_px;
         case 15: return (double)ctx->timing.prepass_group_launches;
+        case 16: return (double)ctx->timing.fills;
+        case 17: return (double)ctx->timing.uploads;
+        case 18: return (double)ctx->timing.readbacks;
         default: return -1.0;
     }
 }

@@ -812,17 +812,49 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const SlicProblem *__r
     }
 }
 
-int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid) {
+// The tables that depend on the window shapes only, into the open planning blob (no flush): the problems as slic_batch_layout left
+// them -- H, W and the offsets, what the counting and seeding kernels read -- and the tile -> problem table of the sweep's
+// one-dimensional, XCD-aware grid (slic_sweep.hip).  A tiler batch calls this in front of its first read-back, so that the tables
+// travel while the mask and count kernels run; the other callers get it from slic_count_valid / slic_plan_and_seed.  Once per batch.
+int slic_plan_layout(obia_ctx *ctx, SlicBatch &b) {
+    if (b.d_tile_prob) return OBIA_OK;
+    const int np = b.nprob;
+    long long tiles_all = 0;
+    int tile_max = 0;
+    for (int p = 0; p < np; ++p) {
+        SlicProblem &P = b.probs[p];
+        P.tiles_x = cdiv(P.W, SWEEP_TW);
+        P.tiles_y = cdiv(P.H, SWEEP_TH);
+        const int nt = P.tiles_x * P.tiles_y;
+        if (tiles_all + nt > 0x7fff0000LL) { set_error("too many sweep tiles in one batch"); return OBIA_E_INVALID; }
+        P.tile_off = (int)tiles_all;
+        tiles_all += nt;
+        if (nt > tile_max) tile_max = nt;
+    }
+    b.total_tiles_all = tiles_all > 0 ? tiles_all : 1;
+    b.total_tiles = tile_max;
+    std::vector<int> tp((size_t)b.total_tiles_all, 0);
+    for (int p = 0; p < np; ++p)
+        for (int t = 0; t < b.probs[p].tiles_x * b.probs[p].tiles_y; ++t) tp[(size_t)b.probs[p].tile_off + t] = p;
+    b.d_probs = ctx->plan.add(ctx, b.probs.data(), (size_t)np);
+    b.d_tile_prob = ctx->plan.add(ctx, tp.data(), tp.size());
+    if (!b.d_probs || !b.d_tile_prob) return OBIA_E_NOMEM;
+    return OBIA_OK;
+}
+
+int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared) {
     const int np = b.nprob;
     Arena &A = ctx->arena;
     nvalid.assign(np, 0);
-    if (!b.d_probs) b.d_probs = A.get<SlicProblem>(np);
-    if (!b.d_probs) return OBIA_E_NOMEM;
+    OBIA_TRY(slic_plan_layout(ctx, b));
     if (b.masked) {
-        OBIA_TRY(upload_async(ctx, b.d_probs, b.probs.data(), sizeof(SlicProblem) * np));
-        int *d_cnt = A.get<int>(np);
-        if (!d_cnt) return OBIA_E_NOMEM;
-        OBIA_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int) * np, ctx->stream));
+        OBIA_TRY(ctx->plan.flush(ctx));
+        int *d_cnt = d_cnt_cleared;
+        if (!d_cnt) {
+            d_cnt = A.get<int>(np);
+            if (!d_cnt) return OBIA_E_NOMEM;
+            OBIA_TRY(fill_async(ctx, d_cnt, 0, sizeof(int) * np));
+        }
         int blocks = cdiv(b.maxpix, 256 * 16 * 32);
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(count_valid_kernel, dim3(blocks, np), dim3(256), 0, ctx->stream, b.d_probs, b.d_mask, d_cnt);
@@ -840,10 +872,8 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
         for (int p = 0; p < np; ++p)
             if (ext[p].n < 0 || (ext[p].n > 0 && !ext[p].yx && !ext[p].d_yx)) { set_error("external seeds of problem %d: bad set", p); return OBIA_E_INVALID; }
     Arena &A = ctx->arena;
-    // problems carry H, W and their offsets already (slic_batch_layout); upload a first version for the
-    // counting / seeding kernels
-    if (!b.d_probs) b.d_probs = A.get<SlicProblem>(np);
-    if (!b.d_probs) return OBIA_E_NOMEM;
+    // problems carry H, W and their offsets already (slic_batch_layout): a first version for the counting / seeding kernels
+    OBIA_TRY(slic_plan_layout(ctx, b));
     std::vector<int> nvalid;
     if (nvalid_in) nvalid = *nvalid_in;
     else OBIA_TRY(slic_count_valid(ctx, b, nvalid));
@@ -898,10 +928,9 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     b.total_cent = cent_off > 0 ? cent_off : 1;
     b.d_seed = A.get<float>((size_t)b.total_cent * 2);
     b.d_cent_prob = A.get<int>(b.total_cent);
-    SeedGrid *d_grids = A.get<SeedGrid>(np);
+    SeedGrid *d_grids = ctx->plan.add(ctx, grids.data(), (size_t)np);   // (this phase's one table, flushed in front of the seeding kernel)
     if (!b.d_seed || !b.d_cent_prob || !d_grids) return OBIA_E_NOMEM;
-    OBIA_HIP_TRY(hipMemsetAsync(b.d_cent_prob, 0xff, sizeof(int) * b.total_cent, ctx->stream));
-    OBIA_TRY(upload_async(ctx, d_grids, grids.data(), sizeof(SeedGrid) * np));
+    OBIA_TRY(fill_async(ctx, b.d_cent_prob, 0xff, sizeof(int) * b.total_cent));
     std::vector<int> K(np);
     if (ext) {
         // every problem's set behind the one before it (grids[p].cent_off); the centroid -> problem table from the host
@@ -924,7 +953,8 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     } else if (b.masked) {
         int *d_K = A.get<int>(np);
         if (!d_K) return OBIA_E_NOMEM;
-        // (the descriptors slic_count_valid uploaded are still in place: the seeding reads H, W and pix_off only)
+        // (the layout version of the descriptors, slic_plan_layout: the seeding reads H, W and pix_off only)
+        OBIA_TRY(ctx->plan.flush(ctx));
         hipLaunchKernelGGL(seed_masked_kernel, dim3(np), dim3(256), 0, ctx->stream, d_grids, b.d_probs, b.d_mask,
                            b.d_seed, b.d_cent_prob, d_K);
         OBIA_TRY(read_back(ctx, K.data(), d_K, sizeof(int) * np));
@@ -932,12 +962,12 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
     } else {
         int maxK = 1;
         for (int p = 0; p < np; ++p) { K[p] = grids[p].ny * grids[p].nx; if (K[p] > maxK) maxK = K[p]; }
+        OBIA_TRY(ctx->plan.flush(ctx));
         hipLaunchKernelGGL(seed_grid_kernel, dim3(cdiv(maxK, 256), np), dim3(256), 0, ctx->stream, d_grids, np,
                            b.d_seed, b.d_cent_prob);
     }
-    // window steps, bins, tiles
-    int cell_off = 0, tile_max = 0;
-    long long tiles_all = 0;
+    // window steps and bins (the sweep tiles are part of the layout: slic_plan_layout)
+    int cell_off = 0;
     for (int p = 0; p < np; ++p) {
         SlicProblem &P = b.probs[p];
         P.K = K[p];
@@ -956,33 +986,20 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
         long long nc = (long long)P.ncy * P.ncx;
         if (cell_off + nc > 0x7fff0000LL) { set_error("too many bins in one batch"); return OBIA_E_INVALID; }
         cell_off += (int)nc;
-        P.tiles_x = cdiv(P.W, SWEEP_TW);
-        P.tiles_y = cdiv(P.H, SWEEP_TH);
-        const int nt = P.tiles_x * P.tiles_y;
-        P.tile_off = (int)tiles_all;
-        tiles_all += nt;
-        if (nt > tile_max) tile_max = nt;
-    }
-    b.total_tiles_all = tiles_all > 0 ? tiles_all : 1;
-    {   // tile -> problem table of the sweep's one-dimensional, XCD-aware grid (slic_sweep.hip)
-        std::vector<int> tp((size_t)b.total_tiles_all, 0);
-        for (int p = 0; p < np; ++p)
-            for (int t = 0; t < b.probs[p].tiles_x * b.probs[p].tiles_y; ++t) tp[(size_t)b.probs[p].tile_off + t] = p;
-        b.d_tile_prob = A.get<int>(tp.size());
-        if (!b.d_tile_prob) return OBIA_E_NOMEM;
-        OBIA_TRY(upload_async(ctx, b.d_tile_prob, tp.data(), sizeof(int) * tp.size()));   // (pinned ring: tp may go out of scope)
     }
     b.total_cells = cell_off > 0 ? cell_off : 1;
-    b.total_tiles = tile_max;
-    OBIA_TRY(upload_async(ctx, b.d_probs, b.probs.data(), sizeof(SlicProblem) * np));
+    // the complete descriptors, a table of their own beside the layout version (the seeding above may still be reading that one).  They
+    // open the planning phase that ends with the connectivity stage's read-back: whoever queues the sweeps adds its tables and
+    // flushes in front of the first kernel that reads one (slic_sweep.hip: queue_sweeps)
+    b.d_probs = ctx->plan.add(ctx, b.probs.data(), (size_t)np);
+    if (!b.d_probs) return OBIA_E_NOMEM;
     const int RS = CENT_REC + b.CP;
     b.d_cent = A.get<float>((size_t)b.total_cent * RS);
     b.d_head = A.get<int>((size_t)b.total_cells * 2);
     const size_t acc_q = (size_t)b.total_cent * acc_record_qwords(b.CP);
     b.d_acc = A.get<unsigned long long>(acc_q);
     if (!b.d_cent || !b.d_head || !b.d_acc) return OBIA_E_NOMEM;
-    OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * acc_q, ctx->stream));
-    return OBIA_OK;
+    return OBIA_OK;   // (the accumulators are cleared with the sweeps' other buffers: queue_sweeps)
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -228,15 +228,20 @@ struct ExternalSeeds { const double *yx; int n; double step; const float *d_yx =
 int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_segments,
                        const std::vector<int> *nvalid = nullptr, const ExternalSeeds *ext = nullptr);
 // valid (unmasked) pixels per problem: mask.sum() (tiling.py:133, slic_superpixels.py:322)
-int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid);
+// d_cnt_cleared: one zeroed int per problem that the caller cleared beside its own fills (null: allocated and cleared here)
+int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared = nullptr);
+// the tables that depend on the window shapes only (layout version of the problems, tile -> problem table) into the open planning
+// blob; the caller flushes (slic_count_valid and slic_plan_and_seed do, for a caller that did not call it)
+int slic_plan_layout(obia_ctx *ctx, SlicBatch &b);
 
 // Runs the sweeps; labels (pre-connectivity) land in b.d_labels.  Three steps, the same for every caller:
 // slic_run_sweeps queues the sweeps and the read-back of their orphan flag (a valid pixel no window reached) and pixel counters, and
 // returns without a host synchronisation.  Once the caller has synchronised the stream for its own reasons (the tiler: the
 // connectivity stage reads its counters back), slic_sweeps_settle looks at the flag.  When it reports `repeat`, the labels are not
 // final: the caller rewinds the arena to a mark taken before slic_run_sweeps (b.d_mask4 as it was then: the sweeps pack the mask
-// above the mark when it was null), calls slic_rerun_storing -- every sweep stores its labels; complete when it returns -- and
-// computes again whatever it had computed from the labels.
+// above the mark when it was null), calls slic_rerun_storing -- every sweep stores its labels; queued like the first run, its
+// labels are final in stream order -- computes again whatever it had computed from the labels, and after its next synchronisation
+// calls slic_sweeps_settle(ctx, nullptr) for the repeat's pixel counters: the repeat has no round trip of its own either.
 int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b);
 int slic_sweeps_settle(obia_ctx *ctx, bool *repeat);
 int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b);
@@ -282,10 +287,11 @@ __device__ __forceinline__ int cc_resolve_label(const CcResolve &R, long long i)
 #endif
 // labels_out: the dense label map.  deferred (nullable): when given, the final relabel pass is NOT run -- labels_out is not
 // written -- and *deferred describes how to resolve a pixel.  (The component walks mark their pixels in a map of the context's
-// that is all zero between calls, obia_ctx::cc_visited.)
+// that is all zero between calls, obia_ctx::cc_visited.)  d_probs (nullable): `probs` on the device already, as part of an upload
+// the caller has queued (a tiler batch sends the table with its sweeps' descriptors); null: uploaded here.
 int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &probs, const int32_t *labels_in,
                                long long total_pix, int start_label, int32_t *labels_out, int *h_n_labels_out,
-                               CcResolve *deferred = nullptr);
+                               CcResolve *deferred = nullptr, const CcProblem *d_probs = nullptr);
 
 // Connectivity enforcement on one dense (H,W) label map (device pointers).
 int enforce_connectivity_dev(obia_ctx *ctx, const int32_t *labels_in, int H, int W, int min_size,

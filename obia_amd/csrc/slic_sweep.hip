@@ -1711,8 +1711,8 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
         fp.cache_k = A.get<int>(nt * (MAXC + 1));
         fp.cache_q = A.get<unsigned long long>(nt * MAXC * (size_t)(b.CP + 3));
         if (!fp.bin_stamp || !fp.tile_lp || !fp.cache_k || !fp.cache_q) return OBIA_E_NOMEM;
-        OBIA_HIP_TRY(hipMemsetAsync(fp.bin_stamp, 0, sizeof(int) * (size_t)b.total_cells, ctx->stream));
-        OBIA_HIP_TRY(hipMemsetAsync(fp.tile_lp, 0, sizeof(int) * nt, ctx->stream));
+        OBIA_TRY(fill_async(ctx, fp.bin_stamp, 0, sizeof(int) * (size_t)b.total_cells));
+        OBIA_TRY(fill_async(ctx, fp.tile_lp, 0, sizeof(int) * nt));
     }
     {   // candidate lists of the sweep tiles (see the top of the file)
         const size_t nt = (size_t)b.total_tiles_all;
@@ -1731,6 +1731,7 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
         if (!b.d_mask4) return OBIA_E_NOMEM;
         int gq = (maxh_z + 3) / 4;
         if (gq > 16384) gq = 16384;
+        OBIA_TRY(ctx->plan.flush(ctx));   // (the descriptors; a tiler batch comes with the mask packed and flushes once, below)
         hipLaunchKernelGGL(mask_pack4_kernel, dim3(gq, b.nprob), dim3(256), 0, ctx->stream, b.d_probs, b.d_mask, b.d_mask4);
     }
     if (maxh_z > 4096) maxh_z = 4096;
@@ -1748,7 +1749,6 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
         fill_labels(ctx, b);
         debug_sync(ctx, "sweeps: label fill");
     }
-    if (repeat) OBIA_HIP_TRY(hipMemsetAsync(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ, ctx->stream));
     const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
     const bool prepass_visits = std::getenv("OBIA_PREPASS_VISITS") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prepass_runs.py): the spatial pre-pass by pixel visits, not runs
     // Shared pre-pass (slic_prepass_broadcast_kernel): the sweeps of the pre-pass but the last, and the centroid steps between them,
@@ -1787,18 +1787,14 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
         n_act = (int)ap.size();
         act_p_base = ap.front();
         const bool span = ap.back() - ap.front() + 1 == n_act;   // consecutive problems: consecutive tiles, no table in front of a tile
-        int *d_mr = A.get<int>(mr.size());
-        if (!d_mr) return OBIA_E_NOMEM;
-        OBIA_TRY(upload_async(ctx, d_mr, mr.data(), sizeof(int) * mr.size()));
-        d_member_rep = d_mr;
+        d_member_rep = ctx->plan.add(ctx, mr.data(), mr.size());   // (the class tables join the descriptors' upload)
+        if (!d_member_rep) return OBIA_E_NOMEM;
         if (span) {
             act_tiles.base = b.probs[ap.front()].tile_off;
             act_tiles.end = b.probs[ap.back()].tile_off + b.probs[ap.back()].tiles_x * b.probs[ap.back()].tiles_y;
         } else {
-            int *d_ap = A.get<int>(ap.size()), *d_at = A.get<int>(at.size() ? at.size() : 1);
+            const int *d_ap = ctx->plan.add(ctx, ap.data(), ap.size()), *d_at = ctx->plan.add(ctx, at.data(), at.size());
             if (!d_ap || !d_at) return OBIA_E_NOMEM;
-            OBIA_TRY(upload_async(ctx, d_ap, ap.data(), sizeof(int) * ap.size()));
-            if (!at.empty()) OBIA_TRY(upload_async(ctx, d_at, at.data(), sizeof(int) * at.size()));
             d_act_probs = d_ap;
             act_tiles.table = d_at; act_tiles.base = 0; act_tiles.end = (int)at.size();
         }
@@ -1835,10 +1831,17 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             if (grp_split > 0) OBIA_TRY(side_stream(ctx));
         }
     }
-    OBIA_HIP_TRY(hipMemsetAsync(d_px, 0, sizeof(unsigned long long) * 513, ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells, ctx->stream));   // buffer 0 only
-    // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
-    OBIA_HIP_TRY(hipMemsetAsync(b.d_tl_meta, 0xff, sizeof(int) * 3 * (size_t)b.total_tiles_all, ctx->stream));
+    // the planning phase's one upload: the descriptors (slic_plan_and_seed), the class tables above, whatever the caller added
+    OBIA_TRY(ctx->plan.flush(ctx));
+    {   // ... and its one clear: the accumulators (also in front of a repeat), the counters and the flag, the bins, the tiles' lists
+        ClearSet clr(ctx);
+        OBIA_TRY(clr.add(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ));
+        OBIA_TRY(clr.add(d_px, 0, sizeof(unsigned long long) * 513));
+        OBIA_TRY(clr.add(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells));   // buffer 0 only
+        // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
+        OBIA_TRY(clr.add(b.d_tl_meta, 0xff, sizeof(int) * 3 * (size_t)b.total_tiles_all));
+        OBIA_TRY(clr.flush());
+    }
     debug_sync(ctx, "sweeps: memsets");
     bool first = true;
     int sweep_no = 0;
@@ -1852,7 +1855,7 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
             fill_labels(ctx, b);
             // (exit_on_fixed_point: no tile may replay "labels already in place" across the refill -- every tile is evaluated
             // by the first sweep of the main pass)
-            if (fp.tile_lp) OBIA_HIP_TRY(hipMemsetAsync(fp.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all, ctx->stream));
+            if (fp.tile_lp) OBIA_TRY(fill_async(ctx, fp.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all));
         }
         const int iters = ignore_color ? pre_iter : b.max_iter;
         for (int it = 0; it < iters; ++it) {
@@ -1992,40 +1995,43 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     return OBIA_OK;
 }
 
+// the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle, after a synchronisation that
+// somebody else needs anyway (the connectivity stage's read-back): no round trip of their own
+static int defer_counters(obia_ctx *ctx, const unsigned long long *d_px) {
+    if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(unsigned long long) * 513, hipHostMallocDefault));
+    OBIA_HIP_TRY(hipMemcpyAsync(ctx->defer_buf, d_px, sizeof(unsigned long long) * 513, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->timing.readbacks += 1;
+    ctx->defer_pending = true;
+    return OBIA_OK;
+}
+
 int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b) {
     ctx->defer_pending = false;   // (also when this call fails: a settle after it finds nothing to look at)
     unsigned long long *d_px = nullptr;
     ctx->defer_shared_px = 0.0;
     OBIA_TRY(queue_sweeps(ctx, b, false, &d_px, &ctx->defer_shared_px));
-    if (!d_px) return OBIA_OK;
-    // the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle
-    if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(unsigned long long) * 513, hipHostMallocDefault));
-    OBIA_HIP_TRY(hipMemcpyAsync(ctx->defer_buf, d_px, sizeof(unsigned long long) * 513, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->defer_pending = true;
-    return OBIA_OK;
+    return d_px ? defer_counters(ctx, d_px) : OBIA_OK;
 }
 
-// (see slic.hpp) the stream has been synchronised since slic_run_sweeps returned
+// (see slic.hpp) the stream has been synchronised since slic_run_sweeps / slic_rerun_storing returned.  repeat == null: behind a
+// repeat, whose sweeps all store their labels -- only the counters are of interest
 int slic_sweeps_settle(obia_ctx *ctx, bool *repeat) {
-    *repeat = false;
+    if (repeat) *repeat = false;
     if (!ctx->defer_pending) return OBIA_OK;
     ctx->defer_pending = false;
     const unsigned long long *h = ctx->defer_buf;
-    if ((h[512] & 0xffffffffull) != 0ull) { *repeat = true; return OBIA_OK; }   // (the repeat counts its own pixels)
+    if (repeat && (h[512] & 0xffffffffull) != 0ull) { *repeat = true; return OBIA_OK; }   // (the repeat counts its own pixels)
     fold_counters(ctx, h, ctx->defer_shared_px);
     return OBIA_OK;
 }
 
 int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b) {
     ctx->timing.batch_repeats += 1;
+    ctx->defer_pending = false;
     unsigned long long *d_px = nullptr;
-    double shared_px = 0.0;   // (a repeat stores labels in every sweep: nothing is shared)
-    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px, &shared_px));
-    if (!d_px) return OBIA_OK;
-    unsigned long long h[513];
-    OBIA_TRY(read_back(ctx, h, d_px, sizeof(h)));
-    fold_counters(ctx, h, shared_px);
-    return OBIA_OK;
+    ctx->defer_shared_px = 0.0;   // (a repeat stores labels in every sweep: nothing is shared)
+    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px, &ctx->defer_shared_px));
+    return d_px ? defer_counters(ctx, d_px) : OBIA_OK;
 }
 
 }  // namespace obia

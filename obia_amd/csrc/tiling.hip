@@ -397,7 +397,7 @@ static int seed_tiles_skimage(obia_ctx *ctx, TileState &S, const SlicBatch &b, c
     float *d_seeds = A.get<float>(2 * (size_t)total);
     double *d_steps = A.get<double>(2 * (size_t)np);
     if (!d_seeds || !d_steps) return OBIA_E_NOMEM;
-    OBIA_HIP_TRY(hipMemsetAsync(d_steps, 0, sizeof(double) * 2 * (size_t)np, ctx->stream));
+    OBIA_TRY(fill_async(ctx, d_steps, 0, sizeof(double) * 2 * (size_t)np));
     auto ascending_below = [](const int64_t *v, long long n, long long bound) {
         if (v[0] < 0 || v[n - 1] >= bound) return false;
         for (long long i = 1; i < n; ++i) if (v[i] <= v[i - 1]) return false;
@@ -445,8 +445,6 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     for (auto &t : wins) b.windows.push_back(SrcWindow{t.y0, t.x0, t.h, t.w, 0, 0, 0});
     OBIA_TRY(slic_batch_layout(b));
     for (int p = 0; p < np; ++p) { wins[p].pix_off = b.probs[p].pix_off; wins[p].m4_off = b.probs[p].m4_off; }
-    TileWin *d_wins = A.get<TileWin>(np);
-    b.d_windows = A.get<SrcWindow>(np);
     b.d_mask = A.get<uint8_t>((size_t)b.total_pix);
     unsigned *d_mask4 = A.get<unsigned>((size_t)b.total_m4);   // the packed mask of the sweeps, written by tile_mask_kernel<true>
     if (!d_mask4) return OBIA_E_NOMEM;
@@ -477,14 +475,27 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         }
     }
     b.d_labels = A.get<int32_t>((size_t)b.total_pix);
-    if (!d_wins || !b.d_windows || !b.d_mask || !b.d_feat || !b.d_labels) return OBIA_E_NOMEM;
-    OBIA_TRY(upload_async(ctx, d_wins, wins.data(), sizeof(TileWin) * np));   // (pinned ring: no stream sync per small table)
-    OBIA_TRY(upload_async(ctx, b.d_windows, b.windows.data(), sizeof(SrcWindow) * np));
-    int *d_tile_any = A.get<int>(np);
-    if (!d_tile_any) return OBIA_E_NOMEM;
+    if (!b.d_mask || !b.d_feat || !b.d_labels) return OBIA_E_NOMEM;
+    // first planning phase, up to the read-back of the valid counts: everything that depends on the window shapes alone is ONE upload,
+    // queued here so that it travels while the mask and count kernels run -- the windows in both forms, the layout version of the
+    // problems and the tile -> problem table (slic_plan_layout) -- and the phase's fills are ONE clear
+    TileWin *d_wins = ctx->plan.add(ctx, wins.data(), (size_t)np);
+    b.d_windows = ctx->plan.add(ctx, b.windows.data(), (size_t)np);
+    if (!d_wins || !b.d_windows) return OBIA_E_NOMEM;
+    OBIA_TRY(slic_plan_layout(ctx, b));
+    OBIA_TRY(ctx->plan.flush(ctx));
+    int *d_tile_any = A.get<int>(np), *d_cnt = A.get<int>(np);
+    if (!d_tile_any || !d_cnt) return OBIA_E_NOMEM;
+    {
+        ClearSet clr(ctx);
+        if (white) {
+            OBIA_TRY(clr.add(S.inside, 0, sizeof(unsigned) * (size_t)S.next_id));
+            OBIA_TRY(clr.add(d_tile_any, 0, sizeof(int) * (size_t)np));
+        }
+        OBIA_TRY(clr.add(d_cnt, 0, sizeof(int) * (size_t)np));   // (slic_count_valid: the tiler always hands slic a mask)
+        OBIA_TRY(clr.flush());
+    }
     if (white) {
-        OBIA_HIP_TRY(hipMemsetAsync(S.inside, 0, sizeof(unsigned) * (size_t)S.next_id, ctx->stream));
-        OBIA_HIP_TRY(hipMemsetAsync(d_tile_any, 0, sizeof(int) * (size_t)np, ctx->stream));
         hipLaunchKernelGGL(tile_count_inside_kernel, dim3(grid_rows(wins), np), dim3(256), 0, ctx->stream, d_wins, S.G, S.W, S.inside, d_tile_any);
     }
     {
@@ -512,7 +523,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     }
     std::vector<int> nvalid;
     debug_sync(ctx, "tiler: mask + features");
-    OBIA_TRY(slic_count_valid(ctx, b, nvalid));
+    OBIA_TRY(slic_count_valid(ctx, b, nvalid, d_cnt));
     debug_sync(ctx, "tiler: count_valid");
     std::vector<int> nseg(np);
     const double pixel_area = S.tp.pixel_width * S.tp.pixel_height;
@@ -529,6 +540,15 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     if (S.seeding == OBIA_SEEDING_SKIMAGE) OBIA_TRY(seed_tiles_skimage(ctx, S, b, nvalid, nseg, ext));
     OBIA_TRY(slic_plan_and_seed(ctx, b, nseg, &nvalid, ext.empty() ? nullptr : ext.data()));
     debug_sync(ctx, "tiler: plan_and_seed");
+    // the connectivity stage's table joins the upload of the sweeps' descriptors (slic_plan_and_seed left it open; the sweeps flush)
+    std::vector<CcProblem> cps(np);
+    for (int p = 0; p < np; ++p) {
+        const SlicProblem &P = b.probs[p];
+        const auto [min_size, max_size] = slic_cc_sizes(S.sp.min_size_factor, S.sp.max_size_factor, P.n_valid, P.K);
+        cps[p] = CcProblem{P.H, P.W, P.pix_off, min_size, max_size};
+    }
+    const CcProblem *d_cps = S.sp.enforce_connectivity ? ctx->plan.add(ctx, cps.data(), (size_t)np) : nullptr;
+    if (S.sp.enforce_connectivity && !d_cps) return OBIA_E_NOMEM;
     // (a batch whose sweeps all store their labels never shares its pre-pass: the whole black pre-pass is there to run beside, as before)
     if (!white && S.pf.planned && !S.pf.launched)
         OBIA_TRY(prefetch_white_launch(ctx, S, OBIA_PREFETCH_BESIDE != 0 || b.exit_on_fixed_point || b.slic_zero));
@@ -539,20 +559,15 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     int n_new = 0;
     CcResolve resolve{};
     if (S.sp.enforce_connectivity) {
-        std::vector<CcProblem> cps(np);
-        for (int p = 0; p < np; ++p) {
-            const SlicProblem &P = b.probs[p];
-            const auto [min_size, max_size] = slic_cc_sizes(S.sp.min_size_factor, S.sp.max_size_factor, P.n_valid, P.K);
-            cps[p] = CcProblem{P.H, P.W, P.pix_off, min_size, max_size};
-        }
-        OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve));
+        OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve, d_cps));
         bool repeat = false;
         OBIA_TRY(slic_sweeps_settle(ctx, &repeat));
         if (repeat) {   // rare: a valid pixel no window reached kept a label that was not stored -- sweeps with stored labels, stage again
             A.rewind(sweeps_mk);
             b.d_mask4 = mask4;
             OBIA_TRY(slic_rerun_storing(ctx, b));
-            OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve));
+            OBIA_TRY(enforce_connectivity_batch(ctx, cps, b.d_labels, b.total_pix, 1, nullptr, &n_new, &resolve, d_cps));
+            OBIA_TRY(slic_sweeps_settle(ctx, nullptr));   // (the repeat's counters came back beside the connectivity stage's)
         }
         debug_sync(ctx, "tiler: connectivity");
     } else {
@@ -565,11 +580,12 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         for (auto &t : wins) sblocks = std::max(sblocks, cdiv(t.w, 64) * cdiv(t.h, 64));
         hipLaunchKernelGGL(tile_scatter_kernel, dim3(sblocks, np), dim3(64), 0, ctx->stream, d_wins, resolve, S.G, S.W,
                            S.next_id - 1, S.seg_size);
-        OBIA_HIP_TRY(hipMemsetAsync(S.alive + S.next_id, 1, (size_t)n_new, ctx->stream));
+        OBIA_TRY(fill_async(ctx, S.alive + S.next_id, 1, (size_t)n_new));
         S.next_id += n_new;
     }
     OBIA_HIP_TRY(hipGetLastError());
-    // (no synchronisation here: every host table of the batch went through upload_async, and the arena is reused in stream order)
+    // (no synchronisation here: every host table of the batch went through the pinned ring, and the arena is reused in stream order)
+    OBIA_TRY(ctx->plan.flush(ctx));   // (nothing is open on any path that gets here; a table must not outlive its arena scope)
     A.rewind(mk);
     return OBIA_OK;
 }
@@ -701,8 +717,8 @@ static int tiler_init(obia_ctx *ctx, TileState &S, const float *img, const uint8
     S.newid = A.get<int>((size_t)cap);
     S.d_total = A.get<long long>(1);
     if (!S.seg_size || !S.inside || !S.alive || !S.newid || !S.d_total) return OBIA_E_NOMEM;
-    OBIA_HIP_TRY(hipMemsetAsync(S.seg_size, 0, sizeof(unsigned) * (size_t)cap, ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(S.alive, 0, (size_t)cap, ctx->stream));
+    OBIA_TRY(fill_async(ctx, S.seg_size, 0, sizeof(unsigned) * (size_t)cap));
+    OBIA_TRY(fill_async(ctx, S.alive, 0, (size_t)cap));
     // corner squares: side buffer/2 in MAP units (tiling.py:189), i.e. buffer/2/pixel_size pixels; a pixel is
     // inside when its centre is (rasterize default all_touched=False)
     S.clx = S.cly = S.clx_in = S.cly_in = S.clx_any = S.cly_any = 0;
@@ -887,7 +903,7 @@ static int tiled_slic_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, 
     OBIA_TRY(check_seeding(seeding, picks));
     OBIA_TRY(tiler_init(ctx, S, img, mask, H, W, C, H, 0, tp, sp, labels_out, 0));
     S.seeding = seeding; S.pick_fn = picks; S.pick_user = picks_user;
-    OBIA_HIP_TRY(hipMemsetAsync(labels_out, 0, sizeof(int32_t) * (size_t)H * W, ctx->stream));
+    OBIA_TRY(fill_async(ctx, labels_out, 0, sizeof(int32_t) * (size_t)H * W));
     const int nty = cdiv(H, tp->tile_size);
     OBIA_TRY(prefetch_white_plan(ctx, S, tp->white_order));               // features of all white tiles: one batch
     OBIA_TRY(tiler_run(ctx, S, false, 0, nty, -1));                       // pass 1: black tiles
@@ -970,7 +986,7 @@ int obia_tiler_set_segments(obia_tiler *t, int first_id, int count, const uint32
     if (first_id + count > t->S.id_cap) { set_error("segment id capacity exceeded (%d + %d > %d)", first_id, count, t->S.id_cap); return OBIA_E_NOMEM; }
     if (count == 0) return OBIA_OK;
     OBIA_HIP_TRY(hipMemcpyAsync(t->S.seg_size + first_id, sizes_dev, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToDevice, t->ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(t->S.alive + first_id, 1, (size_t)count, t->ctx->stream));
+    OBIA_TRY(fill_async(t->ctx, t->S.alive + first_id, 1, (size_t)count));
     if (first_id + count > t->S.next_id) t->S.next_id = first_id + count;
     OBIA_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
     return OBIA_OK;
@@ -1009,7 +1025,7 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
         t->seam_cap = (size_t)n + 2;
     }
     int *ctr = t->seam_buf, *new_list = t->seam_buf + 2;
-    OBIA_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(int) * 2, ctx->stream));
+    OBIA_TRY(fill_async(ctx, ctr, 0, sizeof(int) * 2));
     const int blocks = std::min(cdiv(n, 256), 2048);
     hipLaunchKernelGGL(seam_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, codes_dev, n, my_rank, owner_rank, fmap_dev, fmap_cap, new_list, ctr,
                        ids_out_dev);

@@ -521,10 +521,14 @@ int zonal_moments_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, in
     unsigned *g_n = A.get<unsigned>(nlb);
     double *g_s2 = A.get<double>(nlb), *g_s3 = A.get<double>(nlb), *g_s4 = A.get<double>(nlb);
     if (!g_n || !g_s2 || !g_s3 || !g_s4) return OBIA_E_NOMEM;
-    OBIA_HIP_TRY(hipMemsetAsync(g_n, 0, sizeof(unsigned) * nlb, ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(g_s2, 0, sizeof(double) * nlb, ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(g_s3, 0, sizeof(double) * nlb, ctx->stream));
-    OBIA_HIP_TRY(hipMemsetAsync(g_s4, 0, sizeof(double) * nlb, ctx->stream));
+    {   // the four accumulators: one clear
+        ClearSet clr(ctx);
+        OBIA_TRY(clr.add(g_n, 0, sizeof(unsigned) * nlb));
+        OBIA_TRY(clr.add(g_s2, 0, sizeof(double) * nlb));
+        OBIA_TRY(clr.add(g_s3, 0, sizeof(double) * nlb));
+        OBIA_TRY(clr.add(g_s4, 0, sizeof(double) * nlb));
+        OBIA_TRY(clr.flush());
+    }
     if ((long long)W * C * 4 >= (1ll << 32)) { set_error("a raster row of %lld bytes is not supported (4 GB at most)", (long long)W * C * 4); return OBIA_E_UNSUPPORTED; }
     const int tiles = cdiv(W, ZTW) * cdiv(H, ZTH);
     const bool ident = bl.identity && bl.n == C;
