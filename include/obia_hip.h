@@ -604,14 +604,16 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
 
 /* ---- measurement hooks ------------------------------------------------------------------------------
  * Time of the most recent call's kernels by class, measured with HIP events on the context's
- * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (sum of launches, ms), 1 = number of
- * those launches, 2 = feature preparation, 3 = connectivity, 4 = zonal statistics, 5 = whole call,
+ * stream (bench.py's roofline leg).  `what`: 0 = SLIC colour sweeps (ms): time during which a colour sweep runs, batch by
+ * batch -- the sum of the launches of a batch whose sweeps run one after the other, the UNION of the launches' intervals of a
+ * batch whose colour pass ran as two window groups side by side (see 19), 1 = number of those sweeps (a sweep of a grouped batch
+ * is two launches and counts once), 2 = feature preparation, 3 = connectivity, 4 = zonal statistics, 5 = whole call,
  * 6 = maskSLIC spatial-only pre-pass sweeps (ms), 7 = pixels actually processed by the launches of 0
  * (sum; tiles skipped by exit_on_fixed_point are not counted), 8 = the same for the pre-pass launches,
  * 9 = pixels of the launches of 0 that also stored their labels (only the last sweep of a batch does),
- * 10 / 11 = time during which at least one colour / pre-pass sweep was running (10 equals 0: the colour sweeps run one after the
- * other; 11 is below 6 where a batch's spatial pre-pass ran as two window groups side by side, see 15).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0 and
- * 6 are sums of the kernels' own start-to-end times, as a rocprofv3 kernel trace reports them.
+ * 10 / 11 = time during which at least one colour / pre-pass sweep was running, over the whole call (10 equals 0: batches run one
+ * after the other and 0 is a union inside a grouped one; 11 is below 6 where a batch's spatial pre-pass ran as two window groups side by side, see 15).  The events of a sweep are bound to its dispatch (hipExtLaunchKernelGGL): 0, 6
+ * and 20 are made of the kernels' own start-to-end times, as a rocprofv3 kernel trace reports them.
  * 12 = batches of the call whose sweeps ran a second time with every sweep storing its labels (a valid pixel that no window
  * reached keeps the label of the sweep before: DESIGN.md 3.2 item 5) -- counted whether profiling is on or not.
  * 13 = the part of 8 that no sweep evaluated: pre-pass pixel-sweeps of problems whose class representative ran them (DESIGN.md 3.2,
@@ -622,6 +624,10 @@ int obia_shapley_combine_dev(obia_ctx *ctx, const double *values, int64_t n_rows
  * 2 per grouped sweep, 0 when no batch was grouped -- counted whether profiling is on or not.
  * 16 / 17 / 18 = small commands the call issued besides its kernels: fills (a memset, or one launch of the clear kernel that
  * stands for several), host -> device uploads, device -> host read-backs -- counted whether profiling is on or not.
+ * 19 = colour sweeps launched for one of two window groups of a batch ("Two window groups in flight"): 2 x max_iter
+ * per grouped batch, 0 when no batch was grouped -- counted whether profiling is on or not.
+ * 20 = plain sum of the durations of all colour-sweep launches (ms), overlapping or not: equals 0 when no batch was grouped, above
+ * it by the overlap otherwise.
  * `enabled`: 0 off, 1 every class, 2 only the colour sweeps (an event pair costs ~2.5 us of stream time: with all classes on,
  * a step of the headline workload records ~420 pairs = 1.1 ms; bench.py times its steps in mode 2).                       */
 int obia_set_profiling(obia_ctx *ctx, int enabled);

@@ -260,7 +260,8 @@ class Context:
         lib = load()
         names = ["assign_ms", "sweeps", "features_ms", "connectivity_ms", "zonal_ms", "total_ms", "prepass_ms", "assign_px",
                  "prepass_px", "assign_store_px", "assign_busy_ms", "prepass_busy_ms", "batch_repeats",
-                 "prepass_shared_px", "feature_fused_px", "prepass_group_launches", "fills", "uploads", "readbacks"]
+                 "prepass_shared_px", "feature_fused_px", "prepass_group_launches", "fills", "uploads", "readbacks",
+                 "assign_group_launches", "assign_launch_sum_ms"]
         return {n: lib.obia_last_timing(self._h, i) for i, n in enumerate(names)}
 
     def workspace_bytes(self):

@@ -84,10 +84,14 @@ struct Timing {
     double feat_fused_px = 0;               // pixels whose feature planes were written by a sweep (fused feature pass) instead of the feature pass
     int sweeps = 0;
     int prepass_group_launches = 0;         // spatial pre-pass sweeps launched for one of two window groups (slic_sweep.hip: grouped pre-pass)
+    int assign_group_launches = 0;          // colour sweeps launched for one of two window groups (grouped colour pass): 2 x max_iter per grouped batch
+    int assign_group_batches = 0;           // ... and the batches they belong to (the serial number that ties a launch's span to its batch)
+    double assign_launch_sum_ms = 0;        // plain sum of the durations of all colour-sweep launches, overlapping or not
     int batch_repeats = 0;                  // batches whose sweeps ran again with every sweep storing its labels (a valid pixel no window reached)
-    // time during which at least one colour (pre-pass) sweep was running.  The colour sweeps run one after the other, so
-    // assign_busy_ms equals assign_ms; the sweeps of a grouped pre-pass overlap (two window groups, two streams), so prepass_ms is a
-    // sum of overlapping durations and prepass_busy_ms, their union, is the smaller
+    // time during which at least one colour (pre-pass) sweep was running, over the whole call.  assign_ms is the time during which a
+    // colour sweep runs, batch by batch: a serial launch adds its duration, a grouped colour pass (two window groups, two streams) the
+    // UNION of its launches' intervals -- so assign_busy_ms equals assign_ms either way, and assign_launch_sum_ms is the larger.  The
+    // sweeps of a grouped pre-pass overlap too: prepass_ms is a sum of overlapping durations and prepass_busy_ms, their union, the smaller
     double assign_busy_ms = 0, prepass_busy_ms = 0;
     // small commands issued in the frame, kernels not included: fills (fill_async, clear_ranges: one per launch), host -> device
     // uploads (upload_async, PlanBlob::flush) and device -> host read-backs (read_back, the sweeps' deferred one)
@@ -117,7 +121,7 @@ struct obia_ctx {
     int profiling = 0;               // 0 off, 1 every span, 2 only the colour sweeps (obia_set_profiling)
     obia::Timing timing;
     // event pairs recorded around kernels of interest; resolved (one sync) at the end of the call
-    struct Span { int kind; hipEvent_t a, b; };
+    struct Span { int kind; hipEvent_t a, b; int tag = 0; };   // tag (T_ASSIGN_GRP): 2 x grouped batch of the call + group
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;
     size_t events_used = 0;
@@ -129,11 +133,12 @@ struct obia_ctx {
     // white prefetch may hold aux_fork / aux_join across a batch's sweeps
     hipEvent_t grp_fork = nullptr, grp_join = nullptr;
     int spatial_residency[4] = {0, 0, 0, 0};   // workgroups of slic_spatial_kernel<4 (i + 1)> the device holds at once; 0: not asked yet
+    int sweep_residency[64] = {};              // the same of the colour-sweep kernel variants (slic_sweep.hip: sweep_residency)
 };
 
 namespace obia {
 
-enum TimeKind { T_ASSIGN = 0, T_FEAT = 2, T_CC = 3, T_ZONAL = 4, T_TOTAL = 5, T_PREPASS = 6 };
+enum TimeKind { T_ASSIGN = 0, T_FEAT = 2, T_CC = 3, T_ZONAL = 4, T_TOTAL = 5, T_PREPASS = 6, T_ASSIGN_GRP = 7 };   // T_ASSIGN_GRP: a colour sweep of one window group
 
 // Records a HIP event pair around a region of the context's stream when profiling is on; no host
 // synchronisation happens until resolve_timing().
@@ -147,7 +152,8 @@ struct ScopedSpan {
 // between two stream markers around it (that also times the dispatch, a few microseconds).  Both null when profiling is off.
 struct KernelSpan {
     hipEvent_t a = nullptr, b = nullptr;
-    KernelSpan(obia_ctx *c, int kind);
+    KernelSpan() = default;   // no events: a launch that is not timed
+    KernelSpan(obia_ctx *c, int kind, int tag = 0);
 };
 void begin_timing(obia_ctx *ctx);
 void resolve_timing(obia_ctx *ctx);

@@ -127,11 +127,11 @@ int side_stream(obia_ctx *ctx) {
     return OBIA_OK;
 }
 
-KernelSpan::KernelSpan(obia_ctx *c, int kind) {
-    if (!(c->profiling == 1 || (c->profiling == 2 && kind == T_ASSIGN))) return;
+KernelSpan::KernelSpan(obia_ctx *c, int kind, int tag) {
+    if (!(c->profiling == 1 || (c->profiling == 2 && (kind == T_ASSIGN || kind == T_ASSIGN_GRP)))) return;
     a = get_event(c);
     b = get_event(c);
-    c->spans.push_back(obia_ctx::Span{kind, a, b});
+    c->spans.push_back(obia_ctx::Span{kind, a, b, tag});
 }
 
 void begin_timing(obia_ctx *ctx) {
@@ -145,19 +145,42 @@ void resolve_timing(obia_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     // sweeps: [start, end) of every kernel on the clock of the first one (end = distance from the first kernel's start to this
     // kernel's end, start = end - the kernel's own duration), for the length of their union
-    std::vector<std::pair<double, double>> iv[2];
+    typedef std::vector<std::pair<double, double>> Intervals;
+    auto union_ms = [](Intervals &v) {
+        std::sort(v.begin(), v.end());
+        double busy = 0, lo = 0, hi = -1;
+        for (auto &x : v) {
+            if (hi < lo || x.first > hi) { if (hi > lo) busy += hi - lo; lo = x.first; hi = x.second; }
+            else if (x.second > hi) hi = x.second;
+        }
+        if (hi > lo) busy += hi - lo;
+        return busy;
+    };
+    Intervals iv[2];
+    std::vector<Intervals> grouped;   // the colour sweeps of every grouped batch (two window groups on two streams: slic_sweep.hip)
     hipEvent_t ref = nullptr;
     for (auto &s : ctx->spans) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) { (void)hipGetLastError(); continue; }   // (a launch that was skipped)
-        if (s.kind == T_ASSIGN || s.kind == T_PREPASS) {
+        if (s.kind == T_ASSIGN || s.kind == T_ASSIGN_GRP || s.kind == T_PREPASS) {
             if (!ref) ref = s.a;
             float end = 0;
-            if (hipEventElapsedTime(&end, ref, s.b) == hipSuccess) iv[s.kind == T_ASSIGN ? 0 : 1].emplace_back((double)end - ms, (double)end);
+            if (hipEventElapsedTime(&end, ref, s.b) == hipSuccess) {
+                const std::pair<double, double> x((double)end - ms, (double)end);
+                iv[s.kind == T_PREPASS ? 1 : 0].push_back(x);
+                if (s.kind == T_ASSIGN_GRP) {
+                    const size_t batch = (size_t)(s.tag >> 1);
+                    if (grouped.size() <= batch) grouped.resize(batch + 1);
+                    grouped[batch].push_back(x);
+                }
+            }
             else (void)hipGetLastError();
         }
         switch (s.kind) {
-            case T_ASSIGN: ctx->timing.assign_ms += ms; ctx->timing.sweeps += 1; break;
+            case T_ASSIGN: ctx->timing.assign_ms += ms; ctx->timing.assign_launch_sum_ms += ms; ctx->timing.sweeps += 1; break;
+            // class 0 is the time during which a colour sweep of the batch runs, per sweep of the batch: the two launches of a sweep
+            // are one sweep (counted with group 0's), and the batch's time is the union below
+            case T_ASSIGN_GRP: ctx->timing.assign_launch_sum_ms += ms; if (!(s.tag & 1)) ctx->timing.sweeps += 1; break;
             case T_FEAT: ctx->timing.feat_ms += ms; break;
             case T_CC: ctx->timing.cc_ms += ms; break;
             case T_ZONAL: ctx->timing.zonal_ms += ms; break;
@@ -166,16 +189,9 @@ void resolve_timing(obia_ctx *ctx) {
             default: break;
         }
     }
-    for (int c = 0; c < 2; ++c) {
-        std::sort(iv[c].begin(), iv[c].end());
-        double busy = 0, lo = 0, hi = -1;
-        for (auto &x : iv[c]) {
-            if (hi < lo || x.first > hi) { if (hi > lo) busy += hi - lo; lo = x.first; hi = x.second; }
-            else if (x.second > hi) hi = x.second;
-        }
-        if (hi > lo) busy += hi - lo;
-        (c == 0 ? ctx->timing.assign_busy_ms : ctx->timing.prepass_busy_ms) += busy;
-    }
+    for (auto &g : grouped) ctx->timing.assign_ms += union_ms(g);
+    ctx->timing.assign_busy_ms += union_ms(iv[0]);
+    ctx->timing.prepass_busy_ms += union_ms(iv[1]);
     ctx->spans.clear();
 }
 
@@ -531,6 +547,8 @@ double obia_last_timing(obia_ctx *ctx, int what) {
         case 16: return (double)ctx->timing.fills;
         case 17: return (double)ctx->timing.uploads;
         case 18: return (double)ctx->timing.readbacks;
+        case 19: return (double)ctx->timing.assign_group_launches;
+        case 20: return ctx->timing.assign_launch_sum_ms;
         default: return -1.0;
     }
 }

@@ -1507,8 +1507,10 @@ template <int CP>
 static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
                           int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
                           const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset(),
-                          bool rawin = false, const hipStream_t *on = nullptr) {
-    const hipStream_t stream = on ? *on : ctx->stream;   // (on: the side stream, for the second window group of a grouped pre-pass)
+                          bool rawin = false, const hipStream_t *on = nullptr, int *occupancy = nullptr) {
+    const hipStream_t stream = on ? *on : ctx->stream;   // (on: the side stream, for the second window group of a grouped pass)
+    // occupancy: nothing is launched; the workgroups per compute unit of the colour kernel this call WOULD launch come back (0:
+    // unknown) -- the variant is chosen by the code that launches it (sweep_residency)
     constexpr int XGH = OBIA_XCD_GROUP;
     // (a subset -- the lean kernels of a shared pre-pass only -- is grouped over the XCDs like the whole batch)
     const int ntiles = sub.end >= 0 ? sub.end : (int)b.total_tiles_all, tbase = sub.end >= 0 ? sub.base : 0;
@@ -1521,13 +1523,17 @@ static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int acc
         (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
         b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, tbase, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req
 #define LAUNCH_K_(...)                                                                                               \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_)
+    do {                                                                                                             \
+        if (!occupancy) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_); \
+        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, __VA_ARGS__, NT, 0) != hipSuccess) { (void)hipGetLastError(); *occupancy = 0; } \
+    } while (0)
     // (the lean kernels: the spatial-only pre-pass sweeps, which a shared pre-pass launches for a subset of the tiles)
 #define LAUNCH_KL_(...)                                                                                              \
     hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_, sub.table)
     // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
     // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
     const int pad = CP - b.C;
+    if (occupancy && (rawin || ignore_color)) { *occupancy = 0; return; }   // (asked for the colour kernels only)
     if constexpr (CP <= 12) if (rawin) {   // fused feature pass: the batch's last pre-pass sweep (queue_sweeps)
         RawInput ri;
         ri.src = b.raw_src; ri.Ws = b.raw_ws; ri.wins = b.d_windows; ri.keys = b.d_keys; ri.ratio = b.feat_ratio; ri.planes = b.d_feat;
@@ -1671,8 +1677,56 @@ static int spatial_residency(obia_ctx *ctx, int CP) {
     return r;
 }
 
-// Queues every sweep of the batch on the context's stream (a grouped pre-pass: half of its spatial sweeps on the side stream, joined
-// again before this returns).  repeat: the batch runs again from the seeds with every sweep storing
+// The same of the colour kernel the batch's colour sweeps launch (the main kernel in its padding variant or the low-compactness
+// kernel, masked or not: launch_assign chooses), asked once per context and variant
+static int sweep_residency(obia_ctx *ctx, SlicBatch &b) {
+    const bool collb = b.col_lb && b.d_fbox;
+    int &r = ctx->sweep_residency[(((b.CP / 4 - 1) * 2 + (b.masked ? 1 : 0)) * 4 + (b.CP - b.C)) * 2 + (collb ? 1 : 0)];
+    if (r > 0) return r;
+    int per_cu = 0, cus = 0;
+    const FixedPointState fp;
+    const KernelSpan span;
+    switch (b.CP) {   // (a colour sweep that accumulates and stores no labels; nothing is launched)
+        case 8: launch_assign<8>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
+#ifndef OBIA_ONLY_CP8
+        case 4: launch_assign<4>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
+        case 12: launch_assign<12>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
+        case 16: launch_assign<16>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
+#endif
+        default: break;
+    }
+    if (per_cu <= 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) {
+        (void)hipGetLastError();
+        return 0x7fffffff;   // (unknown: no batch is large enough)
+    }
+    r = per_cu * cus;
+    return r;
+}
+
+// Two window groups: the problems [0, split) and [split, nprob), consecutive and balanced by sweep tiles, a tie going
+// to the later split; 0 when the batch cannot be split.  One choice for the grouped pre-pass and the grouped colour pass.
+static int group_split(const SlicBatch &b) {
+    int split = 0;
+    long long best = -1;
+    for (int p = 1; p < b.nprob; ++p) {
+        const long long t0 = b.probs[p].tile_off, t1 = b.total_tiles_all - t0, d = t0 > t1 ? t0 - t1 : t1 - t0;
+        if (t0 > 0 && t1 > 0 && (best < 0 || d <= best)) { best = d; split = p; }
+    }
+    return split;
+}
+// sweep tiles of the smaller group
+static long long group_min_tiles(const SlicBatch &b, int split) {
+    const long long t0 = b.probs[split].tile_off, t1 = b.total_tiles_all - t0;
+    return t0 < t1 ? t0 : t1;
+}
+// a developer switch of the two groupings (read per batch): 0 never, 2 at any size, else 1 (the size threshold decides)
+static int groups_mode(const char *name) {
+    const char *e = std::getenv(name);
+    return !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1));
+}
+
+// Queues every sweep of the batch on the context's stream (a grouped pre-pass or colour pass: the second window group's launches on
+// the side stream, joined again before this returns).  repeat: the batch runs again from the seeds with every sweep storing
 // its labels (slic_rerun_storing).  *d_px_out: the pixel counters of the sweeps, 256 slots each for the colour and the pre-pass
 // sweeps, and in slot 512 the orphan flag of the sweeps that do not store their labels; null when the batch has no sweep.
 // *shared_px_out: the pixel-sweeps a shared pre-pass covered without evaluating them (0 when nothing was shared).
@@ -1813,23 +1867,28 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
     // every sweep stores its labels (the repeat among them), not under the pre-pass developer switches.  By default only when each
     // group fills the device at least once (spatial_residency): below that a launch does not fill it and the split buys nothing.
     // OBIA_PREPASS_GROUPS (developer switch, read per batch: A/B timing, tests/test_gpu_prepass_groups.py): 0 never, 2 at any size.
-    int grp_split = 0;   // > 0: the groups are the problems [0, grp_split) and [grp_split, nprob)
-    {
-        const char *e = std::getenv("OBIA_PREPASS_GROUPS");
-        const int mode = !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1));
-        if (mode != 0 && n_shared == 0 && b.masked && pre_iter >= 2 && !store_all && !prepass_visits && !prep_grouped && !b.direct &&
-            b.nprob >= 2 && !std::getenv("OBIA_DEBUG_SYNC")) {   // (the stage-by-stage synchronisation watches one stream)
-            long long best = -1;
-            for (int p = 1; p < b.nprob; ++p) {
-                const long long t0 = b.probs[p].tile_off, t1 = b.total_tiles_all - t0, d = t0 > t1 ? t0 - t1 : t1 - t0;
-                if (t0 > 0 && t1 > 0 && (best < 0 || d <= best)) { best = d; grp_split = p; }   // (a tie: the later split)
-            }
-            if (grp_split > 0 && mode != 2) {
-                const long long t0 = b.probs[grp_split].tile_off, t1 = b.total_tiles_all - t0;
-                if ((t0 < t1 ? t0 : t1) < (long long)spatial_residency(ctx, b.CP)) grp_split = 0;
-            }
-            if (grp_split > 0) OBIA_TRY(side_stream(ctx));
-        }
+    //
+    // The colour pass runs the same way (col_split): each group its chain step -> colour sweep for all max_iter sweeps, forked behind
+    // the last whole-batch launch in front of the first colour-pass step -- the last pre-pass sweep of a masked batch (the pre-pass
+    // broadcast and that sweep stay whole-batch), the clears of an unmasked one -- and joined behind each group's last sweep, the one
+    // that stores its labels, in front of the counters' read-back.  The colour kernels (the main one in every padding variant and the
+    // low-compactness one) share nothing more than the spatial ones: the colour boxes are read-only and indexed through P.fb_off, the
+    // planes and labels through P.pix_off.  A batch that shares its PRE-PASS is eligible: its colour pass shares nothing.  Needs two
+    // sweeps at least; by default each group must hold one residency of the colour kernel it launches (sweep_residency).
+    // OBIA_SWEEP_GROUPS: the same switch, independent of the other (tests/test_gpu_sweep_groups.py).
+    int grp_split = 0;   // > 0: the pre-pass groups are the problems [0, grp_split) and [grp_split, nprob)
+    int col_split = 0;   // > 0: the colour-pass groups, likewise
+    if (!store_all && !prepass_visits && !prep_grouped && !b.direct && b.nprob >= 2 &&
+        !std::getenv("OBIA_DEBUG_SYNC")) {   // (the stage-by-stage synchronisation watches one stream)
+        const int split = group_split(b);
+        const int pre_mode = groups_mode("OBIA_PREPASS_GROUPS"), col_mode = groups_mode("OBIA_SWEEP_GROUPS");
+        if (split > 0 && pre_mode != 0 && n_shared == 0 && b.masked && pre_iter >= 2 &&
+            (pre_mode == 2 || group_min_tiles(b, split) >= (long long)spatial_residency(ctx, b.CP)))
+            grp_split = split;
+        if (split > 0 && col_mode != 0 && !(b.masked && b.prepass_only) && b.max_iter >= 2 &&
+            (col_mode == 2 || group_min_tiles(b, split) >= (long long)sweep_residency(ctx, b)))
+            col_split = split;
+        if (grp_split > 0 || col_split > 0) OBIA_TRY(side_stream(ctx));
     }
     // the planning phase's one upload: the descriptors (slic_plan_and_seed), the class tables above, whatever the caller added
     OBIA_TRY(ctx->plan.flush(ctx));
@@ -1890,42 +1949,53 @@ static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long 
                 }
             };
 #undef LAUNCH_PREP_LANE
-            if (grp_split > 0 && ignore_color && it < iters - 1) {
-                // one of the sweeps slic_spatial_kernel decides (see launch_assign: spatial-only, no labels stored), as two groups
+            // a sweep as two window groups: one of the pre-pass sweeps slic_spatial_kernel decides (see launch_assign: spatial-only, no
+            // labels stored), or any sweep of a grouped colour pass
+            const bool pre_groups = grp_split > 0 && ignore_color && it < iters - 1, col_groups = col_split > 0 && !ignore_color;
+            if (pre_groups || col_groups) {
+                const int split = col_groups ? col_split : grp_split;
+                // (the grouped colour pass ends with the batch's very last sweep, which folds nothing and stores its labels -- what
+                // the ungrouped launch below passes; every other grouped sweep accumulates and stores nothing, lists in use)
+                const bool chain_end = it == (col_groups ? iters - 1 : iters - 2), very_last = col_groups && chain_end;
                 hipError_t he = hipSuccess;
-                if (it == 0) {   // fork: behind the batch's fills and whatever else this stream holds for the batch
+                if (it == 0) {   // fork: behind the batch's fills, its pre-pass, and whatever else this stream holds for the batch
                     he = hipEventRecord(ctx->grp_fork, ctx->stream);
                     if (he == hipSuccess) he = hipStreamWaitEvent(ctx->side, ctx->grp_fork, 0);
+                    if (col_groups) ctx->timing.assign_group_batches += 1;
                 }
                 for (int g = 0; g < 2 && he == hipSuccess; ++g) {
-                    const int p0 = g ? grp_split : 0, p1 = g ? b.nprob : grp_split;
+                    const int p0 = g ? split : 0, p1 = g ? b.nprob : split;
                     int kmax_g = 1;
                     for (int p = p0; p < p1; ++p) if (b.probs[p].K > kmax_g) kmax_g = b.probs[p].K;
                     const hipStream_t st = g ? ctx->side : ctx->stream;
                     prep_lane(st, dim3(cdiv(kmax_g, 64), p1 - p0), p0, nullptr, b.probs[p0].cell_off, g ? b.total_cells : b.probs[p1].cell_off);
-                    KernelSpan span(ctx, T_PREPASS);
+                    KernelSpan span(ctx, col_groups ? T_ASSIGN_GRP : T_PREPASS, col_groups ? 2 * (ctx->timing.assign_group_batches - 1) + g : 0);
                     TileSubset sub;
                     sub.base = b.probs[p0].tile_off;
                     sub.end = g ? (int)b.total_tiles_all : b.probs[p1].tile_off;
-                    unsigned long long *pxc = ctx->profiling ? d_px + 256 : nullptr;
-                    switch (b.CP) {   // (accumulate, no colours, no labels, lists in use: what the ungrouped launch below passes for this sweep)
-                        case 8: launch_assign<8>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                    unsigned long long *pxc = ctx->profiling ? d_px + (col_groups ? 0 : 256) : nullptr;
+                    const int ign = col_groups ? 0 : 1, accumulate = very_last ? 0 : 1, store_labels = very_last ? 1 : 0;
+                    switch (b.CP) {
+                        case 8: launch_assign<8>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
 #ifndef OBIA_ONLY_CP8
-                        case 4: launch_assign<4>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-                        case 12: launch_assign<12>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-                        case 16: launch_assign<16>(ctx, b, 1, 1, 0, 0, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                        case 4: launch_assign<4>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                        case 12: launch_assign<12>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
+                        case 16: launch_assign<16>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
 #endif
                         default: he = hipErrorInvalidValue; break;
                     }
-                    ctx->timing.prepass_group_launches += 1;
+                    (col_groups ? ctx->timing.assign_group_launches : ctx->timing.prepass_group_launches) += 1;
                 }
-                if (he == hipSuccess && it == iters - 2) {   // join: in front of the whole-batch step of the last pre-pass sweep, before anything else is queued
+                if (very_last && ctx->profiling) ctx->timing.assign_store_px += (double)b.total_pix;   // (both groups' pixels, once)
+                // join: in front of the whole-batch step of the last pre-pass sweep, or behind the colour pass and in front of the
+                // counters' read-back -- before anything else is queued
+                if (he == hipSuccess && chain_end) {
                     he = hipEventRecord(ctx->grp_join, ctx->side);
                     if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->grp_join, 0);
                 }
                 if (he != hipSuccess) {   // nothing may be left running on the side stream when the caller gets the error
                     (void)hipStreamSynchronize(ctx->side);
-                    set_error("grouped pre-pass: %s", hipGetErrorString(he));
+                    set_error("grouped %s: %s", col_groups ? "colour pass" : "pre-pass", hipGetErrorString(he));
                     return OBIA_E_HIP;
                 }
                 b.d_head_cur = head_cur;
