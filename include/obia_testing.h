@@ -16,6 +16,22 @@ extern "C" {
  * with a length above 0.                                                                                                          */
 int obia_test_clear_ranges_dev(obia_ctx *ctx, void *const *dev_ptrs, const int64_t *bytes, const int32_t *values, int n);
 
+/* The plan of a batch's sweeps (obia_amd/csrc/slic_sweep_plan.hpp: plan_sweeps) as text, for a batch made up from shapes.  No
+ * context and no GPU: pure host code.
+ *   problems     n_problems rows {H, W, K, sy, sx, n_valid, grid_n}: window size, centroids, window steps, valid pixels, the n the
+ *                seeds were laid out for by the grid rule (0: none).  Sweep tiles, bins and the running offsets follow from them.
+ *   settings     {C, masked, max_iter, prepass_iter, prepass_only, exit_on_fixed_point, slic_zero, direct, col_lb (colour boxes
+ *                present), fuse_features (raster and keys present), mask already packed}
+ *   repeat       the batch runs again with every sweep storing its labels
+ *   switches     {OBIA_DEBUG_SYNC, OBIA_PREP_GROUPED, OBIA_PREPASS_VISITS set (0 / 1); OBIA_PREPASS_SHARE (0: off);
+ *                OBIA_PREPASS_GROUPS, OBIA_SWEEP_GROUPS (0, 1, 2)} -- given here, not read from the environment
+ *   residencies  {spatial kernel, colour kernel}: workgroups the device holds at once
+ *   text         receives one command per line in queue order, every launch with its stream ("s0": the context's, "s1": the side
+ *                stream), zero-terminated; OBIA_E_INVALID when text_bytes is too small.
+ * Returns what the driver would: OBIA_E_UNSUPPORTED / OBIA_E_INVALID with the error text for a batch it refuses.                  */
+int obia_test_sweep_plan(const int64_t *problems, int n_problems, const int32_t *settings, int repeat, const int32_t *switches,
+                         const int64_t *residencies, char *text, int64_t text_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,8 @@ _SHARPNESS_SIGNATURES = {
 # include/obia_testing.h: internal pieces driven directly by the test suite, a fourth table (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
+    # the plan of a batch's sweeps as text: pure host code, no context (tests/test_sweep_plan_cpu.py)
+    "obia_test_sweep_plan": (_I, [_P, _I, _P, _I, _P, _P, _P, ctypes.c_int64]),
 }
 
 _lib = None

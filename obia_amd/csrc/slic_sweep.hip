@@ -1495,95 +1495,119 @@ __global__ __launch_bounds__(256) void slic_maxdist_kernel(const SlicProblem *__
         }
 }
 
-// The tiles a sweep launch covers: all of the batch, a span [base, end) of them, or the `end` tiles a device table names.
-struct TileSubset { const int *table = nullptr; int base = 0, end = -1; };
+}  // namespace obia
 
-struct FixedPointState {   // exit_on_fixed_point bookkeeping (device pointers; null when the option is off)
-    int *bin_stamp = nullptr, *tile_lp = nullptr, *cache_k = nullptr;
+// ---- the host driver: plan_sweeps (slic_sweep_plan.hpp) decides what a batch launches, the code below issues it --------------------
+#include "slic_sweep_plan.hpp"
+
+namespace obia {
+
+// What issuing a plan needs besides the batch: the device memory queue_sweeps took for it
+struct SweepBuffers {
+    int *bin_stamp = nullptr, *tile_lp = nullptr, *cache_k = nullptr;   // exit_on_fixed_point bookkeeping (null when the option is off)
     unsigned long long *cache_q = nullptr;
+    unsigned long long *d_px = nullptr;   // the sweeps' pixel counters (queue_sweeps)
+    int *d_orphan = nullptr;              // ... and the orphan flag behind them
+    const int *d_act_probs = nullptr, *d_act_tiles = nullptr, *d_member_rep = nullptr;   // class tables of a shared pre-pass (SweepPlan::ap, at, mr; null: a span)
+    int tpp = 0;                          // tiles per problem if all problems agree, else 0
 };
 
-template <int CP>
-static void launch_assign(obia_ctx *ctx, SlicBatch &b, int ignore_color, int accumulate, int accum_color, int store_labels,
-                          int *orphan_flag, const FixedPointState &fp, int sweep_id, int use_cache, unsigned long long *px_counter,
-                          const KernelSpan &span, const int *head_cur, bool prepass_visits, const TileSubset &sub = TileSubset(),
-                          bool rawin = false, const hipStream_t *on = nullptr, int *occupancy = nullptr) {
-    const hipStream_t stream = on ? *on : ctx->stream;   // (on: the side stream, for the second window group of a grouped pass)
-    // occupancy: nothing is launched; the workgroups per compute unit of the colour kernel this call WOULD launch come back (0:
-    // unknown) -- the variant is chosen by the code that launches it (sweep_residency)
-    constexpr int XGH = OBIA_XCD_GROUP;
-    // (a subset -- the lean kernels of a shared pre-pass only -- is grouped over the XCDs like the whole batch)
-    const int ntiles = sub.end >= 0 ? sub.end : (int)b.total_tiles_all, tbase = sub.end >= 0 ? sub.base : 0;
-    dim3 grid(8 * XGH * (unsigned)((ntiles - tbase + 8 * XGH - 1) / (8 * XGH)));   // whole groups of 8 XCDs x XG tiles (see slic_assign_body)
-    const int RQ = acc_record_qwords(CP);
-    int tpp = b.probs.empty() ? 0 : b.probs[0].tiles_x * b.probs[0].tiles_y;   // tiles per problem if all problems agree, else 0
-    for (auto &P : b.probs) if (P.tiles_x * P.tiles_y != tpp) tpp = 0;
-#define LAUNCH_ARGS_                                                                                                 \
-    b.d_probs, b.d_feat, b.d_mask, b.d_mask4, b.d_cent, head_cur, b.d_labels, b.d_acc, RQ, accumulate, store_labels, b.start_label,      \
-        (float)b.fscale, fp.bin_stamp, fp.tile_lp, fp.cache_k, fp.cache_q, sweep_id, use_cache, px_counter,          \
-        b.d_tile_prob, ntiles, orphan_flag, tpp, b.d_fbox, tbase, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req
-#define LAUNCH_K_(...)                                                                                               \
-    do {                                                                                                             \
-        if (!occupancy) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_); \
-        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, __VA_ARGS__, NT, 0) != hipSuccess) { (void)hipGetLastError(); *occupancy = 0; } \
-    } while (0)
-    // (the lean kernels: the spatial-only pre-pass sweeps, which a shared pre-pass launches for a subset of the tiles)
-#define LAUNCH_KL_(...)                                                                                              \
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_, sub.table)
-    // channels that exist: C of the CP = 4 * ceil(C / 4) the planes and records hold.  The two kernels that run 9 of every 10
-    // sweeps come in a variant per padding (slic_assign_body: NCH); the others treat the padded channels like real ones.
-    const int pad = CP - b.C;
-    if (occupancy && (rawin || ignore_color)) { *occupancy = 0; return; }   // (asked for the colour kernels only)
-    if constexpr (CP <= 12) if (rawin) {   // fused feature pass: the batch's last pre-pass sweep (queue_sweeps)
-        RawInput ri;
-        ri.src = b.raw_src; ri.Ws = b.raw_ws; ri.wins = b.d_windows; ri.keys = b.d_keys; ri.ratio = b.feat_ratio; ri.planes = b.d_feat;
-        hipExtLaunchKernelGGL(HIP_KERNEL_NAME(slic_assign_rawin_kernel<CP>), grid, dim3(NT), 0, stream, span.a, span.b, 0, LAUNCH_ARGS_, ri);
-        ctx->timing.feat_fused_px += (double)b.total_pix;
-        return;
+// f(std::integral_constant<int, CP>) for the padded channel count of a batch; f returns a status
+template <typename F>
+static int with_cp(int CP, F &&f) {
+    switch (CP) {
+        case 8: return f(std::integral_constant<int, 8>());
+#ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
+        case 4: return f(std::integral_constant<int, 4>());
+        case 12: return f(std::integral_constant<int, 12>());
+        case 16: return f(std::integral_constant<int, 16>());
+#endif
+        default: set_error("bad CP"); return OBIA_E_INVALID;
     }
-#define LAUNCH_ASSIGN_(M, I, F, Z) LAUNCH_K_(slic_assign_kernel<CP, M, I, F, Z>)
-#define LAUNCH_MAIN_(M)                                                                                              \
-    do {                                                                                                             \
-        if (pad == 1) LAUNCH_K_(slic_assign_kernel<CP, M, false, false, false, CP - 1>);                             \
-        else if (pad == 2) LAUNCH_K_(slic_assign_kernel<CP, M, false, false, false, CP - 2>);                        \
-        else if (pad == 3) LAUNCH_K_(slic_assign_kernel<CP, M, false, false, false, CP - 3>);                        \
-        else LAUNCH_K_(slic_assign_kernel<CP, M, false, false, false>);                                              \
-    } while (0)
-    // SLIC-zero only changes the colour sweeps (the spatial pre-pass computes no colour term) and is not combined with
-    // the fixed-point cache (the per-cluster scale changes after the records were compared)
-#define LAUNCH_COLLB_(M)                                                                                             \
-    do {                                                                                                             \
-        if (pad == 1) LAUNCH_K_(slic_assign_collb_kernel<CP, M, CP - 1>);                                            \
-        else if (pad == 2) LAUNCH_K_(slic_assign_collb_kernel<CP, M, CP - 2>);                                       \
-        else if (pad == 3) LAUNCH_K_(slic_assign_collb_kernel<CP, M, CP - 3>);                                       \
-        else LAUNCH_K_(slic_assign_collb_kernel<CP, M>);                                                             \
-    } while (0)
-#define LAUNCH_LEAN_(M, F) LAUNCH_KL_(slic_prepass_kernel<CP, M, F>)
-    // a spatial-only sweep that stores no labels and keeps no fixed-point cache is decided by runs (slic_spatial.hip); the others,
-    // and all of them under the developer switch, by the pixel-by-pixel kernel
-#define LAUNCH_ASSIGN(M, I)                                                                                          \
-    do {                                                                                                             \
-        if ((I) && !accum_color) {                                                                                   \
-            if (fp.bin_stamp) LAUNCH_LEAN_(M, true);                                                                 \
-            else if (store_labels || prepass_visits) LAUNCH_LEAN_(M, false);                                         \
-            else LAUNCH_KL_(slic_spatial_kernel<CP>);                                                                \
-        }                                                                                                            \
-        else if (b.slic_zero && !(I)) LAUNCH_ASSIGN_(M, false, false, true);                                         \
-        else if (fp.bin_stamp) LAUNCH_ASSIGN_(M, I, true, false);                                                    \
-        else if (b.col_lb && b.d_fbox && !(I)) LAUNCH_COLLB_(M);                                                     \
-        else if (!(I)) LAUNCH_MAIN_(M);                                                                              \
-        else LAUNCH_ASSIGN_(M, I, false, false);                                                                     \
-    } while (0)
-    if (b.masked) { if (ignore_color) LAUNCH_ASSIGN(true, true); else LAUNCH_ASSIGN(true, false); }
-    else LAUNCH_ASSIGN(false, false);
-#undef LAUNCH_ASSIGN
-#undef LAUNCH_ASSIGN_
-#undef LAUNCH_LEAN_
-#undef LAUNCH_COLLB_
-#undef LAUNCH_MAIN_
-#undef LAUNCH_K_
-#undef LAUNCH_KL_
-#undef LAUNCH_ARGS_
+}
+
+// The kernel of a sweep: f(kernel, extra) for (CP, masked, kernel, padded channels), extra naming the argument the kernel takes behind
+// the common ones.  False when the combination has no kernel.  The launch and the occupancy query both ask here.
+enum SweepExtra { X_NONE, X_TILE_TABLE, X_RAW_INPUT };
+template <typename F>
+static bool with_pad(int pad, F &&f) {
+    if (pad == 0) f(std::integral_constant<int, 0>());
+    else if (pad == 1) f(std::integral_constant<int, 1>());
+    else if (pad == 2) f(std::integral_constant<int, 2>());
+    else if (pad == 3) f(std::integral_constant<int, 3>());
+    return pad >= 0 && pad <= 3;
+}
+template <int CP, bool M, typename F>
+static bool with_sweep_kernel_m(SweepKernel k, int pad, F &&f) {
+    const std::integral_constant<int, X_NONE> none{};
+    const std::integral_constant<int, X_TILE_TABLE> tile_table{};
+    switch (k) {
+        case SweepKernel::SpatialRuns: f(slic_spatial_kernel<CP>, tile_table); return true;
+        case SweepKernel::Lean: f(slic_prepass_kernel<CP, M, false>, tile_table); return true;
+        case SweepKernel::LeanFixpt: f(slic_prepass_kernel<CP, M, true>, tile_table); return true;
+        case SweepKernel::SlicZero: f(slic_assign_kernel<CP, M, false, false, true>, none); return true;
+        case SweepKernel::Fixpt: f(slic_assign_kernel<CP, M, false, true, false>, none); return true;
+        case SweepKernel::Main: return with_pad(pad, [&](auto p) { f(slic_assign_kernel<CP, M, false, false, false, CP - decltype(p)::value>, none); });
+        case SweepKernel::ColLb: return with_pad(pad, [&](auto p) { f(slic_assign_collb_kernel<CP, M, CP - decltype(p)::value>, none); });
+        default: break;
+    }
+    if constexpr (M) {   // the sweeps of a pre-pass that fold colours: masked batches only
+        if (k == SweepKernel::IgnoreColor) { f(slic_assign_kernel<CP, true, true, false, false>, none); return true; }
+        if (k == SweepKernel::FixptSpatial) { f(slic_assign_kernel<CP, true, true, true, false>, none); return true; }
+        if constexpr (CP <= 12)   // (16 channels are never fused: slic_fuse_features)
+            if (k == SweepKernel::Rawin) { f(slic_assign_rawin_kernel<CP>, std::integral_constant<int, X_RAW_INPUT>()); return true; }
+    }
+    return false;
+}
+template <int CP, typename F>
+static bool with_sweep_kernel(bool masked, SweepKernel k, int pad, F &&f) {
+    return masked ? with_sweep_kernel_m<CP, true>(k, pad, f) : with_sweep_kernel_m<CP, false>(k, pad, f);
+}
+
+// One part of a step, on the part's stream: the centroid step, the max-distance kernel where the step asks for it, the sweep
+template <int CP>
+static int launch_part(obia_ctx *ctx, SlicBatch &b, const SweepPlan &pl, const SweepBuffers &sb, const SweepStep &s, const SweepPart &q) {
+    const hipStream_t stream = q.stream ? ctx->side : ctx->stream;
+    const int RQ = acc_record_qwords(CP);
+    int *head_cur = b.d_head + (size_t)s.parity * b.total_cells, *head_nxt = b.d_head + (size_t)(s.parity ^ 1) * b.total_cells;
+    if (s.step_kernel == StepKernel::Lane)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CP>), dim3(cdiv(q.kmax, 64), q.n_probs), dim3(64), 0, stream,
+                           b.d_probs, q.p_base, s.first ? 1 : 0, s.zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt,
+                           q.cell_end, sb.bin_stamp, s.sweep_no, q.cell_base, b.d_ref, b.d_tl_req, q.table ? sb.d_act_probs : nullptr);
+    else {   // (OBIA_PREP_GROUPED: always the whole batch)
+        const bool g16 = s.step_kernel == StepKernel::Grouped16;
+        hipLaunchKernelGGL(g16 ? slic_prep_kernel<16> : slic_prep_kernel<32>, dim3(cdiv(b.total_cent * (g16 ? 16LL : 32LL), 256)), dim3(256), 0,
+                           stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, s.first ? 1 : 0, s.zmode, b.d_seed, b.d_acc,
+                           1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, sb.bin_stamp, s.sweep_no, 0, 0, b.d_ref, b.d_tl_req);
+    }
+    debug_sync(ctx, "sweeps: prep");
+    if (s.maxdist)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(b.masked ? slic_maxdist_kernel<CP, true> : slic_maxdist_kernel<CP, false>), dim3(pl.maxdist_rows, b.nprob),
+                           dim3(256), 0, stream, b.d_probs, b.d_feat, b.d_mask, b.d_labels, b.d_cent, b.start_label, b.C);
+    // whole groups of 8 XCDs x XG tiles (see slic_assign_body); a subset -- a window group, or the representatives of a shared pre-pass --
+    // is grouped over the XCDs like the whole batch
+    const dim3 grid(8 * OBIA_XCD_GROUP * (unsigned)((q.tile_end - q.tile_base + 8 * OBIA_XCD_GROUP - 1) / (8 * OBIA_XCD_GROUP)));
+    unsigned long long *px_counter = ctx->profiling ? sb.d_px + s.counter_slot : nullptr;
+    // events bound to the dispatch (a colour sweep of one window group: tagged with its batch and group)
+    const KernelSpan span(ctx, s.timing, s.timing == T_ASSIGN_GRP ? 2 * (ctx->timing.assign_group_batches - 1) + q.stream : 0);
+    const bool found = with_sweep_kernel<CP>(b.masked, s.kernel, CP - s.nch, [&](auto kernel, auto extra) {
+        auto launch = [&](auto... more) {
+            hipExtLaunchKernelGGL(kernel, grid, dim3(NT), 0, stream, span.a, span.b, 0, b.d_probs, b.d_feat, b.d_mask, b.d_mask4, b.d_cent, head_cur,
+                                  b.d_labels, b.d_acc, RQ, s.accumulate, s.store_labels, b.start_label, (float)b.fscale, sb.bin_stamp, sb.tile_lp,
+                                  sb.cache_k, sb.cache_q, s.sweep_no, s.use_cache, px_counter, b.d_tile_prob, q.tile_end, sb.d_orphan, sb.tpp, b.d_fbox,
+                                  q.tile_base, b.C, b.d_tl_k, b.d_tl_fp, b.d_tl_meta, b.d_tl_req, more...);
+        };
+        if constexpr (decltype(extra)::value == X_TILE_TABLE) launch(q.table ? sb.d_act_tiles : nullptr);
+        else if constexpr (decltype(extra)::value == X_RAW_INPUT) {   // fused feature pass
+            RawInput ri;
+            ri.src = b.raw_src; ri.Ws = b.raw_ws; ri.wins = b.d_windows; ri.keys = b.d_keys; ri.ratio = b.feat_ratio; ri.planes = b.d_feat;
+            launch(ri);
+            ctx->timing.feat_fused_px += (double)b.total_pix;
+        } else launch();
+    });
+    debug_sync(ctx, s.spatial ? "sweeps: pre-pass sweep" : "sweeps: colour sweep");
+    if (!found) { set_error("no sweep kernel for this batch"); return OBIA_E_INVALID; }
+    return OBIA_OK;
 }
 
 // d_mask -> d_mask4 (slic.hpp): dword (q, x) = the mask bytes of the rows 4q .. 4q+3 at column x.  Once per batch; every sweep then
@@ -1639,90 +1663,91 @@ __global__ void fill_i32_kernel(int32_t *p, long long n, int32_t v) {
 
 // nearest[:] = start_label - 1 (before the loop of _slic_cython)
 static void fill_labels(obia_ctx *ctx, SlicBatch &b) {
-    const long long n = b.total_pix;
-    int blocks = cdiv(n, 256 * 8);
-    if (blocks > 65535) blocks = 65535;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, n, b.start_label - 1);
+    const int blocks = std::max(1, std::min(cdiv(b.total_pix, 256 * 8), 65535));
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, b.total_pix, b.start_label - 1);
 }
 
 // h: the 513 slots of the sweeps' pixel counters (slic_run_sweeps); the profiling totals of the batch.  shared_px: pixel-sweeps of
 // the pre-pass that were covered by a class representative's sweeps and not evaluated (they count as covered, and on their own)
 static void fold_counters(obia_ctx *ctx, const unsigned long long *h, double shared_px) {
-    if (ctx->profiling) {
-        for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
-        ctx->timing.prepass_px += shared_px;
-        ctx->timing.prepass_shared_px += shared_px;
-    }
+    if (!ctx->profiling) return;
+    for (int i = 0; i < 256; ++i) { ctx->timing.assign_px += (double)h[i]; ctx->timing.prepass_px += (double)h[256 + i]; }
+    ctx->timing.prepass_px += shared_px;
+    ctx->timing.prepass_shared_px += shared_px;
 }
 
-// Workgroups of slic_spatial_kernel<CP> the device holds at once (occupancy x compute units), asked once per context and CP
-static int spatial_residency(obia_ctx *ctx, int CP) {
-    int &r = ctx->spatial_residency[CP / 4 - 1];
-    if (r > 0) return r;
+// Workgroups of a sweep kernel the device holds at once (occupancy x compute units), asked once per context and variant and kept in
+// `cached`; 0x7fffffff when unknown (no batch is large enough)
+static int kernel_residency(obia_ctx *ctx, const SlicBatch &b, SweepKernel k, int &cached) {
+    if (cached > 0) return cached;
     int per_cu = 0, cus = 0;
-    hipError_t e = hipErrorInvalidValue;
-    switch (CP) {
-        case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<8>, NT, 0); break;
-#ifndef OBIA_ONLY_CP8
-        case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<4>, NT, 0); break;
-        case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<12>, NT, 0); break;
-        case 16: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, slic_spatial_kernel<16>, NT, 0); break;
-#endif
-        default: break;
-    }
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    if (e != hipSuccess || per_cu <= 0 || cus <= 0) { (void)hipGetLastError(); return 0x7fffffff; }   // (unknown: no batch is large enough)
-    r = per_cu * cus;
-    return r;
-}
-
-// The same of the colour kernel the batch's colour sweeps launch (the main kernel in its padding variant or the low-compactness
-// kernel, masked or not: launch_assign chooses), asked once per context and variant
-static int sweep_residency(obia_ctx *ctx, SlicBatch &b) {
-    const bool collb = b.col_lb && b.d_fbox;
-    int &r = ctx->sweep_residency[(((b.CP / 4 - 1) * 2 + (b.masked ? 1 : 0)) * 4 + (b.CP - b.C)) * 2 + (collb ? 1 : 0)];
-    if (r > 0) return r;
-    int per_cu = 0, cus = 0;
-    const FixedPointState fp;
-    const KernelSpan span;
-    switch (b.CP) {   // (a colour sweep that accumulates and stores no labels; nothing is launched)
-        case 8: launch_assign<8>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
-#ifndef OBIA_ONLY_CP8
-        case 4: launch_assign<4>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
-        case 12: launch_assign<12>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
-        case 16: launch_assign<16>(ctx, b, 0, 1, 1, 0, nullptr, fp, 0, 1, nullptr, span, nullptr, false, TileSubset(), false, nullptr, &per_cu); break;
-#endif
-        default: break;
-    }
+    (void)with_cp(b.CP, [&](auto cp) {
+        with_sweep_kernel<decltype(cp)::value>(b.masked, k, k == SweepKernel::SpatialRuns ? 0 : b.CP - b.C, [&](auto kernel, auto) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, NT, 0) != hipSuccess) per_cu = 0;
+        });
+        return OBIA_OK;
+    });
     if (per_cu <= 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) {
         (void)hipGetLastError();
-        return 0x7fffffff;   // (unknown: no batch is large enough)
+        return 0x7fffffff;
     }
-    r = per_cu * cus;
-    return r;
+    return cached = per_cu * cus;
+}
+// ... of slic_spatial_kernel<CP>, and of the colour kernel the batch's colour sweeps launch (the main kernel in its padding variant or
+// the low-compactness kernel, masked or not: colour_sweep_kernel)
+static int spatial_residency(obia_ctx *ctx, const SlicBatch &b) { return kernel_residency(ctx, b, SweepKernel::SpatialRuns, ctx->spatial_residency[b.CP / 4 - 1]); }
+static int sweep_residency(obia_ctx *ctx, const SlicBatch &b) {
+    const int variant = (((b.CP / 4 - 1) * 2 + (b.masked ? 1 : 0)) * 4 + (b.CP - b.C)) * 2 + (b.col_lb && b.d_fbox ? 1 : 0);
+    return kernel_residency(ctx, b, colour_sweep_kernel(b), ctx->sweep_residency[variant]);
 }
 
-// Two window groups: the problems [0, split) and [split, nprob), consecutive and balanced by sweep tiles, a tie going
-// to the later split; 0 when the batch cannot be split.  One choice for the grouped pre-pass and the grouped colour pass.
-static int group_split(const SlicBatch &b) {
-    int split = 0;
-    long long best = -1;
-    for (int p = 1; p < b.nprob; ++p) {
-        const long long t0 = b.probs[p].tile_off, t1 = b.total_tiles_all - t0, d = t0 > t1 ? t0 - t1 : t1 - t0;
-        if (t0 > 0 && t1 > 0 && (best < 0 || d <= best)) { best = d; split = p; }
+// Queues the steps of a plan: for every step and each of its parts the centroid step, then the sweep, on the part's stream; around
+// them what the step asks for.  Between a fork and its join nothing may be left running on the side stream when the caller gets an
+// error: the side stream is synchronised first.
+template <int CP>
+static int issue_steps(obia_ctx *ctx, SlicBatch &b, const SweepPlan &pl, const SweepBuffers &sb) {
+    const int RQ = acc_record_qwords(CP);
+    bool forked = false;
+    for (const SweepStep &s : pl.steps) {
+        const bool colour = !s.spatial, grouped = s.nparts == 2;
+        if (s.refill) {
+            fill_labels(ctx, b);
+            if (sb.tile_lp) OBIA_TRY(fill_async(ctx, sb.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all));
+        }
+        if (s.broadcast) {
+            hipLaunchKernelGGL(slic_prepass_broadcast_kernel, dim3(cdiv(pl.kmax_mem, 64), pl.n_shared), dim3(64), 0, ctx->stream, b.d_probs,
+                               sb.d_member_rep, b.CP, RQ, b.d_acc, b.d_cent, b.d_ref);
+            debug_sync(ctx, "sweeps: pre-pass broadcast");
+        }
+        hipError_t he = hipSuccess;
+        int rc = OBIA_OK;
+        if (s.fork) {   // behind the batch's fills, its pre-pass, and whatever else this stream holds for the batch
+            forked = true;
+            he = hipEventRecord(ctx->grp_fork, ctx->stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(ctx->side, ctx->grp_fork, 0);
+            if (colour) ctx->timing.assign_group_batches += 1;
+        }
+        if (ctx->profiling && colour && s.store_labels) ctx->timing.assign_store_px += (double)b.total_pix;   // (both groups' pixels, once)
+        for (int i = 0; i < s.nparts && he == hipSuccess && rc == OBIA_OK; ++i) {
+            rc = launch_part<CP>(ctx, b, pl, sb, s, s.part[i]);
+            if (grouped) (colour ? ctx->timing.assign_group_launches : ctx->timing.prepass_group_launches) += 1;
+        }
+        // join: in front of the whole-batch step of the last pre-pass sweep, or behind the colour pass and in front of the counters'
+        // read-back -- before anything else is queued
+        if (s.join && he == hipSuccess && rc == OBIA_OK) {
+            he = hipEventRecord(ctx->grp_join, ctx->side);
+            if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->grp_join, 0);
+            forked = he != hipSuccess;
+        }
+        if (he != hipSuccess || rc != OBIA_OK) {
+            if (forked) (void)hipStreamSynchronize(ctx->side);
+            if (he == hipSuccess) return rc;
+            set_error("grouped %s: %s", colour ? "colour pass" : "pre-pass", hipGetErrorString(he));
+            return OBIA_E_HIP;
+        }
+        b.d_head_cur = b.d_head + (size_t)s.parity * b.total_cells;
     }
-    return split;
-}
-// sweep tiles of the smaller group
-static long long group_min_tiles(const SlicBatch &b, int split) {
-    const long long t0 = b.probs[split].tile_off, t1 = b.total_tiles_all - t0;
-    return t0 < t1 ? t0 : t1;
-}
-// a developer switch of the two groupings (read per batch): 0 never, 2 at any size, else 1 (the size threshold decides)
-static int groups_mode(const char *name) {
-    const char *e = std::getenv(name);
-    return !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1));
+    return OBIA_OK;
 }
 
 // Queues every sweep of the batch on the context's stream (a grouped pre-pass or colour pass: the second window group's launches on
@@ -1733,341 +1758,97 @@ static int groups_mode(const char *name) {
 static int queue_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat, unsigned long long **d_px_out, double *shared_px_out) {
     *d_px_out = nullptr;
     *shared_px_out = 0.0;
-    if (std::getenv("OBIA_DEBUG_SYNC"))
+    const SweepSwitches sw = read_sweep_switches();
+    if (sw.debug_sync)
         for (size_t p = 0; p < b.probs.size(); ++p) {
             const SlicProblem &P = b.probs[p];
             fprintf(stderr, "[obia debug]   problem %zu: %dx%d K %d steps %d %d bins %dx%d cell_off %d cent_off %d tiles %dx%d tile_off %d n_valid %d (total_cent %d total_cells %d tiles_all %lld)\n",
                     p, P.H, P.W, P.K, P.sy, P.sx, P.ncy, P.ncx, P.cell_off, P.cent_off, P.tiles_y, P.tiles_x, P.tile_off, P.n_valid,
                     b.total_cent, b.total_cells, b.total_tiles_all);
         }
-    if (b.total_tiles <= 0 || b.max_iter <= 0) { fill_labels(ctx, b); return OBIA_OK; }   // no sweep: every pixel keeps the fill value
-    // the sweep addresses a footprint's pixels as a 64-bit wave-uniform base plus a 32-bit lane offset (16 rows x W x 64 B)
-    for (auto &P : b.probs)
-        if (P.W >= (1 << 22)) { set_error("rasters / tile windows wider than 4194303 pixels are not supported (got %d)", P.W); return OBIA_E_UNSUPPORTED; }
-    const int passes = (b.masked && !b.prepass_only) ? 2 : 1;   // maskSLIC: spatial-only pre-pass first (slic_superpixels.py:310-314)
-    if (b.fuse_features && (!b.masked || b.exit_on_fixed_point || b.slic_zero || b.direct || b.col_lb || b.C != b.CP || b.CP > 12 || !b.raw_src || !b.d_keys)) {
-        set_error("fused feature pass on a batch that cannot take it");   // (slic_fuse_features decides; nothing else may set the flag)
-        return OBIA_E_INVALID;
-    }
-    // sweeps of the pre-pass: max_iter like every pass, unless the stage entry asks for another count (obia_slic_stages::prepass_iters)
-    const int pre_iter = (b.masked && b.prepass_iter > 0) ? b.prepass_iter : b.max_iter;
-    const int total_sweeps = b.masked ? pre_iter + (passes - 1) * b.max_iter : b.max_iter;
+    // the plan; a residency is asked for only where a grouping hangs on it
+    const SweepGrouping grouping = sweep_grouping(b, repeat, sw);
+    SweepResidencies res;
+    if (grouping.pre_asks) res.spatial = spatial_residency(ctx, b);
+    if (grouping.col_asks) res.colour = sweep_residency(ctx, b);
+    SweepPlan pl;
+    OBIA_TRY(plan_sweeps(b, repeat, sw, grouping, res, pl));
+    if (pl.no_sweep) { fill_labels(ctx, b); return OBIA_OK; }
+
     const int RQ = acc_record_qwords(b.CP);
+    const size_t nt = (size_t)b.total_tiles_all;
     Arena &A = ctx->arena;
-    unsigned long long *d_px = A.get<unsigned long long>(513);
-    if (!d_px) return OBIA_E_NOMEM;
-    int *d_orphan = reinterpret_cast<int *>(d_px + 512);
-    FixedPointState fp;
-    if (b.exit_on_fixed_point) {
-        const size_t nt = (size_t)b.total_tiles_all;
-        fp.bin_stamp = A.get<int>((size_t)b.total_cells);
-        fp.tile_lp = A.get<int>(nt);
-        fp.cache_k = A.get<int>(nt * (MAXC + 1));
-        fp.cache_q = A.get<unsigned long long>(nt * MAXC * (size_t)(b.CP + 3));
-        if (!fp.bin_stamp || !fp.tile_lp || !fp.cache_k || !fp.cache_q) return OBIA_E_NOMEM;
-        OBIA_TRY(fill_async(ctx, fp.bin_stamp, 0, sizeof(int) * (size_t)b.total_cells));
-        OBIA_TRY(fill_async(ctx, fp.tile_lp, 0, sizeof(int) * nt));
+    SweepBuffers sb;
+    sb.d_px = A.get<unsigned long long>(513);
+    if (!sb.d_px) return OBIA_E_NOMEM;
+    sb.d_orphan = reinterpret_cast<int *>(sb.d_px + 512);
+    if (pl.fixed_point) {
+        sb.bin_stamp = A.get<int>((size_t)b.total_cells);
+        sb.tile_lp = A.get<int>(nt);
+        sb.cache_k = A.get<int>(nt * (MAXC + 1));
+        sb.cache_q = A.get<unsigned long long>(nt * MAXC * (size_t)(b.CP + 3));
+        if (!sb.bin_stamp || !sb.tile_lp || !sb.cache_k || !sb.cache_q) return OBIA_E_NOMEM;
+        OBIA_TRY(fill_async(ctx, sb.bin_stamp, 0, sizeof(int) * (size_t)b.total_cells));
+        OBIA_TRY(fill_async(ctx, sb.tile_lp, 0, sizeof(int) * nt));
     }
-    {   // candidate lists of the sweep tiles (see the top of the file)
-        const size_t nt = (size_t)b.total_tiles_all;
-        b.d_tl_k = A.get<int>(nt * MAXC);
-        b.d_tl_fp = A.get<unsigned>(nt * NT);
-        b.d_tl_meta = A.get<int>(nt * 3);   // {entries, build word} per tile, then the rebuild requests: ONE fill resets all three
-        b.d_tl_req = b.d_tl_meta ? b.d_tl_meta + nt * 2 : nullptr;
-        b.d_ref = A.get<float>((size_t)b.total_cent * 2);
-        if (!b.d_tl_k || !b.d_tl_fp || !b.d_tl_meta || !b.d_tl_req || !b.d_ref) return OBIA_E_NOMEM;
-    }
-    int maxh_z = 1, kmax = 1;
-    for (auto &P : b.probs) { if (P.H > maxh_z) maxh_z = P.H; if (P.K > kmax) kmax = P.K; }
-    if (b.masked && b.d_mask && !b.d_mask4) {   // the packed mask of the sweeps (problems whose mask hides nothing never read it); the
-                                                // tiler's mask kernel writes it on the way (tiling.hip: tile_mask_kernel<true>)
+    // candidate lists of the sweep tiles (see the top of the file)
+    b.d_tl_k = A.get<int>(nt * MAXC);
+    b.d_tl_fp = A.get<unsigned>(nt * NT);
+    b.d_tl_meta = A.get<int>(nt * 3);   // {entries, build word} per tile, then the rebuild requests: ONE fill resets all three
+    b.d_tl_req = b.d_tl_meta ? b.d_tl_meta + nt * 2 : nullptr;
+    b.d_ref = A.get<float>((size_t)b.total_cent * 2);
+    if (!b.d_tl_k || !b.d_tl_fp || !b.d_tl_meta || !b.d_tl_req || !b.d_ref) return OBIA_E_NOMEM;
+    if (pl.pack_mask) {
         b.d_mask4 = A.get<unsigned>((size_t)b.total_m4);
         if (!b.d_mask4) return OBIA_E_NOMEM;
-        int gq = (maxh_z + 3) / 4;
-        if (gq > 16384) gq = 16384;
-        OBIA_TRY(ctx->plan.flush(ctx));   // (the descriptors; a tiler batch comes with the mask packed and flushes once, below)
-        hipLaunchKernelGGL(mask_pack4_kernel, dim3(gq, b.nprob), dim3(256), 0, ctx->stream, b.d_probs, b.d_mask, b.d_mask4);
     }
-    if (maxh_z > 4096) maxh_z = 4096;
-
-    // store_all = false: only the very last sweep stores its labels (the others' labels are dead stores unless a valid pixel is
-    // reached by no window -- see the label stage of the sweep); true: every sweep stores, the reference's literal behaviour,
-    // needed by the fixed-point replay (labels "already in place"), by SLIC-zero (its max-colour-distance pass reads the last
-    // assignment) and by the repeat.
-    const bool store_all = repeat || b.exit_on_fixed_point || b.slic_zero;
-    // The fill value survives in exactly one kind of pixel: a valid one that no window reached ("orphan").  When only the last sweep
-    // stores, such a pixel raises the flag and the caller repeats the batch (slic_sweeps_settle) -- unless the batch has ONE sweep in
-    // all, where the fill value is what the reference keeps.  Every other pixel is written by the last sweep (masked ones included):
-    // the 1.2 GB fill of a bench batch is skipped on the common path.
-    if (store_all || total_sweeps <= 1) {
+    if (pl.n_shared > 0) {   // the class tables join the descriptors' upload
+        sb.d_member_rep = ctx->plan.add(ctx, pl.mr.data(), pl.mr.size());
+        if (!sb.d_member_rep) return OBIA_E_NOMEM;
+        if (!pl.class_span) {
+            sb.d_act_probs = ctx->plan.add(ctx, pl.ap.data(), pl.ap.size());
+            sb.d_act_tiles = ctx->plan.add(ctx, pl.at.data(), pl.at.size());
+            if (!sb.d_act_probs || !sb.d_act_tiles) return OBIA_E_NOMEM;
+        }
+        *shared_px_out = pl.shared_px;
+    }
+    if (pl.pack_mask) {
+        OBIA_TRY(ctx->plan.flush(ctx));   // (the descriptors; a tiler batch comes with the mask packed and flushes once, below)
+        hipLaunchKernelGGL(mask_pack4_kernel, dim3(pl.pack_rows, b.nprob), dim3(256), 0, ctx->stream, b.d_probs, b.d_mask, b.d_mask4);
+    }
+    if (pl.fill_first) {
         fill_labels(ctx, b);
         debug_sync(ctx, "sweeps: label fill");
     }
-    const bool prep_grouped = std::getenv("OBIA_PREP_GROUPED") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prep_kernels.py): the 16-lanes-per-centroid kernel
-    const bool prepass_visits = std::getenv("OBIA_PREPASS_VISITS") != nullptr;   // developer switch (A/B timing, tests/test_gpu_prepass_runs.py): the spatial pre-pass by pixel visits, not runs
-    // Shared pre-pass (slic_prepass_broadcast_kernel): the sweeps of the pre-pass but the last, and the centroid steps between them,
-    // run for the first problem of every class only.  Not when every sweep stores its labels (the repeat, exit_on_fixed_point,
-    // SLIC-zero), with a `spacing`, for the stage entry's pre-pass variants, or when no class has a second member: the path
-    // without sharing, unchanged.  External seeds (seeding="skimage" among them) form no class.  OBIA_PREPASS_SHARE=0: developer switch (A/B timing,
-    // tests/test_gpu_prepass_share.py).
-    std::vector<int> share_rep;
-    int n_shared = 0;
-    {
-        const char *e = std::getenv("OBIA_PREPASS_SHARE");
-        const bool off = e && e[0] == '0';
-        if (!off && b.masked && passes == 2 && pre_iter >= 2 && b.prepass_iter <= 0 && !store_all && !b.direct && !prep_grouped)
-            n_shared = slic_prepass_classes(b.probs, b.grid_n, share_rep);
-    }
-    TileSubset act_tiles;                 // tiles of the problems that run the shared sweeps
-    const int *d_act_probs = nullptr;     // those problems: a table, or the span [act_p_base, act_p_base + n_act)
-    const int *d_member_rep = nullptr;    // {member, representative} of every problem that does not
-    int act_p_base = 0, n_act = b.nprob, kmax_act = kmax, kmax_mem = 1;
-    if (n_shared > 0) {
-        std::vector<int> ap, at, mr;
-        double spx = 0.0;
-        kmax_act = 1;
-        for (int p = 0; p < b.nprob; ++p) {
-            const SlicProblem &P = b.probs[p];
-            if (share_rep[p] == p) {
-                ap.push_back(p);
-                for (int t = 0; t < P.tiles_x * P.tiles_y; ++t) at.push_back(P.tile_off + t);
-                if (P.K > kmax_act) kmax_act = P.K;
-            } else {
-                mr.push_back(p); mr.push_back(share_rep[p]);
-                if (P.K > kmax_mem) kmax_mem = P.K;
-                spx += (double)P.H * (double)P.W * (double)(pre_iter - 1);
-            }
-        }
-        n_act = (int)ap.size();
-        act_p_base = ap.front();
-        const bool span = ap.back() - ap.front() + 1 == n_act;   // consecutive problems: consecutive tiles, no table in front of a tile
-        d_member_rep = ctx->plan.add(ctx, mr.data(), mr.size());   // (the class tables join the descriptors' upload)
-        if (!d_member_rep) return OBIA_E_NOMEM;
-        if (span) {
-            act_tiles.base = b.probs[ap.front()].tile_off;
-            act_tiles.end = b.probs[ap.back()].tile_off + b.probs[ap.back()].tiles_x * b.probs[ap.back()].tiles_y;
-        } else {
-            const int *d_ap = ctx->plan.add(ctx, ap.data(), ap.size()), *d_at = ctx->plan.add(ctx, at.data(), at.size());
-            if (!d_ap || !d_at) return OBIA_E_NOMEM;
-            d_act_probs = d_ap;
-            act_tiles.table = d_at; act_tiles.base = 0; act_tiles.end = (int)at.size();
-        }
-        *shared_px_out = spx;
-    }
-    // Two window groups in flight: the spatial-only sweeps of the pre-pass (slic_spatial_kernel) and the centroid steps
-    // in front of them read and write nothing of another problem of the batch -- centroid and accumulator records, bins, candidate
-    // lists, reference positions, rebuild requests and the packed mask are all indexed through the problem; the two batch-wide words
-    // are the pixel counters (integer atomics) and the orphan flag (every writer stores 1).  So the batch's problems are split into
-    // two groups of consecutive problems, balanced by sweep tiles, and each runs its own chain step -> sweep -> step -> ...: group 0
-    // on the context's stream, group 1 on the side stream, forked behind the fills below and joined in front of the step of the last
-    // pre-pass sweep, which runs on the whole batch as always.  A group's centroid step (a launch bound by wave dispatch that leaves
-    // the GPU all but empty) and its launch boundaries then hide behind the other group's sweep.  A step resets the next sweep's bins
-    // of ITS group only: the other group may be one sweep behind and still reading that buffer.  Sweep numbers (list stamps, the
-    // parity of the bin buffers) advance alike in both groups.  Not for a batch that shares its pre-pass (n_shared > 0), not when
-    // every sweep stores its labels (the repeat among them), not under the pre-pass developer switches.  By default only when each
-    // group fills the device at least once (spatial_residency): below that a launch does not fill it and the split buys nothing.
-    // OBIA_PREPASS_GROUPS (developer switch, read per batch: A/B timing, tests/test_gpu_prepass_groups.py): 0 never, 2 at any size.
-    //
-    // The colour pass runs the same way (col_split): each group its chain step -> colour sweep for all max_iter sweeps, forked behind
-    // the last whole-batch launch in front of the first colour-pass step -- the last pre-pass sweep of a masked batch (the pre-pass
-    // broadcast and that sweep stay whole-batch), the clears of an unmasked one -- and joined behind each group's last sweep, the one
-    // that stores its labels, in front of the counters' read-back.  The colour kernels (the main one in every padding variant and the
-    // low-compactness one) share nothing more than the spatial ones: the colour boxes are read-only and indexed through P.fb_off, the
-    // planes and labels through P.pix_off.  A batch that shares its PRE-PASS is eligible: its colour pass shares nothing.  Needs two
-    // sweeps at least; by default each group must hold one residency of the colour kernel it launches (sweep_residency).
-    // OBIA_SWEEP_GROUPS: the same switch, independent of the other (tests/test_gpu_sweep_groups.py).
-    int grp_split = 0;   // > 0: the pre-pass groups are the problems [0, grp_split) and [grp_split, nprob)
-    int col_split = 0;   // > 0: the colour-pass groups, likewise
-    if (!store_all && !prepass_visits && !prep_grouped && !b.direct && b.nprob >= 2 &&
-        !std::getenv("OBIA_DEBUG_SYNC")) {   // (the stage-by-stage synchronisation watches one stream)
-        const int split = group_split(b);
-        const int pre_mode = groups_mode("OBIA_PREPASS_GROUPS"), col_mode = groups_mode("OBIA_SWEEP_GROUPS");
-        if (split > 0 && pre_mode != 0 && n_shared == 0 && b.masked && pre_iter >= 2 &&
-            (pre_mode == 2 || group_min_tiles(b, split) >= (long long)spatial_residency(ctx, b.CP)))
-            grp_split = split;
-        if (split > 0 && col_mode != 0 && !(b.masked && b.prepass_only) && b.max_iter >= 2 &&
-            (col_mode == 2 || group_min_tiles(b, split) >= (long long)sweep_residency(ctx, b)))
-            col_split = split;
-        if (grp_split > 0 || col_split > 0) OBIA_TRY(side_stream(ctx));
-    }
+    if (pl.grp_split > 0 || pl.col_split > 0) OBIA_TRY(side_stream(ctx));
     // the planning phase's one upload: the descriptors (slic_plan_and_seed), the class tables above, whatever the caller added
     OBIA_TRY(ctx->plan.flush(ctx));
     {   // ... and its one clear: the accumulators (also in front of a repeat), the counters and the flag, the bins, the tiles' lists
         ClearSet clr(ctx);
         OBIA_TRY(clr.add(b.d_acc, 0, sizeof(unsigned long long) * (size_t)b.total_cent * RQ));
-        OBIA_TRY(clr.add(d_px, 0, sizeof(unsigned long long) * 513));
+        OBIA_TRY(clr.add(sb.d_px, 0, sizeof(unsigned long long) * 513));
         OBIA_TRY(clr.add(b.d_head, 0xff, sizeof(int) * (size_t)b.total_cells));   // buffer 0 only
         // no tile has a list, nobody asked for a rebuild (-1 everywhere: the first sweep builds every list)
-        OBIA_TRY(clr.add(b.d_tl_meta, 0xff, sizeof(int) * 3 * (size_t)b.total_tiles_all));
+        OBIA_TRY(clr.add(b.d_tl_meta, 0xff, sizeof(int) * 3 * nt));
         OBIA_TRY(clr.flush());
     }
     debug_sync(ctx, "sweeps: memsets");
-    bool first = true;
-    int sweep_no = 0;
-    for (int pass = 0; pass < passes; ++pass) {
-        const int ignore_color = (b.masked && pass == 0) ? 1 : 0;
-        const bool last_pass = (pass == passes - 1);
-        if (pass > 0 && store_all) {
-            // the main pass is a second call of _slic_cython (slic_superpixels.py:310-318): `nearest` starts from the fill
-            // value again, a pixel no window reaches in its first sweep does not inherit a pre-pass label.  (Only when the
-            // pre-pass stored labels at all: otherwise the fill of the batch's start is still in place.)
-            fill_labels(ctx, b);
-            // (exit_on_fixed_point: no tile may replay "labels already in place" across the refill -- every tile is evaluated
-            // by the first sweep of the main pass)
-            if (fp.tile_lp) OBIA_TRY(fill_async(ctx, fp.tile_lp, 0, sizeof(int) * (size_t)b.total_tiles_all));
-        }
-        const int iters = ignore_color ? pre_iter : b.max_iter;
-        for (int it = 0; it < iters; ++it) {
-            int *head_cur = b.d_head + (size_t)(sweep_no & 1) * b.total_cells;
-            int *head_nxt = b.d_head + (size_t)((sweep_no + 1) & 1) * b.total_cells;
-            ++sweep_no;   // sweep ids start at 1
-            // SLIC-zero: the per-cluster colour scale restarts at 1 with the colour pass and is carried afterwards
-            const int zmode = (b.slic_zero && !ignore_color) ? (it == 0 ? 2 : 1) : 0;
-            // shared pre-pass: this sweep and the step in front of it run for the representatives only; in front of the step of the
-            // last pre-pass sweep the other members receive what they skipped
-            const bool shared_sweep = n_shared > 0 && ignore_color && it < iters - 1;
-            if (n_shared > 0 && ignore_color && it == iters - 1) {
-                hipLaunchKernelGGL(slic_prepass_broadcast_kernel, dim3(cdiv(kmax_mem, 64), n_shared), dim3(64), 0, ctx->stream, b.d_probs,
-                                   d_member_rep, b.CP, RQ, b.d_acc, b.d_cent, b.d_ref);
-                debug_sync(ctx, "sweeps: pre-pass broadcast");
-            }
-            const dim3 prep_grid(cdiv(shared_sweep ? kmax_act : kmax, 64), shared_sweep ? n_act : b.nprob);
-            const int prep_base = shared_sweep ? act_p_base : 0;
-            const int *prep_table = shared_sweep ? d_act_probs : nullptr;
-            // (a launch steps the problems [p_base, p_base + grid.y), or those the table names, and resets the bins [cell_base, cell_end)
-            // of the next sweep's buffer)
-#define LAUNCH_PREP_LANE(CPV)                                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_lane_kernel<CPV>), pgrid, dim3(64), 0, stream, \
-                       b.d_probs, p_base, first ? 1 : 0, zmode, b.d_seed, b.d_acc, RQ, 1.0 / b.fscale, b.d_cent, head_cur, head_nxt, \
-                       cell_end, fp.bin_stamp, sweep_no, cell_base, b.d_ref, b.d_tl_req, table)
-            auto prep_lane = [&](hipStream_t stream, dim3 pgrid, int p_base, const int *table, int cell_base, int cell_end) {
-                switch (b.CP) {
-                    case 4: LAUNCH_PREP_LANE(4); break;
-                    case 8: LAUNCH_PREP_LANE(8); break;
-                    case 12: LAUNCH_PREP_LANE(12); break;
-                    default: LAUNCH_PREP_LANE(16); break;
-                }
-            };
-#undef LAUNCH_PREP_LANE
-            // a sweep as two window groups: one of the pre-pass sweeps slic_spatial_kernel decides (see launch_assign: spatial-only, no
-            // labels stored), or any sweep of a grouped colour pass
-            const bool pre_groups = grp_split > 0 && ignore_color && it < iters - 1, col_groups = col_split > 0 && !ignore_color;
-            if (pre_groups || col_groups) {
-                const int split = col_groups ? col_split : grp_split;
-                // (the grouped colour pass ends with the batch's very last sweep, which folds nothing and stores its labels -- what
-                // the ungrouped launch below passes; every other grouped sweep accumulates and stores nothing, lists in use)
-                const bool chain_end = it == (col_groups ? iters - 1 : iters - 2), very_last = col_groups && chain_end;
-                hipError_t he = hipSuccess;
-                if (it == 0) {   // fork: behind the batch's fills, its pre-pass, and whatever else this stream holds for the batch
-                    he = hipEventRecord(ctx->grp_fork, ctx->stream);
-                    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->side, ctx->grp_fork, 0);
-                    if (col_groups) ctx->timing.assign_group_batches += 1;
-                }
-                for (int g = 0; g < 2 && he == hipSuccess; ++g) {
-                    const int p0 = g ? split : 0, p1 = g ? b.nprob : split;
-                    int kmax_g = 1;
-                    for (int p = p0; p < p1; ++p) if (b.probs[p].K > kmax_g) kmax_g = b.probs[p].K;
-                    const hipStream_t st = g ? ctx->side : ctx->stream;
-                    prep_lane(st, dim3(cdiv(kmax_g, 64), p1 - p0), p0, nullptr, b.probs[p0].cell_off, g ? b.total_cells : b.probs[p1].cell_off);
-                    KernelSpan span(ctx, col_groups ? T_ASSIGN_GRP : T_PREPASS, col_groups ? 2 * (ctx->timing.assign_group_batches - 1) + g : 0);
-                    TileSubset sub;
-                    sub.base = b.probs[p0].tile_off;
-                    sub.end = g ? (int)b.total_tiles_all : b.probs[p1].tile_off;
-                    unsigned long long *pxc = ctx->profiling ? d_px + (col_groups ? 0 : 256) : nullptr;
-                    const int ign = col_groups ? 0 : 1, accumulate = very_last ? 0 : 1, store_labels = very_last ? 1 : 0;
-                    switch (b.CP) {
-                        case 8: launch_assign<8>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-#ifndef OBIA_ONLY_CP8
-                        case 4: launch_assign<4>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-                        case 12: launch_assign<12>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-                        case 16: launch_assign<16>(ctx, b, ign, accumulate, 1 - ign, store_labels, d_orphan, fp, sweep_no, 1, pxc, span, head_cur, false, sub, false, &st); break;
-#endif
-                        default: he = hipErrorInvalidValue; break;
-                    }
-                    (col_groups ? ctx->timing.assign_group_launches : ctx->timing.prepass_group_launches) += 1;
-                }
-                if (very_last && ctx->profiling) ctx->timing.assign_store_px += (double)b.total_pix;   // (both groups' pixels, once)
-                // join: in front of the whole-batch step of the last pre-pass sweep, or behind the colour pass and in front of the
-                // counters' read-back -- before anything else is queued
-                if (he == hipSuccess && chain_end) {
-                    he = hipEventRecord(ctx->grp_join, ctx->side);
-                    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->grp_join, 0);
-                }
-                if (he != hipSuccess) {   // nothing may be left running on the side stream when the caller gets the error
-                    (void)hipStreamSynchronize(ctx->side);
-                    set_error("grouped %s: %s", col_groups ? "colour pass" : "pre-pass", hipGetErrorString(he));
-                    return OBIA_E_HIP;
-                }
-                b.d_head_cur = head_cur;
-                first = false;
-                continue;
-            }
-            if (!prep_grouped) prep_lane(ctx->stream, prep_grid, prep_base, prep_table, 0, b.total_cells);
-            else if (RQ == 16)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<16>), dim3(cdiv(b.total_cent * 16LL, 256)), dim3(256), 0,
-                                   ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
-                                   1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_prep_kernel<32>), dim3(cdiv(b.total_cent * 32LL, 256)), dim3(256), 0,
-                                   ctx->stream, b.d_probs, b.d_cent_prob, b.total_cent, b.CP, first ? 1 : 0, zmode, b.d_seed, b.d_acc,
-                                   1.0 / b.fscale, b.d_cent, head_cur, head_nxt, b.total_cells, fp.bin_stamp, sweep_no, 0, 0, b.d_ref, b.d_tl_req);
-            b.d_head_cur = head_cur;
-            debug_sync(ctx, "sweeps: prep");
-            first = false;
-            if (zmode == 1) {   // the centroids just moved: raise max_dist_color from the assignment of the last sweep
-                dim3 zg(maxh_z, b.nprob);
-#define LAUNCH_MAXDIST(CPV)                                                                                           \
-    do {                                                                                                              \
-        if (b.masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_maxdist_kernel<CPV, true>), zg, dim3(256), 0, ctx->stream, b.d_probs, \
-                                         b.d_feat, b.d_mask, b.d_labels, b.d_cent, b.start_label, b.C);            \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(slic_maxdist_kernel<CPV, false>), zg, dim3(256), 0, ctx->stream, b.d_probs, \
-                                b.d_feat, b.d_mask, b.d_labels, b.d_cent, b.start_label, b.C);                     \
-    } while (0)
-                switch (b.CP) {
-                    case 4: LAUNCH_MAXDIST(4); break;
-                    case 8: LAUNCH_MAXDIST(8); break;
-                    case 12: LAUNCH_MAXDIST(12); break;
-                    default: LAUNCH_MAXDIST(16); break;
-                }
-#undef LAUNCH_MAXDIST
-            }
-            // the update after the very last sweep is never read: skip its accumulation
-            const bool very_last = last_pass && it == iters - 1;
-            const int accumulate = very_last ? 0 : 1;
-            const int accum_color = (!ignore_color || it == iters - 1) ? 1 : 0;
-            const int store_labels = store_all ? 2 : (very_last ? 1 : 0);   // (see orphan_needs_repeat)
-            // the last pre-pass sweep is the only one of its pass that folds colours (they seed the main pass): the
-            // caches written by the earlier pre-pass sweeps hold no colour sums, so it evaluates every tile
-            const int use_cache = (ignore_color && it == iters - 1) ? 0 : 1;
-            // fused feature pass: this sweep -- the first reader of the planes -- writes them from the raster (RAWIN).  Not in the
-            // repeat: the first run has written them
-            const bool rawin = b.fuse_features && !repeat && ignore_color && it == iters - 1;
-            {
-                KernelSpan span(ctx, ignore_color ? T_PREPASS : T_ASSIGN);   // events bound to the dispatch
-                const TileSubset sub = shared_sweep ? act_tiles : TileSubset();
-                unsigned long long *pxc = ctx->profiling ? d_px + (ignore_color ? 256 : 0) : nullptr;
-                if (ctx->profiling && !ignore_color && store_labels) ctx->timing.assign_store_px += (double)b.total_pix;
-                switch (b.CP) {
-                    case 8: launch_assign<8>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
-#ifndef OBIA_ONLY_CP8   /* developer builds (tools/build_variant.sh ... -DOBIA_ONLY_CP8): only the 5..8-band sweep kernels are compiled */
-                    case 4: launch_assign<4>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
-                    case 12: launch_assign<12>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub, rawin); break;
-                    case 16: launch_assign<16>(ctx, b, ignore_color, accumulate, accum_color, store_labels, d_orphan, fp, sweep_no, use_cache, pxc, span, head_cur, prepass_visits, sub); break;   // (never fused: slic_fuse_features)
-#endif
-                    default: set_error("bad CP"); return OBIA_E_INVALID;
-                }
-            }
-            debug_sync(ctx, ignore_color ? "sweeps: pre-pass sweep" : "sweeps: colour sweep");
-        }
-    }
+    sb.tpp = b.probs.empty() ? 0 : b.probs[0].tiles_x * b.probs[0].tiles_y;
+    for (auto &P : b.probs) if (P.tiles_x * P.tiles_y != sb.tpp) sb.tpp = 0;
+    OBIA_TRY(with_cp(b.CP, [&](auto cp) { return issue_steps<decltype(cp)::value>(ctx, b, pl, sb); }));
     OBIA_HIP_TRY(hipGetLastError());
-    *d_px_out = d_px;
+    *d_px_out = sb.d_px;
     return OBIA_OK;
 }
 
-// the flag and the counters travel to pinned memory behind the sweeps; looked at in slic_sweeps_settle, after a synchronisation that
-// somebody else needs anyway (the connectivity stage's read-back): no round trip of their own
-static int defer_counters(obia_ctx *ctx, const unsigned long long *d_px) {
+// Runs queue_sweeps and sends the flag and the counters to pinned memory behind the sweeps; looked at in slic_sweeps_settle, after a
+// synchronisation that somebody else needs anyway (the connectivity stage's read-back): no round trip of their own
+static int run_sweeps(obia_ctx *ctx, SlicBatch &b, bool repeat) {
+    ctx->defer_pending = false;   // (also when this call fails: a settle after it finds nothing to look at)
+    unsigned long long *d_px = nullptr;
+    ctx->defer_shared_px = 0.0;   // (a repeat stores labels in every sweep: nothing is shared)
+    OBIA_TRY(queue_sweeps(ctx, b, repeat, &d_px, &ctx->defer_shared_px));
+    if (!d_px) return OBIA_OK;
     if (!ctx->defer_buf) OBIA_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->defer_buf), sizeof(unsigned long long) * 513, hipHostMallocDefault));
     OBIA_HIP_TRY(hipMemcpyAsync(ctx->defer_buf, d_px, sizeof(unsigned long long) * 513, hipMemcpyDeviceToHost, ctx->stream));
     ctx->timing.readbacks += 1;
@@ -2075,13 +1856,7 @@ static int defer_counters(obia_ctx *ctx, const unsigned long long *d_px) {
     return OBIA_OK;
 }
 
-int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b) {
-    ctx->defer_pending = false;   // (also when this call fails: a settle after it finds nothing to look at)
-    unsigned long long *d_px = nullptr;
-    ctx->defer_shared_px = 0.0;
-    OBIA_TRY(queue_sweeps(ctx, b, false, &d_px, &ctx->defer_shared_px));
-    return d_px ? defer_counters(ctx, d_px) : OBIA_OK;
-}
+int slic_run_sweeps(obia_ctx *ctx, SlicBatch &b) { return run_sweeps(ctx, b, false); }
 
 // (see slic.hpp) the stream has been synchronised since slic_run_sweeps / slic_rerun_storing returned.  repeat == null: behind a
 // repeat, whose sweeps all store their labels -- only the counters are of interest
@@ -2097,11 +1872,7 @@ int slic_sweeps_settle(obia_ctx *ctx, bool *repeat) {
 
 int slic_rerun_storing(obia_ctx *ctx, SlicBatch &b) {
     ctx->timing.batch_repeats += 1;
-    ctx->defer_pending = false;
-    unsigned long long *d_px = nullptr;
-    ctx->defer_shared_px = 0.0;   // (a repeat stores labels in every sweep: nothing is shared)
-    OBIA_TRY(queue_sweeps(ctx, b, true, &d_px, &ctx->defer_shared_px));
-    return d_px ? defer_counters(ctx, d_px) : OBIA_OK;
+    return run_sweeps(ctx, b, true);
 }
 
 }  // namespace obia
