@@ -9,5 +9,7 @@ from .seeds import make_chm_seeds, make_density_seeds, make_canonical_seeds  # n
 from .classify import classify, ClassifiedImage, Forest, standard_scale, forest_predict, acceptable_mask  # noqa: F401
 from .classify import MLP, mlp_predict, predict_segments, forest_shap  # noqa: F401
 from .classify import mlp_shap, mlp_coalition_values, shapley_combine  # noqa: F401
+from . import training  # noqa: F401
+from .training import tile_and_process, process_tile, TrainingTiles, gaussian_blur_u8, chamfer_distance  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
-"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h and include/obia_sharpness.h; the test suite's
-own entry points: include/obia_testing.h).
+"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
+include/obia_training.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -166,7 +166,18 @@ _SHARPNESS_SIGNATURES = {
     "obia_sharp_variance_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_sharp_stretch_f32_dev": (_I, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
 }
-# include/obia_testing.h: internal pieces driven directly by the test suite, a fourth table (tests/test_gpu_clear_ranges.py)
+# include/obia_training.h: the training-tile passes, a fourth table (tests/test_training_restatement_cpu.py and
+# tests/test_gpu_training.py pin it; the three above stay as they are)
+TRAIN_MAX_KSIZE = 31      # OBIA_TRAIN_MAX_KSIZE
+TRAIN_MAX_SIDE = 4096     # OBIA_TRAIN_MAX_SIDE
+TRAIN_MINMAX_WORK = 512   # OBIA_TRAIN_MINMAX_WORK: floats of the min-max pass's work buffer
+_TRAINING_SIGNATURES = {
+    "obia_train_blur_u8_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "obia_train_distance_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "obia_train_compose_u8_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, ctypes.c_double, _P, _P]),
+    "obia_train_minmax_u8_dev": (_I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
+}
+# include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
     # the plan of a batch's sweeps as text: pure host code, no context (tests/test_sweep_plan_cpu.py)
@@ -193,7 +204,8 @@ def load():
             raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items()) + list(_TEST_SIGNATURES.items()):
+        for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
+                                   + list(_TRAINING_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:
