@@ -5,6 +5,8 @@
     Segments.polygons()      -> polygons in map coordinates                   (create_segments back half, :59-77)
     create_tiled_segments()  -> the same for a raster that is processed in tiles (obia.utils.tiling, :62-291)
     slic_edge(), label_segments() -> the consumers of the label raster       (utils/cost.py:44-48, utils/utils.py:12-34)
+    make_chm_seeds() ... grow_crowns() -> seeds, cost surface, one crown per canonical cluster (utils/seeds.py, utils/cost.py; the
+                                crowns are this package's own: the reference has no consumer of the two)
     classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
@@ -23,6 +25,8 @@ from obia_amd.consumers import slic_edge, label_segments           # noqa: E402
 from obia_amd.polygons import polygonize                           # noqa: E402
 from obia_amd.cost import rasterise_slic_gpkg                      # noqa: E402
 from obia_amd.classify import classify                             # noqa: E402
+from obia_amd.cost import chm_gradient                             # noqa: E402
+from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, grow_crowns   # noqa: E402
 
 
 class Image:
@@ -72,7 +76,24 @@ def main():
     print(f"slic_edge(): {100 * float(edges.mean()):.1f} % edge pixels; label_segments(): {labelled}, mixed {mixed}")
     assert len(polygonize(labels, start_label=1)) == n
 
-    # 5. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
+    # 5. crowns: tree tops of a canopy height model and of a point density, the cost surface, the cost-aware merge of the seeds, and
+    #    then every canopy pixel to the cluster it is cheapest to reach.  Crown ids are 1..N; the raster goes where `labels` went.
+    chm = np.zeros((H, W))
+    for cy in range(12, H, 24):
+        for cx in range(12, W, 24):
+            chm = np.maximum(chm, rs.uniform(6, 20) * np.exp(-((yy - cy - rs.uniform(-4, 4)) ** 2 + (xx - cx - rs.uniform(-4, 4)) ** 2)
+                                                               / (2 * rs.uniform(3, 6) ** 2)))
+    chm = chm.astype(np.float32)
+    chm_seeds = make_chm_seeds(chm, affine_transformation=image.affine_transformation)
+    den_seeds = make_density_seeds(1.5 * chm, affine_transformation=image.affine_transformation)
+    cost = chm_gradient(chm).astype(np.float32)                              # one layer of make_cost_surface; the whole surface works alike
+    seeds = make_canonical_seeds(chm_seeds, den_seeds, cost, cost_affine=image.affine_transformation, debug_dist=False)
+    crowns = grow_crowns(cost, seeds, mask=chm > 2.0, cost_affine=image.affine_transformation, max_dist=10.0)      # at most 10 m from a seed
+    crown_table = create_objects(crowns, image, calculate_textural=False, geometry=False)
+    print(f"grow_crowns(): {len(seeds['x'])} seeds in {int(crowns.max())} crowns over {100 * float((crowns > 0).mean()):.0f} % of the raster; "
+          f"{len(polygonize(crowns, image.affine_transformation, start_label=1))} polygons, objects table {crown_table.shape}")
+
+    # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:
         import sklearn  # noqa: F401
     except ImportError:

@@ -11,5 +11,7 @@ from .classify import MLP, mlp_predict, predict_segments, forest_shap  # noqa: F
 from .classify import mlp_shap, mlp_coalition_values, shapley_combine  # noqa: F401
 from . import training  # noqa: F401
 from .training import tile_and_process, process_tile, TrainingTiles, gaussian_blur_u8, chamfer_distance  # noqa: F401
+from . import crowns  # noqa: F401
+from .crowns import cost_allocation, grow_crowns  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h and include/obia_crowns.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("OBIA_HIP_LIB") or os.path.join(_CSRC, "libobia_hip.so
 OBIA_OK = 0
 MASK_SEEDS_CHUNK = 1024   # OBIA_MASK_SEEDS_CHUNK (include/obia_hip.h): centroids the seeding kernels stage in LDS at a time
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_EMPTY, E_NONFINITE = -1, -2, -3, -4, -5, -6
+E_INTERNAL = -7           # OBIA_E_INTERNAL (include/obia_crowns.h): a proven bound was exceeded; check() raises RuntimeError
 
 
 class SlicParams(ctypes.Structure):
@@ -177,6 +178,14 @@ _TRAINING_SIGNATURES = {
     "obia_train_compose_u8_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, ctypes.c_double, _P, _P]),
     "obia_train_minmax_u8_dev": (_I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
 }
+# include/obia_crowns.h: crowns from seeds, a fifth table (tests/test_crowns_restatement_cpu.py and tests/test_gpu_crowns.py pin it; the
+# four above stay as they are)
+CROWNS_TILE = 32          # OBIA_CROWNS_TILE: side of the tile one workgroup relaxes
+_D = ctypes.c_double
+_CROWNS_SIGNATURES = {
+    "obia_crowns_allocate_dev": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _D, _D, _D, _D, _I, _D, _P, _P, _P]),
+    "obia_crowns_last_work": (_I, [_P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -205,7 +214,8 @@ def load():
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
-                                   + list(_TRAINING_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
+                                   + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items())
+                                   + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:
