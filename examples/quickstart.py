@@ -26,7 +26,7 @@ from obia_amd.polygons import polygonize                           # noqa: E402
 from obia_amd.cost import rasterise_slic_gpkg                      # noqa: E402
 from obia_amd.classify import classify                             # noqa: E402
 from obia_amd.cost import chm_gradient                             # noqa: E402
-from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, grow_crowns   # noqa: E402
+from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, canonical_seeds, grow_crowns   # noqa: E402
 
 
 class Image:
@@ -92,6 +92,12 @@ def main():
     crown_table = create_objects(crowns, image, calculate_textural=False, geometry=False)
     print(f"grow_crowns(): {len(seeds['x'])} seeds in {int(crowns.max())} crowns over {100 * float((crowns > 0).mean()):.0f} % of the raster; "
           f"{len(polygonize(crowns, image.affine_transformation, start_label=1))} polygons, objects table {crown_table.shape}")
+    # the table options make_canonical_seeds refuses: a cluster whose heights spread more than 3 m is split at its median, and a seed
+    # within 1.5 m of a later (lower) one of its cluster is dropped
+    split = canonical_seeds(chm_seeds, den_seeds, cost, cost_affine=image.affine_transformation, debug_dist=False, dz_merge=3.0, nms_base=1.5)
+    more = grow_crowns(cost, split, mask=chm > 2.0, cost_affine=image.affine_transformation, max_dist=10.0)
+    print(f"canonical_seeds(dz_merge=3, nms_base=1.5): {len(split['x'])} seeds in {len(np.unique(split['cluster']))} clusters, "
+          f"{int(more.max())} crowns")
 
     # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:

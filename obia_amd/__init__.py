@@ -6,6 +6,8 @@ from .polygons import polygonize, rasterize, PolygonTable  # noqa: F401
 from .cost import rasterise_slic_gpkg  # noqa: F401
 from .geopackage import write_geopackage, read_geopackage  # noqa: F401
 from .seeds import make_chm_seeds, make_density_seeds, make_canonical_seeds  # noqa: F401
+from .seeds import canonical_seeds, sample_heights, stage1_clusters, stage1_rounds, reduce_stage1  # noqa: F401
+from .seeds import split_clusters_by_height, trim_clusters, nms_per_crown  # noqa: F401
 from .classify import classify, ClassifiedImage, Forest, standard_scale, forest_predict, acceptable_mask  # noqa: F401
 from .classify import MLP, mlp_predict, predict_segments, forest_shap  # noqa: F401
 from .classify import mlp_shap, mlp_coalition_values, shapley_combine  # noqa: F401

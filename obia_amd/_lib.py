@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h and include/obia_crowns.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h and include/obia_seed_table.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -186,6 +186,18 @@ _CROWNS_SIGNATURES = {
     "obia_crowns_allocate_dev": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _D, _D, _D, _D, _I, _D, _P, _P, _P]),
     "obia_crowns_last_work": (_I, [_P, _P]),
 }
+# include/obia_seed_table.h: the table options of the canonical seeds, a sixth table (tests/test_seed_table_host.py and
+# tests/test_gpu_seed_table.py pin it; the five above stay as they are)
+_L = ctypes.c_int64
+_F = ctypes.c_float
+_SEED_TABLE_SIGNATURES = {
+    "obia_seedtab_cells_dev": (_I, [_P, _P, _P, _L, _D, _P, _P]),
+    "obia_seedtab_sample_dev": (_I, [_P, _P, _P, _L, _P, _I, _I, _P, _P, _P]),
+    "obia_seedtab_stage1_dev": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _F, _F, _F, _F, _I, _P, _P, _P]),
+    "obia_seedtab_last_work": (_I, [_P, _P]),
+    "obia_seedtab_segments_dev": (_I, [_P, _P, _P, _L, _F, _P, _P, _P]),
+    "obia_seedtab_nms_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _D, _D, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -214,7 +226,7 @@ def load():
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
-                                   + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items())
+                                   + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
                                    + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
