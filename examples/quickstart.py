@@ -7,6 +7,7 @@
     slic_edge(), label_segments() -> the consumers of the label raster       (utils/cost.py:44-48, utils/utils.py:12-34)
     make_chm_seeds() ... grow_crowns() -> seeds, cost surface, one crown per canonical cluster (utils/seeds.py, utils/cost.py; the
                                 crowns are this package's own: the reference has no consumer of the two)
+    box_nms(), assign_boxes(), dissolve_by_box() -> superpixels joined with tree boxes (notebooks/deepfor2.ipynb, assign_fid)
     classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
@@ -27,6 +28,7 @@ from obia_amd.cost import rasterise_slic_gpkg                      # noqa: E402
 from obia_amd.classify import classify                             # noqa: E402
 from obia_amd.cost import chm_gradient                             # noqa: E402
 from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, canonical_seeds, grow_crowns   # noqa: E402
+from obia_amd import box_nms, assign_boxes, dissolve_by_box        # noqa: E402
 
 
 class Image:
@@ -98,6 +100,16 @@ def main():
     more = grow_crowns(cost, split, mask=chm > 2.0, cost_affine=image.affine_transformation, max_dist=10.0)
     print(f"canonical_seeds(dz_merge=3, nms_base=1.5): {len(split['x'])} seeds in {len(np.unique(split['cluster']))} clusters, "
           f"{int(more.max())} crowns")
+
+    # 5b. the other way to crowns, the reference author's: tree boxes (here 6 m squares around the tree tops, in place of a detector's
+    #     predictions), the copies suppressed, every superpixel to the box it shares the most area with, one crown per box
+    sx, sy = np.asarray(chm_seeds["x"]), np.asarray(chm_seeds["y"])
+    tree_boxes = np.stack([sx - 3.0, sy - 3.0, sx + 3.0, sy + 3.0], 1)                 # map bounds (minx, miny, maxx, maxy)
+    _, kept = box_nms(tree_boxes, np.asarray(chm_seeds["ch_max"]), 0.15)
+    fid = assign_boxes(labels, image.affine_transformation, tree_boxes[kept], n_labels=n)
+    box_crowns = dissolve_by_box(labels, fid.assigned)
+    print(f"assign_boxes(): {len(kept)} of {len(tree_boxes)} boxes after box_nms, {int((fid.assigned >= 0).sum())} of {n} segments in a box, "
+          f"{len(polygonize(box_crowns, image.affine_transformation, start_label=1))} crowns")
 
     # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:

@@ -15,5 +15,8 @@ from . import training  # noqa: F401
 from .training import tile_and_process, process_tile, TrainingTiles, gaussian_blur_u8, chamfer_distance  # noqa: F401
 from . import crowns  # noqa: F401
 from .crowns import cost_allocation, grow_crowns  # noqa: F401
+from . import boxes  # noqa: F401
+from .boxes import box_overlaps, assign_boxes, dissolve_by_box, box_iou, box_nms, BoxAssignment, BoxTable  # noqa: F401
+from .boxes import predictions_to_map, save_predictions_to_gpkg, mosaic_predictions  # noqa: F401
 
 __version__ = "0.1.0"

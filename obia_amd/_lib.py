@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h and include/obia_seed_table.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h and include/obia_boxes.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -198,6 +198,18 @@ _SEED_TABLE_SIGNATURES = {
     "obia_seedtab_segments_dev": (_I, [_P, _P, _P, _L, _F, _P, _P, _P]),
     "obia_seedtab_nms_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _D, _D, _P]),
 }
+# include/obia_boxes.h: segments and detection boxes, a seventh table (tests/test_boxes_restatement_cpu.py, tests/test_gpu_boxes.py and
+# tests/test_gpu_boxes_buffers.py pin it; the six above stay as they are)
+BOXES_TABLE = 256         # OBIA_BOXES_TABLE: labels of the LDS table one workgroup counts a box's footprint into
+_I32 = ctypes.c_int32
+_BOXES_SIGNATURES = {
+    "obia_boxes_assign_dev": (_I, [_P, _P, _I, _I, _P, _L, _I32, _P, _P]),
+    "obia_boxes_pair_count_dev": (_I, [_P, _P, _I, _I, _P, _L, _I32, _P, _P]),
+    "obia_boxes_pair_write_dev": (_I, [_P, _P, _I, _I, _P, _L, _I32, _P, _P, _L, _P, _P, _P, _P]),
+    "obia_boxes_dissolve_dev": (_I, [_P, _P, _L, _P, _I32, _P]),
+    "obia_boxes_iou_dev": (_I, [_P, _P, _L, _P, _L, _P]),
+    "obia_boxes_nms_dev": (_I, [_P, _P, _P, _P, _P, _L, _L, _D, _P, ctypes.POINTER(_I32)]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -227,7 +239,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
-                                   + list(_TEST_SIGNATURES.items())):
+                                   + list(_BOXES_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -8,6 +8,7 @@
 // floating-point value, and two runs agree bit for bit.  Nothing is exchanged between workgroups inside a launch: a round of stage 1
 // reads the states the round before it wrote and writes its own into a second buffer.
 #include "common.hpp"
+#include "grid_cells.hpp"
 #include "../../include/obia_seed_table.h"
 
 #include <climits>
@@ -22,20 +23,6 @@ enum : unsigned char { ST_UNDECIDED = 0, ST_FIRED = 1, ST_NOT = 2 };
 __device__ __forceinline__ bool in_ball(double xi, double yi, double xj, double yj, double r) {
     const double dx = xi - xj, dy = yi - yj;
     return dx * dx + dy * dy <= r * r;
-}
-
-// f(q) for every q in the 3 x 3 cells around the cell `key`: per grid row at most 32 steps of a binary search and a run of < n rows
-template <typename F> __device__ __forceinline__ void for_cells(const long long *__restrict__ skey, int n, long long key, long long ncx,
-                                                                F &&f) {
-    for (int dy = -1; dy <= 1; ++dy) {
-        const long long k0 = key + dy * ncx - 1, k1 = k0 + 2;
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (skey[mid] < k0) lo = mid + 1; else hi = mid;
-        }
-        for (int q = lo; q < n && skey[q] <= k1; ++q) f(q);
-    }
 }
 
 __global__ __launch_bounds__(256) void seedtab_cells_kernel(const double *__restrict__ xs, const double *__restrict__ ys, int n, double side,
