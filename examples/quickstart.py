@@ -8,6 +8,7 @@
     make_chm_seeds() ... grow_crowns() -> seeds, cost surface, one crown per canonical cluster (utils/seeds.py, utils/cost.py; the
                                 crowns are this package's own: the reference has no consumer of the two)
     box_nms(), assign_boxes(), dissolve_by_box() -> superpixels joined with tree boxes (notebooks/deepfor2.ipynb, assign_fid)
+    points_to_rasters(), create_objects(pointcloud=) -> CHM and density from points, the point-cloud columns (segment_statistics.py:332-389)
     classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
@@ -29,6 +30,7 @@ from obia_amd.classify import classify                             # noqa: E402
 from obia_amd.cost import chm_gradient                             # noqa: E402
 from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, canonical_seeds, grow_crowns   # noqa: E402
 from obia_amd import box_nms, assign_boxes, dissolve_by_box        # noqa: E402
+from obia_amd import points_to_rasters                             # noqa: E402
 
 
 class Image:
@@ -110,6 +112,21 @@ def main():
     box_crowns = dissolve_by_box(labels, fid.assigned)
     print(f"assign_boxes(): {len(kept)} of {len(tree_boxes)} boxes after box_nms, {int((fid.assigned >= 0).sum())} of {n} segments in a box, "
           f"{len(polygonize(box_crowns, image.affine_transformation, start_label=1))} crowns")
+
+    # 5c. the LiDAR leg: a synthetic cloud (ten returns per square metre under the canopy surface above) -> the CHM and the density
+    #     raster the seeds start from, and the five point-cloud columns of the objects table, one height profile per crown
+    n_pts = 10 * (H // 2) * (W // 2)
+    pc, pr = rs.uniform(0, W, n_pts), rs.uniform(0, H, n_pts)
+    cloud = {"X": 300000.0 + 0.5 * pc, "Y": 2200000.0 - 0.5 * pr,
+             "HeightAboveGround": (chm[pr.astype(int), pc.astype(int)] * rs.beta(2.0, 1.0, n_pts)).astype(np.float32),
+             "Intensity": rs.randint(0, 4096, n_pts).astype(np.uint16)}
+    rasters = points_to_rasters(cloud, image.affine_transformation, (H, W))
+    lidar_seeds = make_chm_seeds(rasters["chm"], affine_transformation=image.affine_transformation)
+    lidar_table = create_objects(crowns, image, voxel_resolution=(0.5, 0.5, 0.5), calculate_textural=False, calculate_structural=True,
+                                 calculate_radiometric=True, pointcloud=cloud, geometry=False)
+    print(f"points_to_rasters(): {n_pts} points, {int(np.isfinite(rasters['chm']).sum())} CHM pixels, {len(lidar_seeds['id'])} tree tops; "
+          f"create_objects(pointcloud=): median ch {float(lidar_table['ch'].median()):.1f} m, pai {float(lidar_table['pai'].median()):.2f}, "
+          f"fhd {float(lidar_table['fhd'].median()):.2f}, mean intensity {float(lidar_table['mean_intensity'].median()):.0f}")
 
     # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:

@@ -18,5 +18,7 @@ from .crowns import cost_allocation, grow_crowns  # noqa: F401
 from . import boxes  # noqa: F401
 from .boxes import box_overlaps, assign_boxes, dissolve_by_box, box_iou, box_nms, BoxAssignment, BoxTable  # noqa: F401
 from .boxes import predictions_to_map, save_predictions_to_gpkg, mosaic_predictions  # noqa: F401
+from . import pointcloud  # noqa: F401
+from .pointcloud import as_points, PointRasters, points_to_rasters, SegmentPoints, segment_point_stats  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h and include/obia_boxes.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h and include/obia_points.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -210,6 +210,16 @@ _BOXES_SIGNATURES = {
     "obia_boxes_iou_dev": (_I, [_P, _P, _L, _P, _L, _P]),
     "obia_boxes_nms_dev": (_I, [_P, _P, _P, _P, _P, _L, _L, _D, _P, ctypes.POINTER(_I32)]),
 }
+# include/obia_points.h: point clouds, an eighth table (tests/test_pointcloud_restatement_cpu.py, tests/test_gpu_pointcloud.py and
+# tests/test_gpu_pointcloud_buffers.py pin it; the seven above stay as they are)
+POINTS_MAX_NZ = 4096      # OBIA_POINTS_MAX_NZ: height bins of a segment's profile
+POINTS_CHUNK = 2048       # OBIA_POINTS_CHUNK: consecutive points one workgroup sums in LDS before it touches global memory
+_POINTS_SIGNATURES = {
+    "obia_points_rasters_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _I, _I, _P, _P]),
+    "obia_points_rasters_finish_dev": (_I, [_P, _P, _P, _I, _I, _D, _P, _P]),
+    "obia_points_segments_dev": (_I, [_P, _P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P]),
+    "obia_points_segment_columns_dev": (_I, [_P, _P, _P, _P, _P, _P, _I32, _I32, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -239,7 +249,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
-                                   + list(_BOXES_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
+                                   + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

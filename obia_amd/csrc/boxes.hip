@@ -265,18 +265,6 @@ __global__ __launch_bounds__(256) void boxes_nms_keep_kernel(const uint8_t *__re
     if (k < n) keep_out[k] = state[k] == ST_KEPT ? 1 : 0;
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// one of the first n_out buffers, the outputs, starts where another output or an input starts (null pointers are not compared)
-template <typename... P> bool shared_start(int n_out, P... ps) {
-    const void *v[] = {static_cast<const void *>(ps)...};
-    const int m = (int)sizeof...(ps);
-    for (int i = 0; i < n_out; ++i)
-        for (int j = i + 1; j < m; ++j)
-            if (v[i] && v[i] == v[j]) return true;
-    return false;
-}
-
 int bad_buffers(const char *what) {
     set_error("boxes: %s: bad arguments (null, misaligned or overlapping buffers)", what);
     return OBIA_E_INVALID;

@@ -190,6 +190,19 @@ static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b)
 // Grid of a grid-stride kernel over n elements in workgroups of 256: one workgroup per 256 elements, 8192 at the most, one at the least.
 static inline unsigned flat_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(cdiv(n, 256), 8192)); }
 
+// Argument checks shared by the entry points whose buffers need only the alignment of their element type (seed_table.hip, boxes.hip,
+// points.hip).  A null pointer is aligned, and is not compared.
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+// one of the first n_out buffers, the outputs, starts where another output or an input starts
+template <typename... P> bool shared_start(int n_out, P... ps) {
+    const void *v[] = {static_cast<const void *>(ps)...};
+    const int m = (int)sizeof...(ps);
+    for (int i = 0; i < n_out; ++i)
+        for (int j = i + 1; j < m; ++j)
+            if (v[i] && v[i] == v[j]) return true;
+    return false;
+}
+
 // ---- the entry layer: what every extern "C" function is made of besides its own argument checks and its body ----------------------
 
 // Prologue, the first statement of every entry point that takes a context (the tiler's go through their session's): refuses a null
@@ -249,6 +262,16 @@ typedef float obia_v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_stream_f4(const void *p) {
     const obia_v4f t = __builtin_nontemporal_load(reinterpret_cast<const obia_v4f *>(p));
     return make_float4(t.x, t.y, t.z, t.w);
+}
+// Order-preserving key of a float32 (zonal.hip, points.hip): unsigned order of the keys is numeric order of the floats, so an integer
+// atomicMin / atomicMax on the key is a minimum / maximum of the value.  No finite float has the key 0.
+__device__ __forceinline__ unsigned zkey(float f) {
+    unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float zunkey(unsigned k) {
+    unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    return __uint_as_float(b);
 }
 #endif
 

@@ -174,8 +174,6 @@ __global__ __launch_bounds__(256) void seedtab_nms_kernel(const double *__restri
 
 thread_local int64_t last_work[2] = {0, 0};
 
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 // the checks every entry point shares; what == the operator's name in the message
 int check_n(const char *what, int64_t n) {
     if (n < 1 || n > (int64_t)INT_MAX) { set_error("seed table: %s: n must be in 1 .. 2^31 - 1, got %lld", what, (long long)n); return OBIA_E_INVALID; }

@@ -62,14 +62,7 @@ template <> __device__ __forceinline__ void ld_raster<3>(const float *p, float *
 __device__ __forceinline__ float zmin(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, -INFINITY); }
 __device__ __forceinline__ float zmax(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, INFINITY); }
 
-__device__ __forceinline__ unsigned zkey(float f) {
-    unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float zunkey(unsigned k) {
-    unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
+// zkey / zunkey, the order-preserving key of a float32 for integer atomicMin / atomicMax: common.hpp
 
 // One workgroup per ZTW x ZTH tile.  A lane owns FOUR bands of ONE pixel column: lane = (column, band quad), LPP = NBP / 4
 // lanes per pixel, so the 64 lanes of a wave read 64 consecutive 16-byte chunks of a raster row (one 1-KB request) and a

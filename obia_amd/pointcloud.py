@@ -1,0 +1,312 @@
+"""Point clouds on the GPU (include/obia_points.h): the LiDAR leg of both chains.
+
+``points_to_rasters`` / :class:`PointRasters` turn points into the canopy height model and the point-density raster that
+``make_chm_seeds``, ``make_density_seeds`` and ``make_cost_surface`` start from; ``segment_point_stats`` / :class:`SegmentPoints` join
+points to the segments of a label raster and form the five point-cloud columns of the objects table (``pai``, ``fhd``, ``ch``,
+``mean_intensity``, ``variance_intensity``), which ``create_objects(..., pointcloud=...)`` fills with them.
+
+The radiometric pair is the reference's (segment_statistics.py:332-389: ``np.mean`` / ``np.var`` of ``Intensity``).  Its structural
+code is gone (:326-329 raises), so the structural columns are this project's definitions: one vertical profile per segment -- the
+segment footprint is the voxel column -- in bins of ``dz``.  Heights are heights above ground as given; reading EPT / LAZ, deriving
+them from raw ``Z``, float intensities and return-number weighting are out of scope.
+
+Both accumulators keep their state on the device and take a cloud in any number of ``add`` calls: every sum is an integer, so the
+result is the same bits for every order and every cut.  NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out; there is no
+CPU path."""
+import collections
+import ctypes
+import math
+
+import numpy as np
+
+from . import _device, _lib
+from .consumers import invert_affine
+from .statistics import _n_labels
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+Points = collections.namedtuple("Points", "x y z intensity is_torch")
+COLUMNS = ("n_points", "ch", "pai", "fhd", "mean_intensity", "variance_intensity")
+COUNTERS = ("outside", "unlabelled", "out_of_range", "in_profile")
+U32_MAX = 2 ** 32 - 1
+
+
+def _need_torch():
+    _device.need_torch("obia_amd.pointcloud")
+
+
+def _field(pc, name):
+    if isinstance(pc, dict):
+        return pc.get(name)
+    names = getattr(getattr(pc, "dtype", None), "names", None)
+    if names is None:
+        raise TypeError("a point cloud is a structured NumPy array or a dict of arrays with X, Y, HeightAboveGround (or Z) and "
+                        "optionally Intensity")
+    return pc[name] if name in names else None
+
+
+def as_points(pointcloud):
+    """The arrays of a point cloud: ``Points(x, y, z, intensity, is_torch)``.
+
+    Accepts the reference's two forms (segment_statistics.py:361-369) -- a structured NumPy array, or a dict -- with the fields
+    ``X``, ``Y``, ``HeightAboveGround`` (``Z`` when that is absent) and optionally ``Intensity``; a dict of CUDA tensors; and a
+    pyforestscan-style list whose first element is such an array.  ``Intensity`` must be uint8 or uint16 (``TypeError`` otherwise:
+    float intensities are out of scope).  Touches no device."""
+    if isinstance(pointcloud, Points):
+        return pointcloud
+    if isinstance(pointcloud, (list, tuple)):
+        if not pointcloud:
+            raise ValueError("the point cloud list is empty")
+        pointcloud = pointcloud[0]
+    x, y = _field(pointcloud, "X"), _field(pointcloud, "Y")
+    z = _field(pointcloud, "HeightAboveGround")
+    if z is None:
+        z = _field(pointcloud, "Z")
+    if x is None or y is None or z is None:
+        raise ValueError("a point cloud needs the fields X, Y and HeightAboveGround (or Z)")
+    inten = _field(pointcloud, "Intensity")
+    is_t = any(_device.is_torch(v) for v in (x, y, z, inten))
+    if is_t and not all(_device.is_torch(v) for v in (x, y, z, inten) if v is not None):
+        raise ValueError("the fields of a point cloud must be all tensors or all arrays")
+    if not is_t:
+        x, y, z = np.asarray(x), np.asarray(y), np.asarray(z)
+        inten = None if inten is None else np.asarray(inten)
+    n = tuple(x.shape)
+    if len(n) != 1 or any(tuple(v.shape) != n for v in (y, z, inten) if v is not None):
+        raise ValueError("the fields of a point cloud must be one-dimensional and of one length")
+    if inten is not None:
+        ok = (torch.uint8, torch.uint16) if is_t else (np.dtype(np.uint8), np.dtype(np.uint16))
+        if inten.dtype not in ok:
+            raise TypeError(f"Intensity must be uint8 or uint16, got {inten.dtype} (float intensities are out of scope)")
+    return Points(x, y, z, inten, is_t)
+
+
+def _device_points(p, dev):
+    """x, y float64, z float32 and the intensity as the bits of uint16 (an int16 tensor) on the device"""
+    x, y = _device.as_dev(p.x, torch.float64, dev), _device.as_dev(p.y, torch.float64, dev)
+    z = _device.as_dev(p.z, torch.float32, dev)
+    inten = None
+    if p.intensity is not None:
+        if p.is_torch:
+            t = p.intensity.to(device=f"cuda:{dev}").contiguous()
+            inten = t.view(torch.int16) if t.dtype == torch.uint16 else t.to(torch.int16)
+        else:
+            inten = torch.as_tensor(np.ascontiguousarray(p.intensity.astype(np.uint16, copy=False)).view(np.int16), device=f"cuda:{dev}")
+    return x, y, z, inten
+
+
+def _forward(affine_transformation):
+    if affine_transformation is None or len(affine_transformation) != 6:
+        raise ValueError("affine_transformation must hold six values [a, b, d, e, xoff, yoff]")
+    t = [float(v) for v in affine_transformation]
+    inv = invert_affine(t)                                      # ValueError when singular
+    return t, (ctypes.c_double * 6)(*inv)
+
+
+def _raster_shape(shape):
+    s = tuple(int(v) for v in shape)
+    if len(s) != 2 or s[0] < 1 or s[1] < 1 or s[0] >= 2 ** 31 or s[1] >= 2 ** 31:
+        raise ValueError(f"shape must be (H, W) with 1 <= H, W < 2^31, got {tuple(shape)}")
+    return s
+
+
+class _Accumulator:
+    """the host-side running total that keeps every uint32 count of the state from wrapping"""
+    total = 0
+
+    def _admit(self, n):
+        if n >= 2 ** 31:
+            raise NotImplementedError("one add takes fewer than 2^31 points: cut the cloud")
+        if self.total + n > U32_MAX:
+            raise OverflowError(f"{self.total} + {n} points could carry a uint32 count past 2^32 - 1")
+
+    def _device_cloud(self, points):
+        p = as_points(points)
+        if p.is_torch:
+            _device.device_of(None, p.x, p.y, p.z, p.intensity)          # refuses CPU tensors
+        self._admit(int(p.x.shape[0]))
+        self._tensor_in = self._tensor_in or p.is_torch
+        return p, int(p.x.shape[0])
+
+
+class PointRasters(_Accumulator):
+    """Canopy height model and point density of a cloud on the grid of a raster: ``add`` points in any number of calls, then
+    ``result``.  ``shape`` = (H, W), ``affine_transformation`` = [a, b, d, e, xoff, yoff] of the raster (any affine map)."""
+
+    def __init__(self, shape, affine_transformation, ctx=None):
+        _need_torch()
+        self.shape = _raster_shape(shape)
+        t, self._inv = _forward(affine_transformation)
+        self.pixel_area = abs(t[0] * t[3] - t[1] * t[2])
+        self.ctx = ctx
+        self.dev = _device.device_of(ctx)
+        self._tensor_in = False
+        self._zkey = self._count = None
+
+    def add(self, points):
+        p, n = self._device_cloud(points)
+        if self._zkey is None and p.is_torch and self.ctx is None:
+            self.dev = _device.device_of(None, p.x)
+        self._planes()
+        x, y, z, _ = _device_points(p._replace(intensity=None), self.dev)
+        lib, c = _device.begin(self.dev, self.ctx)
+        _lib.check(lib.obia_points_rasters_dev(c.handle, x.data_ptr(), y.data_ptr(), z.data_ptr(), n, self._inv, self.shape[0], self.shape[1],
+                                               self._zkey.data_ptr(), self._count.data_ptr()))
+        self.total += n
+        return self
+
+    def _planes(self):
+        if self._zkey is None:
+            self._zkey = torch.zeros(self.shape, dtype=torch.int32, device=f"cuda:{self.dev}")
+            self._count = torch.zeros(self.shape, dtype=torch.int32, device=f"cuda:{self.dev}")
+        return self._zkey, self._count
+
+    def state(self, as_array=False):
+        """the raw state: ``zkey`` and ``count`` (H, W) as int64 values of the uint32 planes"""
+        zk, count = self._planes()
+        return _device.out({"zkey": _u32(zk), "count": _u32(count)}, as_array or self._tensor_in)
+
+    def result(self, as_array=False):
+        """``{"chm", "density", "count"}``: (H, W) float32, float32 and int64.  ``chm`` is the highest finite height of a pixel's
+        points, NaN where there is none; ``density`` = count / pixel area; ``count`` every point of the pixel.  NumPy unless a
+        tensor was added; ``as_array=True`` leaves CUDA tensors whatever came in."""
+        zk, count = self._planes()
+        chm = torch.empty(self.shape, dtype=torch.float32, device=zk.device)
+        density = torch.empty_like(chm)
+        lib, c = _device.begin(self.dev, self.ctx)
+        _lib.check(lib.obia_points_rasters_finish_dev(c.handle, self._zkey.data_ptr(), self._count.data_ptr(), self.shape[0], self.shape[1],
+                                                      self.pixel_area, chm.data_ptr(), density.data_ptr()))
+        count = _u32(self._count)
+        return _device.out({"chm": chm, "density": density, "count": count}, as_array or self._tensor_in)
+
+
+def points_to_rasters(points, affine_transformation, shape, as_array=False, ctx=None):
+    """One shot of :class:`PointRasters`: ``{"chm", "density", "count"}`` of a cloud on the (H, W) grid of ``affine_transformation``."""
+    return PointRasters(shape, affine_transformation, ctx=ctx).add(points).result(as_array=as_array)
+
+
+def _u32(t):
+    """a uint32 state array (kept as int32 bits) as int64 values"""
+    return t.to(torch.int64) & 0xFFFFFFFF
+
+
+class SegmentPoints(_Accumulator):
+    """Points joined to the segments of a label raster.  Row ``label - start_label`` of every result belongs to ``label``;
+    N = ``n_labels`` (default: the largest label - ``start_label`` + 1) as in ``zonal_stats``, so a row exists for a label that does
+    not occur.  The vertical profile of a segment has ``nz = floor(z_max / dz) + 1`` bins of ``dz``; a point enters it when its
+    height is finite, >= 0 and below ``nz * dz``."""
+
+    def __init__(self, labels, affine_transformation, dz, z_max, start_label=1, n_labels=None, ctx=None):
+        _need_torch()
+        dz, z_max = float(dz), float(z_max)
+        if not (math.isfinite(dz) and dz > 0.0):
+            raise ValueError(f"dz must be finite and positive, got {dz!r}")
+        if not (math.isfinite(z_max) and z_max >= 0.0):
+            raise ValueError(f"z_max must be finite and not negative, got {z_max!r}")
+        shape = tuple(labels.shape)
+        if len(shape) != 2 or 0 in shape:
+            raise ValueError(f"labels must be a non-empty (H, W) raster, got shape {shape}")
+        self.shape = _raster_shape(shape)
+        _, self._inv = _forward(affine_transformation)
+        nzf = math.floor(z_max / dz) + 1
+        if nzf > _lib.POINTS_MAX_NZ:
+            raise NotImplementedError(f"z_max / dz gives {nzf} height bins, more than {_lib.POINTS_MAX_NZ}")
+        self.dz, self.z_max, self.nz, self.start_label, self.ctx = dz, z_max, int(nzf), int(start_label), ctx
+        self._tensor_in = _device.is_torch(labels)
+        self.dev = _device.device_of(ctx, labels)
+        self._labels = _device.as_dev(labels, torch.int32, self.dev)
+        self.N = _n_labels(n_labels, self._labels, self.start_label)
+        self._rows = max(self.N, 1)                              # the state of a raster without rows is one unused row
+        if self._rows * self.nz >= 2 ** 31:
+            raise NotImplementedError(f"{self._rows} segments x {self.nz} height bins: the profile must have fewer than 2^31 cells")
+        d = self._labels.device
+        self._profile = torch.zeros((self._rows, self.nz), dtype=torch.int32, device=d)
+        self._top = torch.zeros(self._rows, dtype=torch.int32, device=d)
+        self._n_int = torch.zeros(self._rows, dtype=torch.int32, device=d)
+        self._s1 = torch.zeros(self._rows, dtype=torch.int64, device=d)
+        self._s2 = torch.zeros(self._rows, dtype=torch.int64, device=d)
+        self._counters = torch.zeros(4, dtype=torch.int64, device=d)
+        self.has_intensity = None
+
+    def add(self, points):
+        p, n = self._device_cloud(points)
+        if n and self.has_intensity is not None and self.has_intensity != (p.intensity is not None):
+            raise ValueError("every add of one accumulator comes with Intensity, or none does")
+        x, y, z, inten = _device_points(p, self.dev)
+        lib, c = _device.begin(self.dev, self.ctx)
+        H, W = self.shape
+        _lib.check(lib.obia_points_segments_dev(c.handle, x.data_ptr(), y.data_ptr(), z.data_ptr(), None if inten is None else inten.data_ptr(),
+                                                n, self._inv, self._labels.data_ptr(), H, W, self.start_label, self.N, self.nz, self.dz,
+                                                self._profile.data_ptr(), self._top.data_ptr(), self._n_int.data_ptr(), self._s1.data_ptr(),
+                                                self._s2.data_ptr(), self._counters.data_ptr()))
+        if n:
+            self.has_intensity = p.intensity is not None
+        self.total += n
+        return self
+
+    def _out(self, v, as_array=False):
+        return _device.out(v, as_array or self._tensor_in)
+
+    def profile(self, as_array=False):
+        """(N, nz) int64: the points of every segment per height bin"""
+        return self._out(_u32(self._profile[:self.N]), as_array)
+
+    def counters(self):
+        """dict of Python ints: points ``outside`` the raster, inside but ``unlabelled`` (no row), with a row but ``out_of_range``
+        (NaN, negative or above the profile) and ``in_profile``"""
+        return dict(zip(COUNTERS, (int(v) for v in self._counters.cpu().tolist())))
+
+    def state(self, as_array=False):
+        """the raw state: ``profile`` (N, nz), ``top``, ``n_int`` (N,) as int64 values of the uint32 arrays, ``s1``, ``s2`` (N,)
+        int64 bits of the uint64 sums, ``counters`` (4,) int64"""
+        N = self.N
+        return self._out({"profile": _u32(self._profile[:N]), "top": _u32(self._top[:N]), "n_int": _u32(self._n_int[:N]),
+                          "s1": self._s1[:N].clone(), "s2": self._s2[:N].clone(), "counters": self._counters.clone()}, as_array)
+
+    def columns(self, min_height=1.0, beer_lambert_constant=1.0, pad=False, as_array=False):
+        """The (N,) columns ``n_points`` (int64), ``ch``, ``pai``, ``fhd``, ``mean_intensity``, ``variance_intensity`` (float64) and,
+        with ``pad=True``, ``pad`` (N, nz): include/obia_points.h has every formula.  ``ch`` is the highest height of the profile;
+        ``pai`` = log(n_all / n_below) / k, the Beer-Lambert gap fraction of the canopy above ``min_height`` (NaN without a return
+        from below it); ``fhd`` the Shannon entropy of the profile above ``min_height``; the intensity pair is ``np.mean`` /
+        ``np.var`` over every point of the segment.  Rows without points are NaN."""
+        mh, k = float(min_height), float(beer_lambert_constant)
+        if not math.isfinite(mh):
+            raise ValueError(f"min_height must be finite, got {min_height!r}")
+        if not (math.isfinite(k) and k > 0.0):
+            raise ValueError(f"beer_lambert_constant must be finite and positive, got {beer_lambert_constant!r}")
+        d = self._labels.device
+        out = {"n_points": torch.empty(self._rows, dtype=torch.int64, device=d)}
+        for name in COLUMNS[1:]:
+            out[name] = torch.empty(self._rows, dtype=torch.float64, device=d)
+        if pad:
+            out["pad"] = torch.empty((self._rows, self.nz), dtype=torch.float64, device=d)
+        lib, c = _device.begin(self.dev, self.ctx)
+        if self.N:
+            _lib.check(lib.obia_points_segment_columns_dev(c.handle, self._profile.data_ptr(), self._top.data_ptr(), self._n_int.data_ptr(),
+                                                           self._s1.data_ptr(), self._s2.data_ptr(), self.N, self.nz, self.dz, mh, k,
+                                                           *(out[name].data_ptr() for name in COLUMNS), out["pad"].data_ptr() if pad else None))
+        return self._out({name: v[:self.N] for name, v in out.items()}, as_array)
+
+
+def segment_point_stats(points, labels, affine_transformation, dz, z_max=None, start_label=1, n_labels=None, min_height=1.0,
+                        beer_lambert_constant=1.0, pad=False, as_array=False, ctx=None):
+    """One shot of :class:`SegmentPoints`: the columns of :meth:`SegmentPoints.columns` plus ``profile`` (N, nz) and ``counters``.
+    ``z_max=None`` takes the largest finite height of the cloud (0 when there is none)."""
+    _need_torch()
+    p = as_points(points)
+    if z_max is None:
+        dev = _device.device_of(ctx, labels, p.x)
+        z = _device.as_dev(p.z, torch.float32, dev)
+        z = z[torch.isfinite(z)]
+        z_max = max(float(z.max()), 0.0) if z.numel() else 0.0
+    sp = SegmentPoints(labels, affine_transformation, dz, z_max, start_label=start_label, n_labels=n_labels, ctx=ctx)
+    if p.is_torch:
+        sp._tensor_in = True
+    sp.add(p)
+    res = sp.columns(min_height=min_height, beer_lambert_constant=beer_lambert_constant, pad=pad, as_array=as_array)
+    res["profile"] = sp.profile(as_array=as_array)
+    res["counters"] = sp.counters()
+    return res

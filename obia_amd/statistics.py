@@ -165,10 +165,16 @@ def create_objects(segments, image, ept=None, ept_srs=None, spectral_bands=None,
                    calc_mean=True, calc_variance=True, calc_min=True, calc_max=True, calc_skewness=True, calc_kurtosis=True,
                    calc_contrast=True, calc_dissimilarity=True, calc_homogeneity=True, calc_ASM=True, calc_energy=True,
                    calc_correlation=True, calc_pai=True, calc_fhd=True, calc_ch=True, calc_mean_intensity=True,
-                   calc_variance_intensity=True, *, start_label=1, geometry=True, ctx=None):
+                   calc_variance_intensity=True, *, start_label=1, pointcloud=None, geometry=True, ctx=None):
     """Mirror of obia create_objects (segment_statistics.py:392-511): same positional order, same defaults, same column
     set and order -- ``calculate_textural`` defaults to True, the five point-cloud columns are present and NaN (their flags
     default to True while the point-cloud workflow itself raises, :435-439), ``geometry`` comes last.
+
+    ``pointcloud``: what :func:`obia_amd.pointcloud.as_points` accepts (a structured array or a dict with ``X``, ``Y``,
+    ``HeightAboveGround`` and optionally ``Intensity``).  With it ``calculate_structural=True`` fills ``pai``, ``fhd`` and ``ch``
+    and ``calculate_radiometric=True`` fills ``mean_intensity`` and ``variance_intensity``, each where its ``calc_*`` flag is
+    set; it needs ``voxel_resolution`` (dx, dy, dz) -- only dz is used: the segment footprint is the voxel column -- and the
+    image's ``affine_transformation``.  Without it both flags raise as the reference does, and so does ``ept``.
 
     ``segments``: the label raster from create_segments (one 4-connected component per label, so "pixels inside polygon p"
     are "pixels carrying label p") or the table create_segments(as_table=True) returned.  ``image``: object
@@ -183,9 +189,18 @@ def create_objects(segments, image, ept=None, ept_srs=None, spectral_bands=None,
     if not (calculate_spectral or calculate_textural or calculate_structural or calculate_radiometric):
         raise ValueError("At least one of 'calculate_spectral', 'calculate_textural', 'calculate_structural', or "
                          "'calculate_radiometric' must be True.")
-    if ept is not None or calculate_structural or calculate_radiometric:
+    if ept is not None or ((calculate_structural or calculate_radiometric) and pointcloud is None):
         raise NotImplementedError("Point-cloud workflows are temporarily disabled. "
                                   "Use spectral/textural statistics only for now.")
+    if pointcloud is not None:
+        try:
+            voxel = [float(v) for v in voxel_resolution]
+        except TypeError:
+            voxel = []
+        if len(voxel) != 3 or not all(np.isfinite(v) and v > 0.0 for v in voxel):
+            raise ValueError(f"pointcloud needs voxel_resolution = (dx, dy, dz), three positive numbers, got {voxel_resolution!r}")
+        if getattr(image, "affine_transformation", None) is None:
+            raise ValueError("pointcloud needs the image's affine_transformation to place the points on the raster")
     labels, seg_table = _labels_of(segments)
     img_data = image.img_data if hasattr(image, "img_data") else image
     C = img_data.shape[2]
@@ -219,7 +234,17 @@ def create_objects(segments, image, ept=None, ept_srs=None, spectral_bands=None,
         for j, b in enumerate(textural_bands):
             for name, _ in tex_names:
                 data[f"b{b}_{name}"] = tx[name][present, j]
-    for c in cols:                                 # textural columns when calculate_textural=False, point-cloud columns: NaN
+    if pointcloud is not None and (calculate_structural or calculate_radiometric):
+        from .pointcloud import segment_point_stats
+        pc = segment_point_stats(pointcloud, labels, image.affine_transformation, voxel[2], start_label=start_label, n_labels=n, ctx=ctx)
+        pc = _device.out(pc, False)
+        wanted = [(name, on and calculate_structural) for name, on in (("pai", calc_pai), ("fhd", calc_fhd), ("ch", calc_ch))]
+        wanted += [(name, on and calculate_radiometric) for name, on in (("mean_intensity", calc_mean_intensity),
+                                                                        ("variance_intensity", calc_variance_intensity))]
+        for name, on in wanted:
+            if on:
+                data[name] = pc[name][present]
+    for c in cols:                                 # textural columns when calculate_textural=False, point-cloud columns not asked for: NaN
         if c not in data and c != "geometry":
             data[c] = np.full(n_rows, np.nan)
     geoms = [None] * n_rows
