@@ -32,6 +32,21 @@ int obia_test_clear_ranges_dev(obia_ctx *ctx, void *const *dev_ptrs, const int64
 int obia_test_sweep_plan(const int64_t *problems, int n_problems, const int32_t *settings, int repeat, const int32_t *switches,
                          const int64_t *residencies, char *text, int64_t text_bytes);
 
+/* The grid of a clamped launch (obia_amd/csrc/launch_grids.hpp) by its name there.  No context and no GPU: pure host code.
+ *   name     a launch of the table in launch_grids.hpp, e.g. "flat", "image_rows", "cost_sobel"
+ *   sizes    the n_sizes sizes that launch's function takes, in its order (obia_test_launch_grid_names lists them), each in
+ *            1 .. 2^31 - 1: a raster side, a row count, or a flat count (`np`, the problems of a batch: 65535 at the most); products are
+ *            formed in 64 bits
+ *   out4     receives {grid.x, grid.y, trips.x, trips.y}: the workgroups per axis and, per axis, the trips of the stride loop of the
+ *            workgroup with the most work -- 1 up to the clamp, 2 from one unit of work past it.  A unit is what the launch
+ *            expression gives one workgroup per trip (256 elements or chunks, a row, a tile row, a box).
+ * OBIA_E_INVALID with the error text for an unknown name, a wrong n_sizes or a size out of range.                                */
+int obia_test_launch_grid(const char *name, const int64_t *sizes, int n_sizes, int64_t *out4);
+
+/* The names obia_test_launch_grid knows, one per line: "name size size ...", zero-terminated; OBIA_E_INVALID when text_bytes is too
+ * small.                                                                                                                        */
+int obia_test_launch_grid_names(char *text, int64_t text_bytes);
+
 #ifdef __cplusplus
 }
 #endif

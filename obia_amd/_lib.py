@@ -225,6 +225,9 @@ _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
     # the plan of a batch's sweeps as text: pure host code, no context (tests/test_sweep_plan_cpu.py)
     "obia_test_sweep_plan": (_I, [_P, _I, _P, _I, _P, _P, _P, ctypes.c_int64]),
+    # the grid of a clamped launch by name, and the names: pure host code, no context (tests/test_launch_grids_cpu.py)
+    "obia_test_launch_grid": (_I, [ctypes.c_char_p, _P, _I, _P]),
+    "obia_test_launch_grid_names": (_I, [_P, ctypes.c_int64]),
 }
 
 _lib = None

@@ -293,7 +293,7 @@ int check_boxes(obia_ctx *ctx, const char *what, const double *boxes, int64_t n,
 }
 
 // workgroups of a walk: every box its own up to 4096, which then take the boxes in turn
-unsigned walk_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 4096); }
+unsigned walk_grid(int64_t n) { return (unsigned)grids::boxes_walk(n).x.n; }
 
 // MODE_MAX or MODE_COUNT over all boxes, again over those a pass of which did not fit, P doubled, until none is left
 template <int MODE> int walk_until_fit(obia_ctx *ctx, WalkArgs &A, int64_t n) {
@@ -426,7 +426,7 @@ int obia_boxes_iou_dev(obia_ctx *ctx, const double *a, int64_t na, const double 
         return OBIA_E_INVALID;
     }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
-        const dim3 grid((unsigned)std::min<long long>(cdiv(nb, 256), 4096), (unsigned)std::min<long long>(na, 4096));
+        const dim3 grid = to_dim3(grids::boxes_iou(na, nb));
         hipLaunchKernelGGL(boxes_iou_kernel, grid, dim3(256), 0, ctx->stream, a, (long long)na, b, (long long)nb, out);
         OBIA_HIP_TRY(hipGetLastError());
         return OBIA_OK;

@@ -922,8 +922,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
     if (!d_probs || !parent || !size || !newlab || !block_sums) return OBIA_E_NOMEM;
     OBIA_TRY(ctx->plan.flush(ctx));
     OBIA_TRY(fill_async(ctx, lrbits_block, 0, sizeof(unsigned long long) * ((size_t)((n + 63) / 64) + LR_HEAD)));
-    int gs = cdiv(n, 256 * 4);
-    if (gs > 65535 * 4) gs = 65535 * 4;
+    const int gs = (int)grids::cc_flat(n).x.n;
     {
         int max_tiles = 1;
         long long max_seam = 1;
@@ -934,8 +933,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
             if (sm > max_seam) max_seam = sm;
         }
         hipLaunchKernelGGL(cc_tile_kernel, dim3(max_tiles, np), dim3(256), 0, ctx->stream, d_probs, labels_in, parent, size, mask_label, lrbits);
-        int sg = cdiv(max_seam, 256);
-        if (sg > 65535) sg = 65535;
+        const int sg = (int)grids::cc_seam(max_seam, np).x.n;
         hipLaunchKernelGGL(cc_seam_kernel, dim3(sg, np), dim3(256), 0, ctx->stream, d_probs, labels_in, parent, mask_label);
     }
     debug_sync(ctx, "cc: tile + seam");

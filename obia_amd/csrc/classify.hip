@@ -309,8 +309,7 @@ static int table_scale(obia_ctx *ctx, const double *table, int64_t n_rows, int n
     hipLaunchKernelGGL(scale_partial_kernel<1>, grid, dim3(256), 0, ctx->stream, table, (long long)n_rows, F, mean_out, p1, p2, pcnt);
     hipLaunchKernelGGL(scale_var_kernel, dim3(F), dim3(64), 0, ctx->stream, p1, p2, B, F, mean_out, cnt, scale_out);
     const long long total = (long long)n_rows * F;
-    const int tb = (int)(cdiv(total, 256) < 2048 ? cdiv(total, 256) : 2048);
-    hipLaunchKernelGGL(scale_transform_kernel<OUT>, dim3(tb), dim3(256), 0, ctx->stream, table, total, F, mean_out, scale_out, scaled_out);
+    hipLaunchKernelGGL(scale_transform_kernel<OUT>, to_dim3(grids::scale_transform(n_rows, F)), dim3(256), 0, ctx->stream, table, total, F, mean_out, scale_out, scaled_out);
     OBIA_HIP_TRY(hipGetLastError());
     OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return OBIA_OK;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/obia_hip.h"
+#include "launch_grids.hpp"
 
 struct obia_ctx;
 
@@ -187,8 +188,10 @@ int side_stream(obia_ctx *ctx);   // makes sure `side` and the events of both it
 void debug_sync(obia_ctx *ctx, const char *stage);
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// The grid of a clamped launch (launch_grids.hpp: every clamp is a named host function there) as the launch takes it.
+static inline dim3 to_dim3(const grids::Grid &g) { return dim3((unsigned)g.x.n, (unsigned)g.y.n); }
 // Grid of a grid-stride kernel over n elements in workgroups of 256: one workgroup per 256 elements, 8192 at the most, one at the least.
-static inline unsigned flat_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(cdiv(n, 256), 8192)); }
+static inline unsigned flat_grid(long long n) { return (unsigned)grids::flat(n).x.n; }
 
 // Argument checks shared by the entry points whose buffers need only the alignment of their element type (seed_table.hip, boxes.hip,
 // points.hip).  A null pointer is aligned, and is not compared.

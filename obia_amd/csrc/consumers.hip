@@ -74,7 +74,7 @@ int obia_label_edges_u8_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, 
     unsigned long long *d_n = ctx->arena.get<unsigned long long>(1);
     if (!d_n) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(label_edges_kernel, dim3(H < 8192 ? H : 8192), dim3(256), 0, ctx->stream, labels, H, W, edge_out, d_n);
+    hipLaunchKernelGGL(label_edges_kernel, to_dim3(grids::label_edges(H)), dim3(256), 0, ctx->stream, labels, H, W, edge_out, d_n);
     OBIA_HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
     OBIA_TRY(read_back(ctx, &h, d_n, sizeof(h)));

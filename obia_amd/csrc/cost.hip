@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void cost_ndvi_kernel(const float *__restrict_
 // ---------------------------------------------------------------------------------------------------------------- sobel
 // scipy's correlate1d keeps each line in double and detects the symmetry of the weights: [-1, 0, 1] is evaluated as
 // x[0] * 0 + (x[-1] - x[+1]) * -1, [1, 2, 1] as x[0] * 2 + (x[-1] + x[+1]) * 1; the first pass is stored as float32.
-constexpr int SB_TW = 64, SB_TH = 16;
+constexpr int SB_TW = grids::COST_SOBEL_TW, SB_TH = grids::COST_SOBEL_TH;
 
 __device__ __forceinline__ float sobel_diff(float m, float c, float p) {
     return (float)(((double)c * 0.0) + (((double)m - (double)p) * -1.0));
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void cost_sobel_kernel(const float *__restrict
 // instead of walking all digits, and no candidate set is ever built.
 constexpr int SEL_MAXB = 12;                 // widest digit: 4096 bins
 constexpr int SEL_NB = 1 << SEL_MAXB;
-constexpr int SEL_THREADS = 1024;
+constexpr int SEL_THREADS = grids::COST_SELECT_THREADS;
 
 struct SelState {
     unsigned long long n;                    // valid (non-NaN) values        } read back together
@@ -360,7 +360,7 @@ template <typename F> int sel_run(obia_ctx *ctx, const F *x, long long n, double
     unsigned *hist = ctx->arena.get<unsigned>(4 * SEL_NB);
     if (!st || !hist) return OBIA_E_NOMEM;
     const long long nv = n / (16 / (long long)sizeof(F));
-    const int grid = (int)std::max(1LL, std::min<long long>(512, cdiv(nv, SEL_THREADS)));
+    const int grid = (int)grids::cost_select(nv).x.n;
     hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(256), 0, ctx->stream, st, hist);
     sel_launch_level<F, 0>(ctx, x, n, st, hist, q_lo, q_hi, grid);
     sel_launch_level<F, 1>(ctx, x, n, st, hist, q_lo, q_hi, grid);
@@ -388,7 +388,7 @@ template <typename F> int sel_run(obia_ctx *ctx, const F *x, long long n, double
 // e -= p * log(p) / ln 2 over the grey levels in ascending order (p = count / pop).  The terms come from a host table
 // T[pop][count] built with libm log; a lane sorts the taps of two vertically adjacent pixels at once (16-bit halves of one
 // 32-bit word, packed min / max) and walks the sorted runs.
-constexpr int EN_TW = 64, EN_TH = 16, EN_R = 3;
+constexpr int EN_TW = grids::COST_ENTROPY_TW, EN_TH = grids::COST_ENTROPY_TH, EN_R = 3;
 constexpr int EN_LW = EN_TW + 2 * EN_R, EN_LH = EN_TH + 2 * EN_R;
 constexpr int EN_TCOLS = 32;                  // T is [30][32]; T[p][0] = 0 (a step that ends no run subtracts zero)
 
@@ -543,9 +543,6 @@ __global__ __launch_bounds__(256) void cost_combine_kernel(const float *__restri
     }
 }
 
-dim3 tile_grid(int H, int W, int tw, int th) { return dim3(cdiv(W, tw), std::min(cdiv(H, th), 65535)); }
-dim3 row_grid(int H, int W) { return dim3(cdiv(W, 256), std::min(H, 65535)); }
-
 }  // namespace
 }  // namespace obia
 
@@ -575,7 +572,7 @@ int obia_cost_ndvi_f32_dev(obia_ctx *ctx, const float *red, const float *nir, in
 int obia_cost_sobel_f32_dev(obia_ctx *ctx, const float *chm, int H, int W, float *grad_out) {
     OBIA_TRY(enter(ctx));
     if (!chm || !grad_out || H <= 0 || W <= 0) { set_error("cost sobel: bad arguments"); return OBIA_E_INVALID; }
-    hipLaunchKernelGGL(cost_sobel_kernel, tile_grid(H, W, SB_TW, SB_TH), dim3(256), 0, ctx->stream, chm, H, W, grad_out);
+    hipLaunchKernelGGL(cost_sobel_kernel, to_dim3(grids::cost_sobel(H, W)), dim3(256), 0, ctx->stream, chm, H, W, grad_out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
@@ -595,7 +592,7 @@ int obia_cost_entropy_f32_dev(obia_ctx *ctx, const float *pan, int H, int W, dou
                               double *out) {
     OBIA_TRY(enter(ctx));
     if (!pan || !table_30x32 || !out || H <= 0 || W <= 0) { set_error("cost entropy: bad arguments"); return OBIA_E_INVALID; }
-    hipLaunchKernelGGL(cost_entropy_kernel, tile_grid(H, W, EN_TW, EN_TH), dim3(256), 0, ctx->stream, pan, H, W, lo, hi, table_30x32, out);
+    hipLaunchKernelGGL(cost_entropy_kernel, to_dim3(grids::cost_entropy(H, W)), dim3(256), 0, ctx->stream, pan, H, W, lo, hi, table_30x32, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
@@ -621,8 +618,7 @@ int obia_cost_edge_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W,
     OBIA_HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), ctx->stream));
     // a few thousand workgroups striding over the rows: one atomic each (a workgroup per row segment made one per 256 pixels,
     // and same-word atomics serialise device-wide)
-    const int gx = std::min(cdiv(W, 256), 16);
-    hipLaunchKernelGGL(cost_edge_count_kernel, dim3(gx, std::min(H, std::max(1, 4096 / gx))), dim3(256), 0, ctx->stream, labels, H, W, d_n);
+    hipLaunchKernelGGL(cost_edge_count_kernel, to_dim3(grids::cost_edge_count(H, W)), dim3(256), 0, ctx->stream, labels, H, W, d_n);
     OBIA_HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
     OBIA_TRY(read_back(ctx, &h, d_n, sizeof(h)));
@@ -639,7 +635,7 @@ int obia_cost_combine_dev(obia_ctx *ctx, const float *grad, const float *gap, co
     }
     CombineArgs a;
     for (int k = 0; k < 4; ++k) { a.lo[k] = lo4[k]; a.hi[k] = hi4[k]; a.w[k] = w4[k]; }
-    hipLaunchKernelGGL(cost_combine_kernel, row_grid(H, W), dim3(256), 0, ctx->stream, grad, gap, tex, labels, H, W, a, out);
+    hipLaunchKernelGGL(cost_combine_kernel, to_dim3(grids::cost_rows(H, W)), dim3(256), 0, ctx->stream, grad, gap, tex, labels, H, W, a, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void clahe_lut_kernel(const unsigned *__restri
     lut[tile * 256 + tid] = (uint8_t)sat_u8(__float2int_rn((float)s_a[tid] * lut_scale));
 }
 
-constexpr int CL_ROWS = 32;     // rows of one interpolation workgroup (256 columns wide)
+constexpr int CL_ROWS = grids::CLAHE_ROWS;     // rows of one interpolation workgroup (256 columns wide)
 
 __global__ __launch_bounds__(256) void clahe_interp_kernel(const uint8_t *__restrict__ in, int H, int W, int nch, int ch, int th, int tw,
                                                            const uint8_t *__restrict__ lut, uint8_t *__restrict__ out) {
@@ -243,20 +243,23 @@ __global__ __launch_bounds__(256) void clahe_interp_kernel(const uint8_t *__rest
     const float xa = txf - (float)tx1, xa1 = 1.0f - xa;
     tx1 = max(tx1, 0);
     tx2 = min(tx2, 7);
-    const int y1 = min(H, ((int)blockIdx.y + 1) * CL_ROWS);
-    for (int y = blockIdx.y * CL_ROWS; y < y1; ++y) {
-        const float tyf = (float)y * inv_th - 0.5f;
-        int ty1 = (int)floorf(tyf);
-        int ty2 = ty1 + 1;
-        const float ya = tyf - (float)ty1, ya1 = 1.0f - ya;
-        ty1 = max(ty1, 0);
-        ty2 = min(ty2, 7);
-        const long long at = ((long long)y * W + x) * nch + ch;
-        const int v = in[at];
-        const float l11 = (float)s_t[(ty1 * 8 + tx1) * 256 + v], l12 = (float)s_t[(ty1 * 8 + tx2) * 256 + v];
-        const float l21 = (float)s_t[(ty2 * 8 + tx1) * 256 + v], l22 = (float)s_t[(ty2 * 8 + tx2) * 256 + v];
-        const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
-        out[at] = (uint8_t)sat_u8(__float2int_rn(res));
+    // row blocks of CL_ROWS rows, strided over grid.y (grids::image_clahe_interp); 64-bit: H + CL_ROWS may pass 2^31
+    for (long long yb = (long long)blockIdx.y * CL_ROWS; yb < H; yb += (long long)gridDim.y * CL_ROWS) {
+        const int y1 = (int)min((long long)H, yb + CL_ROWS);
+        for (int y = (int)yb; y < y1; ++y) {
+            const float tyf = (float)y * inv_th - 0.5f;
+            int ty1 = (int)floorf(tyf);
+            int ty2 = ty1 + 1;
+            const float ya = tyf - (float)ty1, ya1 = 1.0f - ya;
+            ty1 = max(ty1, 0);
+            ty2 = min(ty2, 7);
+            const long long at = ((long long)y * W + x) * nch + ch;
+            const int v = in[at];
+            const float l11 = (float)s_t[(ty1 * 8 + tx1) * 256 + v], l12 = (float)s_t[(ty1 * 8 + tx2) * 256 + v];
+            const float l21 = (float)s_t[(ty2 * 8 + tx1) * 256 + v], l22 = (float)s_t[(ty2 * 8 + tx2) * 256 + v];
+            const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
+            out[at] = (uint8_t)sat_u8(__float2int_rn(res));
+        }
     }
 }
 
@@ -381,11 +384,6 @@ __global__ __launch_bounds__(256) void mark_kernel(const uint8_t *__restrict__ i
     }
 }
 
-dim3 rows_grid(int H, long long chunks_per_row) {
-    const int gx = (int)std::max<long long>(1, std::min<long long>(cdiv(chunks_per_row, 256), 64));
-    return dim3(gx, std::min(H, 65535));
-}
-
 constexpr long long MAX_W = INT_MAX / 3 - 8;      // 3 W + 14 fits int
 
 }  // namespace
@@ -405,7 +403,7 @@ int obia_image_stretch_u8_dev(obia_ctx *ctx, const void *plane, int is_f64, int6
         OBIA_HIP_TRY(hipMemsetAsync(out, 0, (size_t)n, ctx->stream));
         return OBIA_OK;
     }
-    const dim3 grid(flat_grid(n / 4 + 2));
+    const dim3 grid = to_dim3(grids::image_stretch(n));
     const double d = hi - lo;
     if (is_f64)
         hipLaunchKernelGGL(stretch_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double *)plane, (long long)n, lo, d, out);
@@ -422,7 +420,7 @@ int obia_image_gray_hist_dev(obia_ctx *ctx, const uint8_t *pixels, int nch, int6
         return OBIA_E_INVALID;
     }
     OBIA_HIP_TRY(hipMemsetAsync(hist256_out, 0, 256 * sizeof(int64_t), ctx->stream));
-    hipLaunchKernelGGL(gray_hist_kernel, dim3(std::min(flat_grid(n / 4 + 2), 2048u)), dim3(256), 0, ctx->stream, pixels, nch, (long long)n,
+    hipLaunchKernelGGL(gray_hist_kernel, to_dim3(grids::image_gray_hist(n)), dim3(256), 0, ctx->stream, pixels, nch, (long long)n,
                        gray_out, reinterpret_cast<unsigned long long *>(hist256_out));
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
@@ -434,7 +432,7 @@ int obia_image_lut_u8_dev(obia_ctx *ctx, const uint8_t *in, int64_t n, const uin
         set_error("image lut: bad arguments (rep 1 or 3)");
         return OBIA_E_INVALID;
     }
-    const dim3 grid(flat_grid(n * rep / 4 + 2));
+    const dim3 grid = to_dim3(grids::image_lut(n, rep));
     if (rep == 1)
         hipLaunchKernelGGL(lut_kernel<1>, grid, dim3(256), 0, ctx->stream, in, (long long)n, lut256, out);
     else
@@ -464,10 +462,10 @@ int obia_image_clahe_u8_dev(obia_ctx *ctx, const uint8_t *in, int H, int W, int 
     uint8_t *lut = ctx->arena.get<uint8_t>(64 * 256);
     if (!hist || !lut) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemsetAsync(hist, 0, 64 * 256 * sizeof(unsigned), ctx->stream));
-    const int rows = std::max(std::max(1, 16384 / tw), cdiv(th, 65535));      // ~16 K pixels per workgroup; grid.y <= 65535
-    hipLaunchKernelGGL(clahe_hist_kernel, dim3(64, cdiv(th, rows)), dim3(256), 0, ctx->stream, in, H, W, nch, ch, th, tw, rows, hist);
+    const int rows = (int)grids::image_clahe_hist_rows(th, tw);      // ~16 K pixels per workgroup; grid.y <= 65535
+    hipLaunchKernelGGL(clahe_hist_kernel, to_dim3(grids::image_clahe_hist(th, tw)), dim3(256), 0, ctx->stream, in, H, W, nch, ch, th, tw, rows, hist);
     hipLaunchKernelGGL(clahe_lut_kernel, dim3(64), dim3(256), 0, ctx->stream, hist, clip, lut_scale, lut);
-    hipLaunchKernelGGL(clahe_interp_kernel, dim3(cdiv(W, 256), cdiv(H, CL_ROWS)), dim3(256), 0, ctx->stream, in, H, W, nch, ch, th, tw, lut,
+    hipLaunchKernelGGL(clahe_interp_kernel, to_dim3(grids::image_clahe_interp(H, W)), dim3(256), 0, ctx->stream, in, H, W, nch, ch, th, tw, lut,
                        out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
@@ -476,7 +474,7 @@ int obia_image_clahe_u8_dev(obia_ctx *ctx, const uint8_t *in, int H, int W, int 
 int obia_image_boundaries_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, uint8_t *out) {
     OBIA_TRY(enter(ctx));
     if (!labels || !out || H <= 0 || W <= 0 || W > MAX_W) { set_error("image boundaries: bad arguments"); return OBIA_E_INVALID; }
-    hipLaunchKernelGGL(boundaries_kernel, rows_grid(H, W / 4 + 2), dim3(256), 0, ctx->stream, labels, H, W, out);
+    hipLaunchKernelGGL(boundaries_kernel, to_dim3(grids::image_rows(H, W)), dim3(256), 0, ctx->stream, labels, H, W, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
@@ -489,7 +487,7 @@ int obia_image_mark_u8_dev(obia_ctx *ctx, const uint8_t *image, int nch, const i
         return OBIA_E_INVALID;
     }
     const uint32_t color = (uint32_t)rgb3[0] | ((uint32_t)rgb3[1] << 8) | ((uint32_t)rgb3[2] << 16);
-    hipLaunchKernelGGL(mark_kernel, rows_grid(H, W / 4 + 2), dim3(256), 0, ctx->stream, image, nch, labels, H, W, table256, color, out);
+    hipLaunchKernelGGL(mark_kernel, to_dim3(grids::image_rows(H, W)), dim3(256), 0, ctx->stream, image, nch, labels, H, W, table256, color, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }

@@ -305,7 +305,7 @@ int obia_points_segments_dev(obia_ctx *ctx, const double *x, const double *y, co
         A.s2 = reinterpret_cast<unsigned long long *>(s2);
         A.counters = reinterpret_cast<unsigned long long *>(counters);
         // every chunk its own workgroup up to five per CU of 256, which then take the chunks in turn
-        const unsigned grid = (unsigned)std::min<long long>(cdiv(n, CHUNK), 1280);
+        const unsigned grid = (unsigned)grids::points_segments(n).x.n;
         hipLaunchKernelGGL(points_segments_kernel, dim3(grid), dim3(256), 0, ctx->stream, A);
         OBIA_HIP_TRY(hipGetLastError());
         return OBIA_OK;

@@ -229,8 +229,7 @@ static int polygon_plan(obia_ctx *ctx, const int32_t *lab, int H, int W, int sta
     pl.d_totals = A.get<long long>(3);
     if (!cnt || !pl.d_totals) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemsetAsync(pl.d_totals, 0, 3 * sizeof(long long), ctx->stream));
-    int g = cdiv(n, 256 * 4);
-    if (g > 262144) g = 262144;
+    const int g = (int)grids::polygons_candidates(n).x.n;
     hipLaunchKernelGGL(poly_candidate_count_kernel, dim3(g), dim3(256), 0, ctx->stream, lab, H, W, start_label, cnt);
     OBIA_TRY(exclusive_scan_i32(ctx, cnt, n, cnt, pl.d_totals));
     long long h = 0;

@@ -17,7 +17,7 @@
 
 namespace obia {
 
-constexpr int QT = 16;          // tile side
+constexpr int QT = grids::QS_TILE;   // tile side
 constexpr int QKW_MAX = 15;     // largest half-window staged in LDS (kernel_size <= 5)
 constexpr int QC_MAX = 16;      // bands accepted (the feature pass packs at most 16)
 
@@ -92,51 +92,33 @@ __global__ __launch_bounds__(QT * QT) void qs_density_parent_kernel(const double
     extern __shared__ double s_tile[];   // [C (+1 in phase 2: density)][side][side]
     const int side = QT + 2 * kw;
     const int planes = C + (phase == 2 ? 1 : 0);
-    const int ty0 = blockIdx.y * QT, tx0 = blockIdx.x * QT;
+    const int tx0 = blockIdx.x * QT;
     const long long npix = (long long)H * W;
-    for (int i = threadIdx.x; i < planes * side * side; i += QT * QT) {
-        const int pl = i / (side * side), rem = i - pl * side * side;
-        const int yy = ty0 - kw + rem / side, xx = tx0 - kw + rem % side;
-        double v = 0.0;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W)
-            v = (pl < C) ? img[(long long)pl * npix + (long long)yy * W + xx] : dens[(long long)yy * W + xx];
-        s_tile[i] = v;
-    }
-    __syncthreads();
     const int ly = threadIdx.x / QT, lx = threadIdx.x % QT;
-    const int r = ty0 + ly, c = tx0 + lx;
-    if (r >= H || c >= W) return;
-    double cur[C];
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) cur[ch] = s_tile[(ch * side + ly + kw) * side + lx + kw];
-    const int r0 = max(r - kw, 0), r1 = min(r + kw + 1, H), c0 = max(c - kw, 0), c1 = min(c + kw + 1, W);
-    if (phase == 1) {
-        double acc = 0.0;
-        for (int r_ = r0; r_ < r1; ++r_) {
-            const double tr = (double)(r - r_);
-            for (int c_ = c0; c_ < c1; ++c_) {
-                double dist = 0.0;
-#pragma unroll
-                for (int ch = 0; ch < C; ++ch) {
-                    const double t = cur[ch] - s_tile[(ch * side + (r_ - ty0 + kw)) * side + (c_ - tx0 + kw)];
-                    dist += t * t;
-                }
-                dist += tr * tr;
-                const double tc = (double)(c - c_);
-                dist += tc * tc;
-                acc += exp(dist * inv);
-            }
+    // tile rows strided over grid.y (grids::quickshift_density); every lane of the workgroup takes the same number of trips
+    for (long long t = blockIdx.y; t * QT < H; t += gridDim.y) {
+        const int ty0 = (int)(t * QT);
+        __syncthreads();                 // the previous trip's neighbourhood has been read by every lane
+        for (int i = threadIdx.x; i < planes * side * side; i += QT * QT) {
+            const int pl = i / (side * side), rem = i - pl * side * side;
+            const int yy = ty0 - kw + rem / side, xx = tx0 - kw + rem % side;
+            double v = 0.0;
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W)
+                v = (pl < C) ? img[(long long)pl * npix + (long long)yy * W + xx] : dens[(long long)yy * W + xx];
+            s_tile[i] = v;
         }
-        // "this will break ties that otherwise would give us headache": densities += normal(scale=1e-5)
-        dens[(long long)r * W + c] = acc + (noise ? noise[(long long)r * W + c] : 0.0);
-    } else {
-        const double cd = s_tile[(C * side + ly + kw) * side + lx + kw];
-        double closest = INFINITY;
-        int par = r * W + c;
-        for (int r_ = r0; r_ < r1; ++r_) {
-            const double tr = (double)(r - r_);
-            for (int c_ = c0; c_ < c1; ++c_) {
-                if (s_tile[(C * side + (r_ - ty0 + kw)) * side + (c_ - tx0 + kw)] > cd) {
+        __syncthreads();
+        const int r = ty0 + ly, c = tx0 + lx;
+        if (r >= H || c >= W) continue;
+        double cur[C];
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) cur[ch] = s_tile[(ch * side + ly + kw) * side + lx + kw];
+        const int r0 = max(r - kw, 0), r1 = min(r + kw + 1, H), c0 = max(c - kw, 0), c1 = min(c + kw + 1, W);
+        if (phase == 1) {
+            double acc = 0.0;
+            for (int r_ = r0; r_ < r1; ++r_) {
+                const double tr = (double)(r - r_);
+                for (int c_ = c0; c_ < c1; ++c_) {
                     double dist = 0.0;
 #pragma unroll
                     for (int ch = 0; ch < C; ++ch) {
@@ -146,12 +128,35 @@ __global__ __launch_bounds__(QT * QT) void qs_density_parent_kernel(const double
                     dist += tr * tr;
                     const double tc = (double)(c - c_);
                     dist += tc * tc;
-                    if (dist < closest) { closest = dist; par = r_ * W + c_; }
+                    acc += exp(dist * inv);
                 }
             }
+            // "this will break ties that otherwise would give us headache": densities += normal(scale=1e-5)
+            dens[(long long)r * W + c] = acc + (noise ? noise[(long long)r * W + c] : 0.0);
+        } else {
+            const double cd = s_tile[(C * side + ly + kw) * side + lx + kw];
+            double closest = INFINITY;
+            int par = r * W + c;
+            for (int r_ = r0; r_ < r1; ++r_) {
+                const double tr = (double)(r - r_);
+                for (int c_ = c0; c_ < c1; ++c_) {
+                    if (s_tile[(C * side + (r_ - ty0 + kw)) * side + (c_ - tx0 + kw)] > cd) {
+                        double dist = 0.0;
+#pragma unroll
+                        for (int ch = 0; ch < C; ++ch) {
+                            const double t = cur[ch] - s_tile[(ch * side + (r_ - ty0 + kw)) * side + (c_ - tx0 + kw)];
+                            dist += t * t;
+                        }
+                        dist += tr * tr;
+                        const double tc = (double)(c - c_);
+                        dist += tc * tc;
+                        if (dist < closest) { closest = dist; par = r_ * W + c_; }
+                    }
+                }
+            }
+            parent[(long long)r * W + c] = par;
+            dist_parent[(long long)r * W + c] = sqrt(closest);
         }
-        parent[(long long)r * W + c] = par;
-        dist_parent[(long long)r * W + c] = sqrt(closest);
     }
 }
 
@@ -162,42 +167,46 @@ __global__ __launch_bounds__(QT * QT) void qs_density_parent_global_kernel(const
                                                                           double *__restrict__ dens, int *__restrict__ parent,
                                                                           double *__restrict__ dist_parent) {
     const int ly = threadIdx.x / QT, lx = threadIdx.x % QT;
-    const int r = blockIdx.y * QT + ly, c = blockIdx.x * QT + lx;
-    if (r >= H || c >= W) return;
-    const long long npix = (long long)H * W;
-    const long long me = (long long)r * W + c;
-    double cur[QC_MAX];
+    const int c = blockIdx.x * QT + lx;
+    if (c >= W) return;
+    // tile rows strided over grid.y (grids::quickshift_density)
+    for (long long t = blockIdx.y; t * QT + ly < H; t += gridDim.y) {
+        const int r = (int)(t * QT) + ly;
+        const long long npix = (long long)H * W;
+        const long long me = (long long)r * W + c;
+        double cur[QC_MAX];
 #pragma unroll
-    for (int ch = 0; ch < QC_MAX; ++ch) cur[ch] = ch < C ? img[(long long)ch * npix + me] : 0.0;
-    const int r0 = max(r - kw, 0), r1 = min(r + kw + 1, H), c0 = max(c - kw, 0), c1 = min(c + kw + 1, W);
-    auto dist_to = [&](int r_, int c_) {
-        const long long q = (long long)r_ * W + c_;
-        double dist = 0.0;
+        for (int ch = 0; ch < QC_MAX; ++ch) cur[ch] = ch < C ? img[(long long)ch * npix + me] : 0.0;
+        const int r0 = max(r - kw, 0), r1 = min(r + kw + 1, H), c0 = max(c - kw, 0), c1 = min(c + kw + 1, W);
+        auto dist_to = [&](int r_, int c_) {
+            const long long q = (long long)r_ * W + c_;
+            double dist = 0.0;
 #pragma unroll
-        for (int ch = 0; ch < QC_MAX; ++ch)
-            if (ch < C) { const double t = cur[ch] - img[(long long)ch * npix + q]; dist += t * t; }
-        const double tr = (double)(r - r_), tc = (double)(c - c_);
-        dist += tr * tr;
-        dist += tc * tc;
-        return dist;
-    };
-    if (phase == 1) {
-        double acc = 0.0;
-        for (int r_ = r0; r_ < r1; ++r_)
-            for (int c_ = c0; c_ < c1; ++c_) acc += exp(dist_to(r_, c_) * inv);
-        dens[me] = acc + (noise ? noise[me] : 0.0);
-    } else {
-        const double cd = dens[me];
-        double closest = INFINITY;
-        int par = (int)me;
-        for (int r_ = r0; r_ < r1; ++r_)
-            for (int c_ = c0; c_ < c1; ++c_)
-                if (dens[(long long)r_ * W + c_] > cd) {
-                    const double dist = dist_to(r_, c_);
-                    if (dist < closest) { closest = dist; par = r_ * W + c_; }
-                }
-        parent[me] = par;
-        dist_parent[me] = sqrt(closest);
+            for (int ch = 0; ch < QC_MAX; ++ch)
+                if (ch < C) { const double t = cur[ch] - img[(long long)ch * npix + q]; dist += t * t; }
+            const double tr = (double)(r - r_), tc = (double)(c - c_);
+            dist += tr * tr;
+            dist += tc * tc;
+            return dist;
+        };
+        if (phase == 1) {
+            double acc = 0.0;
+            for (int r_ = r0; r_ < r1; ++r_)
+                for (int c_ = c0; c_ < c1; ++c_) acc += exp(dist_to(r_, c_) * inv);
+            dens[me] = acc + (noise ? noise[me] : 0.0);
+        } else {
+            const double cd = dens[me];
+            double closest = INFINITY;
+            int par = (int)me;
+            for (int r_ = r0; r_ < r1; ++r_)
+                for (int c_ = c0; c_ < c1; ++c_)
+                    if (dens[(long long)r_ * W + c_] > cd) {
+                        const double dist = dist_to(r_, c_);
+                        if (dist < closest) { closest = dist; par = r_ * W + c_; }
+                    }
+            parent[me] = par;
+            dist_parent[me] = sqrt(closest);
+        }
     }
 }
 
@@ -321,8 +330,7 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
     if (!b.d_windows || !b.d_feat || !d_img || !d_dens || !d_dp || !d_par || !d_par2 || !d_rank || !d_bs || !d_flags) return OBIA_E_NOMEM;
     OBIA_HIP_TRY(hipMemcpyAsync(b.d_windows, b.windows.data(), sizeof(SrcWindow), hipMemcpyHostToDevice, ctx->stream));
     OBIA_TRY(slic_prepare_features(ctx, b, img, W));
-    int gs = cdiv(n, 256 * 4);
-    if (gs > 65535) gs = 65535;
+    const int gs = (int)grids::quickshift_flat(n).x.n;
     const bool smoothing = sigma > 1e-15;
     hipLaunchKernelGGL(qs_prepare_kernel, dim3(gs), dim3(256), 0, ctx->stream, b.d_feat, b.CP, C, n, convert2lab ? 1 : 0, smoothing ? 1.0 : ratio, d_img);
     if (smoothing) {   // rows, then columns (gaussian_filter walks the axes in order; the band axis has sigma 0), then `* ratio`
@@ -331,8 +339,7 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
         double *d_w = A.get<double>(w.size()), *d_tmp = A.get<double>((size_t)n * C);
         if (!d_w || !d_tmp) return OBIA_E_NOMEM;
         OBIA_TRY(upload_async(ctx, d_w, w.data(), sizeof(double) * w.size()));
-        int gg = cdiv(n * C, 256);
-        if (gg > 65535) gg = 65535;
+        const int gg = (int)grids::quickshift_gauss(n * C).x.n;
         hipLaunchKernelGGL(qs_gauss_axis_kernel, dim3(gg), dim3(256), 0, ctx->stream, d_img, d_tmp, H, W, n * C, 1, d_w, r, 1.0);
         hipLaunchKernelGGL(qs_gauss_axis_kernel, dim3(gg), dim3(256), 0, ctx->stream, d_tmp, d_img, H, W, n * C, 0, d_w, r, ratio);
     }
@@ -347,7 +354,7 @@ static int quickshift_dev(obia_ctx *ctx, const float *img, int H, int W, int C, 
     // 2. density, 3. parent
     const double inv = -0.5 / (kernel_size * kernel_size);
     const int side = QT + 2 * kw;
-    dim3 grid(cdiv(W, QT), cdiv(H, QT));
+    const dim3 grid = to_dim3(grids::quickshift_density(H, W));
 #define QS_LAUNCH(CV, PH) do {                                                                                         \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&qs_density_parent_kernel<CV>),                          \
                               hipFuncAttributeMaxDynamicSharedMemorySize,                                             \

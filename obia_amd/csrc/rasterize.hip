@@ -37,7 +37,7 @@ constexpr int RS_MAX_EDGES = OBIA_RAST_SMALL_EDGES;
 constexpr int RS_SIDE = 64;          // rows = lanes, columns = bits of two 32-bit words
 constexpr int RS_WAVES = 4;
 constexpr int RL_BAND_ROWS = 8;
-constexpr int RL_TILE_W = 2048;      // columns of one workgroup's bit plane: 8 rows x 64 words = 2 KiB of LDS
+constexpr int RL_TILE_W = grids::RAST_LARGE_TILE_W;      // columns of one workgroup's bit plane: 8 rows x 64 words = 2 KiB of LDS
 constexpr int RL_WORDS = RL_TILE_W / 32;
 
 struct RastLarge { int s, r0, r1, c0, c1, vlo, nv, ring_lo, ring_hi; long long band_base; };
@@ -299,7 +299,7 @@ int rasterize_polygons_dev(obia_ctx *ctx, const double *xy_pix, const int64_t *r
     g_last_small = g_last_large = 0;
     const int S = (int)n_shapes;
     OBIA_HIP_TRY(hipMemsetAsync(out, 0xff, (size_t)n * sizeof(int32_t), ctx->stream));      // every pixel: shape index -1
-    const int g_px = (int)std::min<long long>(cdiv(n, 256 * 4), 16384);
+    const int g_px = (int)grids::rast_value(n).x.n;
     if (n_rings > 0) {
         Arena &A = ctx->arena;
         unsigned long long *ctr = A.get<unsigned long long>(RC_N);
@@ -335,7 +335,7 @@ int rasterize_polygons_dev(obia_ctx *ctx, const double *xy_pix, const int64_t *r
             long long *band_off = A.get<long long>((size_t)n_bands);
             if (!band_owner || !band_n || !band_off) return OBIA_E_NOMEM;
             OBIA_HIP_TRY(hipMemsetAsync(band_n, 0, (size_t)n_bands * sizeof(int), ctx->stream));
-            const dim3 g_bin((unsigned)n_large, (unsigned)std::min<long long>(cdiv((long long)h[RC_MAX_NV], 256), 64));
+            const dim3 g_bin = to_dim3(grids::rast_band_bin(n_large, (long long)h[RC_MAX_NV]));
             hipLaunchKernelGGL(rast_band_owner_kernel, dim3((unsigned)n_large), dim3(256), 0, ctx->stream, large, band_owner);
             hipLaunchKernelGGL(rast_band_bin_kernel<false>, g_bin, dim3(256), 0, ctx->stream, xy, ring_offset, large, band_n, band_off,
                                (int2 *)nullptr);
@@ -350,7 +350,7 @@ int rasterize_polygons_dev(obia_ctx *ctx, const double *xy_pix, const int64_t *r
                 hipLaunchKernelGGL(rast_band_bin_kernel<true>, g_bin, dim3(256), 0, ctx->stream, xy, ring_offset, large, band_n, band_off,
                                    entries);
                 debug_sync(ctx, "rasterize: band lists");
-                const dim3 g_large((unsigned)n_bands, (unsigned)std::min<long long>(cdiv((long long)h[RC_MAX_W], RL_TILE_W), 1024));
+                const dim3 g_large = to_dim3(grids::rast_large(n_bands, (long long)h[RC_MAX_W]));
                 hipLaunchKernelGGL(rast_large_kernel, g_large, dim3(256), 0, ctx->stream, xy, large, band_owner, band_n, band_off, entries, W,
                                    out);
                 debug_sync(ctx, "rasterize: large shapes");

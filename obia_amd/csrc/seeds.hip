@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void seeds_gauss_kernel(const float *__restric
 // ------------------------------------------------------------------------------------------------------- maximum filter
 // A 64 x 16 tile and its d-pixel halo (reflect) in LDS, NaN staged as -inf; row maxima over 2d + 1 taps, then column maxima;
 // flag = g is not NaN && g == max && g >= threshold.
-constexpr int MX_TW = 64, MX_TH = 16, MX_MAXD = 32;
+constexpr int MX_TW = grids::SEEDS_FLAG_TW, MX_TH = grids::SEEDS_FLAG_TH, MX_MAXD = 32;
 constexpr int CHUNK = 4096;                   // pixels of one compaction block: 256 lanes x 16 flag bytes
 
 __global__ __launch_bounds__(256) void seeds_flag_kernel(const float *__restrict__ g, int H, int W, int d, float thr,
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void seeds_scatter_kernel(const uint8_t *__res
 }
 
 // ---------------------------------------------------------------------------------------------------------------- pairs
-constexpr int PT = 64;                        // a pair tile is PT x PT seeds
+constexpr int PT = grids::SEEDS_PAIR_TILE;    // a pair tile is PT x PT seeds
 constexpr int PAIR_MAX_SAMPLES = 128;         // NumPy's pairwise sum is restated up to its 128-element block
 
 struct PairArgs {
@@ -442,10 +442,7 @@ int pair_setup(obia_ctx *ctx, const double *xs, const double *ys, int n, const f
     return OBIA_OK;
 }
 
-int pair_grid(int n) {
-    const long long nt = (n + PT - 1) / PT;
-    return (int)std::max(1LL, std::min<long long>(nt * (nt + 1) / 2, 256 * 16));
-}
+int pair_grid(int n) { return (int)grids::seeds_pairs(n).x.n; }
 
 }  // namespace
 }  // namespace obia
@@ -479,7 +476,7 @@ int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double
         float *tmp = ctx->arena.get<float>((size_t)n);
         if (!d_w || !tmp) return OBIA_E_NOMEM;
         OBIA_TRY(upload_async(ctx, d_w, w.data(), sizeof(double) * w.size()));
-        const dim3 grid((unsigned)std::min<long long>(cdiv(n, 256), 16384));
+        const dim3 grid = to_dim3(grids::seeds_gauss(n));
         hipLaunchKernelGGL(seeds_gauss_kernel<0>, grid, dim3(256), 0, ctx->stream, plane, tmp, H, W, d_w, r);
         hipLaunchKernelGGL(seeds_gauss_kernel<1>, grid, dim3(256), 0, ctx->stream, tmp, smooth_out, H, W, d_w, r);
         g = smooth_out;
@@ -490,7 +487,7 @@ int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double
     if ((long long)nchunks * CHUNK > n) OBIA_HIP_TRY(hipMemsetAsync(flags_out + n, 0, (size_t)((long long)nchunks * CHUNK - n), ctx->stream));
     const int d = min_dist_px;
     const size_t lds = sizeof(float) * (size_t)(MX_TH + 2 * d) * (size_t)(2 * MX_TW + 2 * d);
-    hipLaunchKernelGGL(seeds_flag_kernel, dim3(cdiv(W, MX_TW), std::min(cdiv(H, MX_TH), 65535)), dim3(256), lds, ctx->stream, g, H, W, d,
+    hipLaunchKernelGGL(seeds_flag_kernel, to_dim3(grids::seeds_flag(H, W)), dim3(256), lds, ctx->stream, g, H, W, d,
                        threshold, flags_out);
     hipLaunchKernelGGL(seeds_count_kernel, dim3(nchunks), dim3(256), 0, ctx->stream, flags_out, counts);
     hipLaunchKernelGGL(seeds_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, counts, offsets_out, nchunks);

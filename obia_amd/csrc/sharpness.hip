@@ -21,7 +21,7 @@
 namespace obia {
 namespace {
 
-constexpr int MM_GRID = 2048;      // workgroups (at most) of the min / max pass: one partial record of six floats each
+constexpr int MM_GRID = grids::SHARPNESS_MINMAX_PARTS;      // workgroups (at most) of the min / max pass: one partial record of six floats each
 constexpr int LAP_TX = 64, LAP_TY = 32;   // output tile of one stencil workgroup (256 threads, 8 rows each)
 constexpr int BOX_ROWS = 64;       // rows of one axis-1 workgroup: four waves, the first walks a lane per row
 constexpr int BOX_CH1 = 64;        // columns per LDS chunk, one plane (box filter):  64 x 65 cells of 8 bytes = 32.5 KiB
@@ -428,7 +428,7 @@ int obia_sharp_gray_lap_dev(obia_ctx *ctx, const float *raster, int H, int W, in
         if (bands3[b] < 0 || bands3[b] >= C) { set_error("sharp gray_lap: band %d of %d", bands3[b], C); return OBIA_E_INVALID; }
     OBIA_TRY(clear_counter(ctx, "sharp gray_lap", nonfinite_out));
     const long long npx = (long long)H * W;
-    const int nparts = (int)std::min<long long>(cdiv(npx, 256), MM_GRID);
+    const int nparts = (int)grids::sharpness_minmax(npx).x.n;
     ctx->arena.reset();
     float *part = ctx->arena.get<float>(6 * (size_t)MM_GRID);
     float *stats = ctx->arena.get<float>(8);

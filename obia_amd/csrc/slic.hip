@@ -456,7 +456,7 @@ int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *sr
     // (Window by window -- min / max pass and feature pass of one 134-MB window back to back, so that the second read could come from
     // the 256-MB Infinity Cache -- was measured in round 4: features 2.46 -> 3.8 ms per step, step +2.4 ms; the batch-wide passes stay.)
     if (normalize) {
-        int gx = maxh < 2048 ? maxh : 2048;
+        const int gx = (int)grids::slic_band_minmax(maxh, np).x.n;
         // float4 reads need 16-byte aligned rows: C % 4 == 0 and an aligned base pointer
         if (C % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(band_minmax_kernel<4>), dim3(gx, np), dim3(FP_NT), 0, stream, src, Ws, C, d_windows,
@@ -469,7 +469,7 @@ int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *sr
     if (minmax_only) { OBIA_HIP_TRY(hipGetLastError()); return OBIA_OK; }
     const bool box = planes && d_fbox != nullptr;   // colour boxes from the same pass (a block walks footprint bands of 16 rows)
     const int rows = box ? (maxh + 15) / 16 : (planes ? (maxh + 3) / 4 : maxh);
-    dim3 grid(rows < 4096 ? rows : 4096, np);
+    const dim3 grid = to_dim3(grids::slic_feature_rows(rows, np));
     // Smoothing: normalise -> Lab (unscaled, pixel-major) -> the Gaussian passes -> scale + plane layout from the smoothed arrays
     const bool smoothing = smooth && smooth->on();
     if (smoothing && !planes) { set_error("Gaussian pre-smoothing is built for the SLIC feature layout only"); return OBIA_E_UNSUPPORTED; }
@@ -477,7 +477,7 @@ int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *sr
     int planes_norm = normalize, planes_lab = to_lab, dense = 0;
     if (smoothing) {
         OBIA_HIP_TRY(hipMemsetAsync(smooth->d_scratch, 0, sizeof(unsigned) * (size_t)np, stream));
-        dim3 g1(maxh < 4096 ? maxh : 4096, np);
+        const dim3 g1 = to_dim3(grids::slic_feature_rows(maxh, np));
 #define LAUNCH_UNSCALED(CPV) hipLaunchKernelGGL(HIP_KERNEL_NAME(features_kernel<CPV>), g1, dim3(256), 0, stream, src, Ws, C, d_windows, \
                                                 d_keys, normalize, to_lab, 1.0f, smooth->tmp_a, smooth->d_scratch)
         switch (CP) {
@@ -488,8 +488,7 @@ int slic_features_launch(hipStream_t stream, const SlicBatch &b, const float *sr
         }
 #undef LAUNCH_UNSCALED
         float *cur = smooth->tmp_a, *oth = smooth->tmp_b;
-        long long nb = (b.maxpix * CP + 255) / 256;
-        dim3 gg((unsigned)(nb < 65535 ? (nb < 1 ? 1 : nb) : 65535), np);
+        const dim3 gg = to_dim3(grids::slic_gauss(b.maxpix * CP, np));
         for (int ax = 0; ax < 3; ++ax) {
             if (!(smooth->sigma[ax] > 1e-15)) continue;
             if (ax == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(gauss_axis_kernel<0>), gg, dim3(256), 0, stream, d_windows, cur, oth, CP, smooth->d_w[0], smooth->radius[0]);
@@ -629,6 +628,8 @@ void slic_batch_settings(SlicBatch &b, const obia_slic_params &p, int C, int nor
 }
 
 int slic_batch_layout(SlicBatch &b) {
+    // the batch's kernels take their problem from blockIdx.y (launch_grids.hpp: the `np` axes)
+    if ((long long)b.windows.size() > grids::GRID_Y_MAX) { set_error("%zu windows in one batch, the limit is %lld", b.windows.size(), grids::GRID_Y_MAX); return OBIA_E_UNSUPPORTED; }
     b.nprob = (int)b.windows.size();
     b.probs.assign(b.windows.size(), SlicProblem{});
     long long off = 0, foff = 0, boff = 0, m4 = 0;
@@ -1035,9 +1036,7 @@ int slic_stage_outputs(obia_ctx *ctx, const SlicBatch &b, float *features, float
     const float inv_prescale = 1.0f / b.prescale;
     if (features) {
         const long long n = (long long)P.H * P.W * b.C;
-        long long blocks = (n + 255) / 256;
-        if (blocks > 65535) blocks = 65535;
-        hipLaunchKernelGGL(stage_features_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, b.d_feat, P, b.C, b.CP, inv_prescale, features);
+        hipLaunchKernelGGL(stage_features_kernel, to_dim3(grids::slic_stage_features(n)), dim3(256), 0, ctx->stream, b.d_feat, P, b.C, b.CP, inv_prescale, features);
     }
     if (seeds_yx && P.K > 0)
         OBIA_HIP_TRY(hipMemcpyAsync(seeds_yx, b.d_seed + 2 * (size_t)P.cent_off, sizeof(float) * 2 * (size_t)P.K, hipMemcpyDeviceToDevice, ctx->stream));

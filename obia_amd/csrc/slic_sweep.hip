@@ -1663,7 +1663,7 @@ __global__ void fill_i32_kernel(int32_t *p, long long n, int32_t v) {
 
 // nearest[:] = start_label - 1 (before the loop of _slic_cython)
 static void fill_labels(obia_ctx *ctx, SlicBatch &b) {
-    const int blocks = std::max(1, std::min(cdiv(b.total_pix, 256 * 8), 65535));
+    const int blocks = (int)grids::slic_fill_labels(b.total_pix).x.n;
     hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks), dim3(256), 0, ctx->stream, b.d_labels, b.total_pix, b.start_label - 1);
 }
 

@@ -199,8 +199,8 @@ inline int plan_sweeps(const SlicBatch &b, bool repeat, const SweepSwitches &sw,
     // the packed mask of the sweeps (problems whose mask hides nothing never read it); the tiler's mask kernel writes it on the way
     // (tiling.hip: tile_mask_kernel<true>)
     pl.pack_mask = b.masked && b.d_mask && !b.d_mask4;
-    pl.pack_rows = std::min((maxh + 3) / 4, 16384);
-    pl.maxdist_rows = std::min(maxh, 4096);
+    pl.pack_rows = (int)grids::slic_mask_pack(maxh, b.nprob).x.n;
+    pl.maxdist_rows = (int)grids::slic_maxdist(maxh, b.nprob).x.n;
     pl.fixed_point = b.exit_on_fixed_point;
     // The fill value survives in exactly one kind of pixel: a valid one that no window reached ("orphan").  When only the last sweep
     // stores, such a pixel raises the flag and the caller repeats the batch (slic_sweeps_settle) -- unless the batch has ONE sweep in

@@ -281,13 +281,13 @@ int texture_stats_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, in
     OBIA_HIP_TRY(hipMemsetAsync(d_nbig, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(bbox_kernel, dim3(cdiv(W, 64) * cdiv(H, 64)), dim3(64), 0, ctx->stream, labels, H, W, n_labels, start_label, bbox);
     hipLaunchKernelGGL(tex_list_big_kernel, dim3(cdiv(n_labels, 256)), dim3(256), 0, ctx->stream, bbox, n_labels, big_list, d_nbig);
-    int grid = n_labels < 65536 ? n_labels : 65536;
+    const int grid = (int)grids::texture_segments(n_labels).x.n;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(texture_kernel<false>), dim3(grid), dim3(TX_NT), 0, ctx->stream, raw, labels, H, W, C, tb,
                        n_labels, start_label, bbox, (const int *)nullptr, 0, (unsigned *)nullptr, out6);
     int n_big = 0;
     OBIA_TRY(read_back(ctx, &n_big, d_nbig, sizeof(int)));
     if (n_big > 0) {
-        const int gb = n_big < 256 ? n_big : 256;
+        const int gb = (int)grids::texture_big_segments(n_big).x.n;
         unsigned *scratch = A.get<unsigned>((size_t)gb * 65536);
         if (!scratch) return OBIA_E_NOMEM;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(texture_kernel<true>), dim3(gb), dim3(TX_NT), 0, ctx->stream, raw, labels, H, W, C, tb,

@@ -364,7 +364,7 @@ struct TileState {
 static int grid_rows(const std::vector<TileWin> &wins) {   // row-walking kernels: one block per row (capped)
     int g = 1;
     for (auto &t : wins) if (t.h > g) g = t.h;
-    return g > 8192 ? 8192 : g;
+    return (int)grids::tiler_rows(g, 1).x.n;
 }
 
 // One batch of tiles: mask -> features -> plan -> sweeps -> connectivity -> scatter.
@@ -880,8 +880,7 @@ static int tiler_finalize(obia_ctx *ctx, TileState &S, int64_t *n_segments_out) 
     if (!d_partial) return OBIA_E_NOMEM;
     hipLaunchKernelGGL(ids_count_kernel, dim3(nchunks), dim3(1024), 0, ctx->stream, S.alive, S.next_id, d_partial);
     hipLaunchKernelGGL(ids_scan_kernel, dim3(nchunks), dim3(1024), 0, ctx->stream, S.alive, S.next_id, d_partial, S.newid, S.d_total);
-    int g = cdiv((long long)S.H * S.W, 256 * 16);
-    if (g > 65535) g = 65535;
+    const int g = (int)grids::tiler_ids_apply((long long)S.H * S.W).x.n;
     hipLaunchKernelGGL(ids_apply_kernel, dim3(g), dim3(256), 0, ctx->stream, S.G, (long long)S.H * S.W, S.newid);
     OBIA_HIP_TRY(hipGetLastError());
     long long total = 0;
@@ -1026,7 +1025,7 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
     }
     int *ctr = t->seam_buf, *new_list = t->seam_buf + 2;
     OBIA_TRY(fill_async(ctx, ctr, 0, sizeof(int) * 2));
-    const int blocks = std::min(cdiv(n, 256), 2048);
+    const int blocks = (int)grids::tiler_seam(n).x.n;
     hipLaunchKernelGGL(seam_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, codes_dev, n, my_rank, owner_rank, fmap_dev, fmap_cap, new_list, ctr,
                        ids_out_dev);
     int h[2] = {0, 0};

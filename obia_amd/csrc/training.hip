@@ -379,7 +379,7 @@ int obia_train_compose_u8_dev(obia_ctx *ctx, const uint8_t *tile, const uint8_t 
     OBIA_TRY(clear_counter(ctx, "train compose", bad_mask_out));
     const long long npx = (long long)H * W;
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(bad_mask_out);
-    const unsigned grid = flat_grid((3 * npx + 6) / 4);
+    const unsigned grid = (unsigned)grids::training_compose(npx).x.n;
     if (dist)
         hipLaunchKernelGGL(compose_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, tile, blurred, mask, dist, npx, darken_lut,
                            (float)feather, out, bad);
@@ -397,10 +397,10 @@ int obia_train_minmax_u8_dev(obia_ctx *ctx, const float *x, int64_t n, float *wo
         return OBIA_E_INVALID;
     }
     OBIA_TRY(clear_counter(ctx, "train minmax", nonfinite_out));
-    const int nparts = (int)std::min<long long>(cdiv(n, 256), MM_PARTS);
+    const int nparts = (int)grids::training_minmax_reduce(n).x.n;
     hipLaunchKernelGGL(minmax_reduce_kernel, dim3(nparts), dim3(256), 0, ctx->stream, x, (long long)n, work,
                        reinterpret_cast<unsigned long long *>(nonfinite_out));
-    hipLaunchKernelGGL(minmax_scale_kernel, dim3(flat_grid((n + 6) / 4)), dim3(256), 0, ctx->stream, x, (long long)n, (const float *)work,
+    hipLaunchKernelGGL(minmax_scale_kernel, to_dim3(grids::training_minmax_scale(n)), dim3(256), 0, ctx->stream, x, (long long)n, (const float *)work,
                        nparts, out);
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;

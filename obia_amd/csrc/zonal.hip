@@ -540,8 +540,7 @@ int zonal_moments_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, in
     else LAUNCH_ZM(16);
 #undef LAUNCH_ZM
 #undef LAUNCH_ZM_MODE
-    int ib = cdiv((long long)nlb, 256);
-    if (ib > 4096) ib = 4096;
+    const int ib = (int)grids::zonal_labels((long long)nlb).x.n;
     hipLaunchKernelGGL(zonal_moments_finalize_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_n, g_s2, g_s3, g_s4, mean,
                        (long long)nlb, skew, kurt, var);
     OBIA_HIP_TRY(hipGetLastError());
@@ -577,8 +576,7 @@ int zonal_stats_dev(obia_ctx *ctx, const float *raw, const int32_t *labels, int 
     double *g_sum = A.get<double>(nlb), *g_sq = A.get<double>(nlb);
     unsigned *g_mn = A.get<unsigned>(nlb), *g_mx = A.get<unsigned>(nlb), *g_piv = A.get<unsigned>(nlb);
     if (!g_cnt || !g_bcnt || !g_sum || !g_sq || !g_mn || !g_mx || !g_piv) return OBIA_E_NOMEM;
-    int ib = cdiv((long long)nlb, 256);
-    if (ib > 4096) ib = 4096;
+    const int ib = (int)grids::zonal_labels((long long)nlb).x.n;
     hipLaunchKernelGGL(zonal_init_kernel, dim3(ib), dim3(256), 0, ctx->stream, g_cnt, g_bcnt, g_sum, g_sq, g_mn, g_mx, g_piv, (long long)n_labels, bl.n);
     const int tiles = cdiv(W, ZTW) * cdiv(H, ZTH);
     const bool ident = bl.identity && bl.n == C;
