@@ -452,7 +452,9 @@ int obia_tiler_set_seeding(obia_tiler *t, int seeding, obia_pick_fn picks, void 
  * at *first_new_out = obia_tiler_next_id(); the range is registered like obia_tiler_set_segments(first, n_new, 0xffffffff...)
  * (sizes follow from the caller's view of its halo).  *max_owner_id_out = the largest owner id on the seam: when it is
  * >= fmap_cap the ids beyond the map were left out (ids_out 0) and the caller calls again with a larger map (entries kept; what
- * the first call imported -- *n_new_out ids from *first_new_out -- stays imported).                                          */
+ * the first call imported -- *n_new_out ids from *first_new_out -- stays imported).
+ * OBIA_E_NOMEM when the new ids do not fit the session (obia_tiler_next_id() + n_new > its id capacity): nothing is imported,
+ * fmap_dev, code_of_dev, the id counter and the alive flags are what they were before the call; ids_out_dev is unspecified.    */
 int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int my_rank, int owner_rank,
                            int32_t *fmap_dev, int fmap_cap, int32_t *code_of_dev, int32_t *ids_out_dev,
                            int *first_new_out, int *n_new_out, int *max_owner_id_out);

@@ -47,6 +47,10 @@ int obia_test_launch_grid(const char *name, const int64_t *sizes, int n_sizes, i
  * small.                                                                                                                        */
 int obia_test_launch_grid_names(char *text, int64_t text_bytes);
 
+/* The largest number of new ids of one obia_tiler_import_seam that is ranked by the one-workgroup sort in LDS; an import that
+ * brings more is ranked by counting.  A constant of the build: no context and no GPU.                                           */
+int obia_test_seam_sort_limit(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,8 @@ _TEST_SIGNATURES = {
     # the grid of a clamped launch by name, and the names: pure host code, no context (tests/test_launch_grids_cpu.py)
     "obia_test_launch_grid": (_I, [ctypes.c_char_p, _P, _I, _P]),
     "obia_test_launch_grid_names": (_I, [_P, ctypes.c_int64]),
+    # the most new ids a seam import ranks by its LDS sort; above it the counting kernel (tests/test_gpu_seam_import.py)
+    "obia_test_seam_sort_limit": (_I, []),
 }
 
 _lib = None

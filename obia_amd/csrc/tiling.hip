@@ -22,6 +22,7 @@
 // All tiles of a pass (or of one white tile-row) are ONE batch for the SLIC engine and for the
 // connectivity kernels: no per-tile launches, two host read-backs per batch.
 #include "slic.hpp"
+#include "../../include/obia_testing.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -666,6 +667,10 @@ __global__ __launch_bounds__(256) void seam_translate_kernel(const int32_t *__re
         if (t > 0 && t < cap) ids[i] = fmap[t];
     }
 }
+// a refused import (no room for its new ids) takes its claims back: -1 -> 0, so a later import on the same map meets these ids as new
+__global__ __launch_bounds__(256) void seam_unclaim_kernel(const int *__restrict__ new_list, int m, int32_t *__restrict__ fmap) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) fmap[new_list[i]] = 0;
+}
 __global__ void seam_register_kernel(unsigned *__restrict__ seg_size, uint8_t *__restrict__ alive, int first, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) { seg_size[first + i] = 0xffffffffu; alive[first + i] = 1; }
@@ -1032,7 +1037,13 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
     OBIA_TRY(read_back(ctx, h, ctr, sizeof(h)));   // the one read-back of an import: how many ids are new, the largest id on the seam
     *max_owner_id_out = h[1];
     const int n_new = h[0];
-    if (t->S.next_id + n_new > t->S.id_cap) { set_error("segment id capacity exceeded (%d + %d > %d)", t->S.next_id, n_new, t->S.id_cap); return OBIA_E_NOMEM; }
+    if (t->S.next_id + n_new > t->S.id_cap) {
+        // refused whole: the map entries seam_mark_kernel claimed go back to "not imported", the session's state was not touched
+        hipLaunchKernelGGL(seam_unclaim_kernel, dim3((unsigned)grids::tiler_seam(n_new).x.n), dim3(256), 0, ctx->stream, new_list, n_new, fmap_dev);
+        OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        set_error("segment id capacity exceeded (%d + %d > %d)", t->S.next_id, n_new, t->S.id_cap);
+        return OBIA_E_NOMEM;
+    }
     if (n_new > 0) {
         if (n_new <= SEAM_SORT)
             hipLaunchKernelGGL(seam_assign_sort_kernel, dim3(1), dim3(1024), 0, ctx->stream, new_list, n_new, t->S.next_id, owner_rank, fmap_dev, code_of_dev);
@@ -1051,6 +1062,8 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
     OBIA_HIP_TRY(hipGetLastError());
     return OBIA_OK;
 }
+
+int obia_test_seam_sort_limit(void) { return SEAM_SORT; }
 
 int obia_tiler_finalize(obia_tiler *t, int64_t *n_segments_out) {
     OBIA_TRY(enter(t));

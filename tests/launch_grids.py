@@ -67,6 +67,26 @@ def crossing(name, sizes, vary, axis):
     return lo
 
 
+@functools.lru_cache(maxsize=None)
+def unit(name, sizes, vary, axis):
+    """the largest value of sizes[vary] (the others as given) that `axis` still gives ONE workgroup: what a workgroup takes per trip
+    on that axis -- the column tile of `rast_large`, the side of a pair tile of `seeds_pairs`.  Workgroups do not decrease with a
+    size: bisection."""
+    def g(v):
+        s = list(sizes)
+        s[vary] = v
+        return grid(name, *s)[AXIS[axis] - 2]
+    lo, hi = 1, size_max(names()[name][vary])                  # g(lo) == 1, g(hi) >= 2
+    assert g(lo) == 1 and g(hi) >= 2, (name, sizes, vary, axis)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if g(mid) >= 2:
+            hi = mid
+        else:
+            lo = mid
+    return lo
+
+
 def not_multiple(n, m):
     """n, or the next size that is no multiple of m (the byte-chunking kernels: a head or tail of its own)"""
     return n if m == 1 or n % m else n + 1
@@ -119,6 +139,13 @@ def cases():
     c["boxes_iou_a"] = Case("boxes_iou", (crossing("boxes_iou", (1, 3), 0, "y"), 3), "y", threshold=0)
     c["boxes_iou_b"] = Case("boxes_iou", (2, crossing("boxes_iou", (2, 1), 1, "x")), "x", threshold=1)
     c["points_segments"] = Case("points_segments", (crossing("points_segments", (1,), 0, "x") + 257,), "x")
+    # the seed merge: pair tiles past grid.x; the rasteriser's large shapes: vertices of one shape, column tiles of one band
+    c["seeds_pairs"] = Case("seeds_pairs", (crossing("seeds_pairs", (1,), 0, "x") + 37,), "x")
+    c["rast_band_bin"] = Case("rast_band_bin", (1, crossing("rast_band_bin", (1, 1), 1, "y") + 300), "y")
+    c["rast_large"] = Case("rast_large", (2, crossing("rast_large", (2, 1), 1, "y") + 40), "y")       # two bands: 9 rows
+    # masked SLIC on one tall window (rows of four per workgroup and trip), the seam import of the sharded driver
+    c["slic_mask_pack"] = Case("slic_mask_pack", (crossing("slic_mask_pack", (1, 1), 0, "x") + 150, 1), "x")
+    c["tiler_seam"] = Case("tiler_seam", (crossing("tiler_seam", (1,), 0, "x") + 257,), "x")          # tests/test_gpu_seam_import.py
     return c
 
 

@@ -23,6 +23,7 @@ from tests import crowns_restatement as WR
 from tests import image_restatement as IR
 from tests import launch_grids as LG
 from tests import pointcloud_restatement as PR
+from tests import rasterize_restatement as RR
 from tests import seeds_restatement as SR
 from tests import sharpness_restatement as SH
 from tests import training_restatement as TR
@@ -557,3 +558,143 @@ def test_quickshift_rows(oracle, C):
     call(lib.obia_quickshift_f32_dev, it.data_ptr(), H, W, C, 1.0, 3.0, 10.0, 0.0, 0, nt.data_ptr(), 0, out.ptr, ctypes.byref(n))
     judge(out, g["labels"].astype(I32), "labels")
     assert n.value == g["n_labels"]
+
+
+# ---- the rasteriser's large shapes: vertices of one shape past grid.y, column tiles of one band past grid.y --------------------------
+def rasterize_guarded(xy, ring_offset, ring_shape, values, H, W, fill, want, name):
+    """obia_rasterize_polygons_dev into a guarded raster, judged against `want`; returns rasterize_info()"""
+    from obia_amd.polygons import rasterize_info
+    _lib, lib, c = env()
+    ts = [dev(np.asarray(xy, F64)), dev(np.asarray(ring_offset, I64)), dev(np.asarray(ring_shape, I32)), dev(np.asarray(values, I32))]
+    snaps = [snapshot(t) for t in ts]
+    g = guarded((H, W), I32, POISON, "cuda", 1)
+    call(lib.obia_rasterize_polygons_dev, ts[0].data_ptr(), ts[1].data_ptr(), len(ring_shape), ts[2].data_ptr(), ts[3].data_ptr(), len(values),
+         H, W, fill, g.ptr)
+    judge(g, want, name)
+    assert all(unchanged(t, s) for t, s in zip(ts, snaps))
+    return rasterize_info()
+
+
+def test_rast_band_bin():
+    """one shape of more vertices than the 64 x 256 threads of rast_band_bin_kernel take in one trip: a star, a shuffled (self-
+    intersecting) star whose closing edge and ring boundary lie among the second trip's vertices, a small hole after it"""
+    _, nv = crossed("rast_band_bin")
+    first_trip = LG.crossing("rast_band_bin", (1, 1), 1, "y") - 1
+    H = W = 300
+    rs = np.random.RandomState(33)
+    n_a, n_hole = first_trip * 9 // 16, 85
+    n_b = nv - n_a - n_hole
+    assert n_a < first_trip < n_a + n_b - 100                    # the second trip: the end of the second ring, its closing edge, the hole
+    rings = [RR.star(rs, 150.3, 149.6, n_a, 60, 140), RR.star(rs, 148.7, 151.2, n_b, 20, 130, shuffle=True), RR.star(rs, 150.1, 150.4, n_hole, 3, 9)]
+    xy, off, owner = RR.pack([rings])
+    assert len(xy) == nv and off[2] > first_trip
+    want = RR.burn(xy, off, owner, [6], (H, W), fill=-3)
+    assert 10000 < (want == 6).sum() < 60000
+    info = rasterize_guarded(xy, off, owner, [6], H, W, -3, want, "band bin")
+    assert (info["large"], info["small"]) == (1, 0)
+
+
+def test_rast_large():
+    """a band of more column tiles than grid.y holds: a zigzag over the whole width of a 9-row raster (two bands), a small shape burned
+    before it and one after it inside the tiles only the second trip reaches"""
+    n_bands, w = crossed("rast_large")
+    H, W = 9, w
+    T = LG.unit("rast_large", (1, 1), 1, "y")
+    second = (LG.crossing("rast_large", (1, 1), 1, "y") - 1)     # first column (the shape starts at column 0) of the second trip's tiles
+    assert second % T == 0 and 32 <= W - second <= T
+    xs = np.linspace(0.3, W - 0.3, 40)
+    top = np.stack([xs, np.where(np.arange(40) % 2 == 0, 0.2, 3.8)], 1)
+    bottom = np.stack([xs[::-1], np.where(np.arange(40) % 2 == 0, 8.8, 5.2)], 1)
+    zigzag = np.concatenate([top, bottom])
+    shapes = [[RR.rect(W - 38.2, 0.4, W - 20.1, 8.6)], [zigzag], [RR.rect(W - 30.4, 2.3, W - 5.6, 7.7)]]
+    values = np.array([5, 9, 13], I32)
+    xy, off, owner = RR.pack(shapes)
+    assert len(zigzag) == 80
+    c0, c1 = max(RR._first_centre_ge(zigzag[:, 0].min()) - 1, 0), min(RR._first_centre_ge(zigzag[:, 0].max()), W - 1)
+    assert c0 == 0 and LG.trips("rast_large", (n_bands, c1 - c0 + 1), "y") >= 2
+    want = RR.burn(xy, off, owner, values, (H, W), fill=0)
+    tail = want[:, second:]
+    assert {0, 5, 9, 13} <= set(np.unique(tail).tolist()) and (want[:, :second] == 9).sum() > W
+    info = rasterize_guarded(xy, off, owner, values, H, W, 0, want, "large")
+    assert (info["large"], info["small"]) == (1, 2)
+
+
+# ---- the seed merge: pair tiles past grid.x -------------------------------------------------------------------------------------------
+PAIRS_EPS = 1.25                                                 # several hundred clusters on this case (2.0 merges everything)
+
+
+@pytest.fixture(scope="module")
+def pairs():
+    """n seeds whose pair tiles outnumber the workgroups of walk_pairs, the restated distance matrix (once), and which pairs lie in
+    tiles of index >= grid.x: the second trip's"""
+    from tests.test_seeds_restatement_cpu import WEIGHT, XY_THRESH
+    n, = crossed("seeds_pairs")
+    xs, ys, cost, aff = SR.pixel_centre_case(41, n, 130, 160, 0.5)
+    order = np.random.RandomState(42).permutation(n)
+    xs, ys = np.ascontiguousarray(xs[order]), np.ascontiguousarray(ys[order])
+    inv = SR.inverse6(aff)
+    D = SR.distance_matrix(xs, ys, cost, inv, WEIGHT, XY_THRESH, 12)
+    P = LG.unit("seeds_pairs", (1,), 0, "x")                     # side of a pair tile
+    nt, gx = -(-n // P), LG.grid("seeds_pairs", n)[0]
+    assert nt * (nt + 1) // 2 > gx
+    bi, bj = np.minimum.outer(np.arange(n) // P, np.arange(n) // P), np.maximum.outer(np.arange(n) // P, np.arange(n) // P)
+    tile = bi * nt - bi * (bi - 1) // 2 + (bj - bi)              # tile pairs of the upper triangle, rows first (seeds.hip: tile_of)
+    return dict(n=n, xs=xs, ys=ys, cost=cost, inv=inv, D=D, second=tile >= gx, args=(WEIGHT, XY_THRESH))
+
+
+def test_seeds_pairs_link(pairs):
+    from obia_amd import seeds as S
+    p = pairs
+    want = SR.components(p["D"], PAIRS_EPS)
+    assert 1 < want.max() + 1 < p["n"]
+    # the second trip matters: without the links of its tile pairs the components are others
+    assert not np.array_equal(SR.components(np.where(p["second"], np.float32(np.inf), p["D"]), PAIRS_EPS), want)
+    for prune in (None, False):
+        got = S.merge_clusters(p["xs"], p["ys"], p["cost"], p["inv"], *p["args"], PAIRS_EPS, prune=prune)
+        assert got.dtype == I32 and np.array_equal(got, want), prune
+
+
+def test_seeds_pairs_stats(pairs):
+    from obia_amd import seeds as S
+    p = pairs
+    want = np.array(SR.triu_stats(p["D"]), F32)
+    iu = np.triu_indices(p["n"], 1)
+    dv, first = p["D"][iu], ~p["second"][iu]
+    assert 0 < (~first).sum() < first.sum()
+    assert not np.array_equal(np.array([dv[first].min(), np.median(dv[first]), dv[first].max()], F32), want)     # the second trip matters
+    got = S.pair_stats(p["xs"], p["ys"], p["cost"], p["inv"], *p["args"], 12)
+    assert all(isinstance(v, F32) for v in got) and np.array_equal(np.array(got), want), (got, want)
+
+
+# ---- masked SLIC on one tall window: the mask packing past grid.x, and with it the min/max, feature and max-distance rows --------------
+@pytest.mark.parametrize("W", [16, 18], ids=["vector", "bytes"])
+def test_tall_masked_slic(oracle, W):
+    """one band, a window of more rows than mask_pack4_kernel's workgroups take four at a time; labels before and after connectivity
+    equal the oracle's, as tests/test_gpu_random_parity.py demands at compactness >= 5.  W = 16: the kernel's vector path, 18: bytes"""
+    from obia_amd.segmentation import make_params
+    _lib, lib, c = env()
+    H, _ = crossed("slic_mask_pack")
+    first_trip = LG.crossing("slic_mask_pack", (1, 1), 0, "x") - 1
+    for name, rows in (("slic_band_minmax", H), ("slic_feature_rows", H // 16), ("slic_maxdist", H)):
+        assert LG.trips(name, (rows, 1), "x") >= 2, name
+    rs = np.random.RandomState(50 + W)
+    yy, xx = np.mgrid[0:H, 0:W].astype(F64)
+    img = (300 * np.sin(yy / 9.0) * np.cos(xx / 3.0) + 800 + rs.normal(0, 25, (H, W))).astype(F32)[:, :, None]
+    mask = rs.rand(H, W) >= 0.03
+    mask[1000:1050, 5:14] = False
+    mask[first_trip + 40:first_trip + 90, 3:12] = False          # a block only the second trip packs
+    assert first_trip + 90 < H
+    n_seg = H * W // 64
+    ref, ref_pre, _ = oracle.slic(oracle.normalize(img), n_segments=n_seg, compactness=10.0, max_iter=10, start_label=1, convert2lab=False,
+                                  mask=mask.astype(U8), return_all=True)
+    assert (ref[~mask] == 0).all() and ref[first_trip:].max() > ref[:first_trip].max() > 1000
+    params = make_params(n_segments=n_seg, compactness=10.0, convert2lab=False, normalize_bands=True)
+    it, mt = dev(img), dev(mask.astype(U8))
+    snaps = snapshot(it), snapshot(mt)
+    for fn, want, name in ((lib.obia_slic_assign_only_f32_dev, ref_pre, "before connectivity"), (lib.obia_slic_f32_dev, ref, "labels")):
+        g = guarded((H, W), I32, POISON, "cuda", 1)
+        n = ctypes.c_int(-1)
+        call(fn, it.data_ptr(), H, W, 1, mt.data_ptr(), ctypes.byref(params), g.ptr, ctypes.byref(n))
+        judge(g, np.ascontiguousarray(want, I32), name)
+    assert n.value == len(np.unique(ref[ref >= 1]))
+    assert unchanged(it, snaps[0]) and unchanged(mt, snaps[1])

@@ -148,9 +148,10 @@ def covered_entry_points():
 LEFT_OUT = {
     "obia_tiler_create": "labels_local is the session's persistent label raster, read and written by every later call of the session: "
                          "not the output of one call",
-    "obia_tiler_get_alive": "needs an open two-slab session; the builders of tests/test_gpu_distributed.py reach it only through "
-                            "obia_amd.distributed.ShardedTiler, which allocates the buffer itself",
-    "obia_tiler_import_seam": "as obia_tiler_get_alive: ids_out_dev, fmap_dev and code_of_dev are allocated inside ShardedTiler",
+    "obia_tiler_get_alive": "needs an open session and the host's picture of its ids: guarded in tests/test_gpu_seam_import.py "
+                            "(alive_out_dev between poisoned guards after every import), not by a case of this registry",
+    "obia_tiler_import_seam": "as obia_tiler_get_alive: tests/test_gpu_seam_import.py calls it on a HipTilerEngine's handle with ids_out_dev "
+                              "between poisoned guards and the caller's fmap_dev and code_of_dev pre-filled and compared whole",
     "obia_rasterize_info": "four host integers of a developer aid, no device buffer",
     "obia_slic_default_params": "fills a host struct, no buffer",
 }

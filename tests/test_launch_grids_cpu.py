@@ -124,6 +124,25 @@ def test_every_gpu_case_crosses_its_clamp(case):
     LG.check(LG.cases()[case])
 
 
+def test_a_unit_is_the_last_size_of_one_workgroup():
+    """the column tile of the rasteriser's large shapes and the side of a pair tile of the seed merge, as the wide-shape and pair tests
+    take them: one workgroup up to the unit, two from one more -- and the trips follow the units"""
+    for name, sizes, vary, axis in (("rast_large", (1, 1), 1, "y"), ("seeds_pairs", (1,), 0, "x")):
+        u = LG.unit(name, sizes, vary, axis)
+        at, above = list(sizes), list(sizes)
+        at[vary], above[vary] = u, u + 1
+        k = LG.AXIS[axis] - 2
+        assert u >= 32 and LG.grid(name, *at)[k] == 1 and LG.grid(name, *above)[k] >= 2, (name, u)     # (65 seeds: three pair tiles)
+    T = LG.unit("rast_large", (1, 1), 1, "y")
+    assert T % 32 == 0                                           # a tile is whole 32-bit words of the bit plane
+    cap = LG.grid("rast_large", 1, LG.SIZE_MAX)[1]
+    assert LG.crossing("rast_large", (1, 1), 1, "y") == cap * T + 1
+    P = LG.unit("seeds_pairs", (1,), 0, "x")
+    cap = LG.grid("seeds_pairs", LG.SIZE_MAX)[0]
+    nt = -(-LG.crossing("seeds_pairs", (1,), 0, "x") // P)
+    assert nt * (nt + 1) // 2 > cap >= (nt - 1) * nt // 2       # the first seed count whose tile pairs outnumber the workgroups
+
+
 def test_the_two_grids_that_had_no_clamp_have_one():
     """quickshift's density / parent pass and the CLAHE interpolation put a row count into grid.y: clamped like their neighbours"""
     for name, W in (("quickshift_density", 1), ("image_clahe_interp", 8)):
