@@ -51,6 +51,43 @@ int obia_test_launch_grid_names(char *text, int64_t text_bytes);
  * brings more is ranked by counting.  A constant of the build: no context and no GPU.                                           */
 int obia_test_seam_sort_limit(void);
 
+/* The connectivity stage (obia_amd/csrc/cc.hip: enforce_connectivity_batch) on a batch of label maps, as the tiler calls it but with
+ * every setting the caller's: the same entry layer and argument checks as obia_enforce_connectivity_i32_dev, per problem.
+ *   labels_in     device memory: the label maps back to back in problem order, each H * W int32 in row-major order
+ *   problems      host memory: n_problems rows {H, W, min_size, max_size} (max_size below 1 counts as 1); a problem's pixels start at
+ *                 the sum of H * W of the rows before it
+ *   start_label   0 or 1; start_label - 1 marks a masked pixel
+ *   labels_out    device memory of the same layout; n_labels_out (host, nullable) receives the number of surviving components
+ * The rule it pins: problems do not see each other -- equal labels on the last row of one and the first row of the next stay two
+ * components -- and surviving components (size >= the min_size of their problem, after the cut at its max_size) are numbered from
+ * start_label over the WHOLE batch, in problem order and within a problem in raster order of their first pixel.  A small component
+ * takes the final label of the neighbour the reference's walk meets last; one that never finds a labelled neighbour is the literal 0
+ * (with start_label 1 that is the masked label; with start_label 0 it is also the label of the batch's first surviving component).
+ * OBIA_E_INVALID, before any device work, for a null pointer, n_problems outside 1 .. 65535, a shape below 1 and a batch of 2^31
+ * pixels or more.                                                                                                                  */
+int obia_test_enforce_connectivity_batch_dev(obia_ctx *ctx, const int32_t *labels_in, const int64_t *problems, int n_problems,
+                                             int start_label, int32_t *labels_out, int *n_labels_out);
+
+/* What the last enforce_connectivity_batch of the context decided (through whichever entry point: a SLIC call, the tiler, the stage
+ * alone): reset at the start of that function, filled with profiling on or off, all zero before the first call.  `out` receives
+ * OBIA_TEST_CC_REPORT_FIELDS values, in this order:
+ *    0  problems
+ *    1  pixels
+ *    2  surviving components
+ *    3  small components (below their problem's min_size)
+ *    4  pixels of the small components
+ *    5  components cut at max_size (those of at least max_size pixels in the first count; 0: no cut ran, and 2 .. 4 are the first
+ *       count's -- otherwise they are the counts after the cut)
+ *    6  code[] used (0 / 1): the dense one-word-per-pixel pass
+ *    7  evaluation: 0 none (no small component), 1 walks (cc_small_bfs_kernel), 2 pixel lists (cc_settle_eval_kernel)
+ *    8  side the settle rounds started on: 0 from below, 1 from above (0 when no round ran)
+ *    9  rounds run from below
+ *   10  rounds run from above
+ *   11  visited map reallocated by this call (0 / 1)
+ * A round is one evaluation launch and its read-back.  OBIA_E_INVALID for a null context, a null `out` or n below the field count. */
+#define OBIA_TEST_CC_REPORT_FIELDS 12
+int obia_test_cc_report(obia_ctx *ctx, int64_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

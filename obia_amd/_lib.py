@@ -230,6 +230,9 @@ _TEST_SIGNATURES = {
     "obia_test_launch_grid_names": (_I, [_P, ctypes.c_int64]),
     # the most new ids a seam import ranks by its LDS sort; above it the counting kernel (tests/test_gpu_seam_import.py)
     "obia_test_seam_sort_limit": (_I, []),
+    # the connectivity stage on a batch of problems, and what its last call decided (tests/cc_regimes.py)
+    "obia_test_enforce_connectivity_batch_dev": (_I, [_P, _P, _P, _I, _I, _P, ctypes.POINTER(_I)]),
+    "obia_test_cc_report": (_I, [_P, _P, _I]),
 }
 
 _lib = None

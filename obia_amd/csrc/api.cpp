@@ -1,6 +1,7 @@
 // api.cpp -- the C ABI of libobia_hip.so (include/obia_hip.h): argument checking and orchestration of
 // the kernels for the single-raster operators B1 (SLIC) and B2 (zonal statistics).
 #include "slic.hpp"
+#include "../../include/obia_testing.h"
 
 #include <cmath>
 
@@ -232,6 +233,36 @@ int obia_enforce_connectivity_i32_dev(obia_ctx *ctx, const int32_t *labels_in, i
     int n = 0;
     OBIA_TRY(call_frame(ctx, FRAME_TIMING, [&] { return enforce_connectivity_dev(ctx, labels_in, H, W, min_size, max_size, start_label, labels_out, &n); }));
     if (n_labels_out) *n_labels_out = n;
+    return OBIA_OK;
+}
+
+// ---- include/obia_testing.h: the connectivity stage on a batch, and the record of its last call
+int obia_test_enforce_connectivity_batch_dev(obia_ctx *ctx, const int32_t *labels_in, const int64_t *problems, int n_problems,
+                                             int start_label, int32_t *labels_out, int *n_labels_out) {
+    OBIA_TRY(enter(ctx));
+    if (!labels_in || !labels_out || !problems || n_problems < 1) { set_error("bad arguments"); return OBIA_E_INVALID; }
+    if (n_problems > 65535) { set_error("a batch holds 65535 problems at the most (got %d)", n_problems); return OBIA_E_INVALID; }
+    if (start_label != 0 && start_label != 1) { set_error("start_label should be 0 or 1."); return OBIA_E_INVALID; }
+    std::vector<CcProblem> probs((size_t)n_problems);
+    long long total = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const int64_t *r = problems + 4 * (size_t)p;
+        if (r[0] <= 0 || r[1] <= 0 || r[0] > 0x7fffffffLL || r[1] > 0x7fffffffLL) { set_error("problem %d: bad shape (%lld, %lld)", p, (long long)r[0], (long long)r[1]); return OBIA_E_INVALID; }
+        if (r[2] < INT32_MIN || r[2] > INT32_MAX || r[3] < INT32_MIN || r[3] > INT32_MAX) { set_error("problem %d: min_size / max_size out of range", p); return OBIA_E_INVALID; }
+        probs[(size_t)p] = CcProblem{(int)r[0], (int)r[1], total, (int)r[2], r[3] > 0 ? (int)r[3] : 1};
+        if (r[0] * r[1] > 0x7fffffffLL - total) { set_error("batches of 2^31 pixels or more are not supported"); return OBIA_E_INVALID; }
+        total += r[0] * r[1];
+    }
+    int n = 0;
+    OBIA_TRY(call_frame(ctx, FRAME_TIMING, [&] { return enforce_connectivity_batch(ctx, probs, labels_in, total, start_label, labels_out, &n, nullptr); }));
+    if (n_labels_out) *n_labels_out = n;
+    return OBIA_OK;
+}
+
+int obia_test_cc_report(obia_ctx *ctx, int64_t *out, int n) {
+    if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    if (!out || n < obia_ctx::CC_REPORT_FIELDS) { set_error("cc report: room for %d fields is needed", (int)obia_ctx::CC_REPORT_FIELDS); return OBIA_E_INVALID; }
+    std::copy(ctx->cc_report, ctx->cc_report + obia_ctx::CC_REPORT_FIELDS, out);
     return OBIA_OK;
 }
 

@@ -16,9 +16,6 @@
 //     y-1, first-in first-out) stops at max_size pixels, the raster scan later meets the next unlabelled pixel of the
 //     region and starts another capped BFS from there.  Such components are rare; one lane replays each of them
 //     (cc_split_kernel) and rewrites parent / size so that every piece is a component of its own for the stages below.
-// Not reproduced exactly (DESIGN.md "connectivity"): the bookkeeping of small components that find no labelled
-// neighbour on their first BFS and are re-seeded from a later pixel (replayed here with the same start pixels, but
-// neighbours are classified by root order only).
 #include "slic.hpp"
 
 #include <cstdlib>
@@ -900,6 +897,11 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
     Arena &A = ctx->arena;
     const long long n = total_pix;
     const int np = (int)probs.size();
+    // the record of this call (obia_test_cc_report): {problems, pixels, surviving, small, their pixels, cut at max_size, code[] used,
+    // evaluation (0 none, 1 walks, 2 lists), side the rounds started on, rounds from below, rounds from above, visited map reallocated}
+    int64_t *const rep = ctx->cc_report;
+    std::fill(rep, rep + obia_ctx::CC_REPORT_FIELDS, (int64_t)0);
+    rep[0] = np; rep[1] = n;
     if (np <= 0 || n <= 0 || n > 0x7fffffffLL) { set_error("label batch of %lld pixels not supported", n); return OBIA_E_INVALID; }
     const int mask_label = start_label - 1;
     // (d_probs_in: the caller's copy of `probs` on the device, part of an upload it has queued)
@@ -943,6 +945,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
     hipLaunchKernelGGL(cc_rank_scan_kernel, dim3(3), dim3(1024), 0, ctx->stream, block_sums, nb, counters);
     int hc[8];
     OBIA_TRY(read_back(ctx, hc, counters, sizeof(hc)));
+    rep[5] = hc[6];
     if (hc[6] > 0) {
         // some component reaches max_size: cut it the way the reference's capped BFS does, then count again
         const int n_big = hc[6];
@@ -966,6 +969,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
         OBIA_TRY(read_back(ctx, hc, counters, sizeof(hc)));
     }
     const int n_small = hc[0], small_px = hc[1], n_surv = hc[2];
+    rep[2] = n_surv; rep[3] = n_small; rep[4] = small_px;
     int *small_list = A.get<int>(n_small > 0 ? n_small : 1);
     int *small_qoff = A.get<int>(n_small > 0 ? n_small : 1);
     int *target = A.get<int>(n_small > 0 ? n_small : 1);
@@ -999,6 +1003,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                 const size_t want = (size_t)n + (size_t)n / 8;
                 if (hipMalloc(&ctx->cc_visited, want * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); set_error("out of device memory (visited map of %zu pixels)", want); return OBIA_E_NOMEM; }
                 ctx->cc_visited_px = want;
+                rep[11] = 1;
             }
             OBIA_TRY(fill_async(ctx, ctx->cc_visited, 0, sizeof(int32_t) * ctx->cc_visited_px));
         }
@@ -1024,6 +1029,8 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
         // many small components and the reference's "written back as unset" rule in force (start_label 1): dense rounds for the times,
         // one walk per component for its neighbour (see "dense settle rounds"); OBIA_CC_WORKLIST: developer switch, the work list
         const bool dense = use_code && start_label == 1 && !std::getenv("OBIA_CC_WORKLIST");
+        const int first_side = n_small > 8 * (long long)n_surv ? 1 : 0;   // (0: from below, 1: from above at once)
+        rep[6] = use_code; rep[7] = dense ? 2 : 1; rep[8] = first_side;
         if (dense) {
             int *px_g = A.get<int>(small_px), *ccur = A.get<int>(n_small);
             int4 *px_cn = A.get<int4>(small_px);
@@ -1032,7 +1039,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
             for (auto &P : probs) maxh = std::max(maxh, P.H);
             OBIA_TRY(fill_async(ctx, ccur, 0, sizeof(int) * (size_t)n_small));
             hipLaunchKernelGGL(cc_small_pixels_kernel, dim3(maxh, np), dim3(256), 0, ctx->stream, d_probs, code, small_qoff, ccur, px_g, px_cn, small_px);
-            for (int side = (n_small > 8 * (long long)n_surv ? 1 : 0); side < 2 && !converged; ++side) {
+            for (int side = first_side; side < 2 && !converged; ++side) {
                 OBIA_TRY(fill_async(ctx, tag, 0, sizeof(int) * (size_t)n_small));
                 hipLaunchKernelGGL(cc_settle_init_kernel, dim3(cdiv(n_small, 256)), dim3(256), 0, ctx->stream, small_list, n_small, settle, side);
                 int n_items = n_small;
@@ -1046,6 +1053,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                                        settle, work_in, n_items, work_a, cnt, tag, (int)(round & 0x3fffffff));
                     int n_next = 0;
                     OBIA_TRY(read_back(ctx, &n_next, cnt, sizeof(int)));
+                    ++rep[9 + side];
                     if (n_next == 0) { converged = true; break; }
                     work_in = work_a;
                     std::swap(work_a, work_b);
@@ -1056,7 +1064,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                 hipLaunchKernelGGL(cc_small_target_kernel, dim3(cdiv(n_small, 64)), dim3(64), 0, ctx->stream, d_probs, np, code, newlab, small_list,
                                    small_qoff, settle, queue, visited, target, n_small);
         }
-        for (int side = (n_small > 8 * (long long)n_surv ? 1 : 0); !dense && side < 2 && !converged; ++side) {
+        for (int side = first_side; !dense && side < 2 && !converged; ++side) {
             OBIA_TRY(fill_async(ctx, tag, 0, sizeof(int) * (size_t)n_small));
             hipLaunchKernelGGL(cc_settle_init_kernel, dim3(cdiv(n_small, 256)), dim3(256), 0, ctx->stream, small_list, n_small, settle, side);
             int n_items = n_small;
@@ -1078,6 +1086,7 @@ int enforce_connectivity_batch(obia_ctx *ctx, const std::vector<CcProblem> &prob
                                        cnt, tag, (int)(round & 0x3fffffff));
                 int n_next = 0;
                 OBIA_TRY(read_back(ctx, &n_next, cnt, sizeof(int)));
+                ++rep[9 + side];
                 if (n_next == 0) { converged = true; break; }
                 work_in = work_a;
                 std::swap(work_a, work_b);

@@ -116,6 +116,10 @@ struct obia_ctx {
     int32_t *cc_visited = nullptr;
     size_t cc_visited_px = 0;
     bool cc_visited_dirty = false;
+    // what the last enforce_connectivity_batch decided (obia_test_cc_report, include/obia_testing.h lists the fields): reset at its
+    // start, host stores only
+    enum { CC_REPORT_FIELDS = 12 };
+    int64_t cc_report[CC_REPORT_FIELDS] = {};
     char *up_buf = nullptr;          // pinned ring for small host -> device tables (upload_async): no stream sync per upload
     size_t up_bytes = 0, up_used = 0;
     obia::PlanBlob plan;             // the open planning phase's tables (one upload per phase)
