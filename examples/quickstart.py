@@ -9,6 +9,7 @@
                                 crowns are this package's own: the reference has no consumer of the two)
     box_nms(), assign_boxes(), dissolve_by_box() -> superpixels joined with tree boxes (notebooks/deepfor2.ipynb, assign_fid)
     points_to_rasters(), create_objects(pointcloud=) -> CHM and density from points, the point-cloud columns (segment_statistics.py:332-389)
+    normalize_heights()      -> heights above ground from raw elevations     (main.py:26, read_lidar(..., hag=True))
     classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
@@ -31,6 +32,7 @@ from obia_amd.cost import chm_gradient                             # noqa: E402
 from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, canonical_seeds, grow_crowns   # noqa: E402
 from obia_amd import box_nms, assign_boxes, dissolve_by_box        # noqa: E402
 from obia_amd import points_to_rasters                             # noqa: E402
+from obia_amd.pointcloud import normalize_heights                  # noqa: E402
 
 
 class Image:
@@ -127,6 +129,17 @@ def main():
     print(f"points_to_rasters(): {n_pts} points, {int(np.isfinite(rasters['chm']).sum())} CHM pixels, {len(lidar_seeds['id'])} tree tops; "
           f"create_objects(pointcloud=): median ch {float(lidar_table['ch'].median()):.1f} m, pai {float(lidar_table['pai'].median()):.2f}, "
           f"fhd {float(lidar_table['fhd'].median()):.2f}, mean intensity {float(lidar_table['mean_intensity'].median()):.0f}")
+
+    # 5d. the same cloud as a LAS tile delivers it -- elevations and a ground class, no heights: normalize_heights() finds the ground
+    #     under every point (main.py:26, read_lidar(..., hag=True)) and hands on the cloud that points_to_rasters() takes
+    terrain = 120.0 + 0.02 * (cloud["X"] - 300000.0) + 3.0 * np.sin((cloud["Y"] - 2200000.0) / 40.0)
+    is_ground = cloud["HeightAboveGround"] < 0.3
+    raw = {"X": cloud["X"], "Y": cloud["Y"], "Z": terrain + np.where(is_ground, 0.0, cloud["HeightAboveGround"]),
+           "Classification": np.where(is_ground, 2, 5).astype(np.uint8), "Intensity": cloud["Intensity"]}
+    normalized = normalize_heights(raw, count=3, max_distance=10.0)
+    raw_rasters = points_to_rasters(normalized, image.affine_transformation, (H, W))
+    print(f"normalize_heights(): {int(is_ground.sum())} ground points, median height {float(np.nanmedian(normalized['HeightAboveGround'])):.1f} m, "
+          f"{int(np.isfinite(raw_rasters['chm']).sum())} CHM pixels")
 
     # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:

@@ -20,5 +20,6 @@ from .boxes import box_overlaps, assign_boxes, dissolve_by_box, box_iou, box_nms
 from .boxes import predictions_to_map, save_predictions_to_gpkg, mosaic_predictions  # noqa: F401
 from . import pointcloud  # noqa: F401
 from .pointcloud import as_points, PointRasters, points_to_rasters, SegmentPoints, segment_point_stats  # noqa: F401
+from .pointcloud import GroundIndex, height_above_ground, height_above_dtm, normalize_heights  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h and include/obia_points.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h and include/obia_ground.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -220,6 +220,13 @@ _POINTS_SIGNATURES = {
     "obia_points_segments_dev": (_I, [_P, _P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P]),
     "obia_points_segment_columns_dev": (_I, [_P, _P, _P, _P, _P, _P, _I32, _I32, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
 }
+# include/obia_ground.h: height above ground, a ninth table (tests/test_ground_restatement_cpu.py, tests/test_gpu_ground.py pin it; the
+# eight above stay as they are)
+GROUND_MAX_COUNT = 8      # OBIA_GROUND_MAX_COUNT: the most neighbours a query averages
+_GROUND_SIGNATURES = {
+    "obia_ground_query_dev": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _L, _L, _L, _D, _P, _P, _P, _L, _I32, _D, _P, _P, _P]),
+    "obia_ground_dtm_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -257,7 +264,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
-                                   + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_TEST_SIGNATURES.items())):
+                                   + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
+                                   + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -63,6 +63,7 @@ inline Grid seeds_pairs(long long n) {                                          
     return one_axis(strided(nt * (nt + 1) / 2, 256 * 16));
 }
 inline Grid points_segments(long long n) { return one_axis(strided(cdivl(n, OBIA_POINTS_CHUNK), 1280)); }
+inline Grid ground_query(long long n) { return one_axis(strided(cdivl(n, 256), 4096)); }   // a query per lane; its ring walk is long: 16 workgroups per CU of 256
 inline Grid boxes_walk(long long n) { return one_axis(strided(n, 4096)); }              // a box per workgroup and trip
 inline Grid quickshift_flat(long long npx) { return one_axis(strided(cdivl(npx, 256 * 4), 65535)); }
 inline Grid quickshift_gauss(long long n) { return one_axis(strided(cdivl(n, 256), 65535)); }   // n = pixels x bands
@@ -143,6 +144,7 @@ inline const Named *table(int *count) {
     OBIA_GRID1(seeds_gauss, "npx"),
     OBIA_GRID1(seeds_pairs, "n"),
     OBIA_GRID1(points_segments, "n"),
+    OBIA_GRID1(ground_query, "n"),
     OBIA_GRID1(boxes_walk, "n"),
     OBIA_GRID1(quickshift_flat, "npx"),
     OBIA_GRID1(quickshift_gauss, "n"),

@@ -7,8 +7,13 @@ points to the segments of a label raster and form the five point-cloud columns o
 
 The radiometric pair is the reference's (segment_statistics.py:332-389: ``np.mean`` / ``np.var`` of ``Intensity``).  Its structural
 code is gone (:326-329 raises), so the structural columns are this project's definitions: one vertical profile per segment -- the
-segment footprint is the voxel column -- in bins of ``dz``.  Heights are heights above ground as given; reading EPT / LAZ, deriving
-them from raw ``Z``, float intensities and return-number weighting are out of scope.
+segment footprint is the voxel column -- in bins of ``dz``.  These functions take heights above ground as given; reading EPT / LAZ,
+float intensities and return-number weighting are out of scope.
+
+Heights above ground come from raw ``Z`` through :class:`GroundIndex` / ``height_above_ground`` (the ``count`` nearest
+ground-classified points, inverse-distance weighted) or ``height_above_dtm`` (a terrain raster), and ``normalize_heights`` hands the
+result on as a cloud (include/obia_ground.h).  The definitions are modelled on PDAL's ``filters.hag_nn`` and
+``filters.hag_dtm`` -- what pyforestscan's ``read_lidar(..., hag=True)`` runs -- and are NOT compared with PDAL anywhere.
 
 Both accumulators keep their state on the device and take a cloud in any number of ``add`` calls: every sum is an integer, so the
 result is the same bits for every order and every cut.  NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out; there is no
@@ -310,3 +315,238 @@ def segment_point_stats(points, labels, affine_transformation, dz, z_max=None, s
     res["profile"] = sp.profile(as_array=as_array)
     res["counters"] = sp.counters()
     return res
+
+
+# ---------------------------------------------------------------------------------------------- height above ground (obia_ground.h)
+def _raw_fields(pointcloud, names, optional=()):
+    """``({name: values}, is_torch)`` of the named fields of a raw cloud (a dict, a structured array, or a list whose first element is
+    one): all tensors or all arrays, one-dimensional and of one length; a CPU tensor is refused.  Touches no device."""
+    if isinstance(pointcloud, (list, tuple)):
+        if not pointcloud:
+            raise ValueError("the point cloud list is empty")
+        pointcloud = pointcloud[0]
+    f = {name: _field(pointcloud, name) for name in tuple(names) + tuple(optional)}
+    missing = [name for name in names if f[name] is None]
+    if missing:
+        raise ValueError(f"the point cloud has no {', '.join(missing)} field")
+    f = {name: v for name, v in f.items() if v is not None}
+    is_t = any(_device.is_torch(v) for v in f.values())
+    if is_t and not all(_device.is_torch(v) for v in f.values()):
+        raise ValueError("the fields of a point cloud must be all tensors or all arrays")
+    if is_t:
+        _device.device_of(None, *f.values())                                 # refuses CPU tensors
+    else:
+        f = {name: np.asarray(v) for name, v in f.items()}
+    n = tuple(f[names[0]].shape)
+    if len(n) != 1 or any(tuple(v.shape) != n for v in f.values()):
+        raise ValueError("the fields of a point cloud must be one-dimensional and of one length")
+    return f, is_t
+
+
+def _check_query(count, max_distance):
+    c = int(count)
+    if c != count or not 1 <= c <= _lib.GROUND_MAX_COUNT:
+        raise ValueError(f"count must be an integer in 1 .. {_lib.GROUND_MAX_COUNT}, got {count!r}")
+    md = float(max_distance)
+    if not md >= 0.0:
+        raise ValueError(f"max_distance must not be negative (0: no limit), got {max_distance!r}")
+    return c, md
+
+
+def _ground_side(x0, x1, y0, y1, ng):
+    """The cell side of the grid over ``ng`` ground points in [x0, x1] x [y0, y1]: about one point per cell.  With w, h the extent a
+    side s gives at most (w / s + 2) (h / s + 2) = w h / s^2 + 2 (w + h) / s + 4 cells; s >= sqrt(w h / ng) and s >= 2 (w + h) / ng
+    bound that by 2 ng + 4 for every extent and aspect ratio -- a single point, one (x, y), a line.  s is also at least 2^-29 of the
+    largest coordinate, so that |v / s| <= 2^29 and cell indices fit (seeds._grid)."""
+    w, h = x1 - x0, y1 - y0
+    side = max(math.sqrt(w) * math.sqrt(h) / math.sqrt(ng), 2.0 * (w + h) / ng, max(abs(x0), abs(x1), abs(y0), abs(y1)) * 2.0 ** -29)
+    if not math.isfinite(side):
+        raise ValueError("the extent of the ground set is not finite")
+    return side if side > 0.0 else 1.0
+
+
+class GroundIndex:
+    """The ground points of a cloud on a uniform grid, for any number of nearest-neighbour queries (include/obia_ground.h).
+
+    ``ground``: a cloud with ``X``, ``Y``, ``Z`` (a dict of arrays or of CUDA tensors, or a structured array).  Points with a
+    non-finite coordinate or elevation are dropped (``dropped`` counts them) and the index of a ground point is its position among
+    the kept ones; no point left is a ``ValueError``.  ``n_ground``, ``side`` (the cell side) and ``shape`` = (ncy, ncx) describe
+    the grid: ``ncy * ncx <= 4 * n_ground + 16`` for every extent, so memory is O(n_ground).
+
+    The ground height of a query is the elevation of the nearest ground point (``count=1``) or the inverse-squared-distance mean of
+    the ``count`` nearest, ties to the lower index, among those within ``max_distance`` (0: no limit); NaN when there is none or the
+    query is not finite.  Every result is the same bits for every order and every cut of the queries."""
+
+    def __init__(self, ground, *, ctx=None):
+        _need_torch()
+        f, is_t = _raw_fields(ground, ("X", "Y", "Z"))
+        self._build(f["X"], f["Y"], f["Z"], is_t, ctx)
+
+    @classmethod
+    def from_cloud(cls, pointcloud, ground_class=2, *, ctx=None):
+        """the index of the points of ``pointcloud`` whose ``Classification`` equals ``ground_class`` (2: ASPRS ground)"""
+        _need_torch()
+        f, is_t = _raw_fields(pointcloud, ("X", "Y", "Z"), optional=("Classification",))
+        if "Classification" not in f:
+            raise ValueError("the point cloud has no Classification field to take the ground from: pass the ground points")
+        keep = f["Classification"] == int(ground_class)
+        self = cls.__new__(cls)
+        self._build(f["X"][keep], f["Y"][keep], f["Z"][keep], is_t, ctx)
+        return self
+
+    @staticmethod
+    def _admit(ng):
+        if ng == 0:
+            raise ValueError("the ground set is empty: no point with finite X, Y and Z")
+        if ng >= 2 ** 31:
+            raise NotImplementedError("a ground set has fewer than 2^31 points")
+
+    def _build(self, x, y, z, is_t, ctx):
+        dev = _device.device_of(ctx, x, y, z)
+        n_in = int(x.shape[0])
+        if not is_t:                                                         # on the host: an empty set is refused before any device use
+            x, y, z = (np.asarray(v).astype(np.float64, copy=False) for v in (x, y, z))
+            keep = np.isfinite(x) & np.isfinite(y) & np.isfinite(z)
+            if not keep.all():
+                x, y, z = x[keep], y[keep], z[keep]
+            self._admit(int(x.shape[0]))
+        x, y, z = (_device.as_dev(v, torch.float64, dev) for v in (x, y, z))
+        if is_t:
+            keep = torch.isfinite(x) & torch.isfinite(y) & torch.isfinite(z)
+            if not bool(keep.all()):
+                x, y, z = x[keep], y[keep], z[keep]
+        ng = int(x.shape[0])
+        self._admit(ng)
+        # the cell side: about one point per cell, (w / s + 2) (h / s + 2) <= 2 ng + 4 cells whatever the extent and the aspect, and
+        # at least 2^-29 of the largest coordinate, so that |v / side| < 2^30 (seeds._grid)
+        side = _ground_side(float(x.min()), float(x.max()), float(y.min()), float(y.max()), ng)
+        lib, c = _device.begin(dev, ctx)
+        cx = torch.empty(ng, dtype=torch.int32, device=x.device)
+        cy = torch.empty(ng, dtype=torch.int32, device=x.device)
+        while True:
+            _lib.check(lib.obia_seedtab_cells_dev(c.handle, x.data_ptr(), y.data_ptr(), ng, side, cx.data_ptr(), cy.data_ptr()))
+            cx0, cy0 = int(cx.min()), int(cy.min())
+            ncx, ncy = int(cx.max()) - cx0 + 1, int(cy.max()) - cy0 + 1
+            if ncx * ncy <= 4 * ng + 16:
+                break
+            side *= 2.0                                                      # not reached by the side above; the bound holds regardless
+        key = (cy.to(torch.int64) - cy0) * ncx + (cx.to(torch.int64) - cx0)
+        skey, order = torch.sort(key, stable=True)
+        self._gx, self._gy, self._gz = x[order].contiguous(), y[order].contiguous(), z[order].contiguous()
+        self._gidx = order.to(torch.int32).contiguous()
+        self._cell_start = torch.searchsorted(skey, torch.arange(ncx * ncy + 1, dtype=torch.int64, device=x.device)).to(torch.int32).contiguous()
+        self._cell0 = (cx0, cy0)
+        self.ctx, self.dev, self._tensor_in = ctx, dev, is_t
+        self.n_ground, self.side, self.shape, self.dropped = ng, side, (ncy, ncx), n_in - ng
+
+    def _query(self, x, y, z, count, max_distance, with_m=False):
+        """zg (n) float64, hag (n) float32 or None, m (n) uint8 or None of device tensors x, y float64 and z float64 or None"""
+        n = int(x.shape[0])
+        zg = torch.empty(n, dtype=torch.float64, device=x.device)
+        hag = None if z is None else torch.empty(n, dtype=torch.float32, device=x.device)
+        m = torch.empty(n, dtype=torch.uint8, device=x.device) if with_m else None
+        if n:
+            lib, c = _device.begin(self.dev, self.ctx)
+            _lib.check(lib.obia_ground_query_dev(c.handle, self._gx.data_ptr(), self._gy.data_ptr(), self._gz.data_ptr(), self._gidx.data_ptr(),
+                                                 self.n_ground, self._cell_start.data_ptr(), self.shape[1], self.shape[0], self._cell0[0],
+                                                 self._cell0[1], self.side, x.data_ptr(), y.data_ptr(), None if z is None else z.data_ptr(), n,
+                                                 count, max_distance, zg.data_ptr(), None if hag is None else hag.data_ptr(),
+                                                 None if m is None else m.data_ptr()))
+        return zg, hag, m
+
+    def ground_z(self, x, y, count=1, max_distance=0.0):
+        """(n) float64: the ground height under the points ``(x, y)``"""
+        count, md = _check_query(count, max_distance)
+        f, is_t = _raw_fields({"X": x, "Y": y}, ("X", "Y"))
+        xd, yd = (_device.as_dev(f[k], torch.float64, self.dev) for k in ("X", "Y"))
+        return _device.out(self._query(xd, yd, None, count, md)[0], is_t)
+
+    def neighbours(self, x, y, count=1, max_distance=0.0):
+        """(n) uint8: how many ground points the height of each query was formed from"""
+        count, md = _check_query(count, max_distance)
+        f, is_t = _raw_fields({"X": x, "Y": y}, ("X", "Y"))
+        xd, yd = (_device.as_dev(f[k], torch.float64, self.dev) for k in ("X", "Y"))
+        return _device.out(self._query(xd, yd, None, count, md, with_m=True)[2], is_t)
+
+    def height_above_ground(self, pointcloud, count=1, max_distance=0.0):
+        """(n) float32: ``Z`` -- the raw elevation, never ``HeightAboveGround`` -- minus the ground height under each point"""
+        count, md = _check_query(count, max_distance)
+        f, is_t = _raw_fields(pointcloud, ("X", "Y", "Z"))
+        xd, yd, zd = (_device.as_dev(f[k], torch.float64, self.dev) for k in ("X", "Y", "Z"))
+        return _device.out(self._query(xd, yd, zd, count, md)[1], is_t)
+
+    def to_raster(self, shape, affine_transformation, count=1, max_distance=0.0):
+        """The terrain model: (H, W) float32 of the ground height at the pixel centres of ``affine_transformation`` = [a, b, d, e,
+        xoff, yoff], ``x = a (c + 0.5) + b (r + 0.5) + xoff`` and ``y`` likewise in float64.  NumPy unless the index was built from
+        tensors."""
+        count, md = _check_query(count, max_distance)
+        H, W = _raster_shape(shape)
+        t, _ = _forward(affine_transformation)
+        if H * W >= 2 ** 31:
+            raise NotImplementedError("a terrain raster has fewer than 2^31 pixels")
+        d = self._gx.device
+        cc = (torch.arange(W, dtype=torch.float64, device=d) + 0.5).reshape(1, W)
+        rr = (torch.arange(H, dtype=torch.float64, device=d) + 0.5).reshape(H, 1)
+        x = ((cc * t[0] + rr * t[1]) + t[4]).reshape(-1).contiguous()
+        y = ((cc * t[2] + rr * t[3]) + t[5]).reshape(-1).contiguous()
+        zg = self._query(x, y, None, count, md)[0]
+        return _device.out(zg.to(torch.float32).reshape(H, W), self._tensor_in)
+
+
+def _as_index(pointcloud, ground, ground_class, ctx):
+    if isinstance(ground, GroundIndex):
+        return ground
+    if ground is None:
+        return GroundIndex.from_cloud(pointcloud, ground_class=ground_class, ctx=ctx)
+    return GroundIndex(ground, ctx=ctx)
+
+
+def height_above_ground(pointcloud, ground=None, *, ground_class=2, count=1, max_distance=0.0, ctx=None):
+    """(n) float32 heights of the points of ``pointcloud`` (``X``, ``Y``, raw ``Z``) above the ``count`` nearest ground points:
+    ``ground=None`` takes the ground from the cloud's own ``Classification == ground_class``; otherwise ``ground`` is a
+    :class:`GroundIndex` or a cloud of ground points.  A ground point comes out +-0 unless a lower-indexed ground point shares its
+    ``(x, y)`` with another elevation."""
+    _need_torch()
+    _check_query(count, max_distance)
+    _raw_fields(pointcloud, ("X", "Y", "Z"))
+    return _as_index(pointcloud, ground, ground_class, ctx).height_above_ground(pointcloud, count=count, max_distance=max_distance)
+
+
+def height_above_dtm(pointcloud, dtm, affine_transformation, ctx=None):
+    """(n) float32 heights of the points of ``pointcloud`` above the terrain raster ``dtm`` (H, W) float32 with
+    ``affine_transformation`` = [a, b, d, e, xoff, yoff]: raw ``Z`` minus the pixel that contains the point (the pixel rule of
+    include/obia_points.h); NaN outside the raster and on a pixel that is not finite."""
+    _need_torch()
+    f, is_t = _raw_fields(pointcloud, ("X", "Y", "Z"))
+    shape = tuple(dtm.shape)
+    if len(shape) != 2 or 0 in shape:
+        raise ValueError(f"dtm must be a non-empty (H, W) raster, got shape {shape}")
+    H, W = _raster_shape(shape)
+    _, inv = _forward(affine_transformation)
+    dev = _device.device_of(ctx, f["X"], dtm)
+    x, y, z = (_device.as_dev(f[k], torch.float64, dev) for k in ("X", "Y", "Z"))
+    r = _device.as_dev(dtm, torch.float32, dev)
+    n = int(x.shape[0])
+    hag = torch.empty(n, dtype=torch.float32, device=x.device)
+    if n:
+        lib, c = _device.begin(dev, ctx)
+        _lib.check(lib.obia_ground_dtm_dev(c.handle, x.data_ptr(), y.data_ptr(), z.data_ptr(), n, inv, r.data_ptr(), H, W, None, hag.data_ptr()))
+    return _device.out(hag, is_t)
+
+
+def normalize_heights(pointcloud, ground=None, *, dtm=None, affine_transformation=None, ground_class=2, count=1, max_distance=0.0, ctx=None):
+    """A raw cloud as ``{"X", "Y", "HeightAboveGround"}`` (and ``"Intensity"`` when it has one), ready for ``points_to_rasters``,
+    ``segment_point_stats`` and ``create_objects(pointcloud=)``: heights above ``dtm`` (with its ``affine_transformation``) when one
+    is given, above the nearest ground points as in :func:`height_above_ground` otherwise."""
+    _need_torch()
+    f, _ = _raw_fields(pointcloud, ("X", "Y", "Z"), optional=("Intensity",))
+    if dtm is not None:
+        if ground is not None:
+            raise ValueError("give the ground points or a dtm, not both")
+        hag = height_above_dtm(pointcloud, dtm, affine_transformation, ctx=ctx)
+    else:
+        hag = height_above_ground(pointcloud, ground, ground_class=ground_class, count=count, max_distance=max_distance, ctx=ctx)
+    out = {"X": f["X"], "Y": f["Y"], "HeightAboveGround": hag}
+    if "Intensity" in f:
+        out["Intensity"] = f["Intensity"]
+    return out
