@@ -62,6 +62,8 @@ const char *obia_last_error(void);
 /* Create a context on `device_id` with its own HIP stream / on a caller-owned hipStream_t. */
 obia_ctx *obia_create(int device_id);
 obia_ctx *obia_create_on_stream(int device_id, void *hip_stream);
+/* A context that an open tiler session holds (obia_tiler_create, below) is NOT destroyed: the call sets the error text and returns,
+ * nothing the session uses is freed.  obia_tiler_destroy comes first, then obia_destroy.                                         */
 void obia_destroy(obia_ctx *ctx);
 int obia_synchronize(obia_ctx *ctx);
 /* bytes of device workspace currently held by the context */
@@ -424,7 +426,11 @@ int obia_tiled_slic_seeded_f32(obia_ctx *ctx, const float *img_hwc, const uint8_
  * and registers the segments it imported with obia_tiler_set_segments (their pixel counts as seen locally;
  * 0xffffffff for a segment that continues beyond the halo and can therefore never be "within" a window).
  * tile rows are GLOBAL indices; row_parity -1 = all rows, 0/1 = rows of that parity (white_order 1).
- * The context must not be used for other calls while a session is open.                                         */
+ * A session HOLDS its context from obia_tiler_create to obia_tiler_destroy: its persistent state lives in the
+ * context's workspace, which every other call would reset.  While it is open every entry point that takes that
+ * context -- a second obia_tiler_create included, which returns null -- answers OBIA_E_INVALID with the text
+ * "context is held by an open tiler session" and touches nothing; the session's own entry points are unaffected.
+ * Work for other calls needs a context of its own.                                                                */
 typedef struct obia_tiler obia_tiler;
 obia_tiler *obia_tiler_create(obia_ctx *ctx, const float *img_local, const uint8_t *mask_local, int H_local, int W, int C,
                               int H_global, int row0, const obia_tiling_params *tiling, const obia_slic_params *params,

@@ -88,6 +88,23 @@ int obia_test_enforce_connectivity_batch_dev(obia_ctx *ctx, const int32_t *label
 #define OBIA_TEST_CC_REPORT_FIELDS 12
 int obia_test_cc_report(obia_ctx *ctx, int64_t *out, int n);
 
+/* A used context with KNOWN contents (tests/test_gpu_workspace_history.py): every workspace buffer comes from a bump allocator that
+ * keeps its memory between calls, so an operator must write each buffer before it reads it.  Waits for the context's stream and
+ * side stream, makes the arena ONE block of at least reserve_bytes (it allocates, then resets: several blocks are merged, so the
+ * next call's frame neither frees nor grows as long as the operator needs no more than the block), and sets every byte of the block
+ * -- its whole size, not reserve_bytes -- to `byte`.  The pinned host areas are filled too: the read-back buffer, the upload ring
+ * when no upload is queued, the deferred read-back's landing area when none is pending.  The visited map of the connectivity
+ * stage is NOT touched: its contract is "all zero between calls", and visited_nonzero_out (nullable) receives the number of its
+ * words that are not zero -- 0 when the map does not exist or is flagged dirty (the next call clears it).  held_out (nullable)
+ * receives obia_workspace_bytes().  Plain fills only: hipMemsetAsync and host memset.
+ * OBIA_E_INVALID for a null context, a byte outside 0 .. 255, a negative reserve_bytes and a context held by an open tiler session
+ * (nothing is touched); OBIA_E_NOMEM when the block cannot be allocated.                                                          */
+int obia_test_poison_workspace_dev(obia_ctx *ctx, int64_t reserve_bytes, int byte, int64_t *held_out, int64_t *visited_nonzero_out);
+
+/* The visited map's count alone, as obia_test_poison_workspace_dev reports it, with nothing written: waits for the context's
+ * streams and counts.  Reads only, so a context held by a session is served.  OBIA_E_INVALID for a null context or output.       */
+int obia_test_visited_nonzero(obia_ctx *ctx, int64_t *visited_nonzero_out);
+
 #ifdef __cplusplus
 }
 #endif

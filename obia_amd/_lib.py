@@ -240,6 +240,10 @@ _TEST_SIGNATURES = {
     # the connectivity stage on a batch of problems, and what its last call decided (tests/cc_regimes.py)
     "obia_test_enforce_connectivity_batch_dev": (_I, [_P, _P, _P, _I, _I, _P, ctypes.POINTER(_I)]),
     "obia_test_cc_report": (_I, [_P, _P, _I]),
+    # a used context with known contents: the workspace filled with one byte, the visited map's non-zero words counted
+    # (tests/test_gpu_workspace_history.py)
+    "obia_test_poison_workspace_dev": (_I, [_P, ctypes.c_int64, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "obia_test_visited_nonzero": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib = None

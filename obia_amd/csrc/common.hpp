@@ -52,6 +52,10 @@ class Arena {
     void rewind(const Mark &m);
     size_t capacity() const;
     bool failed() const { return failed_; }
+    // Test support (obia_test_poison_workspace_dev): makes the arena ONE block of at least `bytes` -- allocates, then resets, which
+    // merges several blocks into one -- so that the next frame's reset() neither frees nor grows.  Returns the block (null: the
+    // allocation failed) and its whole size.  Nothing may be running on the arena's memory.
+    char *one_block(size_t bytes, size_t *size_out);
 
   private:
     struct Block { char *p; size_t size; size_t used; };
@@ -139,6 +143,9 @@ struct obia_ctx {
     hipEvent_t grp_fork = nullptr, grp_join = nullptr;
     int spatial_residency[4] = {0, 0, 0, 0};   // workgroups of slic_spatial_kernel<4 (i + 1)> the device holds at once; 0: not asked yet
     int sweep_residency[64] = {};              // the same of the colour-sweep kernel variants (slic_sweep.hip: sweep_residency)
+    // the open tiler session (obia_tiler_create sets it, obia_tiler_destroy clears it): its persistent state lives in the arena, so
+    // enter() refuses every call but the session's own while it is set
+    const void *session = nullptr;
 };
 
 namespace obia {
@@ -213,8 +220,11 @@ template <typename... P> bool shared_start(int n_out, P... ps) {
 // ---- the entry layer: what every extern "C" function is made of besides its own argument checks and its body ----------------------
 
 // Prologue, the first statement of every entry point that takes a context (the tiler's go through their session's): refuses a null
-// context (OBIA_E_INVALID) before any HIP call and selects the context's device.
-int enter(obia_ctx *ctx);
+// context (OBIA_E_INVALID) before any HIP call and selects the context's device.  A context held by an open tiler session is refused
+// too (OBIA_E_INVALID, "context is held by an open tiler session") unless `session` is that session: a frame of another call would
+// reset -- and, with more than one block, free -- the arena the session's state lives in.
+extern const char *const SESSION_HELD;   // the text of that refusal
+int enter(obia_ctx *ctx, const void *session = nullptr);
 
 // Error path of every entry point that returns with its work done: nothing this library queued may still be running when the caller
 // gets the error back -- it is about to free the buffers.  Waits for the context's stream and its side stream, returns rc.

@@ -92,6 +92,17 @@ void Arena::release() {
     blocks_.clear();
 }
 
+char *Arena::one_block(size_t bytes, size_t *size_out) {
+    reset();
+    if (blocks_.size() != 1 || blocks_[0].size < bytes) {
+        if (!alloc(bytes)) return nullptr;   // (a second block when the first is too small ...)
+        reset();                             // (... which this merges with it: one block of the high-water mark and an eighth)
+    }
+    if (blocks_.size() != 1 || blocks_[0].size < bytes) { set_error("workspace hipMalloc of %zu bytes failed", bytes); return nullptr; }
+    *size_out = blocks_[0].size;
+    return blocks_[0].p;
+}
+
 size_t Arena::capacity() const {
     size_t t = 0;
     for (auto &b : blocks_) t += b.size;
@@ -355,8 +366,11 @@ int upload_async(obia_ctx *ctx, void *dev_dst, const void *host_src, size_t byte
     return OBIA_OK;
 }
 
-int enter(obia_ctx *ctx) {
+const char *const SESSION_HELD = "context is held by an open tiler session";
+
+int enter(obia_ctx *ctx, const void *session) {
     if (!ctx) { set_error("null context"); return OBIA_E_INVALID; }
+    if (ctx->session && ctx->session != session) { set_error("%s", SESSION_HELD); return OBIA_E_INVALID; }
     if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", ctx->device); return OBIA_E_HIP; }
     return OBIA_OK;
 }
@@ -464,6 +478,7 @@ obia_ctx *obia_create_on_stream(int device_id, void *hip_stream) { return create
 
 void obia_destroy(obia_ctx *ctx) {
     if (!ctx) return;
+    if (ctx->session) { set_error("%s: obia_tiler_destroy comes first, the context was not destroyed", SESSION_HELD); return; }
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     ctx->arena.release();
@@ -497,6 +512,43 @@ int obia_test_clear_ranges_dev(obia_ctx *ctx, void *const *dev_ptrs, const int64
         for (int i = 0; i < n; ++i) OBIA_TRY(clr.add(dev_ptrs[i], values[i], (size_t)bytes[i]));
         return clr.flush();
     });
+}
+
+// the words of the visited map that are not zero (0: there is no map, or it is flagged dirty and the next call clears it)
+static int visited_nonzero(obia_ctx *ctx, int64_t *out) {
+    *out = 0;
+    if (!ctx->cc_visited || ctx->cc_visited_dirty || ctx->cc_visited_px == 0) return OBIA_OK;
+    std::vector<int32_t> h(ctx->cc_visited_px);
+    OBIA_HIP_TRY(hipMemcpy(h.data(), ctx->cc_visited, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+    *out = (int64_t)(h.size() - (size_t)std::count(h.begin(), h.end(), 0));
+    return OBIA_OK;
+}
+
+int obia_test_poison_workspace_dev(obia_ctx *ctx, int64_t reserve_bytes, int byte, int64_t *held_out, int64_t *visited_nonzero_out) {
+    OBIA_TRY(enter(ctx));   // (refuses a context held by a session: its state lives in the arena)
+    if (byte < 0 || byte > 255 || reserve_bytes < 0) { set_error("poison: byte %d outside 0..255 or negative reserve", byte); return OBIA_E_INVALID; }
+    (void)quiesce(ctx, 0);
+    ctx->plan.drop();
+    size_t size = 0;
+    char *block = ctx->arena.one_block((size_t)reserve_bytes, &size);
+    if (!block) return OBIA_E_NOMEM;
+    OBIA_HIP_TRY(hipMemsetAsync(block, byte, size, ctx->stream));
+    OBIA_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->pinned) memset(ctx->pinned, byte, ctx->pinned_bytes);
+    if (ctx->up_buf && ctx->up_used == 0) memset(ctx->up_buf, byte, ctx->up_bytes);
+    if (ctx->defer_buf && !ctx->defer_pending) memset(ctx->defer_buf, byte, sizeof(unsigned long long) * 513);
+    int64_t nz = 0;
+    OBIA_TRY(visited_nonzero(ctx, &nz));
+    if (held_out) *held_out = (int64_t)ctx->arena.capacity();
+    if (visited_nonzero_out) *visited_nonzero_out = nz;
+    return OBIA_OK;
+}
+
+int obia_test_visited_nonzero(obia_ctx *ctx, int64_t *visited_nonzero_out) {
+    if (!ctx || !visited_nonzero_out) { set_error("null context or null output"); return OBIA_E_INVALID; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", ctx->device); return OBIA_E_HIP; }
+    (void)quiesce(ctx, 0);
+    return visited_nonzero(ctx, visited_nonzero_out);
 }
 
 int64_t obia_workspace_bytes(obia_ctx *ctx) { return ctx ? (int64_t)ctx->arena.capacity() : 0; }

@@ -941,7 +941,7 @@ using namespace obia;
 // starts -- a failure in between must not return while that pass can still read the caller's raster and write arena memory.
 static int enter(obia_tiler *t) {
     if (!t) { set_error("null tiler"); return OBIA_E_INVALID; }
-    return enter(t->ctx);
+    return enter(t->ctx, t);
 }
 
 extern "C" {
@@ -949,21 +949,23 @@ extern "C" {
 obia_tiler *obia_tiler_create(obia_ctx *ctx, const float *img_local, const uint8_t *mask_local, int H_local, int W, int C,
                               int H_global, int row0, const obia_tiling_params *tiling, const obia_slic_params *params,
                               int32_t *labels_local, int extra_ids) {
-    if (enter(ctx) != OBIA_OK) return nullptr;
+    if (enter(ctx) != OBIA_OK) return nullptr;   // (a context that another session holds is refused here: no frame begins)
     frame_begin(ctx, FRAME_TIMING);   // the session is one frame: obia_tiler_destroy() ends it
     obia_tiler *t = new obia_tiler();
     t->ctx = ctx;
     if (tiler_init(ctx, t->S, img_local, mask_local, H_local, W, C, H_global, row0, tiling, params, labels_local,
                    extra_ids < 0 ? 0 : extra_ids) != OBIA_OK) { delete t; return nullptr; }
+    ctx->session = t;   // from here to obia_tiler_destroy the context serves this session alone (common.hpp: enter)
     return t;
 }
 
 void obia_tiler_destroy(obia_tiler *t) {
     if (!t) return;
-    (void)enter(t->ctx);
+    (void)enter(t->ctx, t);
     (void)quiesce(t->ctx, 0);   // (a session dropped half-way may have left the white feature pass on its side stream)
     if (t->seam_buf) (void)hipFree(t->seam_buf);
     resolve_timing(t->ctx);
+    t->ctx->session = nullptr;
     delete t;
 }
 

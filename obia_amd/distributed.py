@@ -64,14 +64,20 @@ class HipTilerEngine:
         self.tp = _lib.TilingParams()
         self.tp.tile_size, self.tp.buffer, self.tp.white_order = int(tile_size), int(buffer), 1
         self.tp.crown_radius, self.tp.pixel_width, self.tp.pixel_height = float(crown_radius), float(pixel_size[0]), float(pixel_size[1])
-        self.ctx = ctx or _lib.default_context(img.device.index or 0)
+        # A session holds its context until close(): the library refuses every other call on it (include/obia_hip.h).  Without a
+        # caller's context the engine therefore makes one of its own -- never the default context every wrapper shares.
+        self.h = None
+        self._own_ctx = ctx is None
+        self.ctx = _lib.Context(img.device.index or 0) if ctx is None else ctx
         self.lib = _lib.load()
         torch.cuda.current_stream(img.device).synchronize()
         self.h = self.lib.obia_tiler_create(self.ctx.handle, img.data_ptr(), mask.data_ptr() if mask is not None else None,
                                             H, W, C, int(Hg), int(row0), ctypes.byref(self.tp), ctypes.byref(self.params),
                                             self.G.data_ptr(), int(extra_ids))
         if not self.h:
-            raise ValueError(_lib.last_error())
+            msg = _lib.last_error()
+            self.close()
+            raise ValueError(msg)
         self.picks = None
         if rule == _lib.SEEDING_SKIMAGE:
             self.picks = MaskSeedPickSource()      # (kept alive for the session's lifetime: the library calls it from every pass)
@@ -119,9 +125,19 @@ class HipTilerEngine:
         _lib.check(self.lib.obia_tiler_set_alive(self.h, a.data_ptr(), int(a.numel())))
 
     def close(self):
-        if self.h:
+        """ends the session (the context serves other calls again) and closes the context the engine made for itself"""
+        if getattr(self, "h", None):
             self.lib.obia_tiler_destroy(self.h)
             self.h = None
+        if getattr(self, "_own_ctx", False):
+            self._own_ctx = False
+            self.ctx.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class TorchComm:

@@ -247,7 +247,8 @@ def test_config4_eight_slab_partition_equals_whole_raster(raster_c4):
             torch.cuda.set_device(0)
             r = comm.rank
             ctx = _lib.Context(0)
-            t = ShardedTiler(img[r * R * T:(r + 1) * R * T], None, H, R, T, B, 5, (0.5, 0.5), ctx=ctx, comm=comm, compactness=10.0)
+            # (the session holds a context of its own until t.close(): `ctx` serves the statistics call made while it is still open)
+            t = ShardedTiler(img[r * R * T:(r + 1) * R * T], None, H, R, T, B, 5, (0.5, 0.5), comm=comm, compactness=10.0)
             labels, n = t.run()
             lab[r * R * T:(r + 1) * R * T] = labels
             ext_img, dense, n_owned = t.owned_labels()

@@ -156,13 +156,8 @@ def test_tiler_with_a_corner_length_that_is_not_a_whole_number_of_pixels(oracle,
     assert n == n_ref and np.array_equal(lab.cpu().numpy(), ref)
 
 
-def test_tiler_batch_with_orphan_pixels_equals_the_oracle(oracle):
-    """A valid pixel that no window reaches keeps the label of the sweep before, which the tiler's sweeps do not store: the batch's
-    orphan flag -- read after the connectivity stage since round 4 (slic_sweeps_settle) -- makes the batch
-    run again with every sweep storing, and the connectivity stage with it.  Islands of a few valid pixels far from every seed
-    (farther than two grid steps) produce such pixels in black and in white tiles."""
-    from obia_amd.tiling import create_tiled_segments
-    from oracle import tiler
+def orphan_islands_case():
+    """256 x 300 x 4, a block that gets the seeds and islands of two and three valid pixels 80 pixels away from it: (img, mask, keywords)"""
     rs = np.random.RandomState(12)
     H, W = 256, 300
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
@@ -171,7 +166,17 @@ def test_tiler_batch_with_orphan_pixels_equals_the_oracle(oracle):
     mask[:, :70] = True                       # a block that gets the seeds ...
     mask[10:250:40, 150:152] = True           # ... and islands 80 pixels away from it, two pixels wide
     mask[30:250:40, 260:263] = True
-    kw = dict(tile_size=128, buffer=16, crown_radius=6.0, pixel_size=(1.0, 1.0), compactness=10.0)
+    return img, mask, dict(tile_size=128, buffer=16, crown_radius=6.0, pixel_size=(1.0, 1.0), compactness=10.0)
+
+
+def test_tiler_batch_with_orphan_pixels_equals_the_oracle(oracle):
+    """A valid pixel that no window reaches keeps the label of the sweep before, which the tiler's sweeps do not store: the batch's
+    orphan flag -- read after the connectivity stage since round 4 (slic_sweeps_settle) -- makes the batch
+    run again with every sweep storing, and the connectivity stage with it.  Islands of a few valid pixels far from every seed
+    (farther than two grid steps) produce such pixels in black and in white tiles."""
+    from obia_amd.tiling import create_tiled_segments
+    from oracle import tiler
+    img, mask, kw = orphan_islands_case()
     from obia_amd import _lib
     ctx = _lib.Context(0)
     ref, n_ref = tiler.create_tiled_segments(img, mask, **kw)

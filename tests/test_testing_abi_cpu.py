@@ -18,7 +18,8 @@ def test_the_table_is_the_header():
     syms = declared("obia_testing.h")
     assert syms == set(_lib._TEST_SIGNATURES) == {"obia_test_clear_ranges_dev", "obia_test_sweep_plan", "obia_test_launch_grid",
                                                        "obia_test_launch_grid_names", "obia_test_seam_sort_limit",
-                                                       "obia_test_enforce_connectivity_batch_dev", "obia_test_cc_report"}
+                                                       "obia_test_enforce_connectivity_batch_dev", "obia_test_cc_report",
+                                                       "obia_test_poison_workspace_dev", "obia_test_visited_nonzero"}
     assert not syms & set(_lib._SIGNATURES) and not syms & declared("obia_hip.h")
     lib = _lib.load()
     for name, (res, args) in _lib._TEST_SIGNATURES.items():
