@@ -10,6 +10,7 @@
     box_nms(), assign_boxes(), dissolve_by_box() -> superpixels joined with tree boxes (notebooks/deepfor2.ipynb, assign_fid)
     points_to_rasters(), create_objects(pointcloud=) -> CHM and density from points, the point-cloud columns (segment_statistics.py:332-389)
     normalize_heights()      -> heights above ground from raw elevations     (main.py:26, read_lidar(..., hag=True))
+    classify_ground()        -> the ground class of an unclassified cloud     (the host run of PDAL before main.py)
     classify()               -> class and margin per segment, class raster    (obia.classification.classify, classify.py:68-175)
 
 Needs an MI355X (there is no CPU path).  Writes quickstart_objects.csv, quickstart_segments.geojson and segments.gpkg next to itself.
@@ -32,7 +33,7 @@ from obia_amd.cost import chm_gradient                             # noqa: E402
 from obia_amd import make_chm_seeds, make_density_seeds, make_canonical_seeds, canonical_seeds, grow_crowns   # noqa: E402
 from obia_amd import box_nms, assign_boxes, dissolve_by_box        # noqa: E402
 from obia_amd import points_to_rasters                             # noqa: E402
-from obia_amd.pointcloud import normalize_heights                  # noqa: E402
+from obia_amd.pointcloud import classify_ground, normalize_heights  # noqa: E402
 
 
 class Image:
@@ -140,6 +141,15 @@ def main():
     raw_rasters = points_to_rasters(normalized, image.affine_transformation, (H, W))
     print(f"normalize_heights(): {int(is_ground.sum())} ground points, median height {float(np.nanmedian(normalized['HeightAboveGround'])):.1f} m, "
           f"{int(np.isfinite(raw_rasters['chm']).sum())} CHM pixels")
+
+    # 5e. ... and as a drone delivers it -- no ground class at all: classify_ground() finds the ground points with a progressive
+    #     morphological filter, and normalize_heights() goes on from there
+    unclassified = {k: v for k, v in raw.items() if k != "Classification"}
+    found = classify_ground(unclassified, cell_size=1.0)
+    renormalized = normalize_heights(found, count=3, max_distance=10.0)
+    agree = float(((found["Classification"] == 2) == is_ground).mean())
+    print(f"classify_ground(): {int((found['Classification'] == 2).sum())} ground points found, {100 * agree:.1f} % of the points as labelled above, "
+          f"median height {float(np.nanmedian(renormalized['HeightAboveGround'])):.1f} m")
 
     # 6. classification (needs scikit-learn for the training): label segments from points, train on them, predict every segment
     try:

