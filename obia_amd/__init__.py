@@ -22,5 +22,8 @@ from . import pointcloud  # noqa: F401
 from .pointcloud import as_points, PointRasters, points_to_rasters, SegmentPoints, segment_point_stats  # noqa: F401
 from .pointcloud import GroundIndex, height_above_ground, height_above_dtm, normalize_heights  # noqa: F401
 from .pointcloud import grey_erosion, grey_dilation, grey_opening, pmf_schedule, GroundFilter, ground_filter, classify_ground  # noqa: F401
+from . import adjacency  # noqa: F401
+from .adjacency import SegmentGraph, segment_graph, compact_roots, relabel, merge_by_threshold, dissolve_by_class  # noqa: F401
+from .adjacency import merge_similar, context_columns  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h and include/obia_groundfilter.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h and include/obia_adjacency.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -243,6 +243,23 @@ _GROUNDFILTER_BINDINGS = {
     "obia_gf_threshold_dev": (_I, [_P, _P, _I, _I, ctypes.POINTER(_I32), ctypes.POINTER(_D), _I, _P, _P, _P, _P]),
     "obia_gf_classify_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
+# include/obia_adjacency.h: the segment adjacency graph, an eleventh table (tests/test_adjacency_restatement_cpu.py,
+# tests/test_gpu_adjacency.py and tests/test_gpu_adjacency_buffers.py pin it; the ten above stay as they are).  Named _BINDINGS for the
+# reason given above _GROUNDFILTER_BINDINGS: tests/workspace_history.py has no rows for these entry points, and
+# tests/test_gpu_adjacency_buffers.py runs every one of them on a poisoned workspace instead.
+ADJ_TILE_H, ADJ_TILE_W = 16, 32   # OBIA_ADJ_TILE_H, OBIA_ADJ_TILE_W: the tile one workgroup counts into its LDS table
+ADJ_TABLE = 2048          # OBIA_ADJ_TABLE: slots of that table
+ADJ_WORK = 4              # OBIA_ADJ_WORK: int32 of scratch the write pass asks for
+_ADJACENCY_BINDINGS = {
+    "obia_adj_tile_count_dev": (_I, [_P, _P, _I, _I, _I32, _I32, _P]),
+    "obia_adj_tile_write_dev": (_I, [_P, _P, _I, _I, _I32, _I32, _P, _L, _P, _P, _P]),
+    "obia_adj_edge_d2_dev": (_I, [_P, _P, _P, _I32, _L, _P, _I, _P]),
+    "obia_adj_neighbor_stats_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _I, _P, _P, _P, _P]),
+    "obia_adj_class_border_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _I, _P]),
+    "obia_adj_best_neighbor_dev": (_I, [_P, _P, _P, _I32, _L, _P, _P, _P]),
+    "obia_adj_components_dev": (_I, [_P, _P, _P, _I32, _L, _P, _P]),
+    "obia_adj_relabel_dev": (_I, [_P, _P, _L, _I32, _I32, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -285,7 +302,7 @@ def load():
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
                                    + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
-                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_TEST_SIGNATURES.items())):
+                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_ADJACENCY_BINDINGS.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "../../include/obia_adjacency.h"
 #include "../../include/obia_groundfilter.h"
 #include "../../include/obia_points.h"
 #include "../../include/obia_training.h"
@@ -99,6 +100,9 @@ inline Grid cost_edge_count(long long H, long long W) {
 // band of OBIA_MORPH_COL_LANES columns in x and a run of OBIA_MORPH_COL_TILE rows per trip in y
 inline Grid morph_rows(long long H, long long W) { return Grid{whole(cdivl(W, OBIA_MORPH_ROW_TILE)), strided(H, GRID_Y_MAX)}; }
 inline Grid morph_cols(long long H, long long W) { return Grid{whole(cdivl(W, OBIA_MORPH_COL_LANES)), strided(cdivl(H, OBIA_MORPH_COL_TILE), 8192)}; }
+// the tile passes of the segment graph (adjacency.hip): a workgroup keeps its LDS table over the tiles it walks on both axes, so a
+// few thousand workgroups clear a table once each
+inline Grid adj_tiles(long long H, long long W) { return Grid{strided(cdivl(W, OBIA_ADJ_TILE_W), 64), strided(cdivl(H, OBIA_ADJ_TILE_H), 128)}; }
 // IoU matrix: 256 boxes of b per workgroup and trip in x, a box of a in y
 inline Grid boxes_iou(long long na, long long nb) { return Grid{strided(cdivl(nb, 256), 4096), strided(na, 4096)}; }
 // large shapes of the rasteriser: a shape (bin) or a row band (large) in x, its vertices / columns in y
@@ -171,6 +175,7 @@ inline const Named *table(int *count) {
     OBIA_GRID2(cost_edge_count, "H W"),
     OBIA_GRID2(morph_rows, "H W"),
     OBIA_GRID2(morph_cols, "H W"),
+    OBIA_GRID2(adj_tiles, "H W"),
     OBIA_GRID2(boxes_iou, "na nb"),
     OBIA_GRID2(rast_band_bin, "n_large max_nv"),
     OBIA_GRID2(rast_large, "n_bands max_w"),
