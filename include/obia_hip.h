@@ -430,7 +430,11 @@ int obia_tiled_slic_seeded_f32(obia_ctx *ctx, const float *img_hwc, const uint8_
  * context's workspace, which every other call would reset.  While it is open every entry point that takes that
  * context -- a second obia_tiler_create included, which returns null -- answers OBIA_E_INVALID with the text
  * "context is held by an open tiler session" and touches nothing; the session's own entry points are unaffected.
- * Work for other calls needs a context of its own.                                                                */
+ * Work for other calls needs a context of its own.
+ * Stream: obia_tiler_create queues its clears and returns without waiting for the context's stream; every other entry point of a
+ * session that queues work (run, set_segments, get_alive, set_alive, import_seam, finalize, destroy) has waited for the stream when
+ * it returns -- the caller reads labels_local and the outputs on a stream of its own.  obia_tiler_next_id and obia_tiler_set_seeding
+ * touch host fields only.  A set_segments of no segments and an import of an empty seam return at once.                    */
 typedef struct obia_tiler obia_tiler;
 obia_tiler *obia_tiler_create(obia_ctx *ctx, const float *img_local, const uint8_t *mask_local, int H_local, int W, int C,
                               int H_global, int row0, const obia_tiling_params *tiling, const obia_slic_params *params,
@@ -474,7 +478,9 @@ int obia_tiler_import_seam(obia_tiler *t, const int32_t *codes_dev, int n, int m
  *   offsets_out int32 [ceil(H * W / 4096) + 1]: peaks before each 4096-pixel chunk; the last entry is the count
  *   n_peaks_out (host): the count -- the one read-back.
  * The gather writes the peaks in row-major order (np.where): row, col, smooth[row, col], plane[row, col]; `smooth` is
- * `plane` itself when sigma == 0.  Outputs hold n_peaks entries.                                                     */
+ * `plane` itself when sigma == 0.  Outputs hold n_peaks entries.
+ * Stream: the peaks call, the link and the stats return a host value and have waited for the context's stream when they return; the
+ * gather and the matrix are asynchronous on it, the caller waits (obia_synchronize) before it reads their outputs.         */
 int obia_seeds_peaks_dev(obia_ctx *ctx, const float *plane, int H, int W, double sigma, int min_dist_px, float threshold,
                          float *smooth_out, uint8_t *flags_out, int32_t *offsets_out, int64_t *n_peaks_out);
 int obia_seeds_peaks_gather_dev(obia_ctx *ctx, const float *plane, const float *smooth, const uint8_t *flags, const int32_t *offsets,

@@ -228,11 +228,8 @@ _GROUND_SIGNATURES = {
     "obia_ground_dtm_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
 # include/obia_groundfilter.h: the ground filter, a tenth table (tests/test_groundfilter_restatement_cpu.py, tests/test_gpu_groundfilter.py and
-# tests/test_gpu_groundfilter_buffers.py pin it; the nine above stay as they are).  Its name does not end in _SIGNATURES on purpose:
-# tests/test_workspace_history_cpu.py compares every name of such a table with the rows of tests/workspace_history.py, and the change
-# that added this table left that file as it was.  A later change that may touch it renames the table to _GROUNDFILTER_SIGNATURES and
-# adds the five rows; until then tests/test_gpu_groundfilter_buffers.py runs every entry point on a poisoned workspace, which is what
-# the rows would ask for.
+# tests/test_gpu_groundfilter_buffers.py pin it; the nine above stay as they are).  Its name ends in _BINDINGS, not _SIGNATURES, for
+# the history of it: tests/workspace_history.py reads the tables of both endings and has the five rows.
 MORPH_MAX_RADIUS = 127    # OBIA_MORPH_MAX_RADIUS: the largest half-width of a grey filter's window
 GF_MAX_STEPS = 16         # OBIA_GF_MAX_STEPS: the most steps of a schedule
 MORPH_ROW_TILE, MORPH_COL_TILE, MORPH_COL_LANES = 1024, 128, 32   # OBIA_MORPH_*: the run of a line pass's workgroup on either axis
@@ -244,9 +241,8 @@ _GROUNDFILTER_BINDINGS = {
     "obia_gf_classify_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
 # include/obia_adjacency.h: the segment adjacency graph, an eleventh table (tests/test_adjacency_restatement_cpu.py,
-# tests/test_gpu_adjacency.py and tests/test_gpu_adjacency_buffers.py pin it; the ten above stay as they are).  Named _BINDINGS for the
-# reason given above _GROUNDFILTER_BINDINGS: tests/workspace_history.py has no rows for these entry points, and
-# tests/test_gpu_adjacency_buffers.py runs every one of them on a poisoned workspace instead.
+# tests/test_gpu_adjacency.py and tests/test_gpu_adjacency_buffers.py pin it; the ten above stay as they are).  Named _BINDINGS like
+# _GROUNDFILTER_BINDINGS; tests/workspace_history.py has the eight rows.
 ADJ_TILE_H, ADJ_TILE_W = 16, 32   # OBIA_ADJ_TILE_H, OBIA_ADJ_TILE_W: the tile one workgroup counts into its LDS table
 ADJ_TABLE = 2048          # OBIA_ADJ_TABLE: slots of that table
 ADJ_WORK = 4              # OBIA_ADJ_WORK: int32 of scratch the write pass asks for

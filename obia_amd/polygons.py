@@ -141,6 +141,7 @@ def polygonize(labels, affine_transformation=None, start_label=0, ctx=None):
     ring_hole = torch.empty((max(R, 1),), dtype=torch.uint8, device=dev)
     ring_off = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
     xy = torch.empty((max(V, 1), 2), dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()   # ring_off's zeros are in place before the context's stream writes the offsets over them
     _lib.check(lib.obia_polygon_rings_i32_dev(c.handle, lab.data_ptr(), H, W, int(start_label), R, V, ring_label.data_ptr(),
                                               ring_hole.data_ptr(), ring_off.data_ptr(), xy.data_ptr(), ctypes.byref(n_r),
                                               ctypes.byref(n_v)))

@@ -77,13 +77,15 @@ def zonal_stats(raw, labels, bands=None, start_label=1, n_labels=None, ctx=None,
     cnt = _buffer(r, (n_labels,), np.int64)
     mean, var = _buffer(r, (n_labels, B), np.float64), _buffer(r, (n_labels, B), np.float64)
     mn, mx = _buffer(r, (n_labels, B), np.float32), _buffer(r, (n_labels, B), np.float32)
+    if moments:
+        # filled on torch's stream before `begin` waits for it: a fill queued between the two calls could land on the second call's result
+        skew, kurt = _buffer(r, (n_labels, B), np.float64, float("nan")), _buffer(r, (n_labels, B), np.float64, float("nan"))
     lib, c = _device.begin(dev, ctx, host=not is_t)
     stats = lib.obia_zonal_stats_f32_dev if is_t else lib.obia_zonal_stats_f32
     _lib.check(stats(c.handle, ptr(r), ptr(lab), H, W, C, _lib.np_ptr(barr), B, n_labels, int(start_label), ptr(cnt), ptr(mean),
                      ptr(var), ptr(mn), ptr(mx)))
     out = {"count": cnt, "mean": mean, "variance": var, "min": mn, "max": mx, "bands": bl}
     if moments:
-        skew, kurt = _buffer(r, (n_labels, B), np.float64, float("nan")), _buffer(r, (n_labels, B), np.float64, float("nan"))
         pivots = (ptr(mean),) if is_t else ()              # (the host entry point keeps the means of its own first pass)
         second = lib.obia_zonal_moments_f32_dev if is_t else lib.obia_zonal_moments_f32
         _lib.check(second(c.handle, ptr(r), ptr(lab), H, W, C, _lib.np_ptr(barr), B, n_labels, int(start_label), *pivots, ptr(skew),

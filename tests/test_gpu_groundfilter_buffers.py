@@ -1,8 +1,9 @@
 """The entry points of include/obia_groundfilter.h through guarded states, outputs and scratch planes (tests/guarded.py, both poisons)
 with every input off a 16-byte boundary (tests/offset_views.py): the results bit for bit, no stray write, no element of an output left
 unwritten (scratch planes are exempt), the inputs unchanged, two runs equal; what is refused writes nothing; and every entry point on
-a context whose workspace was filled by obia_test_poison_workspace_dev equals the same call on a fresh context -- the case the
-decision table of tests/workspace_history.py would hold for these entry points.  Every entry point of the table is exercised here."""
+a context whose workspace was filled by obia_test_poison_workspace_dev equals the same call on a fresh context -- the case
+"body:groundfilter" of the decision table of tests/workspace_history.py runs run_all / judge_all too.  Every entry point of the table
+is exercised here."""
 import ctypes
 import functools
 

@@ -168,6 +168,21 @@ ROWS = {
     "obia_points_segment_columns_dev": exempt(ONE_KERNEL + " (points.hip names the arena nowhere)"),
     "obia_ground_query_dev": exempt(ONE_KERNEL + " (ground.hip names the arena nowhere)"),
     "obia_ground_dtm_dev": exempt(ONE_KERNEL + " (ground.hip names the arena nowhere)"),
+    # ---- include/obia_groundfilter.h: groundfilter.hip names the arena nowhere, every state, scratch plane and counter is the caller's ----
+    "obia_gf_cell_min_dev": run("body:groundfilter", ONE_KERNEL + " (the key plane is the caller's state, cleared by the caller and added to)"),
+    "obia_gf_cell_min_finish_dev": run("body:groundfilter", ONE_KERNEL),
+    "obia_morph_filter_dev": run("body:groundfilter", ONE_KERNEL + " (`tmp` is the caller's, written whole by the row pass before the column pass reads it)"),
+    "obia_gf_threshold_dev": run("body:groundfilter", ONE_KERNEL + " (`tmp0` / `tmp1` are the caller's, each written whole by the pass before the one that reads it)"),
+    "obia_gf_classify_dev": run("body:groundfilter", ONE_KERNEL + " (the four counters are the caller's state, cleared by the caller and added to)"),
+    # ---- include/obia_adjacency.h: adjacency.hip names the arena nowhere, every buffer is the caller's ------------------------------------
+    "obia_adj_tile_count_dev": run("body:adjacency", ONE_KERNEL + " (the tile's table lives in LDS, cleared by its workgroup)"),
+    "obia_adj_tile_write_dev": run("body:adjacency", ONE_KERNEL + " (`work`, the caller's four words, by one fill before the pass; read back after it)"),
+    "obia_adj_edge_d2_dev": run("body:adjacency", ONE_KERNEL),
+    "obia_adj_neighbor_stats_dev": run("body:adjacency", ONE_KERNEL),
+    "obia_adj_class_border_dev": run("body:adjacency", ONE_KERNEL),
+    "obia_adj_best_neighbor_dev": run("body:adjacency", ONE_KERNEL),
+    "obia_adj_components_dev": run("body:adjacency", ONE_KERNEL + " (root_out is written whole by adj_iota_kernel before the link kernel reads it)"),
+    "obia_adj_relabel_dev": run("body:adjacency", ONE_KERNEL),
     # ---- include/obia_testing.h ---------------------------------------------------------------------------------------------------
     "obia_test_clear_ranges_dev": exempt("takes no workspace: the table of ranges is the clear kernel's argument, passed by value"),
     "obia_test_sweep_plan": exempt(NO_CONTEXT),
@@ -194,10 +209,10 @@ ARENA_FILES = {
 
 
 def bound_entry_points():
-    """every name of every signature table of obia_amd/_lib.py"""
+    """every name of every signature table of obia_amd/_lib.py: the tables named *_SIGNATURES and the two named *_BINDINGS"""
     from obia_amd import _lib
     names = []
-    for table in (v for k, v in vars(_lib).items() if k.endswith("_SIGNATURES") and isinstance(v, dict)):
+    for table in (v for k, v in vars(_lib).items() if k.endswith(("_SIGNATURES", "_BINDINGS")) and isinstance(v, dict)):
         names += list(table)
     return names
 
