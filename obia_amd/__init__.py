@@ -25,5 +25,7 @@ from .pointcloud import grey_erosion, grey_dilation, grey_opening, pmf_schedule,
 from . import adjacency  # noqa: F401
 from .adjacency import SegmentGraph, segment_graph, compact_roots, relabel, merge_by_threshold, dissolve_by_class  # noqa: F401
 from .adjacency import merge_similar, context_columns  # noqa: F401
+from . import shapes  # noqa: F401
+from .shapes import ShapeTable, segment_shapes, pair_shapes, shape_columns  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h and include/obia_adjacency.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h, include/obia_adjacency.h and include/obia_shapes.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -256,6 +256,16 @@ _ADJACENCY_BINDINGS = {
     "obia_adj_components_dev": (_I, [_P, _P, _P, _I32, _L, _P, _P]),
     "obia_adj_relabel_dev": (_I, [_P, _P, _L, _I32, _I32, _P, _P]),
 }
+# include/obia_shapes.h: the raster pass of the shape columns, a twelfth table.  Named _ENTRIES on purpose: tests/workspace_history.py
+# and tests/test_gpu_stream_order.py collect every table named *_SIGNATURES or *_BINDINGS and demand a row of their own decision
+# tables for each entry, and those files stay as they are.  tests/test_shapes_restatement_cpu.py, tests/test_gpu_shapes.py and
+# tests/test_gpu_shapes_buffers.py carry the equivalent checks for this table: header == table, a null context, guarded outputs, a
+# poisoned workspace, stream order.
+SHAPE_SUMS = 7            # OBIA_SHAPE_SUMS: columns of the sums table (n, sum r, sum c, sum r^2, sum c^2, sum r c, perimeter)
+SHAPE_TABLE = 1024        # OBIA_SHAPE_TABLE: slots of the LDS table of one workgroup
+_SHAPE_ENTRIES = {
+    "obia_shape_sums_dev": (_I, [_P, _P, _I, _I, _I32, _I32, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -298,7 +308,8 @@ def load():
         for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
                                    + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
-                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_ADJACENCY_BINDINGS.items()) + list(_TEST_SIGNATURES.items())):
+                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_ADJACENCY_BINDINGS.items()) + list(_SHAPE_ENTRIES.items())
+                                   + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:
