@@ -27,5 +27,7 @@ from .adjacency import SegmentGraph, segment_graph, compact_roots, relabel, merg
 from .adjacency import merge_similar, context_columns  # noqa: F401
 from . import shapes  # noqa: F401
 from .shapes import ShapeTable, segment_shapes, pair_shapes, shape_columns  # noqa: F401
+from . import merging  # noqa: F401
+from .merging import RegionState, fusion_cost, merge_pairs, merge_regions, multiresolution_merge  # noqa: F401
 
 __version__ = "0.1.0"

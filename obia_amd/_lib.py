@@ -1,5 +1,5 @@
 """ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h, include/obia_adjacency.h and include/obia_shapes.h; the test suite's own entry points: include/obia_testing.h).
+include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h, include/obia_adjacency.h, include/obia_shapes.h and include/obia_merging.h; the test suite's own entry points: include/obia_testing.h).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -266,6 +266,17 @@ SHAPE_TABLE = 1024        # OBIA_SHAPE_TABLE: slots of the LDS table of one work
 _SHAPE_ENTRIES = {
     "obia_shape_sums_dev": (_I, [_P, _P, _I, _I, _I32, _I32, _P, _P]),
 }
+# include/obia_merging.h: region merging on the graph alone (fusion cost, pair merge, contraction of the CSR), a thirteenth table.
+# Named _ENTRIES for the reason given above _SHAPE_ENTRIES; tests/test_merging_restatement_cpu.py, tests/test_gpu_merging.py and
+# tests/test_gpu_merging_buffers.py carry the equivalent checks for this table.
+MERGE_ROW_CAP = 2048      # OBIA_MERGE_ROW_CAP: gathered entries of a row one workgroup sorts in LDS; a longer row is sorted in the scratch
+_MERGE_ENTRIES = {
+    "obia_merge_cost_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _P, _P, _I, _P, _P, _P, _D, _D, _P]),
+    "obia_merge_pairs_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "obia_merge_contract_rows_dev": (_I, [_P, _P, _I32, _L, _P, _P]),
+    "obia_merge_contract_count_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _P, _P, _P, _P, _P]),
+    "obia_merge_contract_write_dev": (_I, [_P, _I32, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+}
 # include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
@@ -309,7 +320,7 @@ def load():
                                    + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
                                    + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
                                    + list(_GROUNDFILTER_BINDINGS.items()) + list(_ADJACENCY_BINDINGS.items()) + list(_SHAPE_ENTRIES.items())
-                                   + list(_TEST_SIGNATURES.items())):
+                                   + list(_MERGE_ENTRIES.items()) + list(_TEST_SIGNATURES.items())):
             try:
                 fn = getattr(lib, name)
             except AttributeError:

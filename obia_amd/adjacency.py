@@ -202,6 +202,50 @@ class SegmentGraph:
         taken as a truth value, is set on i->j or on j->i.  Pseudo entries link nothing."""
         return self._out(self._components(link))
 
+    def _contract(self, root):
+        """the three calls of include/obia_merging.h, CONTRACTION, with torch's prefix sums between them; ``root`` (N) int32 on the
+        device, already checked"""
+        N, nnz, dev = self.n_labels, self.nnz, self._indptr.device
+        raw = torch.empty(N, dtype=torch.int64, device=dev)
+        lib, c, head = self._begin()
+        _lib.check(lib.obia_merge_contract_rows_dev(c.handle, _ptr(self._indptr), N, nnz, _ptr(root), _ptr(raw)))
+        raw_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        raw_ptr[1:] = torch.cumsum(raw, 0)
+        key_work = torch.empty(nnz, dtype=torch.int32, device=dev)
+        border_work = torch.empty(nnz, dtype=torch.int64, device=dev)
+        cursor = torch.empty(N, dtype=torch.int32, device=dev)
+        count = torch.empty(N, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()                 # raw_ptr is complete before the context's stream reads it
+        _lib.check(lib.obia_merge_contract_count_dev(*head, _ptr(self._border), N, nnz, _ptr(root), _ptr(raw_ptr), _ptr(key_work), _ptr(border_work),
+                                                     _ptr(cursor), _ptr(count)))
+        indptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        indptr[1:] = torch.cumsum(count.to(torch.int64), 0)
+        total = int(indptr[-1])                                      # (waits for torch's stream: indptr is complete)
+        neighbor = torch.empty(total, dtype=torch.int32, device=dev)
+        border = torch.empty(total, dtype=torch.int64, device=dev)
+        _lib.check(lib.obia_merge_contract_write_dev(c.handle, N, nnz, _ptr(raw_ptr), _ptr(count), _ptr(key_work), _ptr(border_work), _ptr(indptr),
+                                                     total, _ptr(neighbor), _ptr(border)))
+        return SegmentGraph(indptr, neighbor, border, N, self.start_label, ctx=self._ctx, as_tensor=self._is_t)
+
+    def contract(self, root):
+        """The graph of the objects ``root`` (N) forms -- ``root[i]`` is the row the segment i goes to, with ``root[root[i]] ==
+        root[i]``, as :meth:`components` gives it -- without another pass over the raster (include/obia_merging.h, CONTRACTION): row
+        r holds the entries of all its members with every neighbour mapped through ``root``, the entries inside an object dropped
+        and equal neighbours combined, their borders added.  Every other row is empty; ``n_labels`` and ``start_label`` stay.  It
+        equals ``segment_graph(relabel(labels, root + start_label), start_label, n_labels=N)`` array for array, and is the graph
+        counterpart of :meth:`obia_amd.shapes.ShapeTable.merge`."""
+        N = self.n_labels
+        r = _device.as_dev(root, torch.int32, self._dev)
+        if tuple(r.shape) != (N,):
+            raise ValueError(f"root must be an (n_labels,) column with n_labels = {N}, got shape {tuple(r.shape)}")
+        if N:
+            r64 = r.to(torch.int64)
+            if int(r64.min()) < 0 or int(r64.max()) >= N:
+                raise ValueError("root must hold rows 0 .. n_labels - 1")
+            if not bool((r64[r64] == r64).all()):
+                raise ValueError("root must satisfy root[root[i]] == root[i]")
+        return self._contract(r)
+
 
 def segment_graph(labels, start_label=1, n_labels=None, ctx=None):
     """The :class:`SegmentGraph` of a label raster (H, W): label l is segment l - ``start_label`` when that lies in 0 .. ``n_labels``

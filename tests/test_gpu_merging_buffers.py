@@ -1,0 +1,266 @@
+"""The entry points of include/obia_merging.h through guarded outputs (tests/guarded.py, both poisons) with every buffer off a 16-byte
+boundary (tests/offset_views.py): the results bit for bit against tests/merging_restatement.py, no stray write, no element left
+unwritten, the inputs unchanged, two runs equal; what is refused writes nothing and leaves the context as it was; the calls on a
+context whose workspace was filled by obia_test_poison_workspace_dev equal the same calls on a fresh context; and the wrappers under
+tests/stream_order.py: an input produced late on torch's stream is waited for, and the context's stream is idle when a call returns.
+obia_amd._lib._MERGE_ENTRIES is no *_SIGNATURES or *_BINDINGS table, so the decision tables of tests/workspace_history.py and
+tests/test_gpu_stream_order.py do not list it: these are the equivalent checks.  Every entry point of the table is exercised here."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+from tests import adjacency_restatement as R
+from tests import merging_restatement as M
+from tests import stream_order as SO
+from tests.guarded import POISONS, guarded, snapshot, unchanged
+from tests.offset_views import offset_view
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+EXERCISED = ("obia_merge_cost_dev", "obia_merge_pairs_dev", "obia_merge_contract_rows_dev", "obia_merge_contract_count_dev",
+             "obia_merge_contract_write_dev")
+F64, I32, I64 = np.float64, np.int32, np.int64
+TH, TW = 16, 32
+H, W, START, N, F = 2 * TH + 3, 2 * TW + 5, 1, 40, 3
+SHAPE, COMPACT = 0.3, 0.4
+WEIGHTS = np.array([0.5, 1.0, 2.0], F64)
+
+
+@functools.lru_cache(maxsize=None)
+def case():
+    rs = np.random.RandomState(29)
+    labels = np.kron(rs.randint(-1, N + 2, (-(-H // 3), -(-W // 4))), np.ones((3, 4), int))[:H, :W].astype(I32)
+    labels[labels == 5] = 4                                                    # label 5 occurs nowhere: an empty row that must be written
+    raw = (rs.uniform(0, 50, (H, W, F)) + 20.0 * (labels[:, :, None] % 7)).astype(np.float32)
+    st = M.state_of(raw, labels, START, n_labels=N)
+    partner = M.round_partner(st, 1e9, WEIGHTS, SHAPE, COMPACT)[0]
+    root = M.pair_root(partner, N)
+    assert st.area[4] == 0 and (partner >= 0).sum() >= 10 and (root != np.arange(N)).sum() >= 5
+    nnz = len(st.neighbor)
+    lens = np.diff(st.indptr)
+    raw_count = np.zeros(N, I64)
+    np.add.at(raw_count, root, lens)
+    raw_ptr = np.concatenate([[0], np.cumsum(raw_count)]).astype(I64)
+    cptr, cnb, cbd = M.contract(*st.graph(), N, root)
+    area, mean, m2, perimeter, box = M.merge_tables(st, partner)
+    want = dict(cost=M.cost(st, WEIGHTS, SHAPE, COMPACT), area=area, mean=mean, m2=m2, perimeter=perimeter, box=box, raw_count=raw_count,
+                count=np.diff(cptr).astype(I32), neighbor=cnb, border=cbd)
+    ins = dict(indptr=st.indptr, neighbor=st.neighbor, border=st.border, area=st.area, mean=st.mean, m2=st.m2, perimeter=st.perimeter,
+               box=st.box, weights=WEIGHTS, partner=partner, root=root, raw_ptr=raw_ptr, out_ptr=cptr)
+    return dict(st=st, nnz=nnz, nnz_out=len(cnb), want=want, ins=ins)
+
+
+def dev_off(a, k):
+    t = offset_view(torch.as_tensor(np.ascontiguousarray(a)).cuda(), k)
+    torch.cuda.synchronize()
+    return t
+
+
+def run_all(ctx, k, poison):
+    """the five entry points on guarded outputs, every buffer k elements off a boundary; returns (outputs, scratch, inputs)"""
+    from obia_amd import _lib
+    lib = _lib.load()
+    r = case()
+    nnz, nnz_out = r["nnz"], r["nnz_out"]
+    d = {name: dev_off(a, k) for name, a in r["ins"].items()}
+    p = {name: t.data_ptr() for name, t in d.items()}
+    o = {"cost": guarded(nnz, F64, poison, "cuda", k), "area": guarded(N, I64, poison, "cuda", k), "mean": guarded((N, F), F64, poison, "cuda", k),
+         "m2": guarded((N, F), F64, poison, "cuda", k), "perimeter": guarded(N, I64, poison, "cuda", k), "box": guarded((N, 4), I32, poison, "cuda", k),
+         "raw_count": guarded(N, I64, poison, "cuda", k), "count": guarded(N, I32, poison, "cuda", k),
+         "neighbor": guarded(nnz_out, I32, poison, "cuda", k), "border": guarded(nnz_out, I64, poison, "cuda", k)}
+    w = {"key_work": guarded(nnz, I32, poison, "cuda", k), "border_work": guarded(nnz, I64, poison, "cuda", k),
+         "cursor_work": guarded(N, I32, poison, "cuda", k)}
+    h = ctx.handle
+    calls = [
+        lib.obia_merge_cost_dev(h, p["indptr"], p["neighbor"], p["border"], N, nnz, p["area"], p["mean"], p["m2"], F, p["weights"], p["perimeter"],
+                                p["box"], 1.0 - SHAPE, COMPACT, o["cost"].ptr),
+        lib.obia_merge_pairs_dev(h, p["indptr"], p["neighbor"], p["border"], N, nnz, p["partner"], p["area"], p["mean"], p["m2"], F, p["perimeter"],
+                                 p["box"], o["area"].ptr, o["mean"].ptr, o["m2"].ptr, o["perimeter"].ptr, o["box"].ptr),
+        lib.obia_merge_contract_rows_dev(h, p["indptr"], N, nnz, p["root"], o["raw_count"].ptr),
+        lib.obia_merge_contract_count_dev(h, p["indptr"], p["neighbor"], p["border"], N, nnz, p["root"], p["raw_ptr"], w["key_work"].ptr,
+                                          w["border_work"].ptr, w["cursor_work"].ptr, o["count"].ptr),
+    ]
+    torch.cuda.synchronize()
+    assert R.same_bits(o["count"].host(), r["want"]["count"])                  # the write pass is handed the count's own result
+    calls.append(lib.obia_merge_contract_write_dev(h, N, nnz, p["raw_ptr"], o["count"].ptr, w["key_work"].ptr, w["border_work"].ptr, p["out_ptr"],
+                                                   nnz_out, o["neighbor"].ptr, o["border"].ptr))
+    assert calls == [0] * 5, (calls, _lib.last_error())
+    torch.cuda.synchronize()
+    return o, w, d
+
+
+def judge_all(o, w):
+    r = case()
+    got = {name: g.host() for name, g in o.items()}
+    for name, g in o.items():
+        assert R.same_bits(got[name], r["want"][name]), name
+        assert g.findings(name=name) == []                                   # no stray write, every element written
+    for name, g in w.items():
+        assert g.stray().size == 0, name                                     # scratch: what it holds is not specified, where it ends is
+    return got
+
+
+def test_every_entry_point_of_the_table_is_exercised():
+    from obia_amd import _lib
+    assert set(EXERCISED) == set(_lib._MERGE_ENTRIES)
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("poison", POISONS, ids=[f"{p:02X}" for p in POISONS])
+def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
+    """every int32 buffer 4, 8 and 12 bytes past a 16-byte boundary, every 8-byte buffer 8 bytes (k odd)"""
+    from obia_amd import _lib
+    ctx = _lib.default_context(0)
+    runs = []
+    for _ in range(2):
+        o, w, d = run_all(ctx, k, poison)
+        assert d["neighbor"].data_ptr() % 16 == 4 * k and d["mean"].data_ptr() % 16 == (8 * k) % 16
+        assert o["box"].ptr % 16 == 4 * k and o["cost"].ptr % 16 == (8 * k) % 16 and w["key_work"].ptr % 16 == 4 * k
+        snaps = {name: snapshot(t) for name, t in d.items()}
+        got = judge_all(o, w)
+        assert all(unchanged(d[name], snaps[name]) for name in d)
+        assert all(np.array_equal(d[name].cpu().numpy(), case()["ins"][name]) or name in ("mean", "m2") for name in d)
+        assert all(R.same_bits(d[name].cpu().numpy(), case()["ins"][name]) for name in ("mean", "m2"))
+        runs.append({name: a.tobytes() for name, a in got.items()})
+    assert runs[0] == runs[1]
+
+
+@pytest.mark.parametrize("poison", POISONS, ids=[f"{p:02X}" for p in POISONS])
+def test_refusals_write_nothing_and_leave_the_context_intact(poison):
+    from obia_amd import _lib
+    lib, ctx = _lib.load(), _lib.Context(0)
+    try:
+        r, k = case(), 1
+        nnz, nnz_out = r["nnz"], r["nnz_out"]
+        d = {name: dev_off(a, k) for name, a in r["ins"].items()}
+        snaps = {name: snapshot(t) for name, t in d.items()}
+        p = {name: t.data_ptr() for name, t in d.items()}
+        g = {"cost": guarded(nnz, F64, poison, "cuda", k), "area": guarded(N, I64, poison, "cuda", k), "mean": guarded((N, F), F64, poison, "cuda", k),
+             "m2": guarded((N, F), F64, poison, "cuda", k), "perimeter": guarded(N, I64, poison, "cuda", k), "box": guarded((N, 4), I32, poison, "cuda", k),
+             "raw_count": guarded(N, I64, poison, "cuda", k), "count": guarded(N, I32, poison, "cuda", k), "key": guarded(nnz, I32, poison, "cuda", k),
+             "bwork": guarded(nnz, I64, poison, "cuda", k), "cursor": guarded(N, I32, poison, "cuda", k),
+             "neighbor": guarded(nnz_out, I32, poison, "cuda", k), "border": guarded(nnz_out, I64, poison, "cuda", k)}
+        q = {name: v.ptr for name, v in g.items()}
+        held = ctx.workspace_bytes()
+        h = ctx.handle
+
+        def cost(n_=N, nnz_=nnz, F_=F, out=q["cost"], **kw):
+            a = dict(p, **kw)
+            return lib.obia_merge_cost_dev(h, a["indptr"], a["neighbor"], a["border"], n_, nnz_, a["area"], a["mean"], a["m2"], F_, a["weights"],
+                                           a["perimeter"], a["box"], 0.7, 0.4, out)
+
+        def pairs(n_=N, nnz_=nnz, F_=F, area=q["area"], mean=q["mean"], m2=q["m2"], perimeter=q["perimeter"], box=q["box"], **kw):
+            a = dict(p, **kw)
+            return lib.obia_merge_pairs_dev(h, a["indptr"], a["neighbor"], a["border"], n_, nnz_, a["partner"], a["area"], a["mean"], a["m2"], F_,
+                                            a["perimeter"], a["box"], area, mean, m2, perimeter, box)
+
+        def rows(n_=N, nnz_=nnz, out=q["raw_count"], **kw):
+            a = dict(p, **kw)
+            return lib.obia_merge_contract_rows_dev(h, a["indptr"], n_, nnz_, a["root"], out)
+
+        def count(n_=N, nnz_=nnz, key=q["key"], bwork=q["bwork"], cursor=q["cursor"], out=q["count"], **kw):
+            a = dict(p, **kw)
+            return lib.obia_merge_contract_count_dev(h, a["indptr"], a["neighbor"], a["border"], n_, nnz_, a["root"], a["raw_ptr"], key, bwork,
+                                                     cursor, out)
+
+        def write(n_=N, nnz_=nnz, nnz_out_=nnz_out, cnt=p["root"], key=p["neighbor"], bwork=p["border"], nb=q["neighbor"], bd=q["border"], **kw):
+            a = dict(p, **kw)
+            return lib.obia_merge_contract_write_dev(h, n_, nnz_, a["raw_ptr"], cnt, key, bwork, a["out_ptr"], nnz_out_, nb, bd)
+
+        invalid = [cost(indptr=None), cost(neighbor=None), cost(border=None), cost(area=None), cost(mean=None), cost(m2=None), cost(weights=None),
+                   cost(perimeter=None), cost(box=None), cost(out=None), cost(out=q["cost"] + 4), cost(mean=p["mean"] + 4), cost(box=p["box"] + 2),
+                   cost(out=p["mean"]), cost(n_=-1), cost(n_=2 ** 31 - 2), cost(F_=0), cost(nnz_=-1),
+                   pairs(partner=None), pairs(area=None), pairs(mean=None), pairs(box=None), pairs(area=q["area"] + 4), pairs(box=q["box"] + 2),
+                   pairs(partner=p["partner"] + 2), pairs(area=q["perimeter"]), pairs(mean=p["mean"]), pairs(n_=-1), pairs(F_=-2), pairs(nnz_=-1),
+                   rows(indptr=None), rows(root=None), rows(out=None), rows(out=q["raw_count"] + 4), rows(out=p["indptr"]), rows(n_=-1), rows(nnz_=-1),
+                   count(root=None), count(raw_ptr=None), count(key=None), count(bwork=None), count(cursor=None), count(out=None),
+                   count(key=q["key"] + 2), count(bwork=q["bwork"] + 4), count(out=q["cursor"]), count(key=p["neighbor"]), count(n_=-1), count(nnz_=-1),
+                   write(raw_ptr=None), write(cnt=None), write(key=None), write(bwork=None), write(out_ptr=None), write(nb=None), write(bd=None),
+                   write(nb=q["neighbor"] + 2), write(bd=q["border"] + 4), write(nb=p["neighbor"]), write(n_=-1), write(nnz_=-1), write(nnz_out_=-1)]
+        assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+        unsupported = [cost(nnz_=2 ** 31), cost(n_=2 ** 30, F_=2), pairs(nnz_=2 ** 31), pairs(n_=2 ** 30, F_=2), rows(nnz_=2 ** 31), count(nnz_=2 ** 31),
+                       write(nnz_=2 ** 31), write(nnz_out_=2 ** 31)]
+        assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported
+        torch.cuda.synchronize()
+        assert all(v.untouched() and v.stray().size == 0 for v in g.values()) and all(unchanged(d[name], snaps[name]) for name in d)
+        # calls that have nothing to do are valid and write nothing
+        assert [cost(n_=0, nnz_=0), pairs(n_=0, nnz_=0), rows(n_=0, nnz_=0), count(n_=0, nnz_=0), write(n_=0, nnz_=0, nnz_out_=0)] == [0] * 5
+        torch.cuda.synchronize()
+        assert all(v.untouched() and v.stray().size == 0 for v in g.values()) and ctx.workspace_bytes() == held
+        # and the context serves the next call as a fresh one would
+        assert cost(out=q["cost"]) == 0
+        torch.cuda.synchronize()
+        want = M.cost(r["st"], WEIGHTS, 1.0 - 0.7, 0.4)
+        assert R.same_bits(g["cost"].host(), want) and g["cost"].findings(name="cost") == [] and ctx.workspace_bytes() == held
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("byte", [0x01, 0xFF])
+def test_a_used_context_gives_what_a_fresh_one_gives(byte):
+    """the entry points on a fresh context against the same calls on a context whose workspace, one block of 64 MiB, holds `byte` in
+    every byte: equal bit for bit, twice, and the context holds what it held -- the calls take nothing from the workspace"""
+    from obia_amd import _lib
+    lib = _lib.load()
+    fresh, used = _lib.Context(0), _lib.Context(0)
+    try:
+        want = {name: a.tobytes() for name, a in judge_all(*run_all(fresh, 1, POISONS[0])[:2]).items()}
+        held, nz = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        torch.cuda.synchronize()
+        _lib.check(lib.obia_test_poison_workspace_dev(used.handle, 64 << 20, byte, ctypes.byref(held), ctypes.byref(nz)))
+        assert held.value >= 64 << 20 and used.workspace_bytes() == held.value
+        for _ in range(2):
+            assert {name: a.tobytes() for name, a in judge_all(*run_all(used, 1, POISONS[0])[:2]).items()} == want
+            assert used.workspace_bytes() == held.value
+    finally:
+        fresh.close()
+        used.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ stream order
+DELAY_MS = 20.0      # four times tests/stream_order.py's MIN_MS, as tests/test_gpu_shapes_buffers.py has it
+
+
+@pytest.mark.parametrize("arrangement", ["A", "B", "C"])
+def test_stream_order_of_the_wrappers(arrangement):
+    """A: torch on a fresh stream t, the context on a stream of its own, the means and the partners late on t (they hold 0x5A bytes
+    until a delay has passed): at every ABI entry t is idle and the results are right.  B: the context on a second torch stream s with
+    a delay in front of every call's kernels: every call returns with s idle.  C: the context on t."""
+    from obia_amd import RegionState, SegmentGraph, _lib, fusion_cost, merge_pairs
+    real, r = _lib.load(), case()
+    st = r["st"]
+    t = torch.cuda.Stream()
+    s = torch.cuda.Stream() if arrangement == "B" else None
+    delay = None if arrangement == "C" else SO.Delay(DELAY_MS)
+    with torch.cuda.stream(t):
+        ctx = _lib.Context(0, stream={"A": None, "B": s and s.cuda_stream, "C": t.cuda_stream}[arrangement])
+        try:
+            with SO.Instrumented(real, t, s, delay) as ins:
+                mean, partner = torch.as_tensor(st.mean).cuda(), torch.as_tensor(r["ins"]["partner"]).cuda()
+                if delay is not None:
+                    mean, partner = SO.late(mean, t, delay), SO.late(partner, t, delay)
+                g = SegmentGraph(torch.as_tensor(st.indptr).cuda(), torch.as_tensor(st.neighbor).cuda(), torch.as_tensor(st.border).cuda(), N, START,
+                                 ctx=ctx)
+                state = RegionState(torch.as_tensor(st.area).cuda(), mean, torch.as_tensor(st.m2).cuda(), torch.as_tensor(st.perimeter).cuda(),
+                                    torch.as_tensor(st.box).cuda(), g)
+                cost = fusion_cost(state, WEIGHTS, SHAPE, COMPACT)
+                merged = merge_pairs(state, partner)
+                s_idle = s is None or s.query()
+                got = dict(cost=cost.cpu().numpy(), area=merged.area.cpu().numpy(), mean=merged.mean.cpu().numpy(), m2=merged.m2.cpu().numpy(),
+                           perimeter=merged.perimeter.cpu().numpy(), box=merged.box.cpu().numpy(), neighbor=merged.graph.neighbor.cpu().numpy(),
+                           border=merged.graph.border.cpu().numpy(), root=merged.root.cpu().numpy())
+        finally:
+            t.synchronize()
+            if s is not None:
+                s.synchronize()
+            ctx.close()
+    log = [rec for rec in ins.log if rec.name in EXERCISED]
+    assert [rec.name for rec in ins.log] == list(EXERCISED), [rec.name for rec in ins.log]
+    assert all(rec.idle_t and not rec.refused for rec in log), "entered with torch's stream busy"
+    assert s_idle and not any(rec.pending_s for rec in log), "the context's stream was still busy when a call returned"
+    for name in ("cost", "area", "mean", "m2", "perimeter", "box", "neighbor", "border"):
+        assert R.same_bits(got[name], r["want"][name]), name
+    assert R.same_bits(got["root"], r["ins"]["root"])
