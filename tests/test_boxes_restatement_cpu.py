@@ -1,19 +1,14 @@
 """Segments and boxes without a GPU: the restatement (tests/boxes_restatement.py) against an exact oracle and hand-checked answers,
-the seventh binding table (include/obia_boxes.h == obia_amd._lib._BOXES_SIGNATURES), the argument checks of obia_amd.boxes that fire
-before the device is touched, and the host glue (predictions_to_map, save_predictions_to_gpkg)."""
-import ctypes
+the argument checks of obia_amd.boxes that fire before the device is touched, and the host glue (predictions_to_map,
+save_predictions_to_gpkg)."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import boxes_restatement as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("obia_boxes_assign_dev", "obia_boxes_pair_count_dev", "obia_boxes_pair_write_dev", "obia_boxes_dissolve_dev",
-           "obia_boxes_iou_dev", "obia_boxes_nms_dev")
 # Every term of the area is fl(fl(wx * wy) * n) with wx and wy one rounded subtraction each: four roundings, (1 + u)^4, u = 2^-53.
 # The nine non-negative terms are added with at most eight rounded additions, (1 + u)^8.  (1 + u)^12 - 1 < 16 u.
 AREA_RTOL = 16 * 2.0 ** -53
@@ -94,49 +89,6 @@ def test_restated_nms_and_iou_known_answers():
     assert keep.tolist() == [True, True, True]                     # "greater than": a threshold equal to the IoU keeps
     keep, _ = R.nms([a, b, c], [0.9, 0.8, 0.7], 0.3, groups=[0, 1, 0])
     assert keep.tolist() == [True, True, True]
-
-
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_boxes_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_boxes.h")
-    assert syms == set(SYMBOLS) == set(_lib._BOXES_SIGNATURES), sorted(syms ^ set(_lib._BOXES_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TRAINING_SIGNATURES, _lib._CROWNS_SIGNATURES,
-                  _lib._SEED_TABLE_SIGNATURES, _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_training.h", "obia_crowns.h", "obia_seed_table.h",
-                   "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    assert not set(_lib.EXPORTED_SYMBOLS) & syms
-    lib = _lib.load()
-    for name, (res, args) in _lib._BOXES_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
-    define = re.search(r"#define\s+OBIA_BOXES_TABLE\s+(\d+)", open(os.path.join(ROOT, "include", "obia_boxes.h")).read())
-    assert int(define.group(1)) == _lib.BOXES_TABLE and _lib.BOXES_TABLE & (_lib.BOXES_TABLE - 1) == 0
-
-
-def test_a_null_context_is_refused_by_every_boxes_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._BOXES_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64) else 0.0 if t is ctypes.c_double else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 def test_public_names():

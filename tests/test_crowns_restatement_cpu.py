@@ -1,17 +1,12 @@
 """Crowns from seeds, host side: the restatement (tests/crowns_restatement.py) against SciPy's Dijkstra, bit for bit, and against answers
-worked out by hand; the argument checks of obia_amd.crowns that fire before the device is touched; the fifth binding table
-(include/obia_crowns.h == obia_amd._lib._CROWNS_SIGNATURES)."""
-import ctypes
+worked out by hand; the argument checks of obia_amd.crowns that fire before the device is touched."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import crowns_restatement as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SQRT2 = math.sqrt(2.0)
 
 
@@ -210,47 +205,3 @@ def test_the_package_exports_the_module():
     pytest.importorskip("torch")
     import obia_amd
     assert obia_amd.cost_allocation is obia_amd.crowns.cost_allocation and obia_amd.grow_crowns is obia_amd.crowns.grow_crowns
-
-
-# ---- the fifth binding table -----------------------------------------------------------------------------------------------------
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_crowns_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_crowns.h")
-    assert len(syms) == 2 and all(s.startswith("obia_crowns_") for s in syms)
-    assert syms == set(_lib._CROWNS_SIGNATURES), sorted(syms ^ set(_lib._CROWNS_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TRAINING_SIGNATURES, _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_training.h", "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    assert not set(_lib.EXPORTED_SYMBOLS) & syms
-    lib = _lib.load()
-    for name, (res, args) in _lib._CROWNS_SIGNATURES.items():                # load() bound the fifth table as it binds the others
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    header = open(os.path.join(ROOT, "include", "obia_crowns.h")).read()
-    assert int(re.search(r"#define OBIA_CROWNS_TILE (\d+)", header).group(1)) == _lib.CROWNS_TILE
-    assert int(re.search(r"#define OBIA_E_INTERNAL \((-\d+)\)", header).group(1)) == _lib.E_INTERNAL
-    assert _lib.E_INTERNAL not in (_lib.E_INVALID, _lib.E_HIP, _lib.E_NOMEM, _lib.E_UNSUPPORTED, _lib.E_EMPTY, _lib.E_NONFINITE)
-    assert lib.obia_abi_version() == 2
-
-
-def test_a_null_context_is_refused_by_every_crowns_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._CROWNS_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int64) else 0.0 if t is ctypes.c_double else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name

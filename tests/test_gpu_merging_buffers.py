@@ -1,11 +1,8 @@
 """The entry points of include/obia_merging.h through guarded outputs (tests/guarded.py, both poisons) with every buffer off a 16-byte
 boundary (tests/offset_views.py): the results bit for bit against tests/merging_restatement.py, no stray write, no element left
-unwritten, the inputs unchanged, two runs equal; what is refused writes nothing and leaves the context as it was; the calls on a
-context whose workspace was filled by obia_test_poison_workspace_dev equal the same calls on a fresh context; and the wrappers under
-tests/stream_order.py: an input produced late on torch's stream is waited for, and the context's stream is idle when a call returns.
-obia_amd._lib._MERGE_ENTRIES is no *_SIGNATURES or *_BINDINGS table, so the decision tables of tests/workspace_history.py and
-tests/test_gpu_stream_order.py do not list it: these are the equivalent checks.  Every entry point of the table is exercised here."""
-import ctypes
+unwritten, the inputs unchanged, two runs equal; what is refused writes nothing and leaves the context as it was.  Every entry point
+of the table is exercised here.  (The calls on a poisoned workspace are the case `body:merging` of tests/test_gpu_workspace_history.py,
+which runs run_all and judge_all below; the wrappers' stream order is the case `merge:cost_and_pairs` of tests/test_gpu_stream_order.py.)"""
 import functools
 
 import numpy as np
@@ -13,7 +10,6 @@ import pytest
 
 from tests import adjacency_restatement as R
 from tests import merging_restatement as M
-from tests import stream_order as SO
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view
 
@@ -197,70 +193,3 @@ def test_refusals_write_nothing_and_leave_the_context_intact(poison):
         assert R.same_bits(g["cost"].host(), want) and g["cost"].findings(name="cost") == [] and ctx.workspace_bytes() == held
     finally:
         ctx.close()
-
-
-@pytest.mark.parametrize("byte", [0x01, 0xFF])
-def test_a_used_context_gives_what_a_fresh_one_gives(byte):
-    """the entry points on a fresh context against the same calls on a context whose workspace, one block of 64 MiB, holds `byte` in
-    every byte: equal bit for bit, twice, and the context holds what it held -- the calls take nothing from the workspace"""
-    from obia_amd import _lib
-    lib = _lib.load()
-    fresh, used = _lib.Context(0), _lib.Context(0)
-    try:
-        want = {name: a.tobytes() for name, a in judge_all(*run_all(fresh, 1, POISONS[0])[:2]).items()}
-        held, nz = ctypes.c_int64(-1), ctypes.c_int64(-1)
-        torch.cuda.synchronize()
-        _lib.check(lib.obia_test_poison_workspace_dev(used.handle, 64 << 20, byte, ctypes.byref(held), ctypes.byref(nz)))
-        assert held.value >= 64 << 20 and used.workspace_bytes() == held.value
-        for _ in range(2):
-            assert {name: a.tobytes() for name, a in judge_all(*run_all(used, 1, POISONS[0])[:2]).items()} == want
-            assert used.workspace_bytes() == held.value
-    finally:
-        fresh.close()
-        used.close()
-
-
-# ------------------------------------------------------------------------------------------------------------------ stream order
-DELAY_MS = 20.0      # four times tests/stream_order.py's MIN_MS, as tests/test_gpu_shapes_buffers.py has it
-
-
-@pytest.mark.parametrize("arrangement", ["A", "B", "C"])
-def test_stream_order_of_the_wrappers(arrangement):
-    """A: torch on a fresh stream t, the context on a stream of its own, the means and the partners late on t (they hold 0x5A bytes
-    until a delay has passed): at every ABI entry t is idle and the results are right.  B: the context on a second torch stream s with
-    a delay in front of every call's kernels: every call returns with s idle.  C: the context on t."""
-    from obia_amd import RegionState, SegmentGraph, _lib, fusion_cost, merge_pairs
-    real, r = _lib.load(), case()
-    st = r["st"]
-    t = torch.cuda.Stream()
-    s = torch.cuda.Stream() if arrangement == "B" else None
-    delay = None if arrangement == "C" else SO.Delay(DELAY_MS)
-    with torch.cuda.stream(t):
-        ctx = _lib.Context(0, stream={"A": None, "B": s and s.cuda_stream, "C": t.cuda_stream}[arrangement])
-        try:
-            with SO.Instrumented(real, t, s, delay) as ins:
-                mean, partner = torch.as_tensor(st.mean).cuda(), torch.as_tensor(r["ins"]["partner"]).cuda()
-                if delay is not None:
-                    mean, partner = SO.late(mean, t, delay), SO.late(partner, t, delay)
-                g = SegmentGraph(torch.as_tensor(st.indptr).cuda(), torch.as_tensor(st.neighbor).cuda(), torch.as_tensor(st.border).cuda(), N, START,
-                                 ctx=ctx)
-                state = RegionState(torch.as_tensor(st.area).cuda(), mean, torch.as_tensor(st.m2).cuda(), torch.as_tensor(st.perimeter).cuda(),
-                                    torch.as_tensor(st.box).cuda(), g)
-                cost = fusion_cost(state, WEIGHTS, SHAPE, COMPACT)
-                merged = merge_pairs(state, partner)
-                s_idle = s is None or s.query()
-                got = dict(cost=cost.cpu().numpy(), area=merged.area.cpu().numpy(), mean=merged.mean.cpu().numpy(), m2=merged.m2.cpu().numpy(),
-                           perimeter=merged.perimeter.cpu().numpy(), box=merged.box.cpu().numpy(), neighbor=merged.graph.neighbor.cpu().numpy(),
-                           border=merged.graph.border.cpu().numpy(), root=merged.root.cpu().numpy())
-        finally:
-            t.synchronize()
-            if s is not None:
-                s.synchronize()
-            ctx.close()
-    log = [rec for rec in ins.log if rec.name in EXERCISED]
-    assert [rec.name for rec in ins.log] == list(EXERCISED), [rec.name for rec in ins.log]
-    assert all(rec.idle_t and not rec.refused for rec in log), "entered with torch's stream busy"
-    assert s_idle and not any(rec.pending_s for rec in log), "the context's stream was still busy when a call returned"
-    for name in ("cost", "area", "mean", "m2", "perimeter", "box", "neighbor", "border"):
-        assert R.same_bits(got[name], r["want"][name]), name
-    assert R.same_bits(got["root"], r["ins"]["root"])

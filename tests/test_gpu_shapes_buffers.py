@@ -1,18 +1,14 @@
 """The entry point of include/obia_shapes.h through guarded outputs (tests/guarded.py, both poisons) with the labels off a 16-byte
 boundary (tests/offset_views.py): the tables bit for bit, no stray write, no element left unwritten, the input unchanged, two runs
-equal; what is refused writes nothing and leaves the context as it was; the call on a context whose workspace was filled by
-obia_test_poison_workspace_dev equals the same call on a fresh context; and the wrapper under tests/stream_order.py: an input
-produced late on torch's stream is waited for, and the context's stream is idle when the wrapper returns.  obia_amd._lib._SHAPE_ENTRIES
-is no *_SIGNATURES or *_BINDINGS table, so the decision tables of tests/workspace_history.py and tests/test_gpu_stream_order.py do not
-list it: these are the equivalent checks.  Every entry point of the table is exercised here."""
-import ctypes
+equal; what is refused writes nothing and leaves the context as it was.  Every entry point of the table is exercised here.  (The
+call on a poisoned workspace is the case `body:shapes` of tests/test_gpu_workspace_history.py, which runs run_all and judge_all below;
+the wrapper's stream order is the case `shapes:segment_shapes` of tests/test_gpu_stream_order.py.)"""
 import functools
 
 import numpy as np
 import pytest
 
 from tests import shapes_restatement as S
-from tests import stream_order as SO
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
 
@@ -120,62 +116,3 @@ def test_refusals_write_nothing_and_leave_the_context_intact(poison):
         assert g["s"].findings(name="sums") == [] and g["b"].findings(name="box") == [] and ctx.workspace_bytes() == held
     finally:
         ctx.close()
-
-
-@pytest.mark.parametrize("byte", [0x01, 0xFF])
-def test_a_used_context_gives_what_a_fresh_one_gives(byte):
-    """the entry point on a fresh context against the same call on a context whose workspace, one block of 64 MiB, holds `byte` in
-    every byte: equal bit for bit, twice, and the context holds what it held -- the call takes nothing from the workspace"""
-    from obia_amd import _lib
-    lib = _lib.load()
-    fresh, used = _lib.Context(0), _lib.Context(0)
-    try:
-        want = {name: a.tobytes() for name, a in judge_all(run_all(fresh, 1, POISONS[0])[0]).items()}
-        held, nz = ctypes.c_int64(-1), ctypes.c_int64(-1)
-        torch.cuda.synchronize()
-        _lib.check(lib.obia_test_poison_workspace_dev(used.handle, 64 << 20, byte, ctypes.byref(held), ctypes.byref(nz)))
-        assert held.value >= 64 << 20 and used.workspace_bytes() == held.value
-        for _ in range(2):
-            assert {name: a.tobytes() for name, a in judge_all(run_all(used, 1, POISONS[0])[0]).items()} == want
-            assert used.workspace_bytes() == held.value
-    finally:
-        fresh.close()
-        used.close()
-
-
-# ------------------------------------------------------------------------------------------------------------------ stream order
-DELAY_MS = 20.0      # the wrapper makes one ABI call, so there is no host gap to scale by: four times tests/stream_order.py's MIN_MS
-
-
-@pytest.mark.parametrize("arrangement", ["A", "B", "C"])
-def test_stream_order_of_the_wrapper(arrangement):
-    """A: torch on a fresh stream t, the context on a stream of its own, the labels late on t (they hold 0x5A bytes until a delay has
-    passed): at the ABI entry t is idle and the result is right.  B: the context on a second torch stream s with a delay in front of
-    the call's kernels: the call returns with s idle (the header: "the call returns with its work done").  C: the context on t."""
-    from obia_amd import _lib, segment_shapes
-    real, r = _lib.load(), case()
-    t = torch.cuda.Stream()
-    s = torch.cuda.Stream() if arrangement == "B" else None
-    delay = None if arrangement == "C" else SO.Delay(DELAY_MS)
-    with torch.cuda.stream(t):
-        ctx = _lib.Context(0, stream={"A": None, "B": s and s.cuda_stream, "C": t.cuda_stream}[arrangement])
-        try:
-            with SO.Instrumented(real, t, s, delay) as ins:
-                lab = torch.as_tensor(r["labels"]).cuda()
-                if delay is not None:
-                    lab = SO.late(lab, t, delay)
-                table = segment_shapes(lab, START, n_labels=N, ctx=ctx)
-                s_idle = s is None or s.query()
-                got = (table.sums.cpu().numpy(), table.box.cpu().numpy(), table.orientation.cpu().numpy())
-        finally:
-            t.synchronize()
-            if s is not None:
-                s.synchronize()
-            ctx.close()
-    log = [rec for rec in ins.log if rec.name in EXERCISED]
-    assert len(log) == 1 and [rec.name for rec in ins.log] == list(EXERCISED), [rec.name for rec in ins.log]
-    assert log[0].idle_t and not log[0].refused, "entered with torch's stream busy"
-    assert s_idle and not log[0].pending_s, "the context's stream was still busy when the call returned"
-    assert S.same_bits(got[0], r["sums"]) and S.same_bits(got[1], r["box"])
-    want = S.derived(r["sums"], r["box"])["orientation"]
-    assert np.array_equal(np.isnan(got[2]), np.isnan(want)) and np.nanmax(np.abs(got[2] - want)) <= 8 * 2.22e-16   # ORIENTATION_BOUND of tests/test_gpu_shapes.py

@@ -23,8 +23,8 @@ handed over as NumPy arrays, which the wrapper uploads itself: `crowns_mask`, `b
 test; all but one are judged by their own plain run only).  `cost_allocation` gets CUDA tensors in `crowns:cost_allocation`.
 "forest_predict's chunked path (classify.py:543)" of the issue is the piece loop of `mlp_shap`, where that line stands:
 `classify:mlp_shap_in_pieces`.  Delays: 4 x the largest host gap between two ABI calls of a
-plain, logged run of the case, at least 5 ms; no case may need more than 100 ms (test_no_case_needs_more_than_the_cap;
-profiles/stream_order_notes.md has the figures).
+plain, logged run of the case, at least 5 ms (FLOOR_MS: 20 ms for the shape and merging wrappers); no case may need more than 100 ms
+(test_no_case_needs_more_than_the_cap; profiles/stream_order_notes.md has the figures).
 
 Stale blocks.  A wrongly ordered read must see poison, not the previous run's correct answer in a block torch's caching allocator
 hands out again.  Before an instrumented run the test drops what it holds, then allocates, fills with 0xA5 and frees tensors of the
@@ -114,6 +114,8 @@ def bits_equal(got, want, what=""):
 
 # ---- new cases: run(ctx, oracle) -> host result, judge(result, oracle) against the operator's restatement -----------------------------
 NEW = {}
+FLOOR_MS = {}             # case -> the least delay in ms, where the 4 x gap rule alone would give too short a one
+CALLS = {}                # case -> the entry points its wrappers call, in order (arrangement B's log but the obia_destroy of the test itself)
 
 
 # -- image previews (tests/image_restatement.py)
@@ -453,6 +455,50 @@ def _adjacency_cases():
     NEW["adj:context_columns"] = Op(context, judge=judge_context)
 
 
+# -- the shape columns and region merging: the wrappers on the cases of their *_buffers files.  Each makes ABI calls with no host gap to
+#    scale a delay by, so the delay has a floor; and the calls a wrapper makes are pinned, in order.
+def _shapes_cases():
+    from tests import shapes_restatement as S
+    from tests import test_gpu_shapes_buffers as TB
+
+    def run(ctx, oracle):
+        from obia_amd import segment_shapes
+        table = segment_shapes(dev(TB.case()["labels"]), TB.START, n_labels=TB.N, ctx=ctx)
+        return host((table.sums, table.box, table.orientation))
+
+    def judge(got, oracle):
+        r = TB.case()
+        assert S.same_bits(got[0], r["sums"]) and S.same_bits(got[1], r["box"])
+        want = S.derived(r["sums"], r["box"])["orientation"]
+        assert np.array_equal(np.isnan(got[2]), np.isnan(want)) and np.nanmax(np.abs(got[2] - want)) <= 8 * 2.22e-16   # ORIENTATION_BOUND of tests/test_gpu_shapes.py
+    NEW["shapes:segment_shapes"] = Op(run, judge=judge)
+    FLOOR_MS["shapes:segment_shapes"], CALLS["shapes:segment_shapes"] = 20.0, TB.EXERCISED
+
+
+def _merging_cases():
+    from tests import adjacency_restatement as R
+    from tests import test_gpu_merging_buffers as TB
+
+    def run(ctx, oracle):
+        from obia_amd import RegionState, SegmentGraph, fusion_cost, merge_pairs
+        r = TB.case()
+        st = r["st"]
+        g = SegmentGraph(dev(st.indptr), dev(st.neighbor), dev(st.border), TB.N, TB.START, ctx=ctx)
+        state = RegionState(dev(st.area), dev(st.mean), dev(st.m2), dev(st.perimeter), dev(st.box), g)
+        cost = fusion_cost(state, TB.WEIGHTS, TB.SHAPE, TB.COMPACT)
+        merged = merge_pairs(state, dev(r["ins"]["partner"]))
+        return host(dict(cost=cost, area=merged.area, mean=merged.mean, m2=merged.m2, perimeter=merged.perimeter, box=merged.box,
+                         neighbor=merged.graph.neighbor, border=merged.graph.border, root=merged.root))
+
+    def judge(got, oracle):
+        r = TB.case()
+        for name in ("cost", "area", "mean", "m2", "perimeter", "box", "neighbor", "border"):
+            assert R.same_bits(got[name], r["want"][name]), name
+        assert R.same_bits(got["root"], r["ins"]["root"])
+    NEW["merge:cost_and_pairs"] = Op(run, judge=judge)
+    FLOOR_MS["merge:cost_and_pairs"], CALLS["merge:cost_and_pairs"] = 20.0, TB.EXERCISED
+
+
 # -- seeds: the CHM seeds and the canonical seeds with every table option (tests/seeds_restatement.py, tests/seed_table_restatement.py)
 def _seeds_cases():
     from tests import seeds_restatement as SR
@@ -731,7 +777,7 @@ def _host_cases():
 
 
 for _build in (_image_cases, _sharpness_cases, _training_cases, _crowns_cases, _pointcloud_cases, _ground_cases, _groundfilter_cases,
-               _adjacency_cases, _seeds_cases, _mlp_shap_pieces, _wrapper_cases, _host_cases):
+               _adjacency_cases, _shapes_cases, _merging_cases, _seeds_cases, _mlp_shap_pieces, _wrapper_cases, _host_cases):
     _build()
 
 REUSED = [name for name in WHT.OPS if not name.startswith("guards:")]
@@ -854,7 +900,7 @@ def measured(name, oracle):
 
 
 def delay_ms(name, oracle):
-    return min(SO.MAX_MS, SO.delay_ms_for(measured(name, oracle)[0][0]))
+    return max(FLOOR_MS.get(name, 0.0), min(SO.MAX_MS, SO.delay_ms_for(measured(name, oracle)[0][0])))
 
 
 def idle_violations(log):
@@ -921,6 +967,8 @@ def test_b_context_on_a_second_stream(oracle, name):
     assert not idle_violations(r.log), f"entered with torch's stream busy: {idle_violations(r.log)}"
     assert not pending_violations(r.log), f"not what the headers declare: {pending_violations(r.log)}"
     assert r.s_idle, "the context's stream was still busy when the wrapper returned"
+    if name in CALLS:
+        assert [rec.name for rec in r.log] == list(CALLS[name]) + ["obia_destroy"], [rec.name for rec in r.log]
     compare(name, r.result, want, oracle, f"{name}, arrangement B")
     with torch.cuda.stream(r.s):                                               # the context is closed: its caller's stream still works
         x = torch.full((257,), 7, dtype=torch.int32, device="cuda")

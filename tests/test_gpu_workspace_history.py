@@ -323,7 +323,7 @@ OPS["body:seed_table"] = Op(_body("tests.test_gpu_seed_table_buffers", _seed_tab
 OPS["body:boxes"] = Op(_body("tests.test_gpu_boxes_buffers", lambda m: m.test_buffers_off_the_boundary_and_guarded_outputs(1, G.POISONS[0])))
 
 
-# -- the ground filter's and the adjacency graph's *_buffers files: run_all takes the context, judge_all judges every output bit for bit
+# -- the ground filter's, the adjacency graph's, the shapes' and the merging's *_buffers files: run_all takes the context, judge_all judges every output bit for bit
 def _groundfilter_body(ctx, oracle):
     from tests import test_gpu_groundfilter_buffers as m
     s, o, scratch, _ = m.run_all(ctx, 1, G.POISONS[0])
@@ -337,8 +337,21 @@ def _adjacency_body(ctx, oracle):
     return {name: np.array(a) for name, a in m.judge_all(o, scratch).items()}   # (the records sorted inside their tiles, as it judges them)
 
 
+def _shapes_body(ctx, oracle):
+    from tests import test_gpu_shapes_buffers as m
+    return {name: np.array(a) for name, a in m.judge_all(m.run_all(ctx, 1, G.POISONS[0])[0]).items()}
+
+
+def _merging_body(ctx, oracle):
+    from tests import test_gpu_merging_buffers as m
+    o, scratch, _ = m.run_all(ctx, 1, G.POISONS[0])
+    return {name: np.array(a) for name, a in m.judge_all(o, scratch).items()}
+
+
 OPS["body:groundfilter"] = Op(_groundfilter_body)
 OPS["body:adjacency"] = Op(_adjacency_body)
+OPS["body:shapes"] = Op(_shapes_body)
+OPS["body:merging"] = Op(_merging_body)
 
 
 # -- boxes: every footprint fits the LDS table / a footprint of more labels than the table, split into passes

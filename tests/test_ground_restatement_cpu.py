@@ -1,11 +1,8 @@
 """Height above ground without a GPU: the restatement (tests/ground_restatement.py) against hand-worked answers; the generators of
 tests/test_gpu_ground.py hold the classes their cases exist for; the cell-side rule keeps the grid within 4 ng + 16 cells; every
-argument refusal of obia_amd.pointcloud's ground functions fires before the library is loaded; the ninth binding table
-(include/obia_ground.h == obia_amd._lib._GROUND_SIGNATURES); a null context is refused; the query launch is a named grid."""
-import ctypes
+argument refusal of obia_amd.pointcloud's ground functions fires before the library is loaded; the query launch is a named grid."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +10,6 @@ import pytest
 from tests import ground_restatement as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("obia_ground_query_dev", "obia_ground_dtm_dev")
 QNAN64, QNAN32 = 0x7FF8000000000000, 0x7FC00000
 
 # a unit lattice of four ground points with elevations 10, 20, 30, 40 in index order
@@ -249,49 +245,6 @@ def test_public_names():
     assert all(sig[k].kind is sig[k].KEYWORD_ONLY for k in ("ground_class", "count", "max_distance"))
     assert (sig["ground_class"].default, sig["count"].default, sig["max_distance"].default) == (2, 1, 0.0)
     assert inspect.signature(P.GroundIndex.from_cloud).parameters["ground_class"].default == 2
-
-
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_ground_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_ground.h")
-    assert syms == set(SYMBOLS) == set(_lib._GROUND_SIGNATURES), sorted(syms ^ set(_lib._GROUND_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TRAINING_SIGNATURES, _lib._CROWNS_SIGNATURES,
-                  _lib._SEED_TABLE_SIGNATURES, _lib._BOXES_SIGNATURES, _lib._POINTS_SIGNATURES, _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_training.h", "obia_crowns.h", "obia_seed_table.h", "obia_boxes.h",
-                   "obia_points.h", "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    assert not set(_lib.EXPORTED_SYMBOLS) & syms
-    lib = _lib.load()
-    for name, (res, args) in _lib._GROUND_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
-    text = open(os.path.join(ROOT, "include", "obia_ground.h")).read()
-    assert int(re.search(r"#define\s+OBIA_GROUND_MAX_COUNT\s+(\d+)", text).group(1)) == _lib.GROUND_MAX_COUNT == G.MAX_COUNT
-
-
-def test_a_null_context_is_refused_by_every_ground_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._GROUND_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64) else 0.0 if t is ctypes.c_double else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 def test_the_query_launch_is_a_named_grid():

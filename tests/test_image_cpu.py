@@ -1,12 +1,10 @@
 """Image previews, host side: the CPU restatement (tests/image_restatement.py) against NumPy, against the committed scikit-image
 goldens and against answers worked out by hand; the argument checks of obia_amd.image / Segments.to_segmented_image that fire before
-any device work; the second binding table (include/obia_image.h == obia_amd._lib._IMAGE_SIGNATURES).
+any device work.
 
 The OpenCV parts (grey conversion, equalizeHist, CLAHE) are restated from OpenCV's algorithm and are NOT compared with cv2 anywhere."""
-import ctypes
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
@@ -248,28 +246,3 @@ def test_to_segmented_image_argument_checks():
         seg.to_segmented_image(PIL.fromarray(np.zeros((6, 9), np.float32)))
     with pytest.raises(ValueError, match="mode 'RGBA'"):
         seg.to_segmented_image(PIL.fromarray(np.zeros((6, 9, 4), np.uint8)))
-
-
-# ---- the second binding table ------------------------------------------------------------------------------------------------
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_image_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_image.h")
-    assert len(syms) == 6 and all(s.startswith("obia_image_") for s in syms)
-    assert syms == set(_lib._IMAGE_SIGNATURES), sorted(syms ^ set(_lib._IMAGE_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]
-    assert not syms & set(_lib._SIGNATURES) and not syms & _declared("obia_hip.h")
-    lib = _lib.load()
-    for name, (res, args) in _lib._IMAGE_SIGNATURES.items():               # load() bound the second table as it binds the first
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2

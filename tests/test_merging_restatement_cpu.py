@@ -1,7 +1,6 @@
 """Region merging without a GPU: the restatement (tests/merging_restatement.py) against the hand check of include/obia_merging.h,
 against the adjacency restatement's graph of the relabelled raster, against np.mean and np.var of a union's pixels; the fixed point;
-the recovery of four patches from 192 blocks; the thirteenth binding table (include/obia_merging.h == obia_amd._lib._MERGE_ENTRIES);
-a null context; what the source file must not do; the refusals of the Python functions that fire before the library is loaded.
+the recovery of four patches from 192 blocks; what the header says; what the source file must not do; the refusals of the Python functions that fire before the library is loaded.
 
 THE CHAN MERGE AGAINST NUMPY.  Over every region of every round of six random block maps merged down to one region, the largest
 relative distance of the merged mean from np.mean of the union's pixels (float64) and of m2 / area from np.var was measured (NumPy
@@ -10,7 +9,6 @@ relative distance of the merged mean from np.mean of the union's pixels (float64
     field                  measured      bound
     mean     (relative)    2.21e-16      1.77e-15
     variance (relative)    1.51e-15      1.21e-14"""
-import ctypes
 import os
 import re
 
@@ -21,8 +19,6 @@ from tests import adjacency_restatement as R
 from tests import merging_restatement as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("obia_merge_cost_dev", "obia_merge_pairs_dev", "obia_merge_contract_rows_dev", "obia_merge_contract_count_dev",
-           "obia_merge_contract_write_dev")
 F64, I32, I64 = np.float64, np.int32, np.int64
 BOUNDS = {"mean": 8 * 2.21e-16, "variance": 8 * 1.51e-15}
 
@@ -153,62 +149,10 @@ def test_the_recovery_case(seed):
     assert counts[-1] == 4 and np.array_equal(M.labels_of(lab, final), patch + 1)
 
 
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return txt, set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def _library():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib
-
-
-def test_merge_entry_table_matches_its_header():
-    _lib = _library()
-    txt, syms = _declared("obia_merging.h")
-    assert syms == set(SYMBOLS) == set(_lib._MERGE_ENTRIES), sorted(syms ^ set(_lib._MERGE_ENTRIES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for name, (res, args) in _lib._MERGE_ENTRIES.items():
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt).group(1)
-        params = [p.strip() for p in proto.split(",")]
-        assert res is ctypes.c_int and len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):
-            is_ptr = "*" in p
-            assert is_ptr == (a is ctypes.c_void_p), (name, p, a)
-            if not is_ptr:
-                assert a is {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "double": ctypes.c_double}[p.split()[0]], (name, p, a)
-    for k, v in vars(_lib).items():
-        if isinstance(v, dict) and k != "_MERGE_ENTRIES" and k.endswith(("_SIGNATURES", "_BINDINGS", "_ENTRIES")):
-            assert not syms & set(v), k                                      # the other tables ...
-    for header in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if header != "obia_merging.h":
-            assert not syms & _declared(header)[1], header                   # ... and headers do not hold the new names
-    lib = _lib.load()
-    for name, (res, args) in _lib._MERGE_ENTRIES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
+# ------------------------------------------------------------------------------------------------- the header and the source
+def test_the_header_says_no_row_is_dropped():
     full = open(os.path.join(ROOT, "include", "obia_merging.h")).read()
-    assert int(re.search(r"#define\s+OBIA_MERGE_ROW_CAP\s+(\d+)", full).group(1)) == _lib.MERGE_ROW_CAP == 2048
     assert "NO ROW IS EVER DROPPED OR TRUNCATED" in full and "The reference has no counterpart" in full and "compared with eCognition" in full
-    # the name of the table keeps it out of the collections of the existing decision tables
-    assert not "_MERGE_ENTRIES".endswith(("_SIGNATURES", "_BINDINGS"))
-    src = open(os.path.join(ROOT, "obia_amd", "_lib.py")).read()
-    assert "list(_MERGE_ENTRIES.items())" in src
-
-
-def test_a_null_context_is_refused_by_every_merge_entry_point():
-    _lib = _library()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._MERGE_ENTRIES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double) else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 def test_the_source_takes_no_workspace_and_every_atomic_is_on_an_integer():

@@ -1,18 +1,10 @@
 """Point clouds without a GPU: the restatement (tests/pointcloud_restatement.py) against hand-worked answers and against the
-reference's arithmetic (np.mean / np.var of Intensity, segment_statistics.py:332-389), the telescoping of ``pad`` to ``pai``, the
-eighth binding table (include/obia_points.h == obia_amd._lib._POINTS_SIGNATURES), and the refusals of obia_amd.pointcloud and
-create_objects that fire before the device is touched."""
-import ctypes
-import os
-import re
-
+reference's arithmetic (np.mean / np.var of Intensity, segment_statistics.py:332-389), the telescoping of ``pad`` to ``pai``, and
+the refusals of obia_amd.pointcloud and create_objects that fire before the device is touched."""
 import numpy as np
 import pytest
 
 from tests import pointcloud_restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("obia_points_rasters_dev", "obia_points_rasters_finish_dev", "obia_points_segments_dev", "obia_points_segment_columns_dev")
 
 # a 2 x 2 raster of unit pixels whose top-left corner is the map point (0, 2): col = X, row = 2 - Y
 AFFINE_2X2 = [1.0, 0.0, 0.0, -1.0, 0.0, 2.0]
@@ -131,50 +123,6 @@ def test_the_key_keeps_the_order_of_the_floats():
     k = R.zkey(z)
     assert (np.diff(k.astype(np.int64)) > 0).all() and (k != 0).all()
     assert np.array_equal(R.zunkey(k).view(np.uint32), z.view(np.uint32))
-
-
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_points_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_points.h")
-    assert syms == set(SYMBOLS) == set(_lib._POINTS_SIGNATURES), sorted(syms ^ set(_lib._POINTS_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TRAINING_SIGNATURES, _lib._CROWNS_SIGNATURES,
-                  _lib._SEED_TABLE_SIGNATURES, _lib._BOXES_SIGNATURES, _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_training.h", "obia_crowns.h", "obia_seed_table.h", "obia_boxes.h",
-                   "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    assert not set(_lib.EXPORTED_SYMBOLS) & syms
-    lib = _lib.load()
-    for name, (res, args) in _lib._POINTS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
-    text = open(os.path.join(ROOT, "include", "obia_points.h")).read()
-    for define, value in (("OBIA_POINTS_MAX_NZ", _lib.POINTS_MAX_NZ), ("OBIA_POINTS_CHUNK", _lib.POINTS_CHUNK)):
-        assert int(re.search(rf"#define\s+{define}\s+(\d+)", text).group(1)) == value
-
-
-def test_a_null_context_is_refused_by_every_points_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._POINTS_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64) else 0.0 if t is ctypes.c_double else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 # ------------------------------------------------------------------------------------------------------ refusals before the device

@@ -1,16 +1,9 @@
-"""The seed-table options, host side: the public names, the sixth binding table (include/obia_seed_table.h ==
-obia_amd._lib._SEED_TABLE_SIGNATURES) and the argument checks of obia_amd.seeds that fire before the device is touched."""
-import ctypes
-import os
-import re
-
+"""The seed-table options, host side: the public names and the argument checks of obia_amd.seeds that fire before the device is
+touched."""
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGES = ("sample_heights", "stage1_clusters", "reduce_stage1", "split_clusters_by_height", "trim_clusters", "nms_per_crown")
-SYMBOLS = ("obia_seedtab_cells_dev", "obia_seedtab_sample_dev", "obia_seedtab_stage1_dev", "obia_seedtab_last_work",
-           "obia_seedtab_segments_dev", "obia_seedtab_nms_dev")
 
 
 def _seeds(n=3, col="ch_max"):
@@ -48,47 +41,6 @@ def test_public_names():
     assert {k: p.default for k, p in sig.parameters.items() if p.kind is p.KEYWORD_ONLY} == want
     assert list(sig.parameters)[4:] == list(want)
     assert "canonical_seeds" in seeds.make_canonical_seeds.__doc__ and "canonical_seeds" in seeds.__doc__
-
-
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_seed_table_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_seed_table.h")
-    assert syms == set(SYMBOLS) == set(_lib._SEED_TABLE_SIGNATURES), sorted(syms ^ set(_lib._SEED_TABLE_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TRAINING_SIGNATURES, _lib._CROWNS_SIGNATURES,
-                  _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_training.h", "obia_crowns.h", "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    # EXPORTED_SYMBOLS is the first table, which tests/test_abi_and_host.py pins to include/obia_hip.h one to one: the new
-    # symbols are exported through the sixth, as the crowns' are through the fifth
-    assert not set(_lib.EXPORTED_SYMBOLS) & syms
-    lib = _lib.load()
-    for name, (res, args) in _lib._SEED_TABLE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
-
-
-def test_a_null_context_is_refused_by_every_seed_table_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._SEED_TABLE_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int64) else 0.0 if t in (ctypes.c_double, ctypes.c_float) else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 BAD_OPTIONS = [(dict(min_eps=-0.5), "min_eps must not be negative"), (dict(min_eps=9), "min_eps must not exceed max_eps"),

@@ -1,8 +1,7 @@
 """The shape columns without a GPU: the restatement (tests/shapes_restatement.py) against a double loop over pixels with Python
 integers and against scikit-image's regionprops (tests/golden/shapes/*.npz, written by tests/golden/gen_goldens_shapes.py); closed
 forms; translation; merge and pair_shapes against recomputation on the relabelled raster; the perimeter against the adjacency
-restatement; the twelfth binding table (include/obia_shapes.h == obia_amd._lib._SHAPE_ENTRIES); a null context; what the source file
-must not do; the refusals of the Python functions that fire before the library is loaded; the overflow rule at its threshold.
+restatement; what the header says; what the source file must not do; the refusals of the Python functions that fire before the library is loaded; the overflow rule at its threshold.
 
 COMPARISON WITH SCIKIT-IMAGE 0.18.3.  Integer fields (area, bbox) are equal.  For the float fields the restatement's largest deviation
 from the goldens over the three maps was measured (NumPy 2.x, x86-64) and the bound is 8 x the measured value:
@@ -18,7 +17,6 @@ from the goldens over the three maps was measured (NumPy 2.x, x86-64) and the bo
     orientation (absolute)    2.78e-15              2.22e-14
 
 No segment of the three maps has equal eigenvalues (smallest relative gap 0.043), so none is left out of the orientation comparison."""
-import ctypes
 import os
 import re
 
@@ -30,7 +28,6 @@ from tests import shapes_restatement as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-SYMBOLS = ("obia_shape_sums_dev",)
 MAPS = ("c2s_256x256x4_c025", "quickstart_128x128x3", "mask_128x160x4_c025")
 F64, I32, I64 = np.float64, np.int32, np.int64
 # 8 x the measured deviations of the module docstring
@@ -223,64 +220,10 @@ def test_pair_shapes_is_the_shape_of_the_union():
             assert all(S.same_bits(pairs[k][e:e + 1], d[k][i:i + 1]) for k in ("compactness", "shape_index", "smoothness"))
 
 
-# ------------------------------------------------------------------------------------------------------ header against table
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return txt, set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def _library():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib
-
-
-def test_shape_entry_table_matches_its_header():
-    _lib = _library()
-    txt, syms = _declared("obia_shapes.h")
-    assert syms == set(SYMBOLS) == set(_lib._SHAPE_ENTRIES), sorted(syms ^ set(_lib._SHAPE_ENTRIES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]                     # the library exports every one of them
-    for name, (res, args) in _lib._SHAPE_ENTRIES.items():
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt).group(1)
-        params = [p.strip() for p in proto.split(",")]
-        assert res is ctypes.c_int and len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):
-            is_ptr = "*" in p
-            assert is_ptr == (a is ctypes.c_void_p), (name, p, a)
-            if not is_ptr:
-                assert a is {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}[p.split()[0]], (name, p, a)
-    for k, v in vars(_lib).items():
-        if isinstance(v, dict) and k != "_SHAPE_ENTRIES" and k.endswith(("_SIGNATURES", "_BINDINGS", "_ENTRIES")):
-            assert not syms & set(v), k                                      # the other tables ...
-    for header in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if header != "obia_shapes.h":
-            assert not syms & _declared(header)[1], header                   # ... and headers do not hold the new names
-    lib = _lib.load()
-    for name, (res, args) in _lib._SHAPE_ENTRIES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert lib.obia_abi_version() == 2
+# ------------------------------------------------------------------------------------------------- the header and the source
+def test_the_header_says_there_is_no_overflow_path():
     full = open(os.path.join(ROOT, "include", "obia_shapes.h")).read()
-    macros = {m: int(re.search(r"#define\s+" + m + r"\s+(\d+)", full).group(1)) for m in ("OBIA_SHAPE_SUMS", "OBIA_SHAPE_TABLE")}
-    assert (macros["OBIA_SHAPE_SUMS"], macros["OBIA_SHAPE_TABLE"]) == (_lib.SHAPE_SUMS, _lib.SHAPE_TABLE) == (7, 1024)
-    # no overflow path: the table holds every segment a tile can hold, with room to spare
-    assert _lib.SHAPE_TABLE & (_lib.SHAPE_TABLE - 1) == 0 and _lib.SHAPE_TABLE > _lib.ADJ_TILE_H * _lib.ADJ_TILE_W
     assert "THERE IS NO OVERFLOW PATH" in full and "NO SUM OVERFLOWS" in full and "The reference has no counterpart" in full
-    # the name of the table keeps it out of the collections of the existing decision tables, and says so
-    src = open(os.path.join(ROOT, "obia_amd", "_lib.py")).read()
-    assert "Named _ENTRIES on purpose" in src
-
-
-def test_a_null_context_is_refused_by_every_shape_entry_point():
-    _lib = _library()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._SHAPE_ENTRIES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64) else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name
 
 
 def test_the_source_takes_no_workspace_and_every_atomic_is_on_an_integer():

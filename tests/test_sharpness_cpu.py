@@ -1,15 +1,12 @@
 """The sharpness raster, host side: the NumPy restatement (tests/sharpness_restatement.py) against the committed SciPy 1.15.3 goldens
 of the box filter (and against SciPy itself where it is installed), the Laplacian against answers worked out by hand, the grey
 expression and the stretch against the reference's NumPy lines; the argument checks of obia_amd.image.rgb_to_gray / box_filter /
-variance_of_laplacian / laplacian that fire before any device work; the third binding table (include/obia_sharpness.h ==
-obia_amd._lib._SHARPNESS_SIGNATURES).
+variance_of_laplacian / laplacian that fire before any device work.
 
 The Laplacian is cv2.Laplacian(gray, CV_32F, ksize=3) restated from OpenCV's algorithm and is NOT compared with cv2 anywhere."""
-import ctypes
 import glob
 import hashlib
 import os
-import re
 
 import numpy as np
 import pytest
@@ -242,31 +239,3 @@ def test_lower_functions_argument_checks():
             I.rgb_to_gray(bad)
     with pytest.raises(TypeError, match="int32"):
         I.rgb_to_gray(np.zeros((6, 7, 3), np.int32))
-
-
-# ---- the third binding table ---------------------------------------------------------------------------------------------------
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_sharpness_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_sharpness.h")
-    assert len(syms) == 5 and all(s.startswith("obia_sharp_") for s in syms)
-    assert syms == set(_lib._SHARPNESS_SIGNATURES), sorted(syms ^ set(_lib._SHARPNESS_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]
-    assert not syms & set(_lib._SIGNATURES) and not syms & set(_lib._IMAGE_SIGNATURES)        # the other two tables ...
-    assert not syms & _declared("obia_hip.h") and not syms & _declared("obia_image.h")        # ... and headers do not hold the new names
-    lib = _lib.load()
-    for name, (res, args) in _lib._SHARPNESS_SIGNATURES.items():             # load() bound the third table as it binds the others
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    header = open(os.path.join(ROOT, "include", "obia_sharpness.h")).read()
-    assert int(re.search(r"#define OBIA_SHARP_MAX_WIN (\d+)", header).group(1)) == _lib.SHARP_MAX_WIN
-    assert lib.obia_abi_version() == 2

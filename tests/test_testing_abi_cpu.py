@@ -1,37 +1,10 @@
-"""include/obia_testing.h without a GPU: the fourth binding table of obia_amd/_lib.py names exactly what the header declares, the
-library exports it, none of it leaks into the operator ABI (include/obia_hip.h), and a null context is refused before anything else;
-`timing()` knows the three command counters (obia_last_timing 16-18)."""
+"""`timing()` knows the three command counters (obia_last_timing 16-18).  (include/obia_testing.h against its binding table, and a
+null context: tests/test_binding_tables_cpu.py and tests/test_entry_layer_cpu.py.)"""
 import os
-import re
 
 from obia_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared(header):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_the_table_is_the_header():
-    syms = declared("obia_testing.h")
-    assert syms == set(_lib._TEST_SIGNATURES) == {"obia_test_clear_ranges_dev", "obia_test_sweep_plan", "obia_test_launch_grid",
-                                                       "obia_test_launch_grid_names", "obia_test_seam_sort_limit",
-                                                       "obia_test_enforce_connectivity_batch_dev", "obia_test_cc_report",
-                                                       "obia_test_poison_workspace_dev", "obia_test_visited_nonzero"}
-    assert not syms & set(_lib._SIGNATURES) and not syms & declared("obia_hip.h")
-    lib = _lib.load()
-    for name, (res, args) in _lib._TEST_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-
-
-def test_a_null_context_is_refused_first():
-    lib = _lib.load()
-    assert lib.obia_synchronize(None) == _lib.E_INVALID
-    assert lib.obia_test_clear_ranges_dev(None, None, None, None, 0) == _lib.E_INVALID
-    assert _lib.last_error() == "null context"
 
 
 def test_timing_names_the_command_counters():

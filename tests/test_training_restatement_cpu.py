@@ -1,20 +1,14 @@
 """The training tiles, host side: the NumPy restatement (tests/training_restatement.py) against things outside it -- the blur against
 SciPy's correlate1d in exact dyadic float64, the chamfer sweep against its closed form and against the Euclidean transform's bounds,
 the tile windows against plain float arithmetic, the annotations against boxes worked out by hand --, the host functions of
-obia_amd.training against the restatement, the argument checks that fire before the device is touched, and the fourth binding table
-(include/obia_training.h == obia_amd._lib._TRAINING_SIGNATURES).
+obia_amd.training against the restatement, and the argument checks that fire before the device is touched.
 
 cv2.GaussianBlur and cv2.distanceTransform are restated from OpenCV's algorithms and are NOT compared with cv2 anywhere."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
 from tests import training_restatement as T
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BLUR_SHAPES = ((1, 1), (2, 3), (3, 7), (9, 4), (13, 17), (70, 131))
 BLUR_KERNELS = ((5, 5), (11, 11), (11, 5), (7, 31), (1, 9))
 
@@ -268,46 +262,3 @@ def test_the_package_exports_the_module():
     import obia_amd
     assert obia_amd.tile_and_process is obia_amd.training.tile_and_process
     assert obia_amd.process_tile is obia_amd.training.process_tile and obia_amd.TrainingTiles is obia_amd.training.TrainingTiles
-
-
-# ---- the fourth binding table ----------------------------------------------------------------------------------------------------
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(obia_[a-z0-9_]+)\s*\(", txt))
-
-
-def test_training_binding_table_matches_its_header():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    syms = _declared("obia_training.h")
-    assert len(syms) == 4 and all(s.startswith("obia_train_") for s in syms)
-    assert syms == set(_lib._TRAINING_SIGNATURES), sorted(syms ^ set(_lib._TRAINING_SIGNATURES))
-    cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [s for s in syms if not hasattr(cdll, s)]
-    for table in (_lib._SIGNATURES, _lib._IMAGE_SIGNATURES, _lib._SHARPNESS_SIGNATURES, _lib._TEST_SIGNATURES):
-        assert not syms & set(table)                                         # the other tables ...
-    for header in ("obia_hip.h", "obia_image.h", "obia_sharpness.h", "obia_testing.h"):
-        assert not syms & _declared(header)                                  # ... and headers do not hold the new names
-    lib = _lib.load()
-    for name, (res, args) in _lib._TRAINING_SIGNATURES.items():              # load() bound the fourth table as it binds the others
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    header = open(os.path.join(ROOT, "include", "obia_training.h")).read()
-    for macro, value in (("OBIA_TRAIN_MAX_KSIZE", _lib.TRAIN_MAX_KSIZE), ("OBIA_TRAIN_MAX_SIDE", _lib.TRAIN_MAX_SIDE),
-                         ("OBIA_TRAIN_MINMAX_WORK", _lib.TRAIN_MINMAX_WORK)):
-        assert int(re.search(rf"#define {macro} (\d+)", header).group(1)) == value
-    assert lib.obia_abi_version() == 2
-
-
-def test_a_null_context_is_refused_by_every_training_entry_point():
-    pytest.importorskip("torch")
-    from obia_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = _lib.load()
-    for name, (_, argtypes) in _lib._TRAINING_SIGNATURES.items():
-        args = [0 if t in (ctypes.c_int, ctypes.c_int64) else 0.0 if t is ctypes.c_double else None for t in argtypes]
-        assert getattr(lib, name)(*args) == _lib.E_INVALID and _lib.last_error() == "null context", name

@@ -183,6 +183,19 @@ ROWS = {
     "obia_adj_best_neighbor_dev": run("body:adjacency", ONE_KERNEL),
     "obia_adj_components_dev": run("body:adjacency", ONE_KERNEL + " (root_out is written whole by adj_iota_kernel before the link kernel reads it)"),
     "obia_adj_relabel_dev": run("body:adjacency", ONE_KERNEL),
+    # ---- include/obia_shapes.h: shapes.hip names the arena nowhere, both tables are the caller's --------------------------------------
+    "obia_shape_sums_dev": run("body:shapes", ONE_KERNEL + " (sums_out and box_out by two fill_async before the tile kernel adds to them; the tile's "
+                                              "keys, accumulators and slot count live in LDS, cleared by their workgroup before its first tile and "
+                                              "again, slot by slot, as it flushes one)"),
+    # ---- include/obia_merging.h: merging.hip names the arena nowhere, every table, scratch row and cursor is the caller's -------------
+    "obia_merge_cost_dev": run("body:merging", ONE_KERNEL + " (a value per entry, written whole; nothing is accumulated)"),
+    "obia_merge_pairs_dev": run("body:merging", ONE_KERNEL + " (a row per segment, written whole; nothing is accumulated)"),
+    "obia_merge_contract_rows_dev": run("body:merging", ONE_KERNEL + " (raw_count_out by fill_async before contract_rows_kernel adds the row lengths to it)"),
+    "obia_merge_contract_count_dev": run("body:merging", ONE_KERNEL + " (`cursor_work`, the caller's, by fill_async before the gather takes its tickets; the "
+                                                         "gather writes every stretch of `key_work` / `border_work` whole before a sort kernel reads it; "
+                                                         "the block sort loads its LDS row, chunk keys and sums before it reads them; count_out is written "
+                                                         "for every row by the one sort kernel whose length class the row falls in)"),
+    "obia_merge_contract_write_dev": run("body:merging", ONE_KERNEL + " (reads the count pass's scratch, writes every entry of neighbor_out / border_out)"),
     # ---- include/obia_testing.h ---------------------------------------------------------------------------------------------------
     "obia_test_clear_ranges_dev": exempt("takes no workspace: the table of ranges is the clear kernel's argument, passed by value"),
     "obia_test_sweep_plan": exempt(NO_CONTEXT),
@@ -209,12 +222,9 @@ ARENA_FILES = {
 
 
 def bound_entry_points():
-    """every name of every signature table of obia_amd/_lib.py: the tables named *_SIGNATURES and the two named *_BINDINGS"""
+    """every name of the registry of obia_amd/_lib.py, in its order"""
     from obia_amd import _lib
-    names = []
-    for table in (v for k, v in vars(_lib).items() if k.endswith(("_SIGNATURES", "_BINDINGS")) and isinstance(v, dict)):
-        names += list(table)
-    return names
+    return _lib.bound_entry_points()
 
 
 def cases():
