@@ -16,7 +16,7 @@
 // are the lock-free union-find of seeds.hip -- roots are the smallest members -- with path halving, in the caller's root array.
 //
 // Nothing here takes memory from the context's workspace: every buffer is the caller's.  Every atomic is an integer atomic.
-#include "common.hpp"
+#include "csr.hpp"
 #include "../../include/obia_adjacency.h"
 
 #include <climits>
@@ -136,28 +136,6 @@ template <bool WRITE> __global__ __launch_bounds__(256) void adj_tile_kernel(Til
             __syncthreads();
         }
 }
-
-// ---- a CSR the caller passes: read defensively (the header: "A CSR THE CALLER PASSES") ---------------------------------------------
-struct Csr {
-    const long long *indptr; const int *neighbor; const long long *border;
-    int N; long long nnz;
-};
-__device__ __forceinline__ void row_range(const Csr &G, int i, long long &lo, long long &hi) {
-    lo = G.indptr[i];
-    hi = G.indptr[i + 1];
-    if (lo < 0) lo = 0;
-    if (hi > G.nnz) hi = G.nnz;
-}
-// the row of entry e: the largest i in 0 .. N - 1 with indptr[i] <= e (N >= 1)
-__device__ __forceinline__ int row_of(const Csr &G, long long e) {
-    int lo = 0, hi = G.N;                                        // indptr[lo] <= e < indptr[hi], by convention at the ends
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (G.indptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ bool is_real(const Csr &G, int j) { return j >= 0 && j < G.N; }
 
 __global__ __launch_bounds__(256) void adj_d2_kernel(Csr G, const double *__restrict__ values, int F, double *__restrict__ d2) {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < G.nnz; e += (long long)gridDim.x * 256) {
@@ -293,32 +271,6 @@ __global__ __launch_bounds__(256) void adj_relabel_kernel(const int *__restrict_
     }
 }
 
-int bad_buffers(const char *what) {
-    set_error("adjacency: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
-}
-int check_labels(const char *what, int32_t n_labels) {
-    if (n_labels < 0 || n_labels > INT_MAX - 2) { set_error("adjacency: %s: n_labels must be in 0 .. 2^31 - 3, got %d", what, n_labels); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-int check_raster(const char *what, int H, int W) {
-    if (H <= 0 || W <= 0) { set_error("adjacency: %s: H and W must be positive, got %d x %d", what, H, W); return OBIA_E_INVALID; }
-    if ((long long)H * W > (long long)INT_MAX) { set_error("adjacency: %s: H * W must be below 2^31, got %d x %d", what, H, W); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
-int check_count(const char *what, const char *name, int64_t n, int64_t least) {
-    if (n < least) { set_error("adjacency: %s: %s must be at least %lld, got %lld", what, name, (long long)least, (long long)n); return OBIA_E_INVALID; }
-    if (n > (int64_t)INT_MAX) { set_error("adjacency: %s: %s must be below 2^31, got %lld", what, name, (long long)n); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
-// the CSR of a table call: indptr whenever there is a row, neighbor whenever there is an entry
-bool csr_missing(const int64_t *indptr, const int32_t *neighbor, int32_t N, int64_t nnz) {
-    return (N > 0 && !indptr) || (nnz > 0 && !neighbor) || misaligned(indptr, 8) || misaligned(neighbor, 4);
-}
-Csr csr_of(const int64_t *indptr, const int32_t *neighbor, const int64_t *border, int32_t N, int64_t nnz) {
-    return Csr{reinterpret_cast<const long long *>(indptr), neighbor, reinterpret_cast<const long long *>(border), N, (long long)nnz};
-}
-
 }  // namespace
 }  // namespace obia
 
@@ -328,9 +280,10 @@ extern "C" {
 
 int obia_adj_tile_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int32_t start_label, int32_t n_labels, int32_t *count_out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !count_out || misaligned(labels, 4) || misaligned(count_out, 4) || shared_start(1, count_out, labels)) return bad_buffers("tile count");
-    OBIA_TRY(check_labels("tile count", n_labels));
-    OBIA_TRY(check_raster("tile count", H, W));
+    const Refusal refuse{"adjacency", "tile count"};
+    if (Buffers().out(count_out).in(labels).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         TileArgs T{};
         T.labels = labels; T.H = H; T.W = W; T.start = start_label; T.N = n_labels; T.count_out = count_out;
@@ -343,12 +296,11 @@ int obia_adj_tile_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, 
 int obia_adj_tile_write_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int32_t start_label, int32_t n_labels, const int64_t *offset,
                             int64_t total, int64_t *key_out, int32_t *edges_out, int32_t *work) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !offset || !work || (total > 0 && (!key_out || !edges_out)) || misaligned(labels, 4) || misaligned(offset, 8) ||
-        misaligned(key_out, 8) || misaligned(edges_out, 4) || misaligned(work, 4) || shared_start(3, key_out, edges_out, work, labels, offset))
-        return bad_buffers("tile write");
-    OBIA_TRY(check_labels("tile write", n_labels));
-    OBIA_TRY(check_raster("tile write", H, W));
-    OBIA_TRY(check_count("tile write", "total", total, 0));
+    const Refusal refuse{"adjacency", "tile write"};
+    if (Buffers().out(key_out, total > 0).out(edges_out, total > 0).out(work).in(labels).in(offset).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
+    OBIA_TRY(refuse.count("total", total, 0));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         TileArgs T{};
         T.labels = labels; T.H = H; T.W = W; T.start = start_label; T.N = n_labels;
@@ -367,13 +319,13 @@ int obia_adj_tile_write_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, 
 int obia_adj_edge_d2_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *neighbor, int32_t n_labels, int64_t nnz, const double *values,
                          int F, double *d2_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("edge d2", n_labels));
-    OBIA_TRY(check_count("edge d2", "F", F, 1));
-    OBIA_TRY(check_count("edge d2", "nnz", nnz, 0));
-    OBIA_TRY(check_count("edge d2", "n_labels * F", (int64_t)n_labels * F, 0));
-    if (csr_missing(indptr, neighbor, n_labels, nnz) || (n_labels > 0 && !values) || (nnz > 0 && !d2_out) || misaligned(values, 8) ||
-        misaligned(d2_out, 8) || shared_start(1, d2_out, indptr, neighbor, values))
-        return bad_buffers("edge d2");
+    const Refusal refuse{"adjacency", "edge d2"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("F", F, 1));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("n_labels * F", (int64_t)n_labels * F, 0));
+    Buffers b;
+    if (list_csr(b, indptr, neighbor, n_labels, nnz).in(values, n_labels > 0).out(d2_out, nnz > 0).bad()) return refuse.buffers();
     if (nnz == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_d2_kernel, to_dim3(grids::flat(nnz)), dim3(256), 0, ctx->stream, csr_of(indptr, neighbor, nullptr, n_labels, nnz),
@@ -387,15 +339,15 @@ int obia_adj_neighbor_stats_dev(obia_ctx *ctx, const int64_t *indptr, const int3
                                 int64_t nnz, const double *values, int F, double *mean_out, double *min_out, double *max_out,
                                 int32_t *used_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("neighbor stats", n_labels));
-    OBIA_TRY(check_count("neighbor stats", "F", F, 1));
-    OBIA_TRY(check_count("neighbor stats", "nnz", nnz, 0));
-    OBIA_TRY(check_count("neighbor stats", "n_labels * F", (int64_t)n_labels * F, 0));
-    if (csr_missing(indptr, neighbor, n_labels, nnz) || (nnz > 0 && !border) || misaligned(border, 8) ||
-        (n_labels > 0 && (!values || !mean_out || !min_out || !max_out || !used_out)) || misaligned(values, 8) || misaligned(mean_out, 8) ||
-        misaligned(min_out, 8) || misaligned(max_out, 8) || misaligned(used_out, 4) ||
-        shared_start(4, mean_out, min_out, max_out, used_out, indptr, neighbor, border, values))
-        return bad_buffers("neighbor stats");
+    const Refusal refuse{"adjacency", "neighbor stats"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("F", F, 1));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("n_labels * F", (int64_t)n_labels * F, 0));
+    const bool rows = n_labels > 0;
+    Buffers b;
+    list_csr(b, indptr, neighbor, border, n_labels, nnz).in(values, rows);
+    if (b.out(mean_out, rows).out(min_out, rows).out(max_out, rows).out(used_out, rows).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_stats_kernel, to_dim3(grids::flat((long long)n_labels * F)), dim3(256), 0, ctx->stream,
@@ -408,13 +360,13 @@ int obia_adj_neighbor_stats_dev(obia_ctx *ctx, const int64_t *indptr, const int3
 int obia_adj_class_border_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *neighbor, const int64_t *border, int32_t n_labels,
                               int64_t nnz, const int32_t *classes, int K, int64_t *out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("class border", n_labels));
-    OBIA_TRY(check_count("class border", "K", K, 1));
-    OBIA_TRY(check_count("class border", "nnz", nnz, 0));
-    OBIA_TRY(check_count("class border", "n_labels * K", (int64_t)n_labels * K, 0));
-    if (csr_missing(indptr, neighbor, n_labels, nnz) || (nnz > 0 && !border) || misaligned(border, 8) || (n_labels > 0 && (!classes || !out)) ||
-        misaligned(classes, 4) || misaligned(out, 8) || shared_start(1, out, indptr, neighbor, border, classes))
-        return bad_buffers("class border");
+    const Refusal refuse{"adjacency", "class border"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("K", K, 1));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("n_labels * K", (int64_t)n_labels * K, 0));
+    Buffers b;
+    if (list_csr(b, indptr, neighbor, border, n_labels, nnz).in(classes, n_labels > 0).out(out, n_labels > 0).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_class_border_kernel, to_dim3(grids::flat(n_labels)), dim3(256), 0, ctx->stream,
@@ -427,11 +379,12 @@ int obia_adj_class_border_dev(obia_ctx *ctx, const int64_t *indptr, const int32_
 int obia_adj_best_neighbor_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *neighbor, int32_t n_labels, int64_t nnz,
                                const double *d2, int32_t *best_out, double *best_d2_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("best neighbor", n_labels));
-    OBIA_TRY(check_count("best neighbor", "nnz", nnz, 0));
-    if (csr_missing(indptr, neighbor, n_labels, nnz) || (nnz > 0 && !d2) || misaligned(d2, 8) || (n_labels > 0 && (!best_out || !best_d2_out)) ||
-        misaligned(best_out, 4) || misaligned(best_d2_out, 8) || shared_start(2, best_out, best_d2_out, indptr, neighbor, d2))
-        return bad_buffers("best neighbor");
+    const Refusal refuse{"adjacency", "best neighbor"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    Buffers b;
+    if (list_csr(b, indptr, neighbor, n_labels, nnz).in(d2, nnz > 0).out(best_out, n_labels > 0).out(best_d2_out, n_labels > 0).bad())
+        return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_best_kernel, to_dim3(grids::flat(n_labels)), dim3(256), 0, ctx->stream, csr_of(indptr, neighbor, nullptr, n_labels, nnz),
@@ -444,11 +397,11 @@ int obia_adj_best_neighbor_dev(obia_ctx *ctx, const int64_t *indptr, const int32
 int obia_adj_components_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *neighbor, int32_t n_labels, int64_t nnz,
                             const uint8_t *link, int32_t *root_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("components", n_labels));
-    OBIA_TRY(check_count("components", "nnz", nnz, 0));
-    if (csr_missing(indptr, neighbor, n_labels, nnz) || (nnz > 0 && !link) || (n_labels > 0 && !root_out) || misaligned(root_out, 4) ||
-        shared_start(1, root_out, indptr, neighbor, link))
-        return bad_buffers("components");
+    const Refusal refuse{"adjacency", "components"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    Buffers b;
+    if (list_csr(b, indptr, neighbor, n_labels, nnz).in(link, nnz > 0).out(root_out, n_labels > 0).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_iota_kernel, to_dim3(grids::flat(n_labels)), dim3(256), 0, ctx->stream, root_out, n_labels);
@@ -467,11 +420,10 @@ int obia_adj_components_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t 
 int obia_adj_relabel_dev(obia_ctx *ctx, const int32_t *labels, int64_t npx, int32_t start_label, int32_t n_labels, const int32_t *map,
                          int32_t *out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("relabel", n_labels));
-    OBIA_TRY(check_count("relabel", "npx", npx, 1));
-    if (!labels || !out || (n_labels > 0 && !map) || misaligned(labels, 4) || misaligned(map, 4) || misaligned(out, 4) ||
-        shared_start(1, out, labels, map))
-        return bad_buffers("relabel");
+    const Refusal refuse{"adjacency", "relabel"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("npx", npx, 1));
+    if (Buffers().out(out).in(labels).in(map, n_labels > 0).bad()) return refuse.buffers();
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(adj_relabel_kernel, to_dim3(grids::flat(npx)), dim3(256), 0, ctx->stream, labels, (long long)npx, start_label, n_labels, map,
                            out);

@@ -265,20 +265,6 @@ __global__ __launch_bounds__(256) void boxes_nms_keep_kernel(const uint8_t *__re
     if (k < n) keep_out[k] = state[k] == ST_KEPT ? 1 : 0;
 }
 
-int bad_buffers(const char *what) {
-    set_error("boxes: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
-}
-int check_n(const char *what, int64_t n) {
-    if (n < 1 || n > (int64_t)INT_MAX) { set_error("boxes: %s: n must be in 1 .. 2^31 - 1, got %lld", what, (long long)n); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-int check_raster(const char *what, int H, int W, int32_t n_labels) {
-    if (H <= 0 || W <= 0) { set_error("boxes: %s: H and W must be positive, got %d x %d", what, H, W); return OBIA_E_INVALID; }
-    if (n_labels < 0 || n_labels == INT_MAX) { set_error("boxes: %s: n_labels must be in 0 .. 2^31 - 2, got %d", what, n_labels); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-
 // the boxes are finite and ordered, and (with a raster) no footprint has 2^31 pixels or more; leaves flags (N_FLAGS ints) all zero
 int check_boxes(obia_ctx *ctx, const char *what, const double *boxes, int64_t n, int H, int W, bool with_raster, int *flags) {
     OBIA_TRY(fill_async(ctx, flags, 0, N_FLAGS * sizeof(int)));
@@ -322,11 +308,10 @@ extern "C" {
 int obia_boxes_assign_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, const double *boxes, int64_t n, int32_t n_labels,
                           int32_t *assigned_out, double *area_out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !boxes || !assigned_out || !area_out || misaligned(labels, 4) || misaligned(boxes, 8) || misaligned(assigned_out, 4) ||
-        misaligned(area_out, 8) || shared_start(2, assigned_out, area_out, labels, boxes))
-        return bad_buffers("assign");
-    OBIA_TRY(check_n("assign", n));
-    OBIA_TRY(check_raster("assign", H, W, n_labels));
+    const Refusal refuse{"boxes", "assign"};
+    if (Buffers().out(assigned_out).out(area_out).in(labels).in(boxes).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
+    OBIA_TRY(refuse.raster(H, W, n_labels));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         const long long m = (long long)n_labels + 1;
         WalkArgs A{};
@@ -354,11 +339,10 @@ int obia_boxes_assign_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, co
 int obia_boxes_pair_count_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, const double *boxes, int64_t n, int32_t n_labels,
                               int64_t *count_out, int32_t *passes_out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !boxes || !count_out || !passes_out || misaligned(labels, 4) || misaligned(boxes, 8) || misaligned(count_out, 8) ||
-        misaligned(passes_out, 4) || shared_start(2, count_out, passes_out, labels, boxes))
-        return bad_buffers("pair count");
-    OBIA_TRY(check_n("pair count", n));
-    OBIA_TRY(check_raster("pair count", H, W, n_labels));
+    const Refusal refuse{"boxes", "pair count"};
+    if (Buffers().out(count_out).out(passes_out).in(labels).in(boxes).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
+    OBIA_TRY(refuse.raster(H, W, n_labels));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         WalkArgs A{};
         A.labels = labels; A.H = H; A.W = W; A.boxes = boxes; A.n = (int)n; A.n_labels = n_labels;
@@ -376,13 +360,11 @@ int obia_boxes_pair_write_dev(obia_ctx *ctx, const int32_t *labels, int H, int W
                               const int64_t *offset, const int32_t *passes, int64_t total, int32_t *box_out, int32_t *segment_out,
                               double *area_out, int32_t *meets_out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !boxes || !offset || !passes || !box_out || !segment_out || !area_out || !meets_out || misaligned(labels, 4) ||
-        misaligned(boxes, 8) || misaligned(offset, 8) || misaligned(passes, 4) || misaligned(box_out, 4) || misaligned(segment_out, 4) ||
-        misaligned(area_out, 8) || misaligned(meets_out, 4) ||
-        shared_start(4, box_out, segment_out, area_out, meets_out, labels, boxes, offset, passes))
-        return bad_buffers("pair write");
-    OBIA_TRY(check_n("pair write", n));
-    OBIA_TRY(check_raster("pair write", H, W, n_labels));
+    const Refusal refuse{"boxes", "pair write"};
+    if (Buffers().out(box_out).out(segment_out).out(area_out).out(meets_out).in(labels).in(boxes).in(offset).in(passes).bad())
+        return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
+    OBIA_TRY(refuse.raster(H, W, n_labels));
     if (total < 1) { set_error("boxes: pair write: total must be at least 1, got %lld", (long long)total); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         WalkArgs A{};
@@ -405,9 +387,7 @@ int obia_boxes_pair_write_dev(obia_ctx *ctx, const int32_t *labels, int H, int W
 
 int obia_boxes_dissolve_dev(obia_ctx *ctx, const int32_t *labels, int64_t npx, const int32_t *assigned, int32_t n_labels, int32_t *out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || !assigned || !out || misaligned(labels, 4) || misaligned(assigned, 4) || misaligned(out, 4) || labels == out ||
-        assigned == out)
-        return bad_buffers("dissolve");
+    if (Buffers().out(out).in(labels).in(assigned).bad()) return Refusal{"boxes", "dissolve"}.buffers();
     if (npx < 1) { set_error("boxes: dissolve: npx must be at least 1, got %lld", (long long)npx); return OBIA_E_INVALID; }
     if (n_labels < 0 || n_labels == INT_MAX) { set_error("boxes: dissolve: n_labels must be in 0 .. 2^31 - 2, got %d", n_labels); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
@@ -420,7 +400,7 @@ int obia_boxes_dissolve_dev(obia_ctx *ctx, const int32_t *labels, int64_t npx, c
 
 int obia_boxes_iou_dev(obia_ctx *ctx, const double *a, int64_t na, const double *b, int64_t nb, double *out) {
     OBIA_TRY(enter(ctx));
-    if (!a || !b || !out || misaligned(a, 8) || misaligned(b, 8) || misaligned(out, 8) || a == out || b == out) return bad_buffers("iou");
+    if (Buffers().out(out).in(a).in(b).bad()) return Refusal{"boxes", "iou"}.buffers();
     if (na < 1 || nb < 1 || na > ((int64_t)1 << 62) / nb) {
         set_error("boxes: iou: na and nb must be at least 1 and na * nb below 2^62, got %lld x %lld", (long long)na, (long long)nb);
         return OBIA_E_INVALID;
@@ -436,10 +416,9 @@ int obia_boxes_iou_dev(obia_ctx *ctx, const double *a, int64_t na, const double 
 int obia_boxes_nms_dev(obia_ctx *ctx, const double *boxes, const int32_t *pos, const int32_t *group, const int64_t *key, int64_t n,
                        int64_t ncx, double iou_threshold, uint8_t *keep_out, int32_t *rounds_out) {
     OBIA_TRY(enter(ctx));
-    if (!boxes || !pos || !key || !keep_out || misaligned(boxes, 8) || misaligned(pos, 4) || misaligned(group, 4) || misaligned(key, 8) ||
-        shared_start(1, keep_out, boxes, pos, group, key))
-        return bad_buffers("nms");
-    OBIA_TRY(check_n("nms", n));
+    const Refusal refuse{"boxes", "nms"};
+    if (Buffers().out(keep_out).in(boxes).in(pos).in(group, OPTIONAL).in(key).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
     if (ncx < 3) { set_error("boxes: nms: ncx must be at least 3, got %lld", (long long)ncx); return OBIA_E_INVALID; }
     if (!(iou_threshold >= 0.0)) { set_error("boxes: nms: iou_threshold must be at least 0, got %g", iou_threshold); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {

@@ -1,8 +1,8 @@
 // common.hpp -- context, device workspace arena, error plumbing shared by the HIP translation units.
 //
-// An extern "C" function is its argument checks and its body between three shared pieces (the entry layer, below): enter(), the
-// prologue; call_frame(), for a call that returns with its work done; Staging, for a call that takes host pointers.  A new operator
-// uses them and writes none of its own.
+// An extern "C" function is its body between four shared pieces (the entry layer, below): enter(), the prologue; Buffers and Refusal
+// (buffer_args.hpp), the argument checks -- every buffer listed once, every refusal worded in one place; call_frame(), for a call that
+// returns with its work done; Staging, for a call that takes host pointers.  A new operator uses them and writes none of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -13,13 +13,14 @@
 #include <vector>
 
 #include "../../include/obia_hip.h"
+#include "buffer_args.hpp"
 #include "launch_grids.hpp"
 
 struct obia_ctx;
 
 namespace obia {
 
-void set_error(const char *fmt, ...);
+void set_error(const char *fmt, ...);   // (buffer_args.hpp declares it too: that header stands alone)
 
 #define OBIA_HIP_TRY(expr)                                                                       \
     do {                                                                                         \
@@ -204,20 +205,7 @@ static inline dim3 to_dim3(const grids::Grid &g) { return dim3((unsigned)g.x.n, 
 // Grid of a grid-stride kernel over n elements in workgroups of 256: one workgroup per 256 elements, 8192 at the most, one at the least.
 static inline unsigned flat_grid(long long n) { return (unsigned)grids::flat(n).x.n; }
 
-// Argument checks shared by the entry points whose buffers need only the alignment of their element type (seed_table.hip, boxes.hip,
-// points.hip).  A null pointer is aligned, and is not compared.
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-// one of the first n_out buffers, the outputs, starts where another output or an input starts
-template <typename... P> bool shared_start(int n_out, P... ps) {
-    const void *v[] = {static_cast<const void *>(ps)...};
-    const int m = (int)sizeof...(ps);
-    for (int i = 0; i < n_out; ++i)
-        for (int j = i + 1; j < m; ++j)
-            if (v[i] && v[i] == v[j]) return true;
-    return false;
-}
-
-// ---- the entry layer: what every extern "C" function is made of besides its own argument checks and its body ----------------------
+// ---- the entry layer: what every extern "C" function is made of besides its body (the argument checks: buffer_args.hpp) -----------
 
 // Prologue, the first statement of every entry point that takes a context (the tiler's go through their session's): refuses a null
 // context (OBIA_E_INVALID) before any HIP call and selects the context's device.  A context held by an open tiler session is refused

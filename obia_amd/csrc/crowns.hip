@@ -266,9 +266,8 @@ int obia_crowns_allocate_dev(obia_ctx *ctx, const float *cost, const uint8_t *ma
                              const int32_t *seed_id, int n, double weight, double len_h, double len_v, double len_d, int connectivity,
                              double max_dist, double *dist_out, int32_t *labels_out, int32_t *rounds_out) {
     OBIA_TRY(enter(ctx));
-    if (!cost || !seed_rc || !seed_id || !dist_out || !labels_out || ((uintptr_t)cost & 3) || ((uintptr_t)seed_rc & 3) ||
-        ((uintptr_t)seed_id & 3) || ((uintptr_t)labels_out & 3) || ((uintptr_t)dist_out & 7) || (const void *)cost == (const void *)dist_out ||
-        (const void *)cost == (const void *)labels_out) {
+    // each output against the cost raster: the two outputs have never been compared with each other
+    if (Buffers().out(dist_out).in(cost).lone(seed_rc).lone(seed_id).bad() || Buffers().out(labels_out).in(cost).bad()) {
         set_error("crowns: bad arguments (null, misaligned or overlapping buffers)");
         return OBIA_E_INVALID;
     }

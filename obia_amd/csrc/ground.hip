@@ -178,16 +178,6 @@ __global__ __launch_bounds__(256) void ground_dtm_kernel(DtmArgs A) {
     }
 }
 
-int bad_buffers(const char *what) {
-    set_error("ground: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
-}
-int check_n(const char *what, int64_t n) {
-    if (n < 0) { set_error("ground: %s: n must not be negative, got %lld", what, (long long)n); return OBIA_E_INVALID; }
-    if (n > (int64_t)INT_MAX) { set_error("ground: %s: n must be below 2^31 per call, got %lld", what, (long long)n); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
-
 template <int K> void launch_query(obia_ctx *ctx, const GroundArgs &A) {
     hipLaunchKernelGGL(ground_query_kernel<K>, to_dim3(grids::ground_query(A.n)), dim3(256), 0, ctx->stream, A);
 }
@@ -204,13 +194,13 @@ int obia_ground_query_dev(obia_ctx *ctx, const double *gx, const double *gy, con
                           const double *y, const double *z, int64_t n, int32_t count, double max_distance, double *zg, float *hag,
                           uint8_t *m) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_n("query", n));
+    const Refusal refuse{"ground", "query"};
+    OBIA_TRY(refuse.n_or_none(n));
     if (ng < 1) { set_error("ground: query: the ground set must hold a point, got ng = %lld", (long long)ng); return OBIA_E_INVALID; }
     if (ng > (int64_t)INT_MAX) { set_error("ground: query: ng must be below 2^31, got %lld", (long long)ng); return OBIA_E_UNSUPPORTED; }
-    if (!gx || !gy || !gz || !gidx || !cell_start || !zg || (n > 0 && (!x || !y)) || (z == nullptr) != (hag == nullptr) || misaligned(gx, 8) ||
-        misaligned(gy, 8) || misaligned(gz, 8) || misaligned(gidx, 4) || misaligned(cell_start, 4) || misaligned(x, 8) || misaligned(y, 8) ||
-        misaligned(z, 8) || misaligned(zg, 8) || misaligned(hag, 4) || shared_start(3, zg, hag, m, gx, gy, gz, gidx, cell_start, x, y, z))
-        return bad_buffers("query");
+    Buffers b;
+    b.in(gx).in(gy).in(gz).in(gidx).in(cell_start).in(x, n > 0).in(y, n > 0).in(z, OPTIONAL);
+    if ((z == nullptr) != (hag == nullptr) || b.out(zg).out(hag, OPTIONAL).out(m, OPTIONAL).bad()) return refuse.buffers();
     if (count < 1 || count > OBIA_GROUND_MAX_COUNT) {
         set_error("ground: query: count must be in 1 .. %d, got %d", OBIA_GROUND_MAX_COUNT, count);
         return OBIA_E_INVALID;
@@ -248,10 +238,9 @@ int obia_ground_query_dev(obia_ctx *ctx, const double *gx, const double *gy, con
 int obia_ground_dtm_dev(obia_ctx *ctx, const double *x, const double *y, const double *z, int64_t n, const double *inv6, const float *dtm,
                         int H, int W, double *zg, float *hag) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_n("dtm", n));
-    if (!inv6 || !dtm || !hag || (n > 0 && (!x || !y || !z)) || misaligned(x, 8) || misaligned(y, 8) || misaligned(z, 8) || misaligned(dtm, 4) ||
-        misaligned(zg, 8) || misaligned(hag, 4) || shared_start(2, zg, hag, x, y, z, dtm))
-        return bad_buffers("dtm");
+    const Refusal refuse{"ground", "dtm"};
+    OBIA_TRY(refuse.n_or_none(n));
+    if (!inv6 || Buffers().in(x, n > 0).in(y, n > 0).in(z, n > 0).in(dtm).out(zg, OPTIONAL).out(hag).bad()) return refuse.buffers();
     if (H <= 0 || W <= 0) { set_error("ground: dtm: H and W must be positive, got %d x %d", H, W); return OBIA_E_INVALID; }
     if (n == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {

@@ -182,20 +182,6 @@ __global__ __launch_bounds__(256) void gf_classify_kernel(Cloud C, const float *
     if (threadIdx.x < 4 && s_counters[threadIdx.x]) atomicAdd(&counters[threadIdx.x], s_counters[threadIdx.x]);
 }
 
-int bad_buffers(const char *what) {
-    set_error("groundfilter: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
-}
-int check_n(const char *what, int64_t n) {
-    if (n < 0) { set_error("groundfilter: %s: n must not be negative, got %lld", what, (long long)n); return OBIA_E_INVALID; }
-    if (n > (int64_t)INT_MAX) { set_error("groundfilter: %s: n must be below 2^31 per call, got %lld", what, (long long)n); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
-int check_raster(const char *what, int H, int W) {
-    if (H <= 0 || W <= 0) { set_error("groundfilter: %s: H and W must be positive, got %d x %d", what, H, W); return OBIA_E_INVALID; }
-    if ((long long)H * W > (long long)INT_MAX) { set_error("groundfilter: %s: H * W must be below 2^31, got %d x %d", what, H, W); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
 int check_radius(const char *what, int r) {
     if (r < 1) { set_error("groundfilter: %s: a radius must be at least 1, got %d", what, r); return OBIA_E_INVALID; }
     if (r > RMAX) { set_error("groundfilter: %s: a radius must not exceed %d, got %d", what, RMAX, r); return OBIA_E_UNSUPPORTED; }
@@ -236,11 +222,10 @@ extern "C" {
 int obia_gf_cell_min_dev(obia_ctx *ctx, const double *x, const double *y, const double *z, int64_t n, const double *inv6, int H, int W,
                          uint32_t *keys) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_n("cell min", n));
-    if (!inv6 || !keys || (n > 0 && (!x || !y || !z)) || misaligned(x, 8) || misaligned(y, 8) || misaligned(z, 8) || misaligned(keys, 4) ||
-        shared_start(1, keys, x, y, z))
-        return bad_buffers("cell min");
-    OBIA_TRY(check_raster("cell min", H, W));
+    const Refusal refuse{"groundfilter", "cell min"};
+    OBIA_TRY(refuse.n_or_none(n));
+    if (!inv6 || Buffers().in(x, n > 0).in(y, n > 0).in(z, n > 0).out(keys).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     if (n == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(gf_cell_min_kernel, to_dim3(grids::flat(n)), dim3(256), 0, ctx->stream, cloud_of(x, y, z, n, inv6, H, W), keys);
@@ -251,8 +236,9 @@ int obia_gf_cell_min_dev(obia_ctx *ctx, const double *x, const double *y, const 
 
 int obia_gf_cell_min_finish_dev(obia_ctx *ctx, const uint32_t *keys, int H, int W, float *zmin) {
     OBIA_TRY(enter(ctx));
-    if (!keys || !zmin || misaligned(keys, 4) || misaligned(zmin, 4) || shared_start(1, zmin, keys)) return bad_buffers("cell min finish");
-    OBIA_TRY(check_raster("cell min finish", H, W));
+    const Refusal refuse{"groundfilter", "cell min finish"};
+    if (Buffers().out(zmin).in(keys).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         const long long npx = (long long)H * W;
         hipLaunchKernelGGL(gf_cell_min_finish_kernel, to_dim3(grids::flat(npx)), dim3(256), 0, ctx->stream, keys, npx, zmin);
@@ -263,9 +249,9 @@ int obia_gf_cell_min_finish_dev(obia_ctx *ctx, const uint32_t *keys, int H, int 
 
 int obia_morph_filter_dev(obia_ctx *ctx, const float *src, int H, int W, int radius, int op, float *tmp, float *dst) {
     OBIA_TRY(enter(ctx));
-    if (!src || !tmp || !dst || misaligned(src, 4) || misaligned(tmp, 4) || misaligned(dst, 4) || shared_start(2, dst, tmp, src))
-        return bad_buffers("filter");
-    OBIA_TRY(check_raster("filter", H, W));
+    const Refusal refuse{"groundfilter", "filter"};
+    if (Buffers().out(dst).out(tmp).in(src).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     if (op != OP_MIN && op != OP_MAX) { set_error("groundfilter: filter: op must be 0 (minimum) or 1 (maximum), got %d", op); return OBIA_E_INVALID; }
     OBIA_TRY(check_radius("filter", radius));
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
@@ -280,10 +266,9 @@ int obia_morph_filter_dev(obia_ctx *ctx, const float *src, int H, int W, int rad
 int obia_gf_threshold_dev(obia_ctx *ctx, const float *zmin, int H, int W, const int32_t *radii, const double *dh, int K, float *tmp0,
                           float *tmp1, float *surface, float *thresh) {
     OBIA_TRY(enter(ctx));
-    if (!zmin || !radii || !dh || !tmp0 || !tmp1 || !surface || !thresh || misaligned(zmin, 4) || misaligned(tmp0, 4) || misaligned(tmp1, 4) ||
-        misaligned(surface, 4) || misaligned(thresh, 4) || shared_start(4, surface, thresh, tmp0, tmp1, zmin))
-        return bad_buffers("threshold");
-    OBIA_TRY(check_raster("threshold", H, W));
+    const Refusal refuse{"groundfilter", "threshold"};
+    if (!radii || !dh || Buffers().out(surface).out(thresh).out(tmp0).out(tmp1).in(zmin).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     if (K < 1 || K > OBIA_GF_MAX_STEPS) { set_error("groundfilter: threshold: K must be in 1 .. %d, got %d", OBIA_GF_MAX_STEPS, K); return OBIA_E_INVALID; }
     for (int k = 0; k < K; ++k) {
         OBIA_TRY(check_radius("threshold", radii[k]));
@@ -310,11 +295,12 @@ int obia_gf_threshold_dev(obia_ctx *ctx, const float *zmin, int H, int W, const 
 int obia_gf_classify_dev(obia_ctx *ctx, const double *x, const double *y, const double *z, int64_t n, const double *inv6,
                          const float *thresh, int H, int W, uint8_t *flags, uint64_t *counters) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_n("classify", n));
-    if (!inv6 || !thresh || !counters || (n > 0 && (!x || !y || !z || !flags)) || misaligned(x, 8) || misaligned(y, 8) || misaligned(z, 8) ||
-        misaligned(thresh, 4) || misaligned(counters, 8) || shared_start(2, flags, counters, x, y, z, thresh))
-        return bad_buffers("classify");
-    OBIA_TRY(check_raster("classify", H, W));
+    const Refusal refuse{"groundfilter", "classify"};
+    OBIA_TRY(refuse.n_or_none(n));
+    Buffers b;
+    b.in(x, n > 0).in(y, n > 0).in(z, n > 0).in(thresh);
+    if (!inv6 || b.out(flags, n > 0).out(counters).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     if (n == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(gf_classify_kernel, to_dim3(grids::flat(n)), dim3(256), 0, ctx->stream, cloud_of(x, y, z, n, inv6, H, W), thresh, flags,

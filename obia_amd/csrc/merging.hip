@@ -16,7 +16,7 @@
 // lies before the sort and nothing after it: keys are sorted, equal keys are summed with integers.  The write pass is a copy.
 //
 // Nothing here takes memory from the context's workspace: every buffer is the caller's.  Every atomic is an integer atomic.
-#include "common.hpp"
+#include "csr.hpp"
 #include "../../include/obia_merging.h"
 
 #include <climits>
@@ -32,27 +32,6 @@ static_assert((size_t)CAP * 12 + 256 * 4 + 257 * 8 + 64 <= 64 * 1024, "row and c
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ double canon(double x) { return x != x ? quiet_nan() : x; }
 
-// ---- a CSR the caller passes: read defensively (obia_adjacency.h: "A CSR THE CALLER PASSES") ----------------------------------------
-struct Csr {
-    const long long *indptr; const int *neighbor; const long long *border;
-    int N; long long nnz;
-};
-__device__ __forceinline__ void row_range(const Csr &G, int i, long long &lo, long long &hi) {
-    lo = G.indptr[i];
-    hi = G.indptr[i + 1];
-    if (lo < 0) lo = 0;
-    if (hi > G.nnz) hi = G.nnz;
-}
-// the row of entry e: the largest i in 0 .. N - 1 with indptr[i] <= e (N >= 1)
-__device__ __forceinline__ int row_of(const Csr &G, long long e) {
-    int lo = 0, hi = G.N;
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (G.indptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ bool is_real(const Csr &G, int j) { return j >= 0 && j < G.N; }
 // a stretch of the scratch: raw_ptr[r] .. raw_ptr[r + 1] - 1, inside 0 .. nnz - 1
 __device__ __forceinline__ void stretch(const long long *raw_ptr, int r, long long nnz, long long &lo, long long &hi) {
     lo = raw_ptr[r];
@@ -398,28 +377,12 @@ __global__ __launch_bounds__(256) void contract_write_kernel(int N, long long nn
     }
 }
 
-int bad_buffers(const char *what) {
-    set_error("merging: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
+// the node tables of a call, read or written: every column whenever there is a row
+Buffers &list_tables(Buffers &b, int32_t N, const int64_t *area, const double *mean, const double *m2, const int64_t *perimeter, const int32_t *box) {
+    return b.in(area, N > 0).in(mean, N > 0).in(m2, N > 0).in(perimeter, N > 0).in(box, N > 0);
 }
-int check_labels(const char *what, int32_t n_labels) {
-    if (n_labels < 0 || n_labels > INT_MAX - 2) { set_error("merging: %s: n_labels must be in 0 .. 2^31 - 3, got %d", what, n_labels); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-int check_count(const char *what, const char *name, int64_t n, int64_t least) {
-    if (n < least) { set_error("merging: %s: %s must be at least %lld, got %lld", what, name, (long long)least, (long long)n); return OBIA_E_INVALID; }
-    if (n > (int64_t)INT_MAX) { set_error("merging: %s: %s must be below 2^31, got %lld", what, name, (long long)n); return OBIA_E_UNSUPPORTED; }
-    return OBIA_OK;
-}
-bool csr_missing(const int64_t *indptr, const int32_t *neighbor, const int64_t *border, int32_t N, int64_t nnz) {
-    return (N > 0 && !indptr) || (nnz > 0 && (!neighbor || !border)) || misaligned(indptr, 8) || misaligned(neighbor, 4) || misaligned(border, 8);
-}
-Csr csr_of(const int64_t *indptr, const int32_t *neighbor, const int64_t *border, int32_t N, int64_t nnz) {
-    return Csr{reinterpret_cast<const long long *>(indptr), neighbor, reinterpret_cast<const long long *>(border), N, (long long)nnz};
-}
-bool tables_missing(int32_t N, const int64_t *area, const double *mean, const double *m2, const int64_t *perimeter, const int32_t *box) {
-    return (N > 0 && (!area || !mean || !m2 || !perimeter || !box)) || misaligned(area, 8) || misaligned(mean, 8) || misaligned(m2, 8) ||
-           misaligned(perimeter, 8) || misaligned(box, 4);
+Buffers &list_tables_out(Buffers &b, int32_t N, int64_t *area, double *mean, double *m2, int64_t *perimeter, int32_t *box) {
+    return b.out(area, N > 0).out(mean, N > 0).out(m2, N > 0).out(perimeter, N > 0).out(box, N > 0);
 }
 Tables tables_of(const int64_t *area, const double *mean, const double *m2, int F, const int64_t *perimeter, const int32_t *box) {
     return Tables{reinterpret_cast<const long long *>(area), mean, m2, F, reinterpret_cast<const long long *>(perimeter), box};
@@ -436,14 +399,14 @@ int obia_merge_cost_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *nei
                         const int64_t *area, const double *mean, const double *m2, int F, const double *band_weights,
                         const int64_t *perimeter, const int32_t *box, double w_color, double w_compact, double *cost_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("cost", n_labels));
-    OBIA_TRY(check_count("cost", "F", F, 1));
-    OBIA_TRY(check_count("cost", "nnz", nnz, 0));
-    OBIA_TRY(check_count("cost", "n_labels * F", (int64_t)n_labels * F, 0));
-    if (csr_missing(indptr, neighbor, border, n_labels, nnz) || tables_missing(n_labels, area, mean, m2, perimeter, box) || !band_weights ||
-        misaligned(band_weights, 8) || (nnz > 0 && !cost_out) || misaligned(cost_out, 8) ||
-        shared_start(1, cost_out, indptr, neighbor, border, area, mean, m2, band_weights, perimeter, box))
-        return bad_buffers("cost");
+    const Refusal refuse{"merging", "cost"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("F", F, 1));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("n_labels * F", (int64_t)n_labels * F, 0));
+    Buffers b;
+    list_csr(b, indptr, neighbor, border, n_labels, nnz);
+    if (list_tables(b, n_labels, area, mean, m2, perimeter, box).in(band_weights).out(cost_out, nnz > 0).bad()) return refuse.buffers();
     if (nnz == 0 || n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(merge_cost_kernel, to_dim3(grids::flat(nnz)), dim3(256), 0, ctx->stream, csr_of(indptr, neighbor, border, n_labels, nnz),
@@ -457,14 +420,15 @@ int obia_merge_pairs_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *ne
                          const int32_t *partner, const int64_t *area, const double *mean, const double *m2, int F, const int64_t *perimeter,
                          const int32_t *box, int64_t *area_out, double *mean_out, double *m2_out, int64_t *perimeter_out, int32_t *box_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("pairs", n_labels));
-    OBIA_TRY(check_count("pairs", "F", F, 1));
-    OBIA_TRY(check_count("pairs", "nnz", nnz, 0));
-    OBIA_TRY(check_count("pairs", "n_labels * F", (int64_t)n_labels * F, 0));
-    if (csr_missing(indptr, neighbor, border, n_labels, nnz) || tables_missing(n_labels, area, mean, m2, perimeter, box) ||
-        tables_missing(n_labels, area_out, mean_out, m2_out, perimeter_out, box_out) || (n_labels > 0 && !partner) || misaligned(partner, 4) ||
-        shared_start(5, area_out, mean_out, m2_out, perimeter_out, box_out, indptr, neighbor, border, partner, area, mean, m2, perimeter, box))
-        return bad_buffers("pairs");
+    const Refusal refuse{"merging", "pairs"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("F", F, 1));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("n_labels * F", (int64_t)n_labels * F, 0));
+    Buffers b;
+    list_csr(b, indptr, neighbor, border, n_labels, nnz).in(partner, n_labels > 0);
+    list_tables(b, n_labels, area, mean, m2, perimeter, box);
+    if (list_tables_out(b, n_labels, area_out, mean_out, m2_out, perimeter_out, box_out).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(merge_pairs_kernel, to_dim3(grids::flat(n_labels)), dim3(256), 0, ctx->stream, csr_of(indptr, neighbor, border, n_labels, nnz),
@@ -478,11 +442,11 @@ int obia_merge_pairs_dev(obia_ctx *ctx, const int64_t *indptr, const int32_t *ne
 int obia_merge_contract_rows_dev(obia_ctx *ctx, const int64_t *indptr, int32_t n_labels, int64_t nnz, const int32_t *root,
                                  int64_t *raw_count_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("contract rows", n_labels));
-    OBIA_TRY(check_count("contract rows", "nnz", nnz, 0));
-    if ((n_labels > 0 && (!indptr || !root || !raw_count_out)) || misaligned(indptr, 8) || misaligned(root, 4) || misaligned(raw_count_out, 8) ||
-        shared_start(1, raw_count_out, indptr, root))
-        return bad_buffers("contract rows");
+    const Refusal refuse{"merging", "contract rows"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    const bool rows = n_labels > 0;
+    if (Buffers().out(raw_count_out, rows).in(indptr, rows).in(root, rows).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         OBIA_TRY(fill_async(ctx, raw_count_out, 0, (size_t)n_labels * sizeof(int64_t)));
@@ -497,13 +461,13 @@ int obia_merge_contract_count_dev(obia_ctx *ctx, const int64_t *indptr, const in
                                   int64_t nnz, const int32_t *root, const int64_t *raw_ptr, int32_t *key_work, int64_t *border_work,
                                   int32_t *cursor_work, int32_t *count_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("contract count", n_labels));
-    OBIA_TRY(check_count("contract count", "nnz", nnz, 0));
-    if (csr_missing(indptr, neighbor, border, n_labels, nnz) || (n_labels > 0 && (!root || !raw_ptr || !cursor_work || !count_out)) ||
-        (nnz > 0 && (!key_work || !border_work)) || misaligned(root, 4) || misaligned(raw_ptr, 8) || misaligned(key_work, 4) ||
-        misaligned(border_work, 8) || misaligned(cursor_work, 4) || misaligned(count_out, 4) ||
-        shared_start(4, key_work, border_work, cursor_work, count_out, indptr, neighbor, border, root, raw_ptr))
-        return bad_buffers("contract count");
+    const Refusal refuse{"merging", "contract count"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    const bool rows = n_labels > 0;
+    Buffers b;
+    list_csr(b, indptr, neighbor, border, n_labels, nnz).in(root, rows).in(raw_ptr, rows);
+    if (b.out(key_work, nnz > 0).out(border_work, nnz > 0).out(cursor_work, rows).out(count_out, rows).bad()) return refuse.buffers();
     if (n_labels == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         const long long *ptr = reinterpret_cast<const long long *>(raw_ptr);
@@ -535,14 +499,14 @@ int obia_merge_contract_write_dev(obia_ctx *ctx, int32_t n_labels, int64_t nnz, 
                                   const int32_t *key_work, const int64_t *border_work, const int64_t *indptr_out, int64_t nnz_out,
                                   int32_t *neighbor_out, int64_t *border_out) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_labels("contract write", n_labels));
-    OBIA_TRY(check_count("contract write", "nnz", nnz, 0));
-    OBIA_TRY(check_count("contract write", "nnz_out", nnz_out, 0));
-    if ((n_labels > 0 && (!raw_ptr || !count || !indptr_out)) || (nnz > 0 && (!key_work || !border_work)) ||
-        (nnz_out > 0 && (!neighbor_out || !border_out)) || misaligned(raw_ptr, 8) || misaligned(count, 4) || misaligned(key_work, 4) ||
-        misaligned(border_work, 8) || misaligned(indptr_out, 8) || misaligned(neighbor_out, 4) || misaligned(border_out, 8) ||
-        shared_start(2, neighbor_out, border_out, raw_ptr, count, key_work, border_work, indptr_out))
-        return bad_buffers("contract write");
+    const Refusal refuse{"merging", "contract write"};
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.count("nnz", nnz, 0));
+    OBIA_TRY(refuse.count("nnz_out", nnz_out, 0));
+    const bool rows = n_labels > 0;
+    Buffers b;
+    b.in(raw_ptr, rows).in(count, rows).in(key_work, nnz > 0).in(border_work, nnz > 0).in(indptr_out, rows);
+    if (b.out(neighbor_out, nnz_out > 0).out(border_out, nnz_out > 0).bad()) return refuse.buffers();
     if (n_labels == 0 || nnz_out == 0 || nnz == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(contract_write_kernel, to_dim3(grids::flat((long long)n_labels * 8)), dim3(256), 0, ctx->stream, n_labels, (long long)nnz,

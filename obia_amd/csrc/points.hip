@@ -223,21 +223,8 @@ __global__ __launch_bounds__(256) void points_columns_kernel(ColArgs A) {
     A.var_i[s] = var;
 }
 
-int bad_buffers(const char *what) {
-    set_error("points: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
-}
-int check_raster(const char *what, int H, int W) {
-    if (H <= 0 || W <= 0) { set_error("points: %s: H and W must be positive, got %d x %d", what, H, W); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-int check_cloud(const char *what, const double *x, const double *y, const float *z, const uint16_t *intensity, int64_t n, const double *inv6) {
-    if (n < 0) { set_error("points: %s: n must not be negative, got %lld", what, (long long)n); return OBIA_E_INVALID; }
-    if (n > (int64_t)INT_MAX) { set_error("points: %s: n must be below 2^31 per call, got %lld", what, (long long)n); return OBIA_E_UNSUPPORTED; }
-    if (!inv6 || (n > 0 && (!x || !y || !z)) || misaligned(x, 8) || misaligned(y, 8) || misaligned(z, 4) || misaligned(intensity, 2))
-        return bad_buffers(what);
-    return OBIA_OK;
-}
+// the columns of a cloud: whenever there is a point
+Buffers &list_cloud(Buffers &b, const double *x, const double *y, const float *z, int64_t n) { return b.in(x, n > 0).in(y, n > 0).in(z, n > 0); }
 Cloud cloud_of(const double *x, const double *y, const float *z, const uint16_t *intensity, int64_t n, const double *t, int H, int W) {
     return Cloud{x, y, z, intensity, (long long)n, t[0], t[1], t[2], t[3], t[4], t[5], H, W};
 }
@@ -253,9 +240,11 @@ extern "C" {
 int obia_points_rasters_dev(obia_ctx *ctx, const double *x, const double *y, const float *z, int64_t n, const double *inv6, int H, int W,
                             uint32_t *zk, uint32_t *count) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_cloud("rasters", x, y, z, nullptr, n, inv6));
-    if (!zk || !count || misaligned(zk, 4) || misaligned(count, 4) || shared_start(2, zk, count, x, y, z)) return bad_buffers("rasters");
-    OBIA_TRY(check_raster("rasters", H, W));
+    const Refusal refuse{"points", "rasters"};
+    OBIA_TRY(refuse.n_or_none(n));
+    Buffers b;
+    if (!inv6 || list_cloud(b, x, y, z, n).out(zk).out(count).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster(H, W));
     if (n == 0) return OBIA_OK;
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(points_rasters_kernel, dim3(flat_grid(n)), dim3(256), 0, ctx->stream, cloud_of(x, y, z, nullptr, n, inv6, H, W), zk,
@@ -268,10 +257,9 @@ int obia_points_rasters_dev(obia_ctx *ctx, const double *x, const double *y, con
 int obia_points_rasters_finish_dev(obia_ctx *ctx, const uint32_t *zk, const uint32_t *count, int H, int W, double pixel_area, float *chm,
                                    float *density) {
     OBIA_TRY(enter(ctx));
-    if (!zk || !count || !chm || !density || misaligned(zk, 4) || misaligned(count, 4) || misaligned(chm, 4) || misaligned(density, 4) ||
-        shared_start(2, chm, density, zk, count))
-        return bad_buffers("rasters finish");
-    OBIA_TRY(check_raster("rasters finish", H, W));
+    const Refusal refuse{"points", "rasters finish"};
+    if (Buffers().out(chm).out(density).in(zk).in(count).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster(H, W));
     if (!positive(pixel_area)) { set_error("points: rasters finish: pixel_area must be finite and positive, got %g", pixel_area); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         const long long npx = (long long)H * W;
@@ -285,12 +273,12 @@ int obia_points_segments_dev(obia_ctx *ctx, const double *x, const double *y, co
                              const double *inv6, const int32_t *labels, int H, int W, int32_t start_label, int32_t N, int32_t nz, double dz,
                              uint32_t *profile, uint32_t *top, uint32_t *n_int, uint64_t *s1, uint64_t *s2, uint64_t *counters) {
     OBIA_TRY(enter(ctx));
-    OBIA_TRY(check_cloud("segments", x, y, z, intensity, n, inv6));
-    if (!labels || !profile || !top || !n_int || !s1 || !s2 || !counters || misaligned(labels, 4) || misaligned(profile, 4) || misaligned(top, 4) ||
-        misaligned(n_int, 4) || misaligned(s1, 8) || misaligned(s2, 8) || misaligned(counters, 8) ||
-        shared_start(6, profile, top, n_int, s1, s2, counters, labels, x, y, z, intensity))
-        return bad_buffers("segments");
-    OBIA_TRY(check_raster("segments", H, W));
+    const Refusal refuse{"points", "segments"};
+    OBIA_TRY(refuse.n_or_none(n));
+    Buffers b;
+    list_cloud(b, x, y, z, n).in(intensity, OPTIONAL).in(labels);
+    if (!inv6 || b.out(profile).out(top).out(n_int).out(s1).out(s2).out(counters).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.raster(H, W));
     if (N < 0 || nz < 1) { set_error("points: segments: N must not be negative and nz at least 1, got %d and %d", N, nz); return OBIA_E_INVALID; }
     if (nz > OBIA_POINTS_MAX_NZ) { set_error("points: segments: nz must not exceed %d, got %d", OBIA_POINTS_MAX_NZ, nz); return OBIA_E_UNSUPPORTED; }
     if ((long long)N * nz > (long long)INT_MAX) { set_error("points: segments: N * nz must be below 2^31, got %d x %d", N, nz); return OBIA_E_UNSUPPORTED; }
@@ -316,12 +304,10 @@ int obia_points_segment_columns_dev(obia_ctx *ctx, const uint32_t *profile, cons
                                     const uint64_t *s2, int32_t N, int32_t nz, double dz, double min_height, double k, int64_t *n_points,
                                     double *ch, double *pai, double *fhd, double *mean_intensity, double *variance_intensity, double *pad) {
     OBIA_TRY(enter(ctx));
-    if (!profile || !top || !n_int || !s1 || !s2 || !n_points || !ch || !pai || !fhd || !mean_intensity || !variance_intensity ||
-        misaligned(profile, 4) || misaligned(top, 4) || misaligned(n_int, 4) || misaligned(s1, 8) || misaligned(s2, 8) || misaligned(n_points, 8) ||
-        misaligned(ch, 8) || misaligned(pai, 8) || misaligned(fhd, 8) || misaligned(mean_intensity, 8) || misaligned(variance_intensity, 8) ||
-        misaligned(pad, 8) ||
-        shared_start(7, n_points, ch, pai, fhd, mean_intensity, variance_intensity, pad, profile, top, n_int, s1, s2))
-        return bad_buffers("segment columns");
+    Buffers b;
+    b.in(profile).in(top).in(n_int).in(s1).in(s2);
+    if (b.out(n_points).out(ch).out(pai).out(fhd).out(mean_intensity).out(variance_intensity).out(pad, OPTIONAL).bad())
+        return Refusal{"points", "segment columns"}.buffers();
     if (N < 1 || nz < 1) { set_error("points: segment columns: N and nz must be at least 1, got %d and %d", N, nz); return OBIA_E_INVALID; }
     if (nz > OBIA_POINTS_MAX_NZ) { set_error("points: segment columns: nz must not exceed %d, got %d", OBIA_POINTS_MAX_NZ, nz); return OBIA_E_UNSUPPORTED; }
     if ((long long)N * nz > (long long)INT_MAX) { set_error("points: segment columns: N * nz must be below 2^31, got %d x %d", N, nz); return OBIA_E_UNSUPPORTED; }

@@ -174,19 +174,10 @@ __global__ __launch_bounds__(256) void seedtab_nms_kernel(const double *__restri
 
 thread_local int64_t last_work[2] = {0, 0};
 
-// the checks every entry point shares; what == the operator's name in the message
-int check_n(const char *what, int64_t n) {
-    if (n < 1 || n > (int64_t)INT_MAX) { set_error("seed table: %s: n must be in 1 .. 2^31 - 1, got %lld", what, (long long)n); return OBIA_E_INVALID; }
+int check_grid(const Refusal &refuse, int64_t n, int64_t ncx) {
+    OBIA_TRY(refuse.n(n));
+    if (ncx < 3) { set_error("seed table: %s: ncx must be at least 3, got %lld", refuse.what, (long long)ncx); return OBIA_E_INVALID; }
     return OBIA_OK;
-}
-int check_grid(const char *what, int64_t n, int64_t ncx) {
-    OBIA_TRY(check_n(what, n));
-    if (ncx < 3) { set_error("seed table: %s: ncx must be at least 3, got %lld", what, (long long)ncx); return OBIA_E_INVALID; }
-    return OBIA_OK;
-}
-int bad_buffers(const char *what) {
-    set_error("seed table: %s: bad arguments (null, misaligned or overlapping buffers)", what);
-    return OBIA_E_INVALID;
 }
 
 }  // namespace
@@ -198,10 +189,9 @@ extern "C" {
 
 int obia_seedtab_cells_dev(obia_ctx *ctx, const double *xs, const double *ys, int64_t n, double side, int32_t *cx_out, int32_t *cy_out) {
     OBIA_TRY(enter(ctx));
-    if (!xs || !ys || !cx_out || !cy_out || misaligned(xs, 8) || misaligned(ys, 8) || misaligned(cx_out, 4) || misaligned(cy_out, 4) ||
-        cx_out == cy_out)
-        return bad_buffers("cells");
-    OBIA_TRY(check_n("cells", n));
+    const Refusal refuse{"seed table", "cells"};
+    if (Buffers().out(cx_out).out(cy_out).lone(xs).lone(ys).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
     if (!(side > 0.0)) { set_error("seed table: cells: the cell side must be positive, got %g", side); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(seedtab_cells_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, xs, ys, (int)n, side, cx_out, cy_out);
@@ -213,10 +203,9 @@ int obia_seedtab_cells_dev(obia_ctx *ctx, const double *xs, const double *ys, in
 int obia_seedtab_sample_dev(obia_ctx *ctx, const double *xs, const double *ys, int64_t n, const float *chm, int H, int W,
                             const double *inv6, float *height_out, uint8_t *valid_out) {
     OBIA_TRY(enter(ctx));
-    if (!xs || !ys || !chm || !inv6 || !height_out || !valid_out || misaligned(xs, 8) || misaligned(ys, 8) || misaligned(chm, 4) ||
-        misaligned(height_out, 4) || (const void *)chm == (const void *)height_out)
-        return bad_buffers("sample");
-    OBIA_TRY(check_n("sample", n));
+    const Refusal refuse{"seed table", "sample"};
+    if (!inv6 || Buffers().out(height_out).in(chm).lone(xs).lone(ys).lone(valid_out).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
     if (H <= 0 || W <= 0) { set_error("seed table: sample: H and W must be positive, got %d x %d", H, W); return OBIA_E_INVALID; }
     for (int i = 0; i < 6; ++i)
         if (!std::isfinite(inv6[i])) { set_error("seed table: sample: the inverse geotransform is not finite"); return OBIA_E_INVALID; }
@@ -233,10 +222,9 @@ int obia_seedtab_stage1_dev(obia_ctx *ctx, const double *xs, const double *ys, c
                             int64_t n, int64_t ncx, float eps_scale, float min_eps, float max_eps, float z_thresh, int min_samples,
                             uint8_t *fired_out, int32_t *owner_out, int32_t *rounds_out) {
     OBIA_TRY(enter(ctx));
-    if (!xs || !ys || !hs || !orig || !key || !fired_out || !owner_out || misaligned(xs, 8) || misaligned(ys, 8) || misaligned(hs, 4) ||
-        misaligned(orig, 4) || misaligned(key, 8) || misaligned(owner_out, 4) || (const void *)orig == (const void *)owner_out)
-        return bad_buffers("stage 1");
-    OBIA_TRY(check_grid("stage 1", n, ncx));
+    const Refusal refuse{"seed table", "stage 1"};
+    if (Buffers().out(owner_out).in(orig).lone(xs).lone(ys).lone(hs).lone(key).lone(fired_out).bad()) return refuse.buffers();
+    OBIA_TRY(check_grid(refuse, n, ncx));
     if (!(min_eps >= 0.0f) || !(max_eps >= min_eps) || !std::isfinite(eps_scale) || std::isnan(z_thresh)) {
         set_error("seed table: stage 1: needs 0 <= min_eps <= max_eps, a finite eps_scale and a z_thresh that is not NaN, got (%g, %g, %g, %g)",
                   (double)min_eps, (double)max_eps, (double)eps_scale, (double)z_thresh);
@@ -292,10 +280,9 @@ int obia_seedtab_last_work(obia_ctx *ctx, int64_t *work_out) {
 int obia_seedtab_segments_dev(obia_ctx *ctx, const int32_t *cluster, const float *heights, int64_t n, float dz_merge, int32_t *rank_out,
                               int32_t *size_out, uint8_t *part_out) {
     OBIA_TRY(enter(ctx));
-    if (!cluster || !heights || !rank_out || !size_out || !part_out || misaligned(cluster, 4) || misaligned(heights, 4) ||
-        misaligned(rank_out, 4) || misaligned(size_out, 4) || rank_out == size_out || cluster == rank_out || cluster == size_out)
-        return bad_buffers("segments");
-    OBIA_TRY(check_n("segments", n));
+    const Refusal refuse{"seed table", "segments"};
+    if (Buffers().out(rank_out).out(size_out).in(cluster).lone(heights).lone(part_out).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.n(n));
     if (std::isnan(dz_merge)) { set_error("seed table: segments: dz_merge is NaN"); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(seedtab_segments_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, cluster, heights, (int)n,
@@ -308,10 +295,9 @@ int obia_seedtab_segments_dev(obia_ctx *ctx, const int32_t *cluster, const float
 int obia_seedtab_nms_dev(obia_ctx *ctx, const double *xs, const double *ys, const float *hs, const int32_t *cluster, const int32_t *pos,
                          const int64_t *key, int64_t n, int64_t ncx, double base, double scale, uint8_t *keep_out) {
     OBIA_TRY(enter(ctx));
-    if (!xs || !ys || !hs || !cluster || !pos || !key || !keep_out || misaligned(xs, 8) || misaligned(ys, 8) || misaligned(hs, 4) ||
-        misaligned(cluster, 4) || misaligned(pos, 4) || misaligned(key, 8))
-        return bad_buffers("nms");
-    OBIA_TRY(check_grid("nms", n, ncx));
+    const Refusal refuse{"seed table", "nms"};
+    if (Buffers().lone(xs).lone(ys).lone(hs).lone(cluster).lone(pos).lone(key).lone(keep_out).bad()) return refuse.buffers();
+    OBIA_TRY(check_grid(refuse, n, ncx));
     if (std::isnan(base) || std::isnan(scale)) { set_error("seed table: nms: nms_base or nms_scale is NaN"); return OBIA_E_INVALID; }
     return call_frame(ctx, FRAME_PLAIN, [&]() -> int {
         hipLaunchKernelGGL(seedtab_nms_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, xs, ys, hs, cluster, pos,

@@ -150,14 +150,10 @@ extern "C" {
 int obia_shape_sums_dev(obia_ctx *ctx, const int32_t *labels, int H, int W, int32_t start_label, int32_t n_labels, int64_t *sums_out,
                         int32_t *box_out) {
     OBIA_TRY(enter(ctx));
-    if (!labels || (n_labels > 0 && (!sums_out || !box_out)) || misaligned(labels, 4) || misaligned(sums_out, 8) || misaligned(box_out, 4) ||
-        shared_start(2, sums_out, box_out, labels)) {
-        set_error("shapes: sums: bad arguments (null, misaligned or overlapping buffers)");
-        return OBIA_E_INVALID;
-    }
-    if (n_labels < 0 || n_labels > INT_MAX - 2) { set_error("shapes: sums: n_labels must be in 0 .. 2^31 - 3, got %d", n_labels); return OBIA_E_INVALID; }
-    if (H <= 0 || W <= 0) { set_error("shapes: sums: H and W must be positive, got %d x %d", H, W); return OBIA_E_INVALID; }
-    if ((long long)H * W > (long long)INT_MAX) { set_error("shapes: sums: H * W must be below 2^31, got %d x %d", H, W); return OBIA_E_UNSUPPORTED; }
+    const Refusal refuse{"shapes", "sums"};
+    if (Buffers().out(sums_out, n_labels > 0).out(box_out, n_labels > 0).in(labels).bad()) return refuse.buffers();
+    OBIA_TRY(refuse.labels(n_labels));
+    OBIA_TRY(refuse.raster_below_2_31(H, W));
     const unsigned __int128 side = (unsigned __int128)(H > W ? H : W);
     if (side * side * (unsigned __int128)((long long)H * W) >= (unsigned __int128)1 << 63) {
         set_error("shapes: sums: max(H, W)^2 * H * W must be below 2^63 (no sum can overflow then), got %d x %d", H, W);

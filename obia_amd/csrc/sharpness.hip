@@ -396,7 +396,7 @@ int sharp_win(const char *who, int win) {
 
 int clear_counter(obia_ctx *ctx, const char *who, int64_t *counter) {
     if (!counter) return OBIA_OK;
-    if ((uintptr_t)counter & 7) { set_error("%s: nonfinite_out must be 8-byte aligned", who); return OBIA_E_INVALID; }
+    if (Buffers().lone<8>(counter).bad()) { set_error("%s: nonfinite_out must be 8-byte aligned", who); return OBIA_E_INVALID; }
     OBIA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(int64_t), ctx->stream));
     return OBIA_OK;
 }
@@ -419,7 +419,7 @@ extern "C" {
 int obia_sharp_gray_lap_dev(obia_ctx *ctx, const float *raster, int H, int W, int C, const int32_t *bands3, float *lap_out,
                             int64_t *nonfinite_out) {
     OBIA_TRY(enter(ctx));
-    if (!raster || !bands3 || !lap_out || C < 1 || ((uintptr_t)raster & 3) || ((uintptr_t)lap_out & 3)) {
+    if (!bands3 || C < 1 || Buffers().lone(raster).lone(lap_out).bad()) {
         set_error("sharp gray_lap: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -446,7 +446,7 @@ int obia_sharp_gray_lap_dev(obia_ctx *ctx, const float *raster, int H, int W, in
 
 int obia_sharp_laplacian_dev(obia_ctx *ctx, const float *gray, int H, int W, float *lap_out, int64_t *nonfinite_out) {
     OBIA_TRY(enter(ctx));
-    if (!gray || !lap_out || gray == lap_out || ((uintptr_t)gray & 3) || ((uintptr_t)lap_out & 3)) {
+    if (Buffers().out(lap_out).in(gray).bad()) {
         set_error("sharp laplacian: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -459,8 +459,7 @@ int obia_sharp_laplacian_dev(obia_ctx *ctx, const float *gray, int H, int W, flo
 
 int obia_sharp_box_dev(obia_ctx *ctx, const float *plane, int H, int W, int win, float *work, float *out, int64_t *nonfinite_out) {
     OBIA_TRY(enter(ctx));
-    if (!plane || !work || !out || plane == out || plane == work || work == out || ((uintptr_t)plane & 3) || ((uintptr_t)work & 3) ||
-        ((uintptr_t)out & 3)) {
+    if (Buffers().out(work).out(out).in(plane).bad()) {
         set_error("sharp box: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -484,8 +483,7 @@ int obia_sharp_box_dev(obia_ctx *ctx, const float *plane, int H, int W, int win,
 
 int obia_sharp_variance_dev(obia_ctx *ctx, const float *lap, int H, int W, int win, float *work, float *out) {
     OBIA_TRY(enter(ctx));
-    if (!lap || !work || !out || lap == out || lap == work || work == out || ((uintptr_t)lap & 3) || ((uintptr_t)work & 3) ||
-        ((uintptr_t)out & 3)) {
+    if (Buffers().out(work).out(out).in(lap).bad()) {
         set_error("sharp variance: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -506,7 +504,7 @@ int obia_sharp_variance_dev(obia_ctx *ctx, const float *lap, int H, int W, int w
 
 int obia_sharp_stretch_f32_dev(obia_ctx *ctx, const float *plane, int64_t n, double lo, double hi, float *out) {
     OBIA_TRY(enter(ctx));
-    if (!plane || !out || n <= 0 || ((uintptr_t)plane & 3) || ((uintptr_t)out & 3)) {
+    if (n <= 0 || Buffers().lone(plane).lone(out).bad()) {
         set_error("sharp stretch: bad arguments");
         return OBIA_E_INVALID;
     }

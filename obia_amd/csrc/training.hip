@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void minmax_scale_kernel(const float *__restri
 
 // ------------------------------------------------------------------------------------------------------------------ host
 int clear_counter(obia_ctx *ctx, const char *who, int64_t *counter) {
-    if (!counter || ((uintptr_t)counter & 7)) { set_error("%s: the counter must be an 8-byte aligned device pointer", who); return OBIA_E_INVALID; }
+    if (Buffers().lone<8>(counter).bad()) { set_error("%s: the counter must be an 8-byte aligned device pointer", who); return OBIA_E_INVALID; }
     OBIA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(int64_t), ctx->stream));
     return OBIA_OK;
 }
@@ -323,7 +323,7 @@ extern "C" {
 int obia_train_blur_u8_dev(obia_ctx *ctx, const uint8_t *src, int H, int W, int nch, int kx, int ky, const int32_t *wx, const int32_t *wy,
                            uint8_t *out) {
     OBIA_TRY(enter(ctx));
-    if (!src || !out || src == out || !wx || !wy || ((uintptr_t)wx & 3) || ((uintptr_t)wy & 3)) {
+    if (Buffers().out(out).in(src).lone(wx).lone(wy).bad()) {
         set_error("train blur: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -347,7 +347,7 @@ int obia_train_blur_u8_dev(obia_ctx *ctx, const uint8_t *src, int H, int W, int 
 
 int obia_train_distance_dev(obia_ctx *ctx, const uint8_t *src, int H, int W, int R, int32_t *work, float *dist_out) {
     OBIA_TRY(enter(ctx));
-    if (!src || !work || !dist_out || (void *)work == (void *)dist_out || ((uintptr_t)work & 3) || ((uintptr_t)dist_out & 3)) {
+    if (Buffers().out(work).out(dist_out).lone(src).bad()) {
         set_error("train distance: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -370,7 +370,7 @@ int obia_train_distance_dev(obia_ctx *ctx, const uint8_t *src, int H, int W, int
 int obia_train_compose_u8_dev(obia_ctx *ctx, const uint8_t *tile, const uint8_t *blurred, const uint8_t *mask, const float *dist, int H,
                               int W, const uint8_t *darken_lut, double feather, uint8_t *out, int64_t *bad_mask_out) {
     OBIA_TRY(enter(ctx));
-    if (!tile || !blurred || !mask || !darken_lut || !out || out == tile || out == blurred || ((uintptr_t)dist & 3)) {
+    if (Buffers().out(out).in(tile).in(blurred).lone(mask).lone(darken_lut).lone(dist, OPTIONAL).bad()) {
         set_error("train compose: bad arguments");
         return OBIA_E_INVALID;
     }
@@ -392,7 +392,7 @@ int obia_train_compose_u8_dev(obia_ctx *ctx, const uint8_t *tile, const uint8_t 
 
 int obia_train_minmax_u8_dev(obia_ctx *ctx, const float *x, int64_t n, float *work, uint8_t *out, int64_t *nonfinite_out) {
     OBIA_TRY(enter(ctx));
-    if (!x || !work || !out || n <= 0 || x == work || ((uintptr_t)x & 3) || ((uintptr_t)work & 3)) {
+    if (n <= 0 || Buffers().out(work).in(x).lone(out).bad()) {
         set_error("train minmax: bad arguments");
         return OBIA_E_INVALID;
     }

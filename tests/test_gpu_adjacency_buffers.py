@@ -13,6 +13,7 @@ import pytest
 from tests import adjacency_restatement as R
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -181,6 +182,17 @@ def test_refusals_write_nothing(poison):
                co(ip=None), co(nb=None), co(l_=None), co(r_=None), co(r_=a + 2), co(n_=-1), co(nz=-1), co(r_=NB),
                rl(l_=None), rl(t_=None), rl(o_=None), rl(l_=L + 1), rl(t_=TB + 2), rl(o_=a + 3), rl(n_=0), rl(n_=-5), rl(s_=-1), rl(o_=L), rl(o_=TB)]
     assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+    # ... and says so in full: a null output, an output one byte on, an output where an input starts
+    why = "adjacency: %s: bad arguments (null, misaligned or overlapping buffers)"
+    assert why % "tile count" == "adjacency: tile count: bad arguments (null, misaligned or overlapping buffers)"
+    refused_saying(why % "tile count", cnt, dict(o_=None), dict(o_=a + 1), dict(o_=L))
+    refused_saying(why % "tile write", wr, dict(k_=None), dict(w_=None), dict(e_=a + 1), dict(k_=q + 1), dict(e_=L), dict(w_=OFF))
+    refused_saying(why % "edge d2", d2, dict(o_=None), dict(o_=x + 1), dict(o_=V), dict(o_=IP))
+    refused_saying(why % "neighbor stats", st, dict(m_=None), dict(u_=None), dict(lo=y + 1), dict(hi=V), dict(u_=NB), dict(m_=x, hi=x))
+    refused_saying(why % "class border", cb, dict(o_=None), dict(o_=q + 1), dict(o_=BD), dict(o_=IP))
+    refused_saying(why % "best neighbor", bn, dict(b_=None), dict(bd_=None), dict(b_=a + 1), dict(bd_=x + 1), dict(bd_=D), dict(b_=NB))
+    refused_saying(why % "components", co, dict(r_=None), dict(r_=a + 1), dict(r_=NB))
+    refused_saying(why % "relabel", rl, dict(o_=None), dict(o_=a + 1), dict(o_=L), dict(o_=TB))
     unsupported = [cnt(H_=65536, W_=32768), wr(H_=46341, W_=46341), wr(tot=2 ** 31), d2(nz=2 ** 31), st(nz=2 ** 31), cb(nz=2 ** 31), bn(nz=2 ** 31),
                    co(nz=2 ** 31), rl(n_=2 ** 31), d2(n_=2 ** 30, F_=2), st(n_=2 ** 30, F_=2), cb(n_=2 ** 30, K_=2)]
     assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported

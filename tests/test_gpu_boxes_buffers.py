@@ -10,6 +10,7 @@ import pytest
 from tests import boxes_restatement as R
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -165,6 +166,22 @@ def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
                lib.obia_boxes_assign_dev(ctx.handle, L, H, W, B, N, NL, a, B), lib.obia_boxes_assign_dev(ctx.handle, L, H, W, B, N, NL, L, d),
                lib.obia_boxes_pair_count_dev(ctx.handle, L, H, W, B, N, NL, B, a)]
     assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+    # ... and says so in full: a null output, an output (the keep flags are bytes: an input) one byte on, an output where an input starts
+    h, AI = ctx.handle, assigned_in.data_ptr()
+    refused_saying("boxes: assign: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_assign_dev,
+                   (h, L, H, W, B, N, NL, None, d), (h, L, H, W, B, N, NL, a + 1, d), (h, L, H, W, B, N, NL, a, B))
+    refused_saying("boxes: pair count: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_pair_count_dev,
+                   (h, L, H, W, B, N, NL, None, a), (h, L, H, W, B, N, NL, q + 1, a), (h, L, H, W, B, N, NL, q, L))
+    refused_saying("boxes: pair write: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_pair_write_dev,
+                   (h, L, H, W, B, N, NL, O, P, T, None, b, d, c4), (h, L, H, W, B, N, NL, O, P, T, a, b, d + 1, c4),
+                   (h, L, H, W, B, N, NL, O, P, T, a, b, d, L))
+    refused_saying("boxes: dissolve: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_dissolve_dev,
+                   (h, L, H * W, AI, NL, None), (h, L, H * W, AI, NL, a + 1), (h, L, H * W, AI, NL, L), (h, L, H * W, AI, NL, AI))
+    refused_saying("boxes: iou: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_iou_dev,
+                   (h, B, 3, B, 3, None), (h, B, 3, B, 3, d + 1), (h, B, 3, BR.data_ptr(), 3, B), (h, BR.data_ptr(), 3, B, 3, B))
+    refused_saying("boxes: nms: bad arguments (null, misaligned or overlapping buffers)", lib.obia_boxes_nms_dev,
+                   (h, B, P, None, K, N, c["ncx"], THR, None, None), (h, B, P + 1, None, K, N, c["ncx"], THR, u, None),
+                   (h, B, P, None, K, N, c["ncx"], THR, B, None))
     nonfin = [lib.obia_boxes_assign_dev(ctx.handle, L, H, W, BN.data_ptr(), N, NL, a, d),
               lib.obia_boxes_pair_count_dev(ctx.handle, L, H, W, BN.data_ptr(), N, NL, q, a),
               lib.obia_boxes_pair_write_dev(ctx.handle, L, H, W, BN.data_ptr(), N, NL, O, P, T, a, b, d, c4),

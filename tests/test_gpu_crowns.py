@@ -242,11 +242,14 @@ def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
                 conn=8, md=-1.0, dist=gd.ptr, labels=gl.ptr)
     for change in (dict(conn=6), dict(weight=-1.0), dict(weight=float("nan")), dict(lh=0.0), dict(ld=float("inf")), dict(md=float("nan")),
                    dict(H=0), dict(n=0), dict(cost=cost.data_ptr() + 2), dict(dist=gd.ptr + 4), dict(labels=gl.ptr + 1), dict(rc=None),
-                   dict(ids=ids.data_ptr() + 3)):
+                   dict(ids=ids.data_ptr() + 3), dict(dist=None), dict(dist=gd.ptr + 1), dict(labels=cost.data_ptr()), dict(dist=cost.data_ptr())):
         a = dict(good, **change)
         rcode = lib.obia_crowns_allocate_dev(ctx.handle, a["cost"], None, a["H"], a["W"], a["rc"], a["ids"], a["n"], a["weight"], a["lh"], a["lv"],
                                              a["ld"], a["conn"], a["md"], a["dist"], a["labels"], None)
         assert rcode == _lib.E_INVALID, (change, rcode)
+        # a null output, an output one byte on, an output where the cost raster starts: the refusal in full
+        if change in (dict(dist=None), dict(dist=gd.ptr + 1), dict(labels=gl.ptr + 1), dict(labels=cost.data_ptr()), dict(dist=cost.data_ptr())):
+            assert _lib.last_error() == "crowns: bad arguments (null, misaligned or overlapping buffers)", change
     assert gd.untouched() and gl.untouched()
 
 

@@ -13,6 +13,7 @@ from tests import launch_grids as LG
 from tests import pointcloud_restatement as R
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -396,6 +397,11 @@ def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
                dtm_call(o, dtm_=dtm.data_ptr() + 2), dtm_call(o, H_=0), dtm_call(o, hag=None), dtm_call(o, zg=o["dzg"].ptr + 4), dtm_call(o, zg=X),
                dtm_call(o, hag=dtm.data_ptr())]
     assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+    # ... and says so in full: a null output, an output one byte on, an output where an input starts
+    refused_saying("ground: query: bad arguments (null, misaligned or overlapping buffers)", query,
+                   dict(o=o, zg=None), dict(o=o, zg=o["zg"].ptr + 1), dict(o=o, hag=o["hag"].ptr + 1), dict(o=o, zg=Z), dict(o=o, m=CS))
+    refused_saying("ground: dtm: bad arguments (null, misaligned or overlapping buffers)", dtm_call,
+                   dict(o=o, hag=None), dict(o=o, zg=o["dzg"].ptr + 1), dict(o=o, hag=o["dhag"].ptr + 1), dict(o=o, zg=Z), dict(o=o, hag=dtm.data_ptr()))
     unsupported = [query(o, n_=2 ** 31), query(o, ng=2 ** 31), dtm_call(o, n_=2 ** 31)]
     assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported
     empty = [query(o, n_=0), query(o, n_=0, x_=None, z_=None, hag=None), dtm_call(o, n_=0), dtm_call(o, n_=0, x_=None)]

@@ -14,6 +14,7 @@ from tests import groundfilter_restatement as R
 from tests import pointcloud_restatement as PR
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -170,6 +171,14 @@ def test_refusals_write_nothing(poison):
                cl(n_=-1), cl(x_=None), cl(z_=Z + 4), cl(inv_=None), cl(t_=None), cl(t_=T + 2), cl(H_=0), cl(fl=None), cl(cn=None), cl(cn=c + 4),
                cl(fl=X), cl(cn=Z)]
     assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+    # ... and says so in full: a null output, an output (the flags are bytes: the counters) one byte on, an output where an input starts
+    why = "groundfilter: %s: bad arguments (null, misaligned or overlapping buffers)"
+    assert why % "cell min" == "groundfilter: cell min: bad arguments (null, misaligned or overlapping buffers)"
+    refused_saying(why % "cell min", cmin, dict(k_=None), dict(k_=a + 1), dict(k_=Z))
+    refused_saying(why % "cell min finish", fin, dict(o_=None), dict(o_=f + 1), dict(o_=KEYS))
+    refused_saying(why % "filter", mf, dict(d_=None), dict(t_=None), dict(d_=f + 1), dict(t_=t0 + 1), dict(d_=P), dict(t_=P), dict(t_=f))
+    refused_saying(why % "threshold", th, dict(S=None), dict(T_=None), dict(S=f + 1), dict(tb=t1 + 1), dict(T_=P), dict(ta=P), dict(S=f, tb=f))
+    refused_saying(why % "classify", cl, dict(fl=None), dict(cn=None), dict(cn=c + 1), dict(fl=T), dict(cn=X))
     unsupported = [cmin(n_=2 ** 31), cl(n_=2 ** 31), cmin(H_=65536, W_=32768), fin(H_=46341, W_=46341), mf(H_=65536, W_=32768), th(H_=2 ** 30, W_=2),
                    cl(H_=32768, W_=65536), mf(r_=128), mf(r_=2 ** 20), th(radii=(1, 128))]
     assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported

@@ -12,6 +12,7 @@ from tests import adjacency_restatement as R
 from tests import merging_restatement as M
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -177,6 +178,17 @@ def test_refusals_write_nothing_and_leave_the_context_intact(poison):
                    write(raw_ptr=None), write(cnt=None), write(key=None), write(bwork=None), write(out_ptr=None), write(nb=None), write(bd=None),
                    write(nb=q["neighbor"] + 2), write(bd=q["border"] + 4), write(nb=p["neighbor"]), write(n_=-1), write(nnz_=-1), write(nnz_out_=-1)]
         assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+        # ... and says so in full: a null output, an output one byte on, an output where an input starts
+        why = "merging: %s: bad arguments (null, misaligned or overlapping buffers)"
+        assert why % "cost" == "merging: cost: bad arguments (null, misaligned or overlapping buffers)"
+        refused_saying(why % "cost", cost, dict(out=None), dict(out=q["cost"] + 1), dict(out=p["weights"]), dict(out=p["border"]))
+        refused_saying(why % "pairs", pairs, dict(area=None), dict(box=None), dict(mean=q["mean"] + 1), dict(box=q["box"] + 1), dict(m2=p["m2"]),
+                       dict(box=p["partner"]), dict(perimeter=p["indptr"]), dict(area=q["perimeter"]))
+        refused_saying(why % "contract rows", rows, dict(out=None), dict(out=q["raw_count"] + 1), dict(out=p["indptr"]))
+        refused_saying(why % "contract count", count, dict(out=None), dict(cursor=None), dict(key=q["key"] + 1), dict(out=q["count"] + 1),
+                       dict(bwork=p["raw_ptr"]), dict(cursor=p["root"]), dict(out=q["cursor"]))
+        refused_saying(why % "contract write", write, dict(nb=None), dict(bd=None), dict(nb=q["neighbor"] + 1), dict(bd=q["border"] + 1),
+                       dict(nb=p["root"]), dict(bd=p["out_ptr"]))
         unsupported = [cost(nnz_=2 ** 31), cost(n_=2 ** 30, F_=2), pairs(nnz_=2 ** 31), pairs(n_=2 ** 30, F_=2), rows(nnz_=2 ** 31), count(nnz_=2 ** 31),
                        write(nnz_=2 ** 31), write(nnz_out_=2 ** 31)]
         assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported

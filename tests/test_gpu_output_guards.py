@@ -1279,9 +1279,10 @@ def test_outputs_between_guards(oracle, name):
 
 # ---- after a refusal -------------------------------------------------------------------------------------------------------------
 def test_a_refused_call_leaves_the_guards_and_the_context_intact(oracle):
-    """Four refusals on ONE context, each with guarded outputs: the code is the header's, no guard byte changes, the polygon buffers stay
-    wholly poison (the capacity check precedes the launch), and a SLIC call on the same context afterwards gives the labels of a fresh
-    context."""
+    """Five refusals on ONE context, each with guarded outputs: the code is the header's, no guard byte changes, the polygon buffers stay
+    wholly poison (the capacity check precedes the launch) and so do those of a call whose buffers are refused (a null output, an output
+    one byte on, an output where an input starts: the text in full), and a SLIC call on the same context afterwards gives the labels of
+    a fresh context."""
     from obia_amd import _lib
     from obia_amd.segmentation import make_params
     lib = _lib.load()
@@ -1328,12 +1329,23 @@ def test_a_refused_call_leaves_the_guards_and_the_context_intact(oracle):
             run.exempt(name, np.ones(run.outs[name][0].shape, bool))
         return lib.obia_mlp_predict_dev(used.handle, ptr(run.dev("x", X)), N, F, ctypes.byref(ms), None, *(x.ptr for x in g))
 
+    def buffers_refused(run):
+        plane = ptr(run.dev("plane", np.ascontiguousarray(img[:, :, 0])))
+        work, out = run.out("work", (H, W), F32, keep_poison=True), run.out("out", (H, W), F32, keep_poison=True)
+        rcs = set()
+        for w, o in ((work.ptr, None), (work.ptr, out.ptr + 1), (work.ptr, plane), (plane, out.ptr), (work.ptr, work.ptr)):
+            rcs.add(lib.obia_sharp_box_dev(used.handle, plane, H, W, 3, w, o, None))
+            assert _lib.last_error() == "sharp box: bad arguments", (w, o)
+        assert len(rcs) == 1
+        return rcs.pop()
+
     flat = img.copy()
     flat[:, :, 2] = 7.0                                      # a constant band: 0 / 0 in normalize_band
     refusals = [("all-zero mask", lambda r: slic_refused(r, img, np.zeros((H, W), U8)), _lib.E_EMPTY, True),
                 ("constant band", lambda r: slic_refused(r, flat, mask), _lib.E_NONFINITE, True),
                 ("cap_rings one short", polygons_refused, _lib.E_NOMEM, False),
-                ("NaN in x", mlp_refused, _lib.E_INVALID, False)]
+                ("NaN in x", mlp_refused, _lib.E_INVALID, False),
+                ("buffers of the box filter", buffers_refused, _lib.E_INVALID, False)]
     try:
         want = good(fresh, POISONS[0])
         judge_slic(oracle, want, img, mask, kw, "full")

@@ -11,6 +11,7 @@ import pytest
 from tests import pointcloud_restatement as R
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -141,6 +142,15 @@ def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
                col(N_=0), col(nz_=0), col(dz_=0.0), col(dz_=nan), col(mh=nan), col(mh=float("inf")), col(k_=0.0), col(k_=-1.0), col(k_=nan),
                col(pr=None), col(pr=P + 2), col(npo=None), col(npo=p + 4), col(ch=d + 4), col(pad=d6 + 4), col(ch=d2), col(pad=d), col(npo=S1)]
     assert invalid == [_lib.E_INVALID] * len(invalid), invalid
+    # ... and says so in full: a null output, an output one byte on, an output where an input starts
+    refused_saying("points: rasters: bad arguments (null, misaligned or overlapping buffers)", lib.obia_points_rasters_dev,
+                   (h, X, Y, Z, n, inv, R.H, R.W, a, None), (h, X, Y, Z, n, inv, R.H, R.W, a, b + 1), (h, X, Y, Z, n, inv, R.H, R.W, Z, b))
+    refused_saying("points: rasters finish: bad arguments (null, misaligned or overlapping buffers)", lib.obia_points_rasters_finish_dev,
+                   (h, ZK, CN, R.H, R.W, 0.25, None, e), (h, ZK, CN, R.H, R.W, 0.25, f, e + 1), (h, ZK, CN, R.H, R.W, 0.25, f, CN))
+    refused_saying("points: segments: bad arguments (null, misaligned or overlapping buffers)", seg,
+                   dict(s2=None), dict(ni=c3 + 1), dict(cn=w + 1), dict(tp=L), dict(s1=X))
+    refused_saying("points: segment columns: bad arguments (null, misaligned or overlapping buffers)", col,
+                   dict(ch=None), dict(npo=p + 1), dict(pad=d6 + 1), dict(ch=S2), dict(pad=P))
     unsupported = [lib.obia_points_rasters_dev(h, X, Y, Z, 2 ** 31, inv, R.H, R.W, a, b), seg(n_=2 ** 31), seg(nz_=4097), seg(N_=2 ** 20, nz_=2048),
                    seg(N_=2 ** 31 - 1, nz_=2), col(nz_=4097), col(N_=2 ** 20, nz_=2048)]
     assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported

@@ -10,6 +10,7 @@ import pytest
 from tests import seed_table_restatement as T
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -138,6 +139,22 @@ def test_buffers_off_the_boundary_and_guarded_outputs(k, poison):
                lib.obia_seedtab_nms_dev(ctx.handle, x, y, h4, i4, i4, k8, N, 1, 1.0, 0.1, u),
                lib.obia_seedtab_nms_dev(ctx.handle, x, y, h4, i4, i4, k8, N, c["ncx"], 1.0, 0.1, None)]
     assert refused == [_lib.E_INVALID] * len(refused), refused
+    # ... and says so in full: a null output, an output (where it is of bytes: an input) one byte on, an output where the input it is
+    # compared with starts (the non-maximum suppression compares nothing)
+    hd, C = ctx.handle, chm.data_ptr()
+    refused_saying("seed table: cells: bad arguments (null, misaligned or overlapping buffers)", lib.obia_seedtab_cells_dev,
+                   (hd, x, y, N, SIDE, None, b), (hd, x, y, N, SIDE, a, b + 1), (hd, x, y, N, SIDE, a, a))
+    refused_saying("seed table: sample: bad arguments (null, misaligned or overlapping buffers)", lib.obia_seedtab_sample_dev,
+                   (hd, x, y, N, C, H, W, inv6, None, u), (hd, x, y, N, C, H, W, inv6, f, None), (hd, x, y, N, C, H, W, inv6, f + 1, u),
+                   (hd, x, y, N, C, H, W, inv6, C, u))
+    refused_saying("seed table: stage 1: bad arguments (null, misaligned or overlapping buffers)", lib.obia_seedtab_stage1_dev,
+                   (hd, x, y, h4, i4, k8, N, c["ncx"], *s1, 3, u, None, None), (hd, x, y, h4, i4, k8, N, c["ncx"], *s1, 3, None, a, None),
+                   (hd, x, y, h4, i4, k8, N, c["ncx"], *s1, 3, u, a + 1, None), (hd, x, y, h4, i4, k8, N, c["ncx"], *s1, 3, u, i4, None))
+    refused_saying("seed table: segments: bad arguments (null, misaligned or overlapping buffers)", lib.obia_seedtab_segments_dev,
+                   (hd, i4, h4, N, 1.0, None, b, u), (hd, i4, h4, N, 1.0, a, b, None), (hd, i4, h4, N, 1.0, a, b + 1, u),
+                   (hd, i4, h4, N, 1.0, a, i4, u), (hd, i4, h4, N, 1.0, i4, b, u))
+    refused_saying("seed table: nms: bad arguments (null, misaligned or overlapping buffers)", lib.obia_seedtab_nms_dev,
+                   (hd, x, y, h4, i4, i4, k8, N, c["ncx"], 1.0, 0.1, None), (hd, x, y, h4 + 1, i4, i4, k8, N, c["ncx"], 1.0, 0.1, u))
     assert all(v.untouched() for v in g.values())
 
 

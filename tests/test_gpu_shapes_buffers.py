@@ -11,6 +11,7 @@ import pytest
 from tests import shapes_restatement as S
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -101,6 +102,9 @@ def test_refusals_write_nothing_and_leave_the_context_intact(poison):
                    sh(n_=2 ** 31 - 2), sh(s_=L), sh(b_=L), sh(s_=b), sh(n_=0, l_=None)]
         assert invalid == [_lib.E_INVALID] * len(invalid), invalid
         assert "null, misaligned or overlapping" in _lib.last_error()
+        # ... in full: a null output, an output one byte on, an output where the labels start
+        refused_saying("shapes: sums: bad arguments (null, misaligned or overlapping buffers)", sh, dict(s_=None), dict(b_=None), dict(s_=s + 1),
+                       dict(b_=b + 1), dict(b_=L), dict(s_=b))
         unsupported = [sh(H_=65536, W_=32768), sh(H_=46341, W_=46341), sh(H_=1, W_=2 ** 21), sh(H_=2 ** 21, W_=1), sh(H_=1024, W_=2 ** 21 - 1)]
         assert unsupported == [_lib.E_UNSUPPORTED] * len(unsupported), unsupported
         torch.cuda.synchronize()

@@ -13,6 +13,7 @@ import pytest
 from tests import sharpness_restatement as S
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -92,6 +93,12 @@ def test_gray_lap(k, shape, poison):
     cnt2 = guarded((1,), np.int64, poison, "cuda", k)
     run(_lib, lib, c, lib.obia_sharp_gray_lap_dev, dev_off(bad, k).data_ptr(), H, W, 5, (ctypes.c_int32 * 3)(*bands), g2.ptr, cnt2.ptr)
     judge(cnt2, np.ones(1, np.int64), "gray_lap counter of one")
+    # a null output, an output one byte on (the raster is compared with nothing), a counter off its boundary: the refusals in full
+    g3, b3, I = guarded((H, W), np.float32, poison, "cuda", k), (ctypes.c_int32 * 3)(*bands), it.data_ptr()
+    refused_saying("sharp gray_lap: bad arguments", lib.obia_sharp_gray_lap_dev, (c.handle, I, H, W, 5, b3, None, None),
+                   (c.handle, I, H, W, 5, b3, g3.ptr + 1, None), (c.handle, I + 1, H, W, 5, b3, g3.ptr, None))
+    refused_saying("sharp gray_lap: nonfinite_out must be 8-byte aligned", lib.obia_sharp_gray_lap_dev, (c.handle, I, H, W, 5, b3, g3.ptr, cnt2.ptr + 4))
+    assert g3.untouched()
 
 
 @pytest.mark.parametrize("k,shape,poison", CASES, ids=IDS)
@@ -111,6 +118,11 @@ def test_laplacian(k, shape, poison):
     g2 = guarded((H, W), np.float32, poison, "cuda", k)
     run(_lib, lib, c, lib.obia_sharp_laplacian_dev, gt.data_ptr(), H, W, g2.ptr, None)
     judge(g2, want, "laplacian alone")
+    # a null output, an output one byte on, an output where the input starts: the refusal in full
+    g3 = guarded((H, W), np.float32, poison, "cuda", k)
+    refused_saying("sharp laplacian: bad arguments", lib.obia_sharp_laplacian_dev, (c.handle, gt.data_ptr(), H, W, None, None),
+                   (c.handle, gt.data_ptr(), H, W, g3.ptr + 1, None), (c.handle, gt.data_ptr(), H, W, gt.data_ptr(), None))
+    assert g3.untouched() and unchanged(gt, snap)
 
 
 @pytest.mark.parametrize("k,shape,poison", CASES, ids=IDS)
@@ -136,6 +148,12 @@ def test_box(k, shape, poison):
     work = guarded((H, W), np.float32, poison, "cuda", k)
     run(_lib, lib, c, lib.obia_sharp_box_dev, pt.data_ptr(), H, W, 0, work.ptr, g.ptr, None, expect=_lib.E_INVALID)
     run(_lib, lib, c, lib.obia_sharp_box_dev, pt.data_ptr(), H, W, _lib.SHARP_MAX_WIN + 1, work.ptr, g.ptr, None, expect=_lib.E_UNSUPPORTED)
+    # a null output, an output one byte on, and each of the three pairs at one start: the refusal in full
+    P = pt.data_ptr()
+    refused_saying("sharp box: bad arguments", lib.obia_sharp_box_dev, (c.handle, P, H, W, 3, work.ptr, None, None),
+                   (c.handle, P, H, W, 3, work.ptr, g.ptr + 1, None), (c.handle, P, H, W, 3, work.ptr, P, None), (c.handle, P, H, W, 3, P, g.ptr, None),
+                   (c.handle, P, H, W, 3, g.ptr, g.ptr, None))
+    assert unchanged(pt, snap)
     assert g.untouched() and work.untouched() and g.findings(exempt=np.ones(shape, bool)) == []
 
 
@@ -156,6 +174,12 @@ def test_variance(k, shape, poison):
             judge(work, np.stack([S.uniform_filter1d(lap, win, 0), S.uniform_filter1d(lap * lap, win, 0)]), "variance work planes")
         else:
             assert work.untouched()
+    # a null output, an output one byte on, and each of the three pairs at one start: the refusal in full
+    g, work, L = guarded((H, W), np.float32, poison, "cuda", k), guarded((2, H, W), np.float32, poison, "cuda", k), lt.data_ptr()
+    refused_saying("sharp variance: bad arguments", lib.obia_sharp_variance_dev, (c.handle, L, H, W, 3, work.ptr, None),
+                   (c.handle, L, H, W, 3, work.ptr + 1, g.ptr), (c.handle, L, H, W, 3, work.ptr, L), (c.handle, L, H, W, 3, L, g.ptr),
+                   (c.handle, L, H, W, 3, g.ptr, g.ptr))
+    assert g.untouched() and work.untouched()
     assert unchanged(lt, snap)
 
 
@@ -175,6 +199,11 @@ def test_stretch(k, shape, poison):
         run(_lib, lib, c, lib.obia_sharp_stretch_f32_dev, xt.data_ptr(), x.size, 3.0, 3.0, z.ptr)
         judge(z, np.clip((x - np.float64(3.0)) / np.float64(0.0), 0, 1).astype(np.float32), "stretch lo == hi")
     assert np.isnan(z.host().flat[0])
+    # a null output, an output one byte on (the input is compared with nothing): the refusal in full
+    g3 = guarded(shape, np.float32, poison, "cuda", k)
+    refused_saying("sharp stretch: bad arguments", lib.obia_sharp_stretch_f32_dev, (c.handle, xt.data_ptr(), x.size, 0.0, 1.0, None),
+                   (c.handle, xt.data_ptr(), x.size, 0.0, 1.0, g3.ptr + 1), (c.handle, xt.data_ptr() + 1, x.size, 0.0, 1.0, g3.ptr))
+    assert g3.untouched()
     assert unchanged(xt, snap)
 
 

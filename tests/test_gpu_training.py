@@ -14,6 +14,7 @@ import pytest
 from tests import training_restatement as T
 from tests.guarded import POISONS, guarded, snapshot, unchanged
 from tests.offset_views import offset_view, residue
+from tests.refusal_text import refused_saying
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -268,6 +269,10 @@ def test_blur_buffers(k, poison):
                 g.ptr, expect=_lib.E_INVALID)
         run(_lib, lib, c, lib.obia_train_blur_u8_dev, it.data_ptr(), shape[0], shape[1], 2, 5, 5, wx.data_ptr(), wy.data_ptr(), g.ptr,
             expect=_lib.E_INVALID)
+        # a null output, the weights (the output is of bytes) one byte on, the output where the image starts: the refusal in full
+        I, X, Y = it.data_ptr(), wx.data_ptr(), wy.data_ptr()
+        refused_saying("train blur: bad arguments", lib.obia_train_blur_u8_dev, (c.handle, I, shape[0], shape[1], nch, 5, 5, X, Y, None),
+                       (c.handle, I, shape[0], shape[1], nch, 5, 5, X + 1, Y, g.ptr), (c.handle, I, shape[0], shape[1], nch, 5, 5, X, Y, I))
         assert g.untouched()
 
 
@@ -304,6 +309,10 @@ def test_distance_buffers(k, poison):
     work = guarded((4, 4), np.int32, poison, "cuda", k)
     run(_lib, lib, c, lib.obia_train_distance_dev, st.data_ptr(), 4, 4, -1, work.ptr, g.ptr, expect=_lib.E_INVALID)
     run(_lib, lib, c, lib.obia_train_distance_dev, st.data_ptr(), 1, _lib.TRAIN_MAX_SIDE + 1, 1, work.ptr, g.ptr, expect=_lib.E_UNSUPPORTED)
+    # a null output, an output one byte on, the output where the work plane starts (the only pair compared): the refusal in full
+    refused_saying("train distance: bad arguments", lib.obia_train_distance_dev, (c.handle, st.data_ptr(), 4, 4, 1, work.ptr, None),
+                   (c.handle, st.data_ptr(), 4, 4, 1, work.ptr, g.ptr + 1), (c.handle, st.data_ptr(), 4, 4, 1, work.ptr + 1, g.ptr),
+                   (c.handle, st.data_ptr(), 4, 4, 1, work.ptr, work.ptr))
     assert g.untouched() and work.untouched()
 
 
@@ -320,6 +329,18 @@ def test_compose_buffers(k, poison):
             judge(cnt, np.zeros(1, np.int64), "compose counter")
             outs.append(out.host())
         assert np.array_equal(outs[0], outs[1])
+    # a null output, the distances (the output is of bytes) one byte on, the output where the tile or the blurred tile starts: the
+    # refusal in full, and nothing written
+    _lib, lib, c = env()
+    (H, W), lut = mask.shape, np.arange(256, dtype=np.uint8)
+    t, b, m, d, lu = (dev_off(a, k).data_ptr() for a in (tile, blurred, mask, dist, lut))
+    out, cnt = guarded((H, W, 3), np.uint8, poison, "cuda", k), guarded((1,), np.int64, poison, "cuda", 0)
+    refused_saying("train compose: bad arguments", lib.obia_train_compose_u8_dev, (c.handle, t, b, m, d, H, W, lu, 3.0, None, cnt.ptr),
+                   (c.handle, t, b, m, d + 1, H, W, lu, 3.0, out.ptr, cnt.ptr), (c.handle, t, b, m, d, H, W, lu, 3.0, t, cnt.ptr),
+                   (c.handle, t, b, m, d, H, W, lu, 3.0, b, cnt.ptr))
+    refused_saying("train compose: the counter must be an 8-byte aligned device pointer", lib.obia_train_compose_u8_dev,
+                   (c.handle, t, b, m, d, H, W, lu, 3.0, out.ptr, cnt.ptr + 4), (c.handle, t, b, m, d, H, W, lu, 3.0, out.ptr, None))
+    assert out.untouched() and cnt.untouched()
 
 
 @pytest.mark.parametrize("k,poison", BUFFER_CASES, ids=BUFFER_IDS)
@@ -352,6 +373,13 @@ def test_minmax_buffers(k, poison):
     cnt = guarded((1,), np.int64, poison, "cuda", 0)
     run(_lib, lib, c, lib.obia_train_minmax_u8_dev, dev_off(x, k).data_ptr(), n, work.ptr, g.ptr, cnt.ptr)
     judge(cnt, np.full(1, 2, np.int64), "minmax counter of two")
+    # a null work buffer, one a byte on (the output is of bytes), one where the input starts (the only pair compared): the refusal in full
+    g, cnt, X = guarded((n,), np.uint8, poison, "cuda", k), guarded((1,), np.int64, poison, "cuda", 0), xt.data_ptr()
+    refused_saying("train minmax: bad arguments", lib.obia_train_minmax_u8_dev, (c.handle, X, n, None, g.ptr, cnt.ptr),
+                   (c.handle, X, n, work.ptr, None, cnt.ptr), (c.handle, X, n, work.ptr + 1, g.ptr, cnt.ptr), (c.handle, X, n, X, g.ptr, cnt.ptr))
+    refused_saying("train minmax: the counter must be an 8-byte aligned device pointer", lib.obia_train_minmax_u8_dev,
+                   (c.handle, X, n, work.ptr, g.ptr, cnt.ptr + 4))
+    assert g.untouched() and cnt.untouched()
 
 
 def test_every_training_entry_point_is_exercised_by_a_buffer_test():
