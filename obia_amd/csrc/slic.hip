@@ -843,7 +843,7 @@ int slic_plan_layout(obia_ctx *ctx, SlicBatch &b) {
     return OBIA_OK;
 }
 
-int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared) {
+int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared, int counted_parts) {
     const int np = b.nprob;
     Arena &A = ctx->arena;
     nvalid.assign(np, 0);
@@ -851,6 +851,14 @@ int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int 
     if (b.masked) {
         OBIA_TRY(ctx->plan.flush(ctx));
         int *d_cnt = d_cnt_cleared;
+        if (counted_parts > 0) {
+            if (!d_cnt) { set_error("slic_count_valid: counts announced without their buffer"); return OBIA_E_INVALID; }
+            std::vector<int> parts((size_t)np * counted_parts);
+            OBIA_TRY(read_back(ctx, parts.data(), d_cnt, sizeof(int) * parts.size()));
+            for (int p = 0; p < np; ++p)
+                for (int q = 0; q < counted_parts; ++q) nvalid[p] += parts[(size_t)p * counted_parts + q];
+            return OBIA_OK;
+        }
         if (!d_cnt) {
             d_cnt = A.get<int>(np);
             if (!d_cnt) return OBIA_E_NOMEM;

@@ -229,7 +229,10 @@ int slic_plan_and_seed(obia_ctx *ctx, SlicBatch &b, const std::vector<int> &n_se
                        const std::vector<int> *nvalid = nullptr, const ExternalSeeds *ext = nullptr);
 // valid (unmasked) pixels per problem: mask.sum() (tiling.py:133, slic_superpixels.py:322)
 // d_cnt_cleared: one zeroed int per problem that the caller cleared beside its own fills (null: allocated and cleared here)
-int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared = nullptr);
+// counted_parts > 0: the kernel that wrote the mask has counted it already (the tiler's mask kernel holds every byte it writes) and
+// left counted_parts partial sums per problem, problem p's at d_cnt_cleared[p * counted_parts ...], every one written (nothing to
+// clear): no counting kernel, the read-back fetches the parts and the host adds them up
+int slic_count_valid(obia_ctx *ctx, SlicBatch &b, std::vector<int> &nvalid, int *d_cnt_cleared = nullptr, int counted_parts = 0);
 // the tables that depend on the window shapes only (layout version of the problems, tile -> problem table) into the open planning
 // blob; the caller flushes (slic_count_valid and slic_plan_and_seed do, for a caller that did not call it)
 int slic_plan_layout(obia_ctx *ctx, SlicBatch &b);
@@ -273,9 +276,10 @@ struct CcProblem { int H, W; long long pix_off; int min_size; int max_size; };  
 // The arrays live in the context's arena: valid until the caller rewinds it.
 struct CcResolve { const int *parent; const int *newlab; const int *small_final; int start_label; int mask_label; };
 #if defined(__HIPCC__)
-__device__ __forceinline__ int cc_resolve_label(const CcResolve &R, long long i) {
+// The label as a function of the pixel's parent alone: pixels with equal parents have equal labels, so a consumer that walks a
+// column resolves where the parent changes and reuses the label above everywhere else (tiling.hip: tile_scatter_kernel).
+__device__ __forceinline__ int cc_resolve_parent(const CcResolve &R, int p) {
     // (a pixel's parent is its tile-local root, whose parent is the root of the component: cc.hip, cc_roots_kernel)
-    const int p = R.parent[i];
     if (p < 0) return R.mask_label;
     const int r = R.parent[p];
     int nl = R.newlab[r];
@@ -284,6 +288,7 @@ __device__ __forceinline__ int cc_resolve_label(const CcResolve &R, long long i)
     if (nl < 0) nl = R.small_final[-nl - 2];
     return (nl >= 0) ? nl + R.start_label : 0;   // `adjacent = 0` when no labelled neighbour exists
 }
+__device__ __forceinline__ int cc_resolve_label(const CcResolve &R, long long i) { return cc_resolve_parent(R, R.parent[i]); }
 #endif
 // labels_out: the dense label map.  deferred (nullable): when given, the final relabel pass is NOT run -- labels_out is not
 // written -- and *deferred describes how to resolve a pixel.  (The component walks mark their pixels in a map of the context's

@@ -62,33 +62,57 @@ __device__ __forceinline__ bool meets_corner(const TileWin &t, int y, int x) {
     return (y >= t.h - t.cly_any) && (x < t.clx_any || x >= t.w - t.clx_any);
 }
 
+// Occupancy map of the label raster (TileState::occ): one bit per 64 x 64 block, in the raster's own coordinates, row-major over
+// occ_bw = cdiv(W, 64) blocks a row.  A block whose bit is clear holds only zeros, so its labels need not be read.  A null map (a
+// session, OBIA_G_OCCUPANCY=0) says nothing: every block counts as occupied.  Windows are not aligned to the blocks in general.
+constexpr int OCC_SHIFT = 6;
+__device__ __forceinline__ bool occ_test(const unsigned *__restrict__ occ, int occ_bw, int gy, int gx) {
+    if (!occ) return true;
+    const int b = (gy >> OCC_SHIFT) * occ_bw + (gx >> OCC_SHIFT);
+    return (occ[b >> 5] >> (b & 31)) & 1u;
+}
+
 // white tiles, step 1: inside[g] = pixels of every existing segment that lie in the window and do not meet a corner square
 // (inside[g] == seg_size[g]  <=>  the segment is `within` tile_polygon)
 // tile_any[tile] = 1 when some existing segment has area inside the polygon -- a pixel in the window that is not wholly inside a
 // corner square: `not intersecting_black_segments.empty or not intersecting_white_segments.empty` (tiling.py:205-212)
+// The kernel walks the window by the blocks of the occupancy map (raster coordinates): a workgroup per 64 x 64 block the window
+// meets, a wave per sixteen of its rows, a lane per column -- so the bit is tested once per workgroup, a workgroup in a clear block
+// ends at once (its labels are zero: they add to neither inside[] nor tile_any), and the rows of an occupied block are read as
+// aligned 256-byte stretches, eight in flight.  Without a map every block is walked.
+constexpr int COUNT_ROWS_PER_WAVE = (1 << OCC_SHIFT) / 4;
 __global__ __launch_bounds__(256) void tile_count_inside_kernel(const TileWin *__restrict__ wins, const int32_t *__restrict__ G,
-                                                                int Wr, unsigned *__restrict__ inside, int *__restrict__ tile_any) {
+                                                                int Wr, unsigned *__restrict__ inside, int *__restrict__ tile_any,
+                                                                const unsigned *__restrict__ occ, int occ_bw) {
     const TileWin t = wins[blockIdx.y];
+    const int cb0 = t.x0 >> OCC_SHIFT, rb0 = t.y0 >> OCC_SHIFT;                      // the first block column / row the window meets
+    const int nbx = ((t.x0 + t.w - 1) >> OCC_SHIFT) - cb0 + 1, nby = ((t.y0 + t.h - 1) >> OCC_SHIFT) - rb0 + 1;
+    if ((int)blockIdx.x >= nbx * nby) return;   // whole workgroup (the grid is sized for the batch's largest window)
+    const int rb = rb0 + (int)blockIdx.x / nbx, cb = cb0 + (int)blockIdx.x % nbx;
+    if (!occ_test(occ, occ_bw, rb << OCC_SHIFT, cb << OCC_SHIFT)) return;            // whole workgroup
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int x = (cb << OCC_SHIFT) + (int)(threadIdx.x & 63) - t.x0;                // the lane's column in the window
+    const bool col_ok = x >= 0 && x < t.w;
+    const int y_first = (rb << OCC_SHIFT) + wv * COUNT_ROWS_PER_WAVE - t.y0;         // the wave's first row in the window (wave-uniform)
     bool seen = false;
-    const int wround = ((t.w + 255) / 256) * 256;   // whole waves stay in the loop for the wave-level histogram
-    for (int y = blockIdx.x; y < t.h; y += gridDim.x) {
-        const bool low = y >= t.h - t.cly_any;   // a row the corner squares reach (workgroup-uniform: the others test no pixel)
-        for (int x0 = 0; x0 < wround; x0 += 4 * 256) {   // four loads in flight
-            int g[4];
+#pragma unroll 1
+    for (int yb = y_first; yb < y_first + COUNT_ROWS_PER_WAVE; yb += 8) {            // eight loads in flight
+        int g[8];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int x = x0 + 256 * u + threadIdx.x;
-                g[u] = 0;
-                if (x < t.w && !(low && wholly_in_corner(t, y, x))) {
-                    g[u] = G[(long long)(t.y0 + y) * Wr + t.x0 + x];
-                    seen |= g[u] > 0;
-                    if (low && meets_corner(t, y, x)) g[u] = 0;   // (a pixel the cut passes through: selected, but not counted as inside)
-                }
+        for (int j = 0; j < 8; ++j) {
+            const int y = yb + j;
+            g[j] = 0;
+            if (y < 0 || y >= t.h) continue;                                         // wave-uniform
+            const bool low = y >= t.h - t.cly_any;   // a row the corner squares reach (wave-uniform: the others test no pixel)
+            if (col_ok && !(low && wholly_in_corner(t, y, x))) {
+                g[j] = G[(long long)(t.y0 + y) * Wr + t.x0 + x];
+                seen |= g[j] > 0;
+                if (low && meets_corner(t, y, x)) g[j] = 0;   // (a pixel the cut passes through: selected, but not counted as inside)
             }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (x0 + 256 * u < wround) wave_hist_add(inside, g[u], g[u] > 0);   // wave-uniform condition
         }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (yb + j >= 0 && yb + j < t.h) wave_hist_add(inside, g[j], g[j] > 0);   // wave-uniform condition
     }
     if (__ballot(seen) && (threadIdx.x & 63) == 0) tile_any[blockIdx.y] = 1;   // (every writer stores the same value)
 }
@@ -100,8 +124,21 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
                                                         int32_t *__restrict__ G, int Wr, int white,
                                                         const unsigned *__restrict__ inside, const unsigned *__restrict__ seg_size,
                                                         uint8_t *__restrict__ alive, uint8_t *__restrict__ dmask,
-                                                        const int *__restrict__ tile_any, unsigned *__restrict__ dmask4) {
+                                                        const int *__restrict__ tile_any, unsigned *__restrict__ dmask4,
+                                                        const unsigned *__restrict__ occ, int occ_bw, int *__restrict__ parts) {
     const TileWin t = wins[blockIdx.y];
+    // parts[tile * gridDim.x + workgroup] = the non-zero mask bytes this workgroup wrote (every byte is 0 or 1): partial sums of the
+    // tile's valid count, mask.sum() (tiling.py:133), which the host adds up after the read-back it makes anyway.  Plain stores, every
+    // slot written: atomics on the tiles' counters serialise, about 8 ns each, and cost more than the counting kernel they replace.
+    __shared__ int s_nz[4];
+    int nz = 0;
+    auto store_count = [&]() {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nz += __shfl_xor(nz, off);
+        if ((threadIdx.x & 63) == 0) s_nz[threadIdx.x >> 6] = nz;
+        __syncthreads();
+        if (threadIdx.x == 0) parts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s_nz[0] + s_nz[1] + s_nz[2] + s_nz[3];
+    };
     // a white tile whose polygon no existing segment intersects keeps the mask it read: neither kept segments (there are none
     // inside the polygon) nor the corner squares are masked out (tiling.py:212, 261-262)
     if (white && tile_any[blockIdx.y] == 0) white = 0;
@@ -127,13 +164,19 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
                 const int x = 4 * x4;
                 unsigned mw[4];
                 int4 g[4];
+                // the block's four pixels of a row lie in one block of the occupancy map (x0 + x is a multiple of four), its four
+                // rows in at most two: when both are clear the labels are not loaded, g stays 0 and `decide` takes its path for no
+                // segment.  (One test for the four loads, so that they are issued together as before; rows of a clear block that
+                // are loaded beside an occupied one hold zeros.)
+                const bool load_g = white && (occ_test(occ, occ_bw, t.y0 + 4 * q, t.x0 + x) || occ_test(occ, occ_bw, t.y0 + min(4 * q + 3, t.h - 1), t.x0 + x));
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int y = 4 * q + j;
-                    const long long gp = (long long)(t.y0 + (y < t.h ? y : t.h - 1)) * Wr + t.x0 + x;
+                    const int gy = t.y0 + (y < t.h ? y : t.h - 1);
+                    const long long gp = (long long)gy * Wr + t.x0 + x;
                     mw[j] = inmask ? *reinterpret_cast<const unsigned *>(inmask + gp) : 0x01010101u;
                     g[j] = make_int4(0, 0, 0, 0);
-                    if (white) g[j] = *reinterpret_cast<const int4 *>(G + gp);
+                    if (load_g) g[j] = *reinterpret_cast<const int4 *>(G + gp);
                 }
                 unsigned out[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -148,6 +191,7 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
                         out[j] |= (unsigned)decide(y, x + u, gp + u, m, gv[u]) << (8 * u);
                     }
                     *reinterpret_cast<unsigned *>(dmask + t.pix_off + (long long)y * t.w + x) = out[j];
+                    nz += __popc(out[j]);
                 }
                 uint4 o;   // column c of the block: byte c of every row
                 unsigned *ov = &o.x;
@@ -157,6 +201,7 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
                             (((out[3] >> (8 * c)) & 0xffu) << 24);
                 *reinterpret_cast<uint4 *>(dmask4 + (long long)t.m4_off + (long long)q * t.w + x) = o;
             }
+        store_count();
         return;
     }
     for (int y = blockIdx.x; y < t.h; y += gridDim.x)
@@ -170,7 +215,8 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
             if (x < t.w) {
                 const long long gp = (long long)(t.y0 + y) * Wr + t.x0 + x;
                 mv[u] = inmask ? (inmask[gp] != 0) : 1;
-                if (white && !in_corner(t, y, x)) gv[u] = G[gp];   // (outside the burned square => not wholly inside it: the segment is selected)
+                // (outside the burned square => not wholly inside it: the segment is selected; a pixel in a clear block has g = 0)
+                if (white && !in_corner(t, y, x) && occ_test(occ, occ_bw, t.y0 + y, t.x0 + x)) gv[u] = G[gp];
             }
         }
 #pragma unroll
@@ -178,9 +224,12 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
             const int x = x0 + 256 * u;
             if (x >= t.w) continue;
             const long long gp = (long long)(t.y0 + y) * Wr + t.x0 + x;
-            dmask[t.pix_off + (long long)y * t.w + x] = decide(y, x, gp, mv[u], gv[u]);
+            const uint8_t m = decide(y, x, gp, mv[u], gv[u]);
+            dmask[t.pix_off + (long long)y * t.w + x] = m;
+            nz += m;
         }
     }
+    store_count();
 }
 
 // step 3: write the new segments of the batch into G with their provisional global ids + size histogram.
@@ -190,7 +239,7 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
 constexpr int TS_SLOTS = 128;
 __global__ __launch_bounds__(64) void tile_scatter_kernel(const TileWin *__restrict__ wins, const CcResolve R,
                                                           int32_t *__restrict__ G, int Wr, int id_base,
-                                                          unsigned *__restrict__ seg_size) {
+                                                          unsigned *__restrict__ seg_size, unsigned *__restrict__ occ, int occ_bw) {
     __shared__ int s_key[TS_SLOTS];
     __shared__ unsigned s_cnt[TS_SLOTS];
     const TileWin t = wins[blockIdx.y];
@@ -218,25 +267,61 @@ __global__ __launch_bounds__(64) void tile_scatter_kernel(const TileWin *__restr
         if (slot >= 0) atomicAdd(&s_cnt[slot], rn);
         else atomicAdd(&seg_size[rid], rn);          // table full: straight to global memory
     };
+    // the workgroup's 64 x 64 pixels meet at most 2 x 2 blocks of the occupancy map: y_split is the window row where the second
+    // block row starts, wrote0 / wrote1 say that this lane stored an id in the first / second block row
+    const int rb0 = (t.y0 + y_lo) >> OCC_SHIFT;
+    const int y_split = ((rb0 + 1) << OCC_SHIFT) - t.y0;
+    bool wrote0 = false, wrote1 = false;
+    // The label of the pixel's component is resolved here (the connectivity pass hands over its tables instead of a label map), and
+    // it depends on the pixel's parent alone: the parents of the eight rows are loaded (coalesced), the two or three gathers behind
+    // them are made only where the parent differs from the one above in the column, every other pixel takes the label above.
+    int p_above = -1, l_above = R.mask_label;   // (every negative parent is a masked pixel: mask_label)
 #pragma unroll 1
     for (int y0 = y_lo; y0 < y_hi; y0 += 8) {       // eight rows in flight
-        int l[8];
+        int par[8], l[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int y = y0 + j;
-            // (the label of the pixel's component, resolved here: the connectivity pass hands over its tables instead of a label map)
-            l[j] = (col_ok && y < y_hi) ? cc_resolve_label(R, t.pix_off + (long long)y * t.w + x) : 0;
+            par[j] = (col_ok && y < y_hi) ? R.parent[t.pix_off + (long long)y * t.w + x] : -1;
+        }
+        unsigned fresh = 0;   // bit j: row j starts a run of parents
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            l[j] = R.mask_label;
+            if (par[j] >= 0 && par[j] != (j ? par[j - 1] : p_above)) { l[j] = cc_resolve_parent(R, par[j]); fresh |= 1u << j; }
         }
 #pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (par[j] >= 0 && !((fresh >> j) & 1u)) l[j] = j ? l[j - 1] : l_above;
+        p_above = par[7]; l_above = l[7];
+#pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int y = y0 + j;
-            const int id = l[j] > 0 ? id_base + l[j] : 0;
-            if (id > 0) G[(long long)(t.y0 + y) * Wr + t.x0 + x] = id;
+            const int id = (col_ok && y < y_hi && l[j] > 0) ? id_base + l[j] : 0;
+            if (id > 0) {
+                G[(long long)(t.y0 + y) * Wr + t.x0 + x] = id;
+                if (y >= y_split) wrote1 = true; else wrote0 = true;
+            }
             if (id != rid) { close_run(); rid = id; rn = 0; }
             rn += 1;
         }
     }
     close_run();
+    // the invariant of the occupancy map: a block's bit is set in the kernel that first stores a non-zero label into it (the readers
+    // are later kernels of the stream).  One atomic per workgroup and block, none when the bit is there already.
+    if (occ) {
+        const int cb0 = (t.x0 + bx * 64) >> OCC_SHIFT;
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const bool mine = (r ? wrote1 : wrote0) && ((t.x0 + x) >> OCC_SHIFT) == cb0 + c;
+                if (__ballot(mine) && lane == 0) {
+                    const int b = (rb0 + r) * occ_bw + cb0 + c;
+                    if (!((occ[b >> 5] >> (b & 31)) & 1u)) atomicOr(&occ[b >> 5], 1u << (b & 31));
+                }
+            }
+    }
     __syncthreads();
     for (int i = lane; i < TS_SLOTS; i += 64)
         if (s_key[i] > 0 && s_cnt[i]) atomicAdd(&seg_size[s_key[i]], s_cnt[i]);
@@ -325,6 +410,13 @@ struct TileState {
     const float *img;
     const uint8_t *inmask;
     int32_t *G;
+    // Occupancy map of G (occ_test): one bit per 64 x 64 block, clear = the block holds only zeros.  tile_scatter_kernel sets a
+    // block's bit in the launch that first stores an id into it; tile_mask_kernel only ever stores zeros, so a bit stays set once
+    // it is (conservative).  Only a one-call run (tiled_slic_dev) has the map: there the library zero-fills G and is its only
+    // writer.  A session (obia_tiler_*) runs on a raster the caller owns and writes between calls -- the sharded driver puts imported
+    // seam rows there -- so its map is null, every block counts as occupied and the kernels read all of G.
+    unsigned *occ = nullptr;
+    int occ_bw = 0;        // blocks per row of the map: cdiv(W, 64)
     unsigned *seg_size, *inside;
     uint8_t *alive;
     int *newid;
@@ -485,32 +577,30 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     if (!d_wins || !b.d_windows) return OBIA_E_NOMEM;
     OBIA_TRY(slic_plan_layout(ctx, b));
     OBIA_TRY(ctx->plan.flush(ctx));
-    int *d_tile_any = A.get<int>(np), *d_cnt = A.get<int>(np);
+    // the mask kernel's form and grid: its workgroups leave partial sums of the tiles' valid counts, one slot each (all written)
+    bool vec4 = (S.W % 4 == 0) && (reinterpret_cast<uintptr_t>(S.inmask) % 4 == 0) && (reinterpret_cast<uintptr_t>(S.G) % 16 == 0) &&
+                (reinterpret_cast<uintptr_t>(b.d_mask) % 4 == 0) && (reinterpret_cast<uintptr_t>(d_mask4) % 16 == 0);
+    for (auto &t : wins) vec4 = vec4 && (t.x0 % 4 == 0) && (t.w % 4 == 0) && (t.pix_off % 4 == 0);
+    const int mask_grid = vec4 ? (grid_rows(wins) + 3) / 4 : grid_rows(wins);
+    int *d_tile_any = A.get<int>(np), *d_cnt = A.get<int>((size_t)np * mask_grid);
     if (!d_tile_any || !d_cnt) return OBIA_E_NOMEM;
-    {
-        ClearSet clr(ctx);
-        if (white) {
-            OBIA_TRY(clr.add(S.inside, 0, sizeof(unsigned) * (size_t)S.next_id));
-            OBIA_TRY(clr.add(d_tile_any, 0, sizeof(int) * (size_t)np));
-        }
-        OBIA_TRY(clr.add(d_cnt, 0, sizeof(int) * (size_t)np));   // (slic_count_valid: the tiler always hands slic a mask)
-        OBIA_TRY(clr.flush());
-    }
     if (white) {
-        hipLaunchKernelGGL(tile_count_inside_kernel, dim3(grid_rows(wins), np), dim3(256), 0, ctx->stream, d_wins, S.G, S.W, S.inside, d_tile_any);
+        ClearSet clr(ctx);
+        OBIA_TRY(clr.add(S.inside, 0, sizeof(unsigned) * (size_t)S.next_id));
+        OBIA_TRY(clr.add(d_tile_any, 0, sizeof(int) * (size_t)np));
+        OBIA_TRY(clr.flush());
+        int cblocks = 1;   // the blocks of the occupancy map a window can meet: one more than its own per axis when it is unaligned
+        for (auto &t : wins) cblocks = std::max(cblocks, (cdiv(t.w, 1 << OCC_SHIFT) + 1) * (cdiv(t.h, 1 << OCC_SHIFT) + 1));
+        hipLaunchKernelGGL(tile_count_inside_kernel, dim3(cblocks, np), dim3(256), 0, ctx->stream, d_wins, S.G, S.W, S.inside, d_tile_any, S.occ,
+                           S.occ_bw);
     }
-    {
-        bool vec4 = (S.W % 4 == 0) && (reinterpret_cast<uintptr_t>(S.inmask) % 4 == 0) && (reinterpret_cast<uintptr_t>(S.G) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(b.d_mask) % 4 == 0) && (reinterpret_cast<uintptr_t>(d_mask4) % 16 == 0);
-        for (auto &t : wins) vec4 = vec4 && (t.x0 % 4 == 0) && (t.w % 4 == 0) && (t.pix_off % 4 == 0);
-        if (vec4) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tile_mask_kernel<true>), dim3((grid_rows(wins) + 3) / 4, np), dim3(256), 0, ctx->stream, d_wins, S.inmask,
-                               S.G, S.W, white ? 1 : 0, S.inside, S.seg_size, S.alive, b.d_mask, d_tile_any, d_mask4);
-            b.d_mask4 = d_mask4;   // (slic_run_sweeps packs the mask itself when nobody did)
-        } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(tile_mask_kernel<false>), dim3(grid_rows(wins), np), dim3(256), 0, ctx->stream, d_wins, S.inmask,
-                               S.G, S.W, white ? 1 : 0, S.inside, S.seg_size, S.alive, b.d_mask, d_tile_any, d_mask4);
-        }
+    if (vec4) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tile_mask_kernel<true>), dim3(mask_grid, np), dim3(256), 0, ctx->stream, d_wins, S.inmask,
+                           S.G, S.W, white ? 1 : 0, S.inside, S.seg_size, S.alive, b.d_mask, d_tile_any, d_mask4, S.occ, S.occ_bw, d_cnt);
+        b.d_mask4 = d_mask4;   // (slic_run_sweeps packs the mask itself when nobody did)
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tile_mask_kernel<false>), dim3(mask_grid, np), dim3(256), 0, ctx->stream, d_wins, S.inmask,
+                           S.G, S.W, white ? 1 : 0, S.inside, S.seg_size, S.alive, b.d_mask, d_tile_any, d_mask4, S.occ, S.occ_bw, d_cnt);
     }
     // per-tile normalisation of every band (create_segments normalises the tile it is given, :32-33)
     std::vector<int> skip;
@@ -524,7 +614,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
     }
     std::vector<int> nvalid;
     debug_sync(ctx, "tiler: mask + features");
-    OBIA_TRY(slic_count_valid(ctx, b, nvalid, d_cnt));
+    OBIA_TRY(slic_count_valid(ctx, b, nvalid, d_cnt, mask_grid));   // (the mask kernel counted what it wrote: the read-back and the partial sums' sum)
     debug_sync(ctx, "tiler: count_valid");
     std::vector<int> nseg(np);
     const double pixel_area = S.tp.pixel_width * S.tp.pixel_height;
@@ -580,7 +670,7 @@ static int run_tile_batch(obia_ctx *ctx, TileState &S, std::vector<TileWin> &win
         int sblocks = 1;
         for (auto &t : wins) sblocks = std::max(sblocks, cdiv(t.w, 64) * cdiv(t.h, 64));
         hipLaunchKernelGGL(tile_scatter_kernel, dim3(sblocks, np), dim3(64), 0, ctx->stream, d_wins, resolve, S.G, S.W,
-                           S.next_id - 1, S.seg_size);
+                           S.next_id - 1, S.seg_size, S.occ, S.occ_bw);
         OBIA_TRY(fill_async(ctx, S.alive + S.next_id, 1, (size_t)n_new));
         S.next_id += n_new;
     }
@@ -697,7 +787,8 @@ static int tiler_check(const float *img, int H, int W, int C, int Hg, int row0, 
 }
 
 static int tiler_init(obia_ctx *ctx, TileState &S, const float *img, const uint8_t *mask, int H, int W, int C, int Hg,
-                      int row0, const obia_tiling_params *tp, const obia_slic_params *sp, int32_t *labels, int extra_ids) {
+                      int row0, const obia_tiling_params *tp, const obia_slic_params *sp, int32_t *labels, int extra_ids,
+                      bool occupancy = false) {   // occupancy: the caller zero-fills `labels` and nobody else writes it (TileState::occ)
     OBIA_TRY(tiler_check(img, H, W, C, Hg, row0, tp, sp, labels));
     const int T = tp->tile_size, B = tp->buffer;
     Arena &A = ctx->arena;
@@ -724,6 +815,14 @@ static int tiler_init(obia_ctx *ctx, TileState &S, const float *img, const uint8
     if (!S.seg_size || !S.inside || !S.alive || !S.newid || !S.d_total) return OBIA_E_NOMEM;
     OBIA_TRY(fill_async(ctx, S.seg_size, 0, sizeof(unsigned) * (size_t)cap));
     OBIA_TRY(fill_async(ctx, S.alive, 0, (size_t)cap));
+    S.occ = nullptr;
+    S.occ_bw = cdiv(W, 1 << OCC_SHIFT);
+    if (occupancy) {
+        const size_t words = ((size_t)S.occ_bw * (size_t)cdiv(H, 1 << OCC_SHIFT) + 31) / 32;
+        S.occ = A.get<unsigned>(words);
+        if (!S.occ) return OBIA_E_NOMEM;
+        OBIA_TRY(fill_async(ctx, S.occ, 0, sizeof(unsigned) * words));
+    }
     // corner squares: side buffer/2 in MAP units (tiling.py:189), i.e. buffer/2/pixel_size pixels; a pixel is
     // inside when its centre is (rasterize default all_touched=False)
     S.clx = S.cly = S.clx_in = S.cly_in = S.clx_any = S.cly_any = 0;
@@ -905,7 +1004,9 @@ static int tiled_slic_dev(obia_ctx *ctx, const float *img, const uint8_t *mask, 
                           int32_t *labels_out, int64_t *n_segments_out) {
     TileState S;
     OBIA_TRY(check_seeding(seeding, picks));
-    OBIA_TRY(tiler_init(ctx, S, img, mask, H, W, C, H, 0, tp, sp, labels_out, 0));
+    // OBIA_G_OCCUPANCY=0 (developer switch, read once per call): no occupancy map, the label passes read every block of the raster
+    const char *occ_env = std::getenv("OBIA_G_OCCUPANCY");
+    OBIA_TRY(tiler_init(ctx, S, img, mask, H, W, C, H, 0, tp, sp, labels_out, 0, !(occ_env && occ_env[0] == '0')));
     S.seeding = seeding; S.pick_fn = picks; S.pick_user = picks_user;
     OBIA_TRY(fill_async(ctx, labels_out, 0, sizeof(int32_t) * (size_t)H * W));
     const int nty = cdiv(H, tp->tile_size);
