@@ -105,6 +105,23 @@ int obia_test_poison_workspace_dev(obia_ctx *ctx, int64_t reserve_bytes, int byt
  * streams and counts.  Reads only, so a context held by a session is served.  OBIA_E_INVALID for a null context or output.       */
 int obia_test_visited_nonzero(obia_ctx *ctx, int64_t *visited_nonzero_out);
 
+/* One primitive of obia_amd/csrc/wave_ops.hpp -- the integer sums, prefix sums and ranks every kernel of the library shares -- on n
+ * int32 values in device memory, with `nt` threads per workgroup; waits.  `op`:
+ *   0  workgroup_exclusive_scan, int32 -> int32 IN PLACE, int64 total        nt 1024
+ *   1  workgroup_exclusive_scan, int32 -> int32 out of place, int32 total    nt 1024
+ *   2  workgroup_exclusive_scan, int32 -> int64                              nt 256, 1024
+ *   3  block_exclusive_scan                                                  nt 256, 1024
+ *   4  block_sum (every thread's result is its workgroup's sum)              nt 256, 1024
+ *   5  block_flag_rank of in[i] != 0                                         nt 256
+ *   6  block_exclusive_scan of in[i], then at once of in[i] + 1: the second  nt 256, 1024
+ * Ops 0 .. 2 run ONE workgroup: out[i] = in[0] + ... + in[i - 1], totals_out[0] = the sum (n = 0 writes only that).  Ops 3 .. 6 run
+ * ceil(n / nt) workgroups, workgroup g on in[g * nt ..): out[i] = the result of element i's thread, totals_out[g] = the total the
+ * primitive hands back (the last workgroup may be partial: its spare threads take part with nothing; n = 0 writes nothing).
+ * Results are widened to int64: out holds n, totals_out one per workgroup.  No workspace is taken.
+ * The (op, nt) pairs served are EXACTLY the instantiations the library's own kernels use, as listed above: another nt, or another
+ * op, is OBIA_E_INVALID, and so are a null or misaligned buffer, out == totals_out and a negative n.                            */
+int obia_test_wave_ops_dev(obia_ctx *ctx, int op, int nt, const int32_t *in, int64_t n, int64_t *out, int64_t *totals_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -276,6 +276,8 @@ _TEST_SIGNATURES = {
     # (tests/test_gpu_workspace_history.py)
     "obia_test_poison_workspace_dev": (_I, [_P, ctypes.c_int64, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "obia_test_visited_nonzero": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    # the wave and workgroup primitives of obia_amd/csrc/wave_ops.hpp, one at a time (tests/test_gpu_wave_ops.py)
+    "obia_test_wave_ops_dev": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, _P]),
 }
 
 # The registry: one table per header of include/, in the order load() binds them.  Everything that enumerates the entry points -- load(),

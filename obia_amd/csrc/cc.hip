@@ -17,6 +17,7 @@
 //     region and starts another capped BFS from there.  Such components are rare; one lane replays each of them
 //     (cc_split_kernel) and rewrites parent / size so that every piece is a component of its own for the stages below.
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 #include <cstdlib>
 
@@ -243,7 +244,6 @@ __global__ __launch_bounds__(SCAN_NT) void cc_rank_blocksum_kernel(const CcProbl
                                                                    long long n, int *__restrict__ block_sums,
                                                                    int *__restrict__ counters /*[0]=n_small [1]=small_px*/,
                                                                    const unsigned long long *__restrict__ rootbits /* null: test parent[] */) {
-    __shared__ int s_w[SCAN_NT / 64], s_ws[SCAN_NT / 64], s_wp[SCAN_NT / 64];
     const long long base = (long long)blockIdx.x * SCAN_CHUNK;
     int c = 0, nsmall = 0, spx = 0, nbig = 0;
     for (int j = 0; j < SCAN_PER; ++j) {
@@ -257,21 +257,16 @@ __global__ __launch_bounds__(SCAN_NT) void cc_rank_blocksum_kernel(const CcProbl
             if (sz >= P.max_size && sz > 1) nbig += 1;   // reaches max_size: the reference cuts it (cc_split_kernel)
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        c += __shfl_xor(c, off); nsmall += __shfl_xor(nsmall, off); spx += __shfl_xor(spx, off); nbig += __shfl_xor(nbig, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_w[threadIdx.x >> 6] = c; s_ws[threadIdx.x >> 6] = nsmall; s_wp[threadIdx.x >> 6] = spx;
-        if (nbig) atomicAdd(&counters[6], nbig);
-    }
-    __syncthreads();
+    nbig = wave_sum(nbig);
+    if ((threadIdx.x & 63) == 0 && nbig) atomicAdd(&counters[6], nbig);
     // three sums per block, scanned by cc_rank_scan_kernel: survivors | small components | pixels of small components.  (Small
     // components used to take their list slot and queue range with two global atomics EACH on two words: with the fragmented
     // label maps of a low compactness -- millions of small components -- that was 24 ms of a 95-ms step.)
+    c = block_sum<SCAN_NT>(c); nsmall = block_sum<SCAN_NT>(nsmall); spx = block_sum<SCAN_NT>(spx);
     if (threadIdx.x == 0) {
-        block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        block_sums[gridDim.x + blockIdx.x] = s_ws[0] + s_ws[1] + s_ws[2] + s_ws[3];
-        block_sums[2 * gridDim.x + blockIdx.x] = s_wp[0] + s_wp[1] + s_wp[2] + s_wp[3];
+        block_sums[blockIdx.x] = c;
+        block_sums[gridDim.x + blockIdx.x] = nsmall;
+        block_sums[2 * gridDim.x + blockIdx.x] = spx;
     }
 }
 
@@ -383,10 +378,7 @@ __global__ __launch_bounds__(64) void cc_rank_blocksum_bits_kernel(const CcProbl
         else { nsmall += 1; spx += sz; }
         if (sz >= P.max_size && sz > 1) nbig += 1;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        c += __shfl_xor(c, off); nsmall += __shfl_xor(nsmall, off); spx += __shfl_xor(spx, off); nbig += __shfl_xor(nbig, off);
-    }
+    c = wave_sum(c); nsmall = wave_sum(nsmall); spx = wave_sum(spx); nbig = wave_sum(nbig);
     if (lane == 0) {
         block_sums[blockIdx.x] = c;
         block_sums[gridDim.x + blockIdx.x] = nsmall;
@@ -411,12 +403,7 @@ __global__ __launch_bounds__(64) void cc_rank_apply_bits_kernel(const CcProblem 
         if (sz >= probs[find_prob(probs, nprob, i)].min_size) c += 1;
         else { ns += 1; px += sz; }
     }
-    int pc = c, pn = ns, pp = px;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int tc = __shfl_up(pc, off), tn = __shfl_up(pn, off), tp = __shfl_up(pp, off);
-        if (lane >= off) { pc += tc; pn += tn; pp += tp; }
-    }
+    const int pc = wave_inclusive_scan(c), pn = wave_inclusive_scan(ns), pp = wave_inclusive_scan(px);
     int run = block_sums[blockIdx.x] + pc - c, srun = block_sums[gridDim.x + blockIdx.x] + pn - ns,
         prun = block_sums[2 * gridDim.x + blockIdx.x] + pp - px;
     for (unsigned long long bits = word; bits; bits &= bits - 1) {
@@ -434,31 +421,12 @@ __global__ __launch_bounds__(64) void cc_rank_apply_bits_kernel(const CcProblem 
 }
 
 // exclusive scan of block_sums in place, single workgroup; total -> counters[2]
-__global__ __launch_bounds__(1024) void cc_rank_scan_kernel(int *__restrict__ block_sums_all, int nb, int *__restrict__ counters) {
-    __shared__ int s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = tid * per, hi = min(lo + per, nb);
+__global__ __launch_bounds__(1024) void cc_rank_scan_kernel(int *block_sums_all, int nb, int *__restrict__ counters) {
     // segment 0: survivors -> counters[2]; 1: small components -> counters[0]; 2: their pixels -> counters[1]
     // (one workgroup per segment: grid = 3)
-    {
-        const int seg = blockIdx.x;
-        int *block_sums = block_sums_all + (size_t)seg * nb;
-        int s = 0;
-        for (int i = lo; i < hi; ++i) s += block_sums[i];
-        s_part[tid] = s;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            int v = (tid >= off) ? s_part[tid - off] : 0;
-            __syncthreads();
-            s_part[tid] += v;
-            __syncthreads();
-        }
-        int run = s_part[tid] - s;
-        for (int i = lo; i < hi; ++i) { const int v = block_sums[i]; block_sums[i] = run; run += v; }
-        if (tid == 1023) counters[seg == 0 ? 2 : seg - 1] = s_part[1023];
-        __syncthreads();
-    }
+    const int seg = blockIdx.x;
+    int *block_sums = block_sums_all + (size_t)seg * nb;
+    workgroup_exclusive_scan<1024>(block_sums, block_sums, nb, &counters[seg == 0 ? 2 : seg - 1]);
 }
 
 // newlab[root] = rank (>= 0) for survivors, -(index+2) for small components (collected in small_list)
@@ -492,10 +460,7 @@ __global__ __launch_bounds__(SCAN_NT) void cc_rank_apply_kernel(const CcProblem 
         const unsigned long long bal = __ballot(flag), sbal = __ballot(small);
         // pixels of the small components in front of this lane inside the wave (inclusive scan by shuffles, then exclusive)
         int pin = small ? sz : 0;
-        if (sbal) {   // wave-uniform
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(pin, off); if (lane >= off) pin += t; }
-        }
+        if (sbal) pin = wave_inclusive_scan(pin);   // wave-uniform
         if (lane == 63) s_wp[wv] = pin;
         if (lane == 0) { s_w[wv] = __popcll(bal); s_ws[wv] = __popcll(sbal); }
         __syncthreads();
@@ -503,9 +468,9 @@ __global__ __launch_bounds__(SCAN_NT) void cc_rank_apply_kernel(const CcProblem 
         for (int w = 0; w < wv; ++w) { before += s_w[w]; sbefore += s_ws[w]; pbefore += s_wp[w]; }
         const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
         const int stotal = s_ws[0] + s_ws[1] + s_ws[2] + s_ws[3], ptotal = s_wp[0] + s_wp[1] + s_wp[2] + s_wp[3];
-        if (flag) newlab[i] = s_run + before + __popcll(bal & ((1ull << lane) - 1ull));
+        if (flag) newlab[i] = s_run + before + lanes_below(bal);
         if (small) {   // slots and queue ranges in raster order of the roots: no atomics
-            const int idx = s_srun + sbefore + __popcll(sbal & ((1ull << lane) - 1ull));
+            const int idx = s_srun + sbefore + lanes_below(sbal);
             small_list[idx] = (int)i;
             small_qoff[idx] = s_prun + pbefore + pin - sz;
             newlab[i] = -(idx + 2);
@@ -708,9 +673,7 @@ __global__ __launch_bounds__(64) void cc_small_bfs_kernel(const CcProblem *__res
         npush = small_component_eval<CODE>(probs, nprob, code, newlab, small_list, small_qoff, start_label, settle, queue, out, target,
                                      work_in, i, work_out, work_cnt, tag, round, s_push);
     // inclusive prefix of the lanes' counts, one atomic for the wave
-    int inc = npush;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if ((int)threadIdx.x >= off) inc += v; }
+    const int inc = wave_inclusive_scan(npush);
     const int total = __shfl(inc, 63);
     if (total == 0) return;
     int base_slot = 0;
@@ -836,9 +799,7 @@ __global__ __launch_bounds__(64) void cc_settle_eval_kernel(const int *__restric
         }
     }
     // inclusive prefix of the lanes' counts, one atomic for the wave
-    int inc = npush;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if ((int)threadIdx.x >= off) inc += v; }
+    const int inc = wave_inclusive_scan(npush);
     const int total = __shfl(inc, 63);
     if (total == 0) return;
     int base_slot = 0;

@@ -3,6 +3,7 @@
 //   forest_predict: the per-row loop of classify.py:135-158 (predict_proba / predict, class filter, margin) for all rows at once
 // Training stays scikit-learn on the host.  Exactness contract: DESIGN.md 3.5g.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -70,8 +71,7 @@ __global__ __launch_bounds__(64) void scale_mean_kernel(const double *__restrict
         n += pcnt[(long long)b * F + c];
     }
     s = wave_sum_fixed(s);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    n = wave_sum(n);
     if (l == 0) {
         mean[c] = s / (double)n;          // 0 / 0 = NaN for an all-NaN column, as np.nansum(x) / 0 gives
         cnt[c] = n;

@@ -4,6 +4,7 @@
 //   sample_labels: the point-in-segment join of `label_segments` (obia/utils/utils.py:12-34, geopandas sjoin with
 //                  predicate "intersects") on a label raster: map coordinates -> inverse affine -> pixel -> label
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 namespace obia {
 
@@ -36,15 +37,8 @@ __global__ __launch_bounds__(256) void label_edges_kernel(const int32_t *__restr
         }
     }
     // one atomic per workgroup (same-word global atomics serialise device-wide)
-    __shared__ unsigned s_c[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-        if (t) atomicAdd(n_edge, (unsigned long long)t);
-    }
+    cnt = block_sum<256>(cnt);
+    if (threadIdx.x == 0 && cnt) atomicAdd(n_edge, (unsigned long long)cnt);
 }
 
 // inv = [a, b, d, e, xoff, yoff] of the INVERSE transform: col = a*X + b*Y + xoff, row = d*X + e*Y + yoff (pixel-corner

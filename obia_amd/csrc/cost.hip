@@ -9,6 +9,7 @@
 // Every stage restates the reference's arithmetic operation for operation (the library is built with -ffp-contract=off);
 // the percentile interpolation itself runs on the host from the order statistics select returns.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -509,15 +510,8 @@ __global__ __launch_bounds__(256) void cost_edge_count_kernel(const int32_t *__r
     unsigned cnt = 0;
     for (int y = blockIdx.y; y < H; y += gridDim.y)
         for (int x = blockIdx.x * 256 + threadIdx.x; x < W; x += gridDim.x * 256) cnt += is_edge(lab, H, W, y, x, (long long)y * W + x);
-    __shared__ unsigned s_c[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-        if (t) atomicAdd(n_edge, (unsigned long long)t);
-    }
+    cnt = block_sum<256>(cnt);
+    if (threadIdx.x == 0 && cnt) atomicAdd(n_edge, (unsigned long long)cnt);
 }
 
 struct CombineArgs {

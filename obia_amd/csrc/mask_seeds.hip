@@ -14,6 +14,7 @@
 //     root needs computing only when the square is below the best square so far -- same index in every case, no K x K roots.
 // No K x K matrix and no (n_valid, 3) coordinate table are stored.
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,39 +28,16 @@ constexpr int MS_CHUNK = OBIA_MASK_SEEDS_CHUNK;   // centroids staged in LDS at 
 // ---- rank -> coordinate ---------------------------------------------------------------------------------------------------------
 // valid pixels of each mask row
 __global__ __launch_bounds__(MS_THREADS) void ms_row_count_kernel(const uint8_t *__restrict__ mask, int W, int *__restrict__ rowcnt) {
-    __shared__ int part[MS_THREADS / 64];
     const uint8_t *row = mask + (size_t)blockIdx.x * W;
     int c = 0;
     for (int x = threadIdx.x; x < W; x += MS_THREADS) c += row[x] != 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    c = block_sum<MS_THREADS>(c);
+    if (threadIdx.x == 0) rowcnt[blockIdx.x] = c;
 }
 
 // exclusive prefix over the rows (one workgroup): rowoff[r] = rank of row r's first valid pixel, rowoff[H] = n_valid
 __global__ __launch_bounds__(1024) void ms_row_scan_kernel(const int *__restrict__ rowcnt, int H, long long *__restrict__ rowoff) {
-    __shared__ long long s[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int r0 = 0; r0 < H; r0 += 1024) {
-        const int r = r0 + (int)threadIdx.x;
-        const long long v = r < H ? rowcnt[r] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const long long t = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0;
-            __syncthreads();
-            s[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (r < H) rowoff[r] = carry + s[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += s[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) rowoff[H] = carry;
+    workgroup_exclusive_scan<1024>(rowcnt, rowoff, H, rowoff + H);
 }
 
 // One workgroup per mask row: the rank of every valid pixel (row offset + prefix inside the row); a pixel whose rank is picks[j]
@@ -67,26 +45,16 @@ __global__ __launch_bounds__(1024) void ms_row_scan_kernel(const int *__restrict
 __global__ __launch_bounds__(MS_THREADS) void ms_gather_kernel(const uint8_t *__restrict__ mask, int W, const long long *__restrict__ rowoff,
                                                                const long long *__restrict__ picks, long long n_picks,
                                                                int2 *__restrict__ out) {
-    __shared__ int wave_cnt[MS_THREADS / 64];
     const int y = blockIdx.x;
     const long long first = rowoff[y];
     if (rowoff[y + 1] == first) return;   // (uniform over the workgroup) no valid pixel in this row
     const uint8_t *row = mask + (size_t)y * W;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long base = first;
     for (int x0 = 0; x0 < W; x0 += MS_THREADS) {
         const int x = x0 + (int)threadIdx.x;
         const bool v = x < W && row[x] != 0;
-        const unsigned long long b = __ballot(v);
-        if (lane == 0) wave_cnt[wave] = __popcll(b);
-        __syncthreads();
-        // set bits of the ballot below this lane (mbcnt: no 64-bit shift by a register, tools/check_shift64.py)
-        int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u)), total = 0;
-        for (int w = 0; w < MS_THREADS / 64; ++w) {
-            const int c = wave_cnt[w];
-            if (w < wave) before += c;
-            total += c;
-        }
+        int total;
+        const int before = block_flag_rank<MS_THREADS>(v, total);
         if (v) {
             const long long rank = base + before;
             if (!picks) {
@@ -101,7 +69,6 @@ __global__ __launch_bounds__(MS_THREADS) void ms_gather_kernel(const uint8_t *__
             }
         }
         base += total;
-        __syncthreads();
     }
 }
 

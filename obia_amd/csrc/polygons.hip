@@ -18,71 +18,37 @@
 // corner of the raster, first vertex repeated at the end; rings come out in raster order of their smallest corner.
 // The host applies the affine transform and groups rings by label (obia_amd/polygons.py).
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 namespace obia {
 
 // ---- ordered compaction helpers: exclusive scan of int32 values, 4096 per workgroup ---------------------------------
 constexpr int PS_NT = 256, PS_PER = 16, PS_CHUNK = PS_NT * PS_PER;
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int *s_wave, int &block_total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < PS_NT / 64; ++w) { if (w < wv) before += s_wave[w]; tot += s_wave[w]; }
-    block_total = tot;
-    __syncthreads();
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(PS_NT) void scan_blocksum_kernel(const int *__restrict__ in, long long n, int *__restrict__ sums) {
-    __shared__ int s_wave[PS_NT / 64];
     const long long base = (long long)blockIdx.x * PS_CHUNK;
     int c = 0;
     for (int j = 0; j < PS_PER; ++j) {
         const long long i = base + (long long)j * PS_NT + threadIdx.x;
         if (i < n) c += in[i];
     }
-    int tot;
-    (void)block_exclusive_scan(c, s_wave, tot);
+    const int tot = block_sum<PS_NT>(c);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
 // exclusive scan of the block sums in place, one workgroup; grand total -> *total
-__global__ __launch_bounds__(1024) void scan_sums_kernel(int *__restrict__ sums, int nb, long long *__restrict__ total) {
-    __shared__ long long s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = tid * per, hi = min(nb, lo + per);
-    long long t = 0;
-    for (int i = lo; i < hi; ++i) t += sums[i];
-    s_part[tid] = t;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int i = 0; i < 1024; ++i) { const long long v = s_part[i]; s_part[i] = run; run += v; }
-        *total = run;
-    }
-    __syncthreads();
-    long long run = s_part[tid];
-    for (int i = lo; i < hi; ++i) { const int v = sums[i]; sums[i] = (int)run; run += v; }
+__global__ __launch_bounds__(1024) void scan_sums_kernel(int *sums, int nb, long long *__restrict__ total) {
+    workgroup_exclusive_scan<1024>(sums, sums, nb, total);
 }
 
 __global__ __launch_bounds__(PS_NT) void scan_apply_kernel(const int *__restrict__ in, long long n, const int *__restrict__ sums,
                                                            int *__restrict__ out) {
-    __shared__ int s_wave[PS_NT / 64];
     const long long base = (long long)blockIdx.x * PS_CHUNK + (long long)threadIdx.x * PS_PER;   // 16 consecutive values per lane
     int v[PS_PER], c = 0;
 #pragma unroll
     for (int j = 0; j < PS_PER; ++j) { v[j] = (base + j < n) ? in[base + j] : 0; c += v[j]; }
     int tot;
-    int run = sums[blockIdx.x] + block_exclusive_scan(c, s_wave, tot);
+    int run = sums[blockIdx.x] + block_exclusive_scan<PS_NT>(c, tot);
 #pragma unroll
     for (int j = 0; j < PS_PER; ++j) { if (base + j < n) out[base + j] = run; run += v[j]; }
 }

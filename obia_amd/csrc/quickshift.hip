@@ -12,6 +12,7 @@
 // neighbourhood of a tile does not fit the LDS (more than 4 bands, or a window wider than the staged one) the same
 // arithmetic runs on the channel planes in global memory (qs_density_parent_global_kernel).
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -229,58 +230,29 @@ __global__ void qs_jump_kernel(const int *__restrict__ pin, int *__restrict__ po
 // labels = np.unique(roots, return_inverse=True)[1]: rank of each root among the roots in ascending pixel order
 constexpr int QS_CHUNK = 4096;
 __global__ __launch_bounds__(256) void qs_rootcount_kernel(const int *__restrict__ parent, long long n, int *__restrict__ block_sums) {
-    __shared__ int s_w[4];
     const long long base = (long long)blockIdx.x * QS_CHUNK;
     int c = 0;
     for (int j = 0; j < QS_CHUNK / 256; ++j) {
         const long long i = base + (long long)j * 256 + threadIdx.x;
         c += (i < n && parent[i] == (int)i);
     }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    c = block_sum<256>(c);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = c;
 }
-__global__ __launch_bounds__(1024) void qs_scan_kernel(int *__restrict__ block_sums, int nb, int *__restrict__ total) {
-    __shared__ int s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = tid * per, hi = min(lo + per, nb);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += block_sums[i];
-    s_part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = (tid >= off) ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int run = s_part[tid] - s;
-    for (int i = lo; i < hi; ++i) { const int v = block_sums[i]; block_sums[i] = run; run += v; }
-    if (tid == 1023) *total = s_part[1023];
+__global__ __launch_bounds__(1024) void qs_scan_kernel(int *block_sums, int nb, int *__restrict__ total) {
+    workgroup_exclusive_scan<1024>(block_sums, block_sums, nb, total);
 }
 __global__ __launch_bounds__(256) void qs_rootrank_kernel(const int *__restrict__ parent, long long n, const int *__restrict__ block_sums,
                                                           int *__restrict__ rank) {
-    __shared__ int s_w[4];
-    __shared__ int s_run;
     const long long base = (long long)blockIdx.x * QS_CHUNK;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_run = block_sums[blockIdx.x];
-    __syncthreads();
+    int run = block_sums[blockIdx.x];   // roots before this pass of the workgroup: the same in every thread
     for (int j = 0; j < QS_CHUNK / 256; ++j) {
         const long long i = base + (long long)j * 256 + threadIdx.x;
         const bool flag = i < n && parent[i] == (int)i;
-        const unsigned long long bal = __ballot(flag);
-        if (lane == 0) s_w[wv] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; ++w) before += s_w[w];
-        if (flag) rank[i] = s_run + before + __popcll(bal & ((1ull << lane) - 1ull));
-        const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
-        if (threadIdx.x == 0) s_run += total;
-        __syncthreads();
+        int total;
+        const int before = block_flag_rank<256>(flag, total);
+        if (flag) rank[i] = run + before;
+        run += total;
     }
 }
 __global__ void qs_labels_kernel(const int *__restrict__ parent, const int *__restrict__ rank, long long n, int32_t *__restrict__ labels) {

@@ -8,6 +8,7 @@
 // Deviation: a NaN never wins the maximum filter and a NaN pixel is never a peak (scipy's answer near a NaN depends on the side
 // the NaN is on); DESIGN.md 5.
 #include "slic.hpp"
+#include "wave_ops.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -96,49 +97,15 @@ __device__ __forceinline__ int flags16(const uint8_t *flags, long long chunk, ui
     return __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
 }
 
-// exclusive prefix of `v` over the 256 threads of the block; *total = the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int *total) {
-    __shared__ int s_w[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < wv; ++k) base += s_w[k];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(256) void seeds_count_kernel(const uint8_t *__restrict__ flags, int *__restrict__ counts) {
     uint4 q;
-    int total;
-    block_excl_scan(flags16(flags, blockIdx.x, q), &total);
+    const int total = block_sum<256>(flags16(flags, blockIdx.x, q));
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // exclusive scan of m ints by one workgroup: out[0 .. m), out[m] = the sum
 __global__ __launch_bounds__(1024) void seeds_scan_kernel(const int *__restrict__ in, int *__restrict__ out, int m) {
-    __shared__ int s_part[1024];
-    const int per = (m + 1023) / 1024;
-    const int a = min(m, (int)threadIdx.x * per), b = min(m, a + per);
-    int s = 0;
-    for (int i = a; i < b; ++i) s += in[i];
-    s_part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < 1024; ++i) { const int v = s_part[i]; s_part[i] = run; run += v; }
-        out[m] = run;
-    }
-    __syncthreads();
-    int run = s_part[threadIdx.x];
-    for (int i = a; i < b; ++i) { const int v = in[i]; out[i] = run; run += v; }
+    workgroup_exclusive_scan<1024>(in, out, m, out + m);
 }
 
 __global__ __launch_bounds__(256) void seeds_scatter_kernel(const uint8_t *__restrict__ flags, const int *__restrict__ offsets,
@@ -148,7 +115,7 @@ __global__ __launch_bounds__(256) void seeds_scatter_kernel(const uint8_t *__res
     uint4 q;
     int total;
     const int c = flags16(flags, blockIdx.x, q);
-    int o = offsets[blockIdx.x] + block_excl_scan(c, &total);
+    int o = offsets[blockIdx.x] + block_exclusive_scan<256>(c, total);
     if (c == 0) return;
     const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
     const long long base = (long long)blockIdx.x * CHUNK + threadIdx.x * 16;

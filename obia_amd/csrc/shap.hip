@@ -10,6 +10,7 @@
 //   shap_main   : lanes = path elements, a wave packs floor(64 / (m + 1)) rows of the SAME path side by side
 // Everything is float64, there is no floating-point atomic, and the order of all additions is fixed by the forest alone.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -169,29 +170,7 @@ __global__ __launch_bounds__(64) void shap_path_kernel(const double *__restrict_
 // Exclusive prefix sum of n int32 counts into int64 (one workgroup: thread t owns a contiguous chunk) and their total.
 __global__ __launch_bounds__(256) void shap_scan_kernel(const int32_t *__restrict__ in, long long n, long long *__restrict__ out,
                                                         long long *__restrict__ total_out) {
-    __shared__ long long part[256];
-    const int tid = threadIdx.x;
-    const long long chunk = (n + 255) / 256;
-    const long long lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    long long s = 0;
-    for (long long i = lo; i < hi; ++i) s += in[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < 256; ++t) {
-            const long long v = part[t];
-            part[t] = run;
-            run += v;
-        }
-        *total_out = run;
-    }
-    __syncthreads();
-    long long run = part[tid];
-    for (long long i = lo; i < hi; ++i) {
-        out[i] = run;
-        run += in[i];
-    }
+    workgroup_exclusive_scan<256>(in, out, n, total_out);
 }
 
 // base[k]: thread k adds the paths in their order (trees ascending, leaves in ascending node index).

@@ -16,6 +16,7 @@
 // (and therefore the whole segmentation) do not depend on the order of the atomics.
 #include "slic.hpp"
 #include "slic_features.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -736,7 +737,7 @@ __global__ __launch_bounds__(256) void seed_masked_kernel(const SeedGrid *__rest
 #pragma unroll
             for (int w = 0; w < 4; ++w) { const int c = s_wave[it & 1][u][w]; total += c; if (w < wv) before += c; }
             if (keep[u]) {
-                const int rank = run + before + __popcll(bal[u] & ((1ull << lane) - 1ull));
+                const int rank = run + before + lanes_below(bal[u]);
                 seed[2 * (size_t)(g.cent_off + rank)] = (float)y[u];
                 seed[2 * (size_t)(g.cent_off + rank) + 1] = (float)x[u];
                 cent_prob[g.cent_off + rank] = p;
@@ -802,15 +803,8 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const SlicProblem *__r
         for (long long j = h0 + nvec * 16 + threadIdx.x; j < npix; j += blockDim.x) c += m[j] != 0;
     }
     // one atomic per workgroup: atomics on one word serialise device-wide
-    __shared__ int s_c[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-        if (tot) atomicAdd(&out[p], tot);
-    }
+    c = block_sum<256>(c);
+    if (threadIdx.x == 0 && c) atomicAdd(&out[p], c);
 }
 
 // The tables that depend on the window shapes only, into the open planning blob (no flush): the problems as slic_batch_layout left

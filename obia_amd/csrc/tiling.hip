@@ -22,6 +22,7 @@
 // All tiles of a pass (or of one white tile-row) are ONE batch for the SLIC engine and for the
 // connectivity kernels: no per-tile launches, two host read-backs per batch.
 #include "slic.hpp"
+#include "wave_ops.hpp"
 #include "../../include/obia_testing.h"
 
 #include <cmath>
@@ -130,14 +131,10 @@ __global__ __launch_bounds__(256) void tile_mask_kernel(const TileWin *__restric
     // parts[tile * gridDim.x + workgroup] = the non-zero mask bytes this workgroup wrote (every byte is 0 or 1): partial sums of the
     // tile's valid count, mask.sum() (tiling.py:133), which the host adds up after the read-back it makes anyway.  Plain stores, every
     // slot written: atomics on the tiles' counters serialise, about 8 ns each, and cost more than the counting kernel they replace.
-    __shared__ int s_nz[4];
     int nz = 0;
     auto store_count = [&]() {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nz += __shfl_xor(nz, off);
-        if ((threadIdx.x & 63) == 0) s_nz[threadIdx.x >> 6] = nz;
-        __syncthreads();
-        if (threadIdx.x == 0) parts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s_nz[0] + s_nz[1] + s_nz[2] + s_nz[3];
+        nz = block_sum<256>(nz);
+        if (threadIdx.x == 0) parts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = nz;
     };
     // a white tile whose polygon no existing segment intersects keeps the mask it read: neither kept segments (there are none
     // inside the polygon) nor the corner squares are masked out (tiling.py:212, 261-262)
@@ -333,57 +330,35 @@ __global__ __launch_bounds__(64) void tile_scatter_kernel(const TileWin *__restr
 constexpr int IDS_CHUNK = 1024 * 16;
 
 __global__ __launch_bounds__(1024) void ids_count_kernel(const uint8_t *__restrict__ alive, int n_ids, int *__restrict__ partial) {
-    __shared__ int s_wave[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int i0 = blockIdx.x * IDS_CHUNK + tid * 16;
     int c = 0;
 #pragma unroll
     for (int q = 0; q < 16; ++q) c += (i0 + q < n_ids) ? (alive[i0 + q] != 0) : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if (lane == 0) s_wave[wv] = c;
-    __syncthreads();
-    if (tid == 0) {
-        int t = 0;
-        for (int w2 = 0; w2 < 16; ++w2) t += s_wave[w2];
-        partial[blockIdx.x] = t;
-    }
+    c = block_sum<1024>(c);
+    if (tid == 0) partial[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(1024) void ids_scan_kernel(const uint8_t *__restrict__ alive, int n_ids, const int *__restrict__ partial,
                                                         int *__restrict__ newid, long long *__restrict__ total) {
-    __shared__ int s_wave[16];
-    __shared__ int s_base[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     // alive ids in the chunks before this one
     int pre = 0;
     for (int j = tid; j < (int)blockIdx.x; j += 1024) pre += partial[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off);
-    if (lane == 0) s_base[wv] = pre;
     const int i0 = blockIdx.x * IDS_CHUNK + tid * 16;
     unsigned char f[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) f[q] = (i0 + q < n_ids) ? alive[i0 + q] : 0;
+    pre = block_sum<1024>(pre);   // (behind the loads: they are in flight before its barriers)
     int c = 0;
 #pragma unroll
     for (int q = 0; q < 16; ++q) c += f[q] != 0;
-    // inclusive scan of c over the wave (shuffle up), then over the 16 waves
-    int inc = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(inc, off);
-        if (lane >= off) inc += v;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    int before = 0;
-    for (int w2 = 0; w2 < 16; ++w2) { before += s_base[w2]; if (w2 < wv) before += s_wave[w2]; }
-    int run = before + inc - c;
+    int chunk_total;
+    int run = pre + block_exclusive_scan<1024>(c, chunk_total);
 #pragma unroll
     for (int q = 0; q < 16; ++q)
         if (i0 + q < n_ids) { if (f[q]) { run += 1; newid[i0 + q] = run; } else newid[i0 + q] = 0; }
-    if (blockIdx.x == gridDim.x - 1 && tid == 1023) *total = before + inc;
+    if (blockIdx.x == gridDim.x - 1 && tid == 1023) *total = pre + chunk_total;
 }
 
 // G[i] = newid[G[i]]: four pixels per lane and step (one 16-byte access, four gathers in flight)

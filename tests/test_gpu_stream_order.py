@@ -776,8 +776,27 @@ def _host_cases():
     NEW["host:create_tiled_segments_skimage"] = Op(tiled_skimage_host)
 
 
+# -- the device primitives' hook (tests/test_gpu_wave_ops.py): a one-workgroup scan and a per-workgroup rank on one late input each
+def _wave_ops_cases():
+    from tests import test_gpu_wave_ops as WO
+    values = np.random.RandomState(5).randint(0, 8, 2 * 1024 + 3)
+    calls = ((WO.SCAN_I64, 1024), (WO.BLOCK_FLAG_RANK, 256))
+
+    def run(ctx, oracle):
+        return tuple(a for op, nt in calls for a in WO.wave_ops(op, nt, values, ctx))
+
+    def judge(got, oracle):
+        want = tuple(a for op, nt in calls for a in WO.expected(op, nt, values))
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            bits_equal(g, w, "wave ops")
+    NEW["test:wave_ops"] = Op(run, judge=judge)
+    CALLS["test:wave_ops"] = ("obia_test_wave_ops_dev",) * len(calls)
+
+
 for _build in (_image_cases, _sharpness_cases, _training_cases, _crowns_cases, _pointcloud_cases, _ground_cases, _groundfilter_cases,
-               _adjacency_cases, _shapes_cases, _merging_cases, _seeds_cases, _mlp_shap_pieces, _wrapper_cases, _host_cases):
+               _adjacency_cases, _shapes_cases, _merging_cases, _seeds_cases, _mlp_shap_pieces, _wrapper_cases, _host_cases,
+               _wave_ops_cases):
     _build()
 
 REUSED = [name for name in WHT.OPS if not name.startswith("guards:")]

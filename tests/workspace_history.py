@@ -206,6 +206,7 @@ ROWS = {
     "obia_test_cc_report": exempt("host only: copies the record of the last connectivity call"),
     "obia_test_poison_workspace_dev": exempt("the instrument itself: every case of the GPU test calls it"),
     "obia_test_visited_nonzero": exempt("the instrument itself: reads the visited map, writes nothing"),
+    "obia_test_wave_ops_dev": exempt("takes no workspace: one kernel on the caller's buffers (the int32 scans run on the first half of out)"),
 }
 
 # Source files of obia_amd/csrc that take memory from the arena, and a case that runs each: tests/test_workspace_history_cpu.py looks
